@@ -1,6 +1,7 @@
 """Contract benchmark: rays/s of the volumetric-rendering hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config lego|fern] [--mode train|infer|render_only] [--strong]
+                    [--full] [--dump-outputs DIR]
 
 N > 1: one process per GPU.  Launched by the driver through ``python -m torch.distributed.run ... bench.py --gpus N``
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) -- or directly: ``python bench.py --gpus N`` re-executes
@@ -22,11 +23,17 @@ Workloads (BASELINE.json `configs`; synthetic, seeded: workloads.py):
                    perturb=0) of a pose_spherical spiral; frames are dealt round-robin over the ranks, no collective
     --strong       (configs[3] as strong scaling): the GLOBAL batch is 32,768 rays, random draws made once for the
                    full batch from a shared seed and sliced per rank
-The default command (``python bench.py`` = 1 GPU, lego training step) also runs SHORT legs of the other single-GPU
-configurations -- fern training step, render_only frames, the 32,768-ray batch -- and reports them under `configs`, each
-with its own north-star gate (PSNR delta of our image vs the reference's image on that configuration's fixture).
-Inputs are resident in HBM before the timed region.  `value` is timed with the per-kernel event timer OFF; the per-kernel
-table (`kernels`, `roofline`) comes from a separate pass over the same steps.  Prints ONE JSON line (rank 0).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) whose `value` / `ms_per_step` are that
+timed region; nothing else runs.  With --dump-outputs DIR it first writes what the last timed step computed (the arrays a caller
+of that step receives: render()'s outputs, the loss, both networks' gradients and updated parameters) as DIR/<name>.npy, float32,
+at most 64 MB in all (larger arrays as a fixed seeded sample of their rows).  The inputs are seeded: the same arguments give the
+same inputs in every run.
+--full adds everything else the benchmark measures or checks, in the same run: the per-kernel table (`kernels`, `roofline`,
+a separate pass over the same steps), the inference and other-datapath legs, the north-star gates, the sustained leg with board
+power, the ROCm-eager and CPU baselines, the N > 1 exchange figures, and -- for the default configuration (1 GPU, lego training
+step) -- SHORT legs of the other single-GPU configurations (fern training step, render_only frames, the 32,768-ray batch), reported
+under `configs`, each with its own north-star gate (PSNR delta of our image vs the reference's image on that configuration's
+fixture).  Inputs are resident in HBM before the timed region; `value` is timed with the per-kernel event timer OFF.
 
 `roofline`: `achieved` = ALGORITHMIC FLOP of the reference's layer stack (1,186,816 per point and forward
 evaluation: run_nerf_helpers.py:96-119) processed by one launch of the dominant kernel / its average launch time, `frac` =
@@ -113,7 +120,15 @@ def parse_args(argv=None):
                          "written (ProcessGroupNCCL, async all-reduce work objects, broadcast, all-gather) and the line carries a multi_gpu block")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group plumbing only (no GPU work): used by the CPU test of the N > 1 launch path")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (per-kernel table / roofline, other datapaths, gates, sustained leg, "
+                         "baselines, the other configurations); without it a run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def relaunch_if_needed(args):
@@ -136,7 +151,10 @@ def relaunch_if_needed(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execve(sys.executable, cmd, env)
+    # a fresh child process (this one may have initialised the HIP runtime above), whose exit status becomes ours
+    import subprocess
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 # --------------------------------------------------------------------------------------------- per-kernel table / roofline
@@ -392,15 +410,31 @@ class Session:
         if self.sync is not None:
             self.sync.finish()
         self.optimizer.step()
+        return rgb, disp, acc, extras, loss
 
     def infer_step(self, i):
         with self.torch.no_grad():
-            self.npa.render(self.H, self.W, self.K, chunk=self.args.chunk, rays=self.batches[i % self.pool], retraw=True, **self.kwargs_test)
+            return self.npa.render(self.H, self.W, self.K, chunk=self.args.chunk, rays=self.batches[i % self.pool], retraw=True,
+                                   **self.kwargs_test)
 
     def frame_step(self, i):
         frame_id = (self.rank + i * self.world) % len(self.spiral)      # parallel.frames_of_rank dealing: frame f -> rank f mod G
         with self.torch.no_grad():
-            self.npa.render(self.fr, self.fr, self.Kf, chunk=self.args.chunk, c2w=self.spiral[frame_id][:3, :4], **self.kwargs_test)
+            return self.npa.render(self.fr, self.fr, self.Kf, chunk=self.args.chunk, c2w=self.spiral[frame_id][:3, :4], **self.kwargs_test)
+
+    def outputs_of(self, mode, ret):
+        """{name: tensor} of what one step hands its caller: render()'s four results (extras by key) and, for a training step, the
+        loss and both networks' gradients and parameters as optimizer.step() left them"""
+        rgb, disp, acc, extras = ret[:4]
+        out = {"rgb_map": rgb, "disp_map": disp, "acc_map": acc}
+        out.update({k: v for k, v in extras.items() if isinstance(v, self.torch.Tensor)})
+        if mode == "train":
+            out["loss"] = ret[4]
+            for tag, net in (("coarse", self.net_c), ("fine", self.net_f)):
+                ps = list(net.parameters())
+                out[f"grad_{tag}"] = self.torch.cat([p.grad.reshape(-1) for p in ps])
+                out[f"params_{tag}"] = self.torch.cat([p.detach().reshape(-1) for p in ps])
+        return out
 
     def step_fn(self, mode):
         return {"train": self.train_step, "infer": self.infer_step, "render_only": self.frame_step}[mode]
@@ -467,6 +501,26 @@ class Session:
             self.sync.close()
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, path):
+    """write {name: tensor} as path/<name>.npy in float32; if the whole exceeds DUMP_BYTES, every array of more than 65,536 values is
+    cut to the same fraction of its rows (along the first axis), chosen by a generator of fixed seed: the files of two runs with the
+    same arguments hold the same rows"""
+    import numpy as np
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    frac = min(1.0, 0.95 * DUMP_BYTES / max(total, 1))
+    os.makedirs(path, exist_ok=True)
+    for k, a in sorted(arrs.items()):
+        if frac < 1.0 and a.size > 65536 and a.ndim >= 1:
+            keep = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, k + ".npy"), np.asarray(a, dtype=np.float32))
+
+
 def _guarded(errors, name, fn):
     """Run a SECONDARY measurement (a `configs` leg, a baseline): the headline has been measured by then and must be printed
     whatever happens here; a failure is recorded in the line under `errors` instead of ending the run."""
@@ -527,18 +581,23 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(precision, steps, warmup, fn, with_kernels):
-        """(seconds for `steps` steps with the per-kernel timer OFF, max over ranks; per-kernel summary of a SEPARATE pass)"""
+    def measure(precision, steps, warmup, fn, with_kernels, capture=None):
+        """(seconds for `steps` steps with the per-kernel timer OFF, max over ranks; per-kernel summary of a SEPARATE pass).
+        capture(ret): called with what the last timed step returned, after the timed region, before anything else runs"""
         npa.set_precision(precision)
         hb.TIMER = None
         for i in range(warmup):
             fn(i)
         barrier()
         t0 = time.perf_counter()
-        for i in range(steps):
+        for i in range(steps - 1):
             fn(i)
+        last = fn(steps - 1)
         barrier()
         el = time.perf_counter() - t0
+        if capture is not None:
+            capture(last)
+        del last
         LAST_LOCAL_SECONDS[0] = el          # this rank's own clock (the N > 1 line reports the spread over ranks)
         if grouped:
             t = torch.tensor([el], dtype=torch.float64, device=dev)
@@ -555,16 +614,22 @@ def main():
             kern = timer.summary()
         return el, kern
 
+    full = args.full
+    torch.manual_seed(0)        # the draws inside render() (perturb, raw noise): the same inputs in every run with the same arguments
     ses = Session(args.config, args, rank, world, dev, args.rays, args.strong)
     n, n_global = ses.n, ses.n_global
     step = ses.step_fn(args.mode)
     rays_per_step = ses.rays_per_step(args.mode)
-    elapsed, kern = measure(args.precision, args.steps, args.warmup, step, with_kernels=True)
-    by_rank = per_rank_ms(LAST_LOCAL_SECONDS[0], args.steps, world) if grouped else None
+
+    def capture(ret):
+        if args.dump_outputs and rank == 0:
+            dump_outputs(ses.outputs_of(args.mode, ret), args.dump_outputs)
+    elapsed, kern = measure(args.precision, args.steps, args.warmup, step, with_kernels=full, capture=capture)
+    by_rank = per_rank_ms(LAST_LOCAL_SECONDS[0], args.steps, world) if (full and grouped) else None
 
     # ---- N > 1: what the exchange costs alone, whether it was overlapped, and whether the ranks still agree
     multi = None
-    if grouped and args.mode == "train":
+    if full and grouped and args.mode == "train":
         bufs = [torch.zeros(hb.N_PARAMS, device=dev) for _ in range(2)]
         for b in bufs:
             dist.all_reduce(b)
@@ -584,7 +649,7 @@ def main():
                  "ranks_identical": parallel.ranks_identical([ses.net_c.flat_params(), ses.net_f.flat_params()]),
                  "rccl_ranks_seen": parallel.ranks_seen(), "backend": dist.get_backend(),
                  "rccl_version": rccl_version() if dist.get_backend() == "nccl" else None}
-    elif grouped:
+    elif full and grouped:
         multi = {"rccl_ranks_seen": parallel.ranks_seen()}
     if multi is not None:
         multi["ms_per_step_by_rank"] = by_rank
@@ -594,7 +659,7 @@ def main():
 
     # ---- secondary numbers of the same run (never the headline)
     other_infer = infer_chain = second = None
-    if args.mode == "train":
+    if full and args.mode == "train":
         k_inf = max(5, args.steps // 2)
         el_i, _ = measure(args.precision, k_inf, 2, ses.infer_step, with_kernels=False)
         infer_chain = None
@@ -613,7 +678,7 @@ def main():
                 el_i = min(el_i, e)
             infer_chain = n * world * k_inf / el_c
         other_infer = n * world * k_inf / el_i
-    if not args.single_datapath and args.mode != "render_only":
+    if full and not args.single_datapath and args.mode != "render_only":
         p2 = "bf16x3" if args.precision == "fp32" else "fp32"
         k2 = max(4, args.steps // 4)
         el2, kern2 = measure(p2, k2, 2, step, with_kernels=True)
@@ -622,7 +687,7 @@ def main():
                   "steps": k2, "ms_per_step": 1e3 * el2 / k2, "roofline": roofline_of(tab2), "kernels": _brief(tab2)}
     errors = {}
     two_word = None
-    if not args.single_datapath and args.mode == "train" and args.precision == "fp16x3" and world == 1:
+    if full and not args.single_datapath and args.mode == "train" and args.precision == "fp16x3" and world == 1:
         # the price of fp32-class GRADIENTS on this datapath: fp16x3w = the same forward, two-word operands in the weight-gradient GEMM
         # (the instrument behind "the 11-bit operand storage costs training nothing detectable")
         def _tw():
@@ -633,7 +698,7 @@ def main():
                     "headline_gradient_vs_fp64": gradient_vs_fp64(dev, "fp16x3")}
         two_word = _guarded(errors, "two_word_datapath", _tw)
     npa.set_precision(args.precision)
-    default_run = (world == 1 and args.mode == "train" and args.config == "lego" and not args.strong and not args.no_configs
+    default_run = (full and world == 1 and args.mode == "train" and args.config == "lego" and not args.strong and not args.no_configs
                    and args.rays == N_RAND)
 
     # ---- the headline leg again, for seconds instead of 0.15 s, with board power and clock sampled meanwhile: the loop `value`
@@ -677,7 +742,7 @@ def main():
     # ---- the reduced INFERENCE class (fp16 main term + fp8 correction terms, csrc/field_ring8.h): never the headline; measured
     # alternately with the headline's inference, with its own north-star gate
     reduced_infer = None
-    if not args.single_datapath and args.mode == "train" and args.precision == "fp16x3" and rank == 0:
+    if full and not args.single_datapath and args.mode == "train" and args.precision == "fp16x3" and rank == 0:
         def _red():
             k_inf = max(5, args.steps // 2)
             best = {"fp16x3": None, "fp16_fp8c": None}
@@ -706,7 +771,7 @@ def main():
         npa.set_precision(args.precision)
 
     bf16x3_leg = None
-    if args.bf16x3_leg and not args.single_datapath and args.mode == "train" and args.precision == "fp16x3":
+    if full and args.bf16x3_leg and not args.single_datapath and args.mode == "train" and args.precision == "fp16x3":
         # rounds 1-3's headline datapath in the same run (bf16 parts: 2^-17 products, 8-bit weight-gradient operands)
         def _b3():
             kb = max(5, args.steps // 2)
@@ -721,7 +786,7 @@ def main():
         npa.set_precision(args.precision)
 
     gate = None
-    if not args.no_gate and rank == 0:
+    if full and not args.no_gate and rank == 0:
         gate = ses.gate(args.precision)
         if args.long and gate is not None:
             gate["training"] = convergence_table(dev, args.long_steps, checkpoints=(args.long_steps // 4, args.long_steps // 2), twins=args.long_twins, twins16=args.long_twins)
@@ -917,7 +982,7 @@ def main():
                        "render_only": "rays/sec (coarse+fine, 64+128 samples), render_only frames"}[args.mode],
             "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-            "scaling": "strong" if args.strong else "weak", "vs_baseline": None,
+            "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "full": full,
             "dtype": DTYPE_NAME[args.precision], "data": "synthetic",
             "config": {"workload": workload, "global_batch_rays": rays_per_step * world if args.mode == "render_only" else n_global,
                        "parallelism": f"ray-shard dp{world}" if args.mode != "render_only" else f"frame-parallel x{world}",
@@ -951,7 +1016,7 @@ def main():
             line["sustained_rays_per_s"] = sustained["train"]["rays_per_s"]
             line["power"] = sustained["train"]["power"]
         eb = None
-        if world == 1 and not args.no_eager_baseline and args.mode != "render_only":
+        if full and world == 1 and not args.no_eager_baseline and args.mode != "render_only":
             eb = _guarded(errors, "rocm_eager_baseline", lambda: rocm_eager_baseline(
                 args.config, dev, n, frame=args.frame if default_run else 0, chunk=args.chunk, pose=ses.spiral[0]))
         if eb is not None:
@@ -972,7 +1037,7 @@ def main():
                 line["speedup_vs_rocm_eager"]["render_only"] = legs["render_only"]["value"] / eb["render_only"]["rays_per_s"]
                 if reduced_infer is not None and reduced_infer.get("render_only"):
                     line["speedup_vs_rocm_eager"]["reduced_render_only"] = reduced_infer["render_only"]["rays_per_s"] / eb["render_only"]["rays_per_s"]
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             cb = _guarded(errors, "cpu_baseline", lambda: cpu_baseline(args.config))
             if cb is not None:
                 line["cpu_baseline"] = cb

@@ -87,3 +87,30 @@ def test_bench_world_size_mismatch_is_an_error():
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--backend", "gloo"],
                          capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
     assert res.returncode != 0 and "--gpus 2" in (res.stderr + res.stdout)
+
+
+def test_dump_outputs_is_float32_bounded_and_seeded(tmp_path):
+    """--dump-outputs: float32 files, the whole within 64 MB; an output too large for that is cut to the same rows in every run"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = {"raw": torch.rand(32768, 192, 4, generator=g), "rgb_map": torch.rand(32768, 3, generator=g, dtype=torch.float64),
+            "loss": torch.tensor(0.25), "grad_fine": torch.rand(595844, generator=g)}
+    for d in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / d))
+    total = 0
+    for nm in ("raw", "rgb_map", "loss", "grad_fine"):
+        a, b = np.load(tmp_path / "a" / f"{nm}.npy"), np.load(tmp_path / "b" / f"{nm}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), nm
+        total += a.nbytes
+    assert total <= bench.DUMP_BYTES
+    assert np.load(tmp_path / "a" / "loss.npy").shape == () and float(np.load(tmp_path / "a" / "loss.npy")) == 0.25
+    raw = np.load(tmp_path / "a" / "raw.npy")
+    assert raw.shape[1:] == (192, 4) and 0 < raw.shape[0] < 32768
+    rows = [i for i in range(32768) if np.array_equal(outs["raw"][i].numpy(), raw[0])]
+    assert len(rows) == 1          # whole rows of the output, not a reshuffle of its values
+    small = {"rgb_map": torch.rand(4096, 3, generator=g)}
+    bench.dump_outputs(small, str(tmp_path / "c"))
+    assert np.array_equal(np.load(tmp_path / "c" / "rgb_map.npy"), small["rgb_map"].numpy())

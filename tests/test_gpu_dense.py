@@ -107,13 +107,13 @@ def test_dense_render_rays_against_the_oracle(npa, dev, name):
         assert cos >= 1.0 - 1e-4, (name, cos)
 
 
-def test_dense_path_through_create_nerf_render_and_adam(npa, dev):
+def test_dense_path_through_create_nerf_render_and_adam(npa, dev, tmp_path):
     """The reference's command line without --use_viewdirs, with --netdepth 4 --netwidth 64 --i_embed -1: create_nerf builds the
     networks, render() runs a frame chunk (c2w branch, ray records built on the device), two optimizer steps lower the loss."""
     parser = npa.config_parser()
     args = parser.parse_args(["--netdepth", "4", "--netwidth", "64", "--netdepth_fine", "6", "--netwidth_fine", "96", "--i_embed", "-1",
                               "--N_samples", "16", "--N_importance", "24", "--white_bkgd", "--dataset_type", "blender", "--no_reload",
-                              "--expname", "dense_test", "--basedir", "/tmp/nerf_dense_test", "--lrate", "2e-3"])
+                              "--expname", "dense_test", "--basedir", str(tmp_path), "--lrate", "2e-3"])
     assert not args.use_viewdirs
     torch.manual_seed(0)
     kw_train, kw_test, start, grad_vars, opt = npa.create_nerf(args, device=dev)

@@ -110,10 +110,12 @@ def test_gate_fixtures_are_the_references_images(which):
     assert g["psnr_delta_db"] == 0.0 and g["target_psnr_db"] >= 30.0 and abs(g["target_psnr_db"] - float(gold["target_psnr_db"])) < 1e-6
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree only exists in the build container")
 def test_oracle_is_bit_identical_to_the_reference():
+    """oracle/pin_against_reference.py's comparisons, function by function, against the reference's values it recorded
+    (`python oracle/pin_against_reference.py --record tests/golden/oracle_pin.npz`; large values as SHA-256 digests)."""
     import pin_against_reference
-    pin_against_reference.main(n_rays=48)
+    gold = np.load(os.path.join(GOLD, "oracle_pin.npz"))
+    pin_against_reference.main(n_rays=48, golden={k: gold[k] for k in gold.files})
 
 
 def test_known_answers():

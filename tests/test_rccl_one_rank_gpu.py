@@ -135,7 +135,7 @@ def test_gradient_sync_over_a_one_rank_rccl_group_is_bit_identical():
 def test_bench_line_over_a_one_rank_rccl_group():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl", "--force-group", "--steps", "3",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--backend", "nccl", "--force-group", "--steps", "3",
                           "--warmup", "2", "--single-datapath", "--no-gate", "--no-cpu-baseline", "--no-eager-baseline", "--no-configs",
                           "--sustained-s", "0"], capture_output=True, text=True, timeout=540, env=_env(), cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]

@@ -109,7 +109,7 @@ def test_bench_line_with_two_ranks():
         pytest.skip("no GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["NERF_ALLOW_SHARED_GPU"] = "1"
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--backend", "gloo", "--steps", "2",
                           "--warmup", "1", "--rays", "1024", "--single-datapath", "--no-gate", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=540, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
