@@ -339,6 +339,31 @@ int nerf_adam_step(float* params, const float* grads, float* exp_avg, float* exp
  * 2 * canonical_index + is_low_part, or -1 for zero padding. */
 int nerf_debug_pack3_table(int* out_host);
 
+/* ---- gradients to the INPUTS of the field and the compositing (additive in ABI v10): rays, sample points, camera poses.
+ * The reference differentiates render() end to end (plain autograd); these entry points carry dL/d(ray records). */
+/* Input gradient of one field evaluation, enqueued after its dgrad (nerf_field_bwd / nerf_field_dgrad / nerf_field_dgrad_split) and
+ * before `delta` is reused: reads the deltas of layers 0 and 5 and of the view branch in whatever layout the dgrad recorded for
+ * `delta` (fp32 rows, bf16 / fp16 tiles with the fp16 delta scale, fp16 hi + lo tiles), the fp32 parameter vector `params`
+ * (nerf_param_count() floats: W0, W5[:, :63], Wv[:, 256:283] are read), the rays [n_rays][ray_stride] and z_vals
+ * [n_rays][n_samples] of the same evaluation, and writes (accumulate = 0) or adds to (accumulate = 1) d_rays[n_rays][11]:
+ * columns 0:3 = sum_s dL/dx_s, 3:6 = sum_s z_s dL/dx_s (x_s = o + z_s d), 6:8 = 0 (near / far: no gradient), 8:11 = dL/d viewdir.
+ * The sum over a ray's samples has a fixed order (no atomics: bit-reproducible).  n_samples = 1 with z = 0 and d = 0 gives per-point
+ * d_pts / d_viewdirs (query_points).  Reads nothing it does not own; changes neither `delta` nor `params`.  NERF_E_BADARG for null
+ * pointers, n_samples <= 0, ray_stride < 11, or a `delta` without a matching layout record (unknown buffer, other ray / sample
+ * count, a layout without a reader). */
+int nerf_field_input_grad(const float* params, const float* delta, const float* rays, int ray_stride, const float* z_vals,
+                          int n_rays, int n_samples, float* d_rays, int accumulate, void* stream);
+/* nerf_raw2outputs_bwd plus the geometry adjoint: d_rays_d[n_rays][3] = (d / |d|) sum_s dz_s dL/d dist_s (dist_s = dz_s |d|, last
+ * dz = 1e10) and d_z_vals[n_rays][n_samples] (through the dists and the depth integral), both WRITTEN; either may be NULL, not both.
+ * d_raw is the same as nerf_raw2outputs_bwd's, bit for bit. */
+int nerf_raw2outputs_bwd_geom(const float* raw, const float* z_vals, const float* rays_d, int dir_stride, int n_rays,
+                              int n_samples, const float* noise, float raw_noise_std, int white_bkgd,
+                              const float* d_rgb, const float* d_acc, const float* d_disp, const float* d_weights,
+                              const float* d_depth, float* d_raw, float* d_rays_d, float* d_z_vals, void* stream);
+/* adjoint of nerf_embed: d_x[n_pts][3] = (accumulate ? d_x + : ) d/dx (out[n_pts][3 + 6 n_freqs] . d_out), the same encoding derivative
+ * as nerf_field_input_grad (sin / cos of the exact 2^k x). */
+int nerf_embed_bwd(const float* x, long n_pts, int n_freqs, const float* d_out, float* d_x, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,9 @@ struct CompositeArgs {
     float* d_raw;           // [N][S][4]
     const float* d_weights; // [N][S] nullable: upstream gradient of the `weights` output
     const float* d_depth;   // [N] nullable: upstream gradient of `depth_map`
+    // geometry adjoint (nerf_raw2outputs_bwd_geom; both NULL = the plain adjoint w.r.t. raw, unchanged)
+    float* d_dirs;          // [N][3] nullable: dL/d rays_d through dists = dz * |rays_d| (written)
+    float* d_z;             // [N][S] nullable: dL/d z_vals through dists and the depth integral (written)
 };
 
 struct FineArgs {
@@ -65,6 +68,10 @@ hipError_t launch_range_scan(const unsigned* rows, size_t n_words, unsigned* wor
 hipError_t launch_mse_fwd(const float* x, const float* y, long n, float* scratch, float* out, hipStream_t stream);
 hipError_t launch_mse_bwd(const float* x, const float* y, long n, const float* g, float* dx, hipStream_t stream);
 hipError_t launch_embed(const float* x, long n_pts, int n_freqs, float* out, hipStream_t stream);
+hipError_t launch_embed_bwd(const float* x, long n_pts, int n_freqs, const float* d_out, float* d_x, int accumulate, hipStream_t stream);
+// input gradients of one field evaluation from its deltas (field_input_grad.hip); kind = the delta buffer's DeltaKind (api_util.h)
+hipError_t launch_field_input_grad(const float* params, const float* delta, int kind, const float* rays, int ray_stride,
+                                   const float* z_vals, int n_rays, int S, float* d_rays, int accumulate, hipStream_t stream);
 hipError_t launch_make_rays(int H, int W, const float* K9, const float* pose12, const float* pose_static12, int ndc,
                             float near, float far, float* rays, int ray_stride, hipStream_t stream);
 hipError_t launch_assemble_rays(const float* rays_o, const float* rays_d, long n, int ndc, int H, int W, float focal,

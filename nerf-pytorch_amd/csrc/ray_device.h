@@ -166,6 +166,7 @@ __device__ __forceinline__ void composite_ray(const CompositeArgs& a, int ray, i
         if (gw) g += gw[i];
         s_gw[i] = g * w;
         segsum += g * w;
+        if (a.d_z) a.d_z[(size_t)ray * S + i] = gdepth * w;         // depth integral sum_j w_j z_j: direct term
         // colour gradients are local
         float* dr = a.d_raw + ((size_t)ray * S + i) * 4;
         dr[0] = w * g0 * (c0 * (1.0f - c0));
@@ -179,10 +180,39 @@ __device__ __forceinline__ void composite_ray(const CompositeArgs& a, int ray, i
     const float suf = wave_incl_scan_add_rev(segsum, lane);
     float R = __shfl_down(suf, 1);          // sum over lanes > this one
     if (lane == 63) R = 0.0f;
+    const bool geo = a.d_dirs || a.d_z;
+    float ddz = 0.0f, dd_last = 0.0f;
     for (int i = hi - 1; i >= lo; --i) {
         const float dalpha = s_alpha[i] - R / s_t[i];
         a.d_raw[((size_t)ray * S + i) * 4 + 3] = dalpha * s_e[i];
         R += s_gw[i];
+        if (geo) {
+            // dL/d dist_i = dalpha * relu(sigma) * exp(-relu(sigma) dist)   (dist_i = dz_i |d|, dz_last = 1e10)
+            const float dz = (i + 1 < S) ? (z[i + 1] - z[i]) : 1e10f;
+            float sg = raw[4 * i + 3];
+            if (a.noise) sg = sg + a.noise[(size_t)ray * S + i] * a.noise_std;
+            const float rs = fmaxf(sg, 0.0f);
+            const float dd = dalpha * (rs * expf(-rs * (dz * dn)));
+            ddz += dz * dd;
+            s_e[i] = dd;                    // (s_e[i] is not read again)
+            if (i == hi - 1) dd_last = dd;
+        }
+    }
+    if (!geo) return;
+    const float tot = wave_sum(ddz);
+    if (a.d_dirs && lane == 0) {
+        const float inv = 1.0f / dn;
+        for (int c = 0; c < 3; ++c) a.d_dirs[(size_t)ray * 3 + c] = (dp[c] * inv) * tot;
+    }
+    if (a.d_z) {
+        // dist_i = (z_{i+1} - z_i) |d|: z_i receives |d| (dL/d dist_{i-1} - dL/d dist_i); dist_{lo-1} is the previous lane's last sample
+        float prev = __shfl_up(dd_last, 1);
+        if (lane == 0) prev = 0.0f;
+        for (int i = lo; i < hi; ++i) {
+            const float cur = (i + 1 < S) ? s_e[i] : 0.0f;
+            a.d_z[(size_t)ray * S + i] += dn * (prev - cur);
+            prev = s_e[i];
+        }
     }
 }
 

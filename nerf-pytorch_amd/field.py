@@ -32,7 +32,26 @@ class Embedder:
         self.out_dim = d + 2 * n * d
 
     def embed(self, inputs):
-        return hb.embed(inputs.float(), self.num_freqs)
+        x = inputs.float()
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _Embed.apply(x, self.num_freqs)
+        return hb.embed(x, self.num_freqs)
+
+
+class _Embed(torch.autograd.Function):
+    """Embedder.embed with its gradient w.r.t. the points (nerf_embed_bwd: the encoding derivative of the input-gradient kernel)"""
+
+    @staticmethod
+    def forward(ctx, x, n_freqs):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        ctx.n_freqs = n_freqs
+        return hb.embed(x, n_freqs)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x, = ctx.saved_tensors
+        return hb.embed_bwd(x, ctx.n_freqs, d_out.to(torch.float32).contiguous()), None
 
 
 def get_embedder(multires, i=0):

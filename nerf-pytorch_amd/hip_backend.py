@@ -78,6 +78,9 @@ def _declare(lib):
         "nerf_dense_wgrad": (i, [p, i, i, p, i, i, l, p, i, p, p, i, p]),
         "nerf_render_rays_infer": (i, [p, p, p, p, i, i, p, p, p, p, p, p, p, p, p, p, p, p, p, p]),
         "nerf_range_scan": (i, [p, i, i, p, p]),
+        "nerf_field_input_grad": (i, [p, p, p, i, p, i, i, p, i, p]),
+        "nerf_raw2outputs_bwd_geom": (i, [p, p, p, i, i, i, p, f, i, p, p, p, p, p, p, p, p, p]),
+        "nerf_embed_bwd": (i, [p, l, i, p, p, i, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError here = header / library mismatch: fail loudly
@@ -96,7 +99,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_adam_step",
            "nerf_render_workspace_floats", "nerf_render_rays_fwd", "nerf_render_rays_bwd", "nerf_render_infer_supported",
            "nerf_render_rays_infer", "nerf_mse_scratch_floats", "nerf_mse_fwd", "nerf_mse_bwd", "nerf_build_inputs", "nerf_dense_fwd", "nerf_dense_dgrad", "nerf_dense_wgrad_scratch_floats",
-           "nerf_dense_wgrad", "nerf_range_scan"]
+           "nerf_dense_wgrad", "nerf_range_scan", "nerf_field_input_grad", "nerf_raw2outputs_bwd_geom", "nerf_embed_bwd"]
 
 
 def lib():
@@ -814,10 +817,20 @@ def raw2outputs(raw, z_vals, rays_d, dir_stride, noise, raw_noise_std, white_bkg
 
 
 def raw2outputs_bwd(raw, z_vals, rays_d, dir_stride, noise, raw_noise_std, white_bkgd, d_rgb, d_acc, d_disp,
-                    rays_d_offset=0, d_weights=None, d_depth=None):
+                    rays_d_offset=0, d_weights=None, d_depth=None, d_rays_d=None, d_z_vals=None):
+    """d_raw; with d_rays_d ([n, 3]) and / or d_z_vals ([n, S]) preallocated fp32 tensors, also the geometry adjoint written into them
+    (nerf_raw2outputs_bwd_geom: d_raw bit-identical)"""
     n, S = z_vals.shape
     d_raw = torch.empty((n, S, 4), dtype=torch.float32, device=raw.device)
     dptr = _ptr(rays_d, "rays_d") + 4 * rays_d_offset
+    if d_rays_d is not None or d_z_vals is not None:
+        _check(lib().nerf_raw2outputs_bwd_geom(_ptr(raw, "raw"), _ptr(z_vals, "z_vals"), dptr, dir_stride, n, S,
+                                               _ptr(noise, "noise", True), float(raw_noise_std), int(bool(white_bkgd)),
+                                               _ptr(d_rgb, "d_rgb"), _ptr(d_acc, "d_acc", True), _ptr(d_disp, "d_disp", True),
+                                               _ptr(d_weights, "d_weights", True), _ptr(d_depth, "d_depth", True), _ptr(d_raw),
+                                               _ptr(d_rays_d, "d_rays_d", True), _ptr(d_z_vals, "d_z_vals", True), _stream()),
+               "nerf_raw2outputs_bwd_geom")
+        return d_raw
     _check(lib().nerf_raw2outputs_bwd(_ptr(raw, "raw"), _ptr(z_vals, "z_vals"), dptr, dir_stride, n, S,
                                       _ptr(noise, "noise", True), float(raw_noise_std), int(bool(white_bkgd)),
                                       _ptr(d_rgb, "d_rgb"), _ptr(d_acc, "d_acc", True), _ptr(d_disp, "d_disp", True),
@@ -847,25 +860,51 @@ def sample_pdf(bins, weights, n_samples, u, u_lin):
     return out
 
 
-def field_bwd(packed, act, d_raw, grad, accumulate, precision="fp32", params=None):
+BYTES_INPUT_GRAD_PER_POINT = 2 * (256 + 256 + 128)      # deltas the input-gradient kernel reads per point (16-bit words; x2 fp32 / hi + lo)
+
+
+def field_bwd(packed, act, d_raw, grad, accumulate, precision="fp32", params=None, input_grad=None):
     """Parameter gradients of one field evaluation into the flat vector `grad`.  `params`: the canonical (flat) parameter
     vector `packed` was made from -- required by the split datapaths, whose folded feature layer needs Wf, bf
-    and Wv[:, :256] to turn G = delta_hv^T h7 into their gradients (csrc/nerf_common.h)."""
-    if precision != "fp32" and params is None:
-        raise NerfHipError("field_bwd: the split datapaths need params= (the flat parameter vector)")
+    and Wv[:, :256] to turn G = delta_hv^T h7 into their gradients (csrc/nerf_common.h).
+    grad=None: no weight gradient (frozen network: dgrad only).  input_grad = (rays, z_vals, d_rays [n, 11], accumulate): the
+    gradient w.r.t. the ray records from the same deltas (nerf_field_input_grad; needs params=, the live fp32 weights)."""
+    if (precision != "fp32" or input_grad is not None) and params is None:
+        raise NerfHipError("field_bwd: the split datapaths and the input gradient need params= (the flat parameter vector)")
     n, S, _ = d_raw.shape
     L = lib()
     dev = d_raw.device
     delta = WORKSPACE.take(delta_floats(n, S, precision), dev)
-    partial = WORKSPACE.take(L.nerf_wgrad_partial_floats(n, S), dev)
+    partial = WORKSPACE.take(L.nerf_wgrad_partial_floats(n, S), dev) if grad is not None else None
     try:
-        return _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partial, n, S, params)
+        return _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partial, n, S, params, input_grad)
     finally:        # stream-ordered: the next lease is written by kernels enqueued after these
         WORKSPACE.give(delta)
         WORKSPACE.give(partial)
 
 
-def _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partial, n, S, params):
+def field_input_grad(params, delta, rays, z_vals, d_rays, accumulate, precision="fp32"):
+    """nerf_field_input_grad: d_rays [n, 11] (+)= dL/d(ray records) of the evaluation whose dgrad left `delta`"""
+    n, S = z_vals.shape
+    P = n * S
+    with _timed("field_input_grad_kernel", 2.0 * P * (2 * 63 * 256 + 27 * 128),
+                BYTES_INPUT_GRAD_PER_POINT * P * (1 if precision in ("bf16x3", "fp16x3", "fp16_fp8c") else 2)):
+        _check(lib().nerf_field_input_grad(_ptr(params, "params"), _ptr(delta, "delta"), _ptr(rays, "rays"), rays.shape[1],
+                                           _ptr(z_vals, "z_vals"), n, S, _ptr(d_rays, "d_rays"), int(bool(accumulate)), _stream()),
+               "nerf_field_input_grad")
+    return d_rays
+
+
+def embed_bwd(x, n_freqs, d_out):
+    """nerf_embed_bwd: d/dx of embed(x) . d_out"""
+    x = x.contiguous()
+    d_x = torch.empty_like(x)
+    _check(lib().nerf_embed_bwd(_ptr(x, "x"), x.numel() // 3, int(n_freqs), _ptr(d_out.contiguous(), "d_out"), _ptr(d_x), 0, _stream()),
+           "nerf_embed_bwd")
+    return d_x
+
+
+def _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partial, n, S, params, input_grad=None):
     split = {"bf16x3": 0, "fp16x3": 1, "fp16x3w": 5}.get(precision)
     two = split == 5
     # what the forward wrote into `act` (the library's own record, nerf_buffer_layout); the weight-gradient call below passes
@@ -886,6 +925,11 @@ def _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partia
                                       _stream()), "nerf_field_dgrad")
     if split in (1, 5):
         RANGE_MONITOR.after_dgrad(delta, n, S)      # (scans the deltas on the steps whose forward was scanned; nothing otherwise)
+    if input_grad is not None:
+        rays, z_vals, d_rays, acc_rays = input_grad
+        field_input_grad(params, delta, rays, z_vals, d_rays, acc_rays, precision)
+    if grad is None:
+        return None
     gemm16 = split is not None          # 16-bit operands streamed straight into the MFMA (wgrad1_kernel)
     datapath = -1
     args = (_ptr(act, "act"), _ptr(delta), _ptr(d_raw, "d_raw"), n, S, _ptr(partial), _ptr(grad, "grad"),

@@ -90,7 +90,8 @@ def _grad_ready(model, flat_grad):
 
 
 class _FieldQuery(torch.autograd.Function):
-    """raw = field(rays, z) for explicit rays/depths; gradients w.r.t. the parameters only."""
+    """raw = field(rays, z) for explicit rays/depths; gradients w.r.t. the parameters (when they require grad) and the ray
+    records (when they do: nerf_field_input_grad -- query_points' points and view directions)."""
 
     @staticmethod
     def forward(ctx, model, rays, z_vals, need, *params):
@@ -102,6 +103,10 @@ class _FieldQuery(torch.autograd.Function):
                                 guard_packed=model.packed_params("fp16x3") if prec == "fp16_fp8c" else None)
         ctx.model, ctx.packed, ctx.act, ctx.prec, ctx.saved_any = model, packed, act, prec, bool(need)
         ctx.param_state = _param_state(model)
+        ctx.rays_grad = bool(ctx.needs_input_grad[1])
+        ctx.wgrad = any(ctx.needs_input_grad[4:])
+        if ctx.rays_grad:
+            ctx.rays, ctx.z = rays.detach(), z_vals
         ctx.set_materialize_grads(False)
         return raw
 
@@ -114,13 +119,18 @@ class _FieldQuery(torch.autograd.Function):
             raise RuntimeError(_FREED_MSG)
         if ctx.prec != "fp32" and _param_state(model) != ctx.param_state:
             raise RuntimeError(_STALE_MSG)
-        grad = torch.empty(hb.N_PARAMS, dtype=torch.float32, device=d_raw.device)
+        grad = torch.empty(hb.N_PARAMS, dtype=torch.float32, device=d_raw.device) if ctx.wgrad else None
+        d_rays = None
+        if ctx.rays_grad:
+            d_rays = torch.empty((ctx.rays.shape[0], 11), dtype=torch.float32, device=d_raw.device)
         hb.field_bwd(ctx.packed, ctx.act, d_raw.contiguous(), grad, accumulate=False, precision=ctx.prec,
-                     params=model.flat_params())
+                     params=model.flat_params(), input_grad=None if d_rays is None else (ctx.rays, ctx.z, d_rays, False))
         hb.WORKSPACE.give(ctx.act)
         ctx.act = None      # ~10 KB per point: back to the workspace pool as soon as the gradient exists
+        if grad is None:
+            return (None, d_rays, None, None) + (None,) * len(_param_slices(model))
         _grad_ready(model, grad)
-        return (None, None, None, None) + _grad_views(model, grad)
+        return (None, d_rays, None, None) + _grad_views(model, grad)
 
 
 def _param_slices(model):
@@ -267,9 +277,14 @@ class _RenderRays(torch.autograd.Function):
         ctx.cfg, ctx.model_c, ctx.model_f = cfg, model_c, model_f
         ctx.same_net = model_f is None or model_f is model_c
         ctx.n_params_c = len(_param_slices(model_c))
+        # which gradients the backward computes: the ray records' (input-gradient kernel), each network's parameters' (weight
+        # gradient; a frozen network gets none: no wgrad launch, no _grad_ready, .grad stays None)
+        ctx.rays_grad = bool(ctx.needs_input_grad[1])
+        ctx.wgrad_c = any(ctx.needs_input_grad[5:5 + ctx.n_params_c])
+        ctx.wgrad_f = ctx.wgrad_c if ctx.same_net else any(ctx.needs_input_grad[5 + ctx.n_params_c:])
         ctx.need = need
         ctx.set_materialize_grads(False)
-        ctx.rays, ctx.rnd = rays, rnd
+        ctx.rays, ctx.rnd = rays.detach(), rnd
         # What the backward needs, WITHOUT the node's own outputs: an output carries grad_fn = this node, so keeping it
         # in ctx.__dict__ is a node -> ctx -> output -> node cycle the garbage collector cannot break (a graph dropped
         # without backward would pin its ~11 GB of saved activations for good).  The one output the backward reads,
@@ -325,9 +340,11 @@ class _RenderRays(torch.autograd.Function):
                     _release(r_)
                 ctx.saved = None
             return none_all
-        grad_c = torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev)
-        grad_f = None if (ctx.same_net or not fine) else torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev)
+        grad_c = torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev) if ctx.wgrad_c else None
+        grad_f = None if (ctx.same_net or not fine or not ctx.wgrad_f) else torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev)
         wrote = {"c": False, "f": False}
+        # dL/d(ray records), summed over both passes (near / far: zero -- render() builds them from Python floats)
+        d_rays_all = torch.zeros((n_all, 11), dtype=torch.float32, device=dev) if ctx.rays_grad else None
 
         def field_grad(rays, model, packed, act, raw, z, noise, up, lo, hi, grad, key):
             d_rgb, d_disp, d_acc, d_raw_up = (None if g is None else g[lo:hi] for g in up)
@@ -335,33 +352,43 @@ class _RenderRays(torch.autograd.Function):
             if d_rgb is None and (d_disp is not None or d_acc is not None):
                 d_rgb = torch.zeros((m, 3), dtype=torch.float32, device=dev)
             c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
+            d_rays = None if d_rays_all is None else d_rays_all[lo:hi]
+            d_dn = None
             if d_rgb is None:       # only `raw` itself (extras['raw'], e.g. a sigma regulariser) carries a gradient
                 d_raw = c(d_raw_up)
             else:
+                if d_rays is not None:
+                    d_dn = torch.empty((m, 3), dtype=torch.float32, device=dev)
                 d_raw = hb.raw2outputs_bwd(raw, z, rays, rays.shape[1], noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
-                                           rays_d_offset=3)
+                                           rays_d_offset=3, d_rays_d=d_dn)
                 if d_raw_up is not None:
                     d_raw += d_raw_up
-            hb.field_bwd(packed, act, d_raw, grad, wrote[key], precision=prec, params=model.flat_params())
-            wrote[key] = True
+            if grad is None and d_rays is None:
+                return
+            hb.field_bwd(packed, act, d_raw, grad, wrote[key], precision=prec, params=model.flat_params(),
+                         input_grad=None if d_rays is None else (rays, z, d_rays, True))
+            if d_dn is not None:
+                d_rays[:, 3:6] += d_dn          # the compositing's |d| term (dists = dz |d|)
+            if grad is not None:
+                wrote[key] = True
 
         shared = ctx.same_net and fine and has(up_f)      # the fine pass adds into the coarse network's gradient
 
         def backprop(r, rays, rnd, lo, hi, last=True):
             if has(up_c):
                 field_grad(rays, ctx.model_c, r["packed_c"], r["act_c"], r["raw_c"], r["z_c"], rnd.get("noise_c"), up_c, lo, hi, grad_c, "c")
-                if last and not shared:     # final: its all-reduce may start under the fine network's backward
+                if last and not shared and grad_c is not None:     # final: its all-reduce may start under the fine network's backward
                     _grad_ready(ctx.model_c, grad_c)
             hb.WORKSPACE.give(r["act_c"])
             r["act_c"] = None
             if fine and has(up_f):
                 if ctx.same_net:
                     field_grad(rays, ctx.model_c, r["packed_f"], r["act_f"], r["raw_f"], r["z_f"], rnd.get("noise_f"), up_f, lo, hi, grad_c, "c")
-                    if last:
+                    if last and grad_c is not None:
                         _grad_ready(ctx.model_c, grad_c)
                 else:
                     field_grad(rays, ctx.model_f, r["packed_f"], r["act_f"], r["raw_f"], r["z_f"], rnd.get("noise_f"), up_f, lo, hi, grad_f, "f")
-                    if last:
+                    if last and grad_f is not None:
                         _grad_ready(ctx.model_f, grad_f)
             _release(r)
 
@@ -385,19 +412,21 @@ class _RenderRays(torch.autograd.Function):
         out_c = none_c
         if wrote["c"]:
             out_c = _grad_views(ctx.model_c, grad_c)
+        lead = (None, d_rays_all) + (None,) * (n_lead - 2)
         if ctx.same_net:
-            return (None,) * n_lead + out_c
+            return lead + out_c
         out_f = none_c
         if wrote["f"]:
             out_f = _grad_views(ctx.model_f, grad_f)
-        return (None,) * n_lead + out_c + out_f
+        return lead + out_c + out_f
 
 
 class _Composite(torch.autograd.Function):
-    """raw2outputs with a gradient w.r.t. raw (for callers that use it standalone)."""
+    """raw2outputs with gradients w.r.t. raw, and w.r.t. z_vals / rays_d when they require grad (nerf_raw2outputs_bwd_geom)."""
 
     @staticmethod
     def forward(ctx, raw, z_vals, rays_d, noise, raw_noise_std, white_bkgd):
+        raw, z_vals, rays_d = raw.detach(), z_vals.detach(), rays_d.detach()
         rgb, disp, acc, w, depth = hb.raw2outputs(raw, z_vals, rays_d, 3, noise, raw_noise_std, white_bkgd)
         ctx.args = (raw, z_vals, rays_d, noise, raw_noise_std, white_bkgd)
         ctx.set_materialize_grads(False)
@@ -412,24 +441,34 @@ class _Composite(torch.autograd.Function):
         if d_rgb is None:
             d_rgb = torch.zeros((raw.shape[0], 3), dtype=torch.float32, device=raw.device)
         c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
+        d_z = torch.empty_like(z_vals) if ctx.needs_input_grad[1] else None
+        d_dn = torch.empty((z_vals.shape[0], 3), dtype=torch.float32, device=raw.device) if ctx.needs_input_grad[2] else None
         d_raw = hb.raw2outputs_bwd(raw, z_vals, rays_d, 3, noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
-                                   d_weights=c(d_w), d_depth=c(d_depth))
-        return d_raw, None, None, None, None, None
+                                   d_weights=c(d_w), d_depth=c(d_depth), d_rays_d=d_dn, d_z_vals=d_z)
+        return d_raw, d_z, d_dn, None, None, None
 
 
 # --------------------------------------------------------------------------- reference call surface
 def query_points(model, pts, viewdirs_per_point):
     """Evaluate the field at explicit points: every point is its own ray record
-    (o = pt, d = 0, z = 0  =>  o + d*z == pt exactly)."""
-    pts = _f32c(pts)
-    vd = _f32c(viewdirs_per_point)
+    (o = pt, d = 0, z = 0  =>  o + d*z == pt exactly).  Points / view directions that require grad receive d_pts / d_viewdirs
+    (the input-gradient kernel in point mode)."""
+    grad_on = torch.is_grad_enabled()
+    in_grad = grad_on and (pts.requires_grad or viewdirs_per_point.requires_grad)
     n = pts.shape[0]
-    rays = torch.zeros((n, 11), dtype=torch.float32, device=pts.device)
-    rays[:, 0:3] = pts
-    rays[:, 8:11] = vd
+    if in_grad:
+        pts = pts.to(torch.float32).contiguous()
+        vd = viewdirs_per_point.to(torch.float32).contiguous()
+        rays = torch.cat([pts, torch.zeros((n, 5), dtype=torch.float32, device=pts.device), vd], -1)
+    else:
+        pts = _f32c(pts)
+        vd = _f32c(viewdirs_per_point)
+        rays = torch.zeros((n, 11), dtype=torch.float32, device=pts.device)
+        rays[:, 0:3] = pts
+        rays[:, 8:11] = vd
     z = torch.zeros((n, 1), dtype=torch.float32, device=pts.device)
     plist = model.param_list()
-    need = torch.is_grad_enabled() and any(p.requires_grad for p in plist)
+    need = grad_on and (in_grad or any(p.requires_grad for p in plist))
     raw = _FieldQuery.apply(model, rays, z, need, *plist)
     return raw.reshape(n, 4)
 
@@ -480,7 +519,8 @@ def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=F
             std = 1.0
         noise = noise.contiguous()
     raw_c = raw.to(torch.float32).contiguous()
-    return _Composite.apply(raw_c, _f32c(z_vals), _f32c(rays_d), noise, std, bool(white_bkgd))
+    f32 = lambda t: t.to(torch.float32).contiguous()        # (differentiable: z_vals / rays_d receive gradients when they require them)
+    return _Composite.apply(raw_c, f32(z_vals), f32(rays_d), noise, std, bool(white_bkgd))
 
 
 def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
@@ -565,7 +605,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                                   "frequencies, view directions) or both general ones (nerf_pytorch_amd.NeRF builds either)")
     if not dense and ray_batch.shape[-1] <= 8:
         raise ValueError("render_rays: these networks use view directions; the ray records need 11 columns (render(use_viewdirs=True))")
-    rays = ray_batch.to(torch.float32).contiguous().detach()
+    rays_grad = torch.is_grad_enabled() and ray_batch.requires_grad
+    if rays_grad and dense:
+        raise NotImplementedError("render_rays: gradients to rays / sample points / camera poses are implemented for the fused "
+                                  "NeRF architecture only, not for general (DenseNeRF) networks")
+    # rays that require grad stay in the graph (d loss / d ray records: nerf_field_input_grad + the compositing's |d| term)
+    rays = ray_batch.to(torch.float32).contiguous()
+    if not rays_grad:
+        rays = rays.detach()
     n = rays.shape[0]
     dev = rays.device
     n_f = int(N_importance)
@@ -636,7 +683,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     if n_f > 0 and not same:
         params = params + network_fine.param_list()
     # activations are saved only when a backward can follow (Function.forward itself always runs in no-grad mode)
-    cfg["need_grad"] = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    cfg["need_grad"] = torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for p in params))
     if cfg["precision"] == "fp16_fp8c" and cfg["need_grad"]:
         cfg["precision"] = "fp16x3"         # the reduced class is an inference form; gradients: the fp16x3 datapath, unchanged
     outs = _RenderRays.apply(cfg, rays, rnd, network_fn, None if (same or n_f <= 0) else network_fine, *params)
@@ -715,12 +762,18 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     """run_nerf.py:69-134: [rgb_map, disp_map, acc_map, extras].  With c2w the ray records are built by one HIP
     launch (get_rays + view directions + ndc_rays + near / far: SURVEY 8 f-2), no [H,W,3] intermediates."""
     # (use_viewdirs=False: the 11-column ray records are built all the same; networks without view directions ignore columns 8-10)
+    req = lambda t: isinstance(t, torch.Tensor) and t.requires_grad
+    geo_grad = torch.is_grad_enabled() and (req(c2w) or req(c2w_staticcam) or (rays is not None and any(req(t) for t in rays)))
+    if geo_grad and c2w is not None:
+        # a pose that requires grad: the reference's own torch ops (get_rays, normalise, ndc_rays) carry d loss / d c2w
+        rays = get_rays(H, W, K, c2w)
+        c2w = None
     if c2w is not None:
         net = kwargs.get("network_fn")
         dev = next(net.parameters()).device if net is not None else (c2w.device if isinstance(c2w, torch.Tensor) else None)
         rays = hb.make_rays(H, W, K, c2w, c2w_staticcam, ndc, near, far, dev)
         sh = (H, W, 3)
-    elif (c2w_staticcam is None and isinstance(rays[0], torch.Tensor) and rays[0].is_cuda
+    elif (not geo_grad and c2w_staticcam is None and isinstance(rays[0], torch.Tensor) and rays[0].is_cuda
           and isinstance(near, (int, float)) and isinstance(far, (int, float))):
         # one launch: view directions + NDC warp + near / far columns -> [N, 11] records (run_nerf.py:100-123)
         rays_o, rays_d = rays
