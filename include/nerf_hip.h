@@ -88,6 +88,28 @@ int nerf_assemble_rays(const float* rays_o, const float* rays_d, long n_rays, in
 int nerf_sample_ray_batch(int H, int W, const float* K_host, const float* pose, int pose_row_stride, const float* image, int h0,
                           int w0, int nh, int nw, int n_rand, unsigned key0, unsigned key1, float* batch_rays, float* target,
                           int* pixels /* nullable */, void* stream);
+/* ---- the use_batching mode of train() (run_nerf.py:676-726; additive in ABI v10): batch `batch` of one epoch over the (view, pixel)
+ * space of n_views training views.  The reference builds rays_rgb [V*H*W, 3, 3] once on the host, shuffles it and slices consecutive
+ * N_rand windows; here position p of the epoch is perm(p), the keyed bijection of nerf_sample_ray_batch applied to [0, V*H*W) and
+ * keyed by (key0, key1), one pair per epoch, and the batch is positions [batch*n_rand, min((batch+1)*n_rand, V*H*W)): the last batch of
+ * an epoch is short, as the reference's slice is.  Position q = v*H*W + j*W + i is pixel (j, i) of view view_ids[v].  Rays come from
+ * the pose table as it is at this launch (no precrop: the reference applies none in this mode).
+ *   view_ids: DEVICE int32 [n_views] indices into the tables (i_train); an index outside [0, n_table) reads nothing and yields NaN;
+ *   poses: DEVICE c2w, view t at poses + t*pose_view_stride, rows pose_row_stride floats apart ([N,3,4], [N,4,4] or a view of either);
+ *   images: DEVICE [H][W][3] fp32 per view, view t at images + t*image_view_stride; K_host: HOST 3x3.
+ * Writes B = min(n_rand, V*H*W - batch*n_rand) rays: batch_rays[2][B][3] = (rays_o, rays_d) as get_rays gives them, target[B][3],
+ * pixels[B] = j*W + i and views[B] = v (both nullable).  NERF_E_BADARG if V*H*W >= 2^32 or batch*n_rand >= V*H*W. */
+int nerf_sample_ray_views(int H, int W, const float* K_host, const int* view_ids, int n_views, int n_table, const float* poses,
+                          long pose_view_stride, int pose_row_stride, const float* images, long image_view_stride, int n_rand, long batch,
+                          unsigned key0, unsigned key1, float* batch_rays, float* target, int* pixels /* nullable */,
+                          int* views /* nullable */, void* stream);
+/* Adjoint of the ray set-up of nerf_sample_ray_batch / nerf_sample_ray_views w.r.t. the camera poses: from d_batch_rays[2][n_rays][3]
+ * (d rays_o, d rays_d), the pixels (j*W + i) and views (position in the view list; NULL = all rays belong to view 0, n_views = 1) of
+ * the same batch, d_pose[n_views][3][4] (accumulate ? += : =) with dR[a][b] = sum_k d_rd[k][a] dir_k[b] and dt[a] = sum_k d_ro[k][a],
+ * dir_k recomputed from the pixel with the forward's arithmetic.  Fixed-order sums, no atomics: bit-reproducible; a view without a ray
+ * gets exact zeros. */
+int nerf_ray_pose_grad(int W, const float* K_host, const float* d_batch_rays, int n_rays, const int* pixels, const int* views /* nullable */,
+                       int n_views, float* d_pose, int accumulate, void* stream);
 
 /* ---- network_query_fn(pts, viewdirs, network_fn) with pts = o + d*z
  * (run_nerf.py:381,385 -> run_network :37-51 -> Embedder :44-45 -> NeRF.forward helpers:96-119).

@@ -145,6 +145,34 @@ int nerf_sample_ray_batch(int H, int W, const float* K_host, const float* pose, 
                                                         batch_rays, target, pixels, (hipStream_t)stream));
 }
 
+int nerf_sample_ray_views(int H, int W, const float* K_host, const int* view_ids, int n_views, int n_table, const float* poses,
+                          long pose_view_stride, int pose_row_stride, const float* images, long image_view_stride, int n_rand, long batch,
+                          unsigned key0, unsigned key1, float* batch_rays, float* target, int* pixels, int* views, void* stream) {
+    REQUIRE(K_host && view_ids && poses && images && batch_rays && target, "null pointer");
+    REQUIRE(H > 0 && W > 0 && n_views > 0 && n_table > 0, "bad size");
+    const long long total = (long long)n_views * H * W;
+    REQUIRE(total < (1LL << 32), "the (view, pixel) space V*H*W must stay below 2^32");
+    REQUIRE(n_rand > 0 && batch >= 0 && (long long)batch * n_rand < total, "batch * n_rand must lie inside the epoch's V*H*W positions");
+    REQUIRE(pose_row_stride >= 4 && pose_view_stride >= 3L * pose_row_stride, "pose rows are at least 4 floats apart, views at least 3 rows");
+    REQUIRE(image_view_stride >= 3L * H * W, "images are at least H*W*3 floats apart");
+    REQUIRE(K_host[0] != 0.0f && K_host[4] != 0.0f, "K has a zero focal length");
+    const long long first = (long long)batch * n_rand;
+    const unsigned n_out = (unsigned)(total - first < n_rand ? total - first : n_rand);
+    return done(__func__, nerf::launch_sample_ray_views(H, W, K_host, view_ids, n_views, n_table, poses, pose_view_stride, pose_row_stride,
+                                                        images, image_view_stride, (unsigned)first, n_out, key0, key1, batch_rays, target,
+                                                        pixels, views, (hipStream_t)stream));
+}
+
+int nerf_ray_pose_grad(int W, const float* K_host, const float* d_batch_rays, int n_rays, const int* pixels, const int* views,
+                       int n_views, float* d_pose, int accumulate, void* stream) {
+    REQUIRE(K_host && d_pose && (n_rays == 0 || (d_batch_rays && pixels)), "null pointer");
+    REQUIRE(W > 0 && n_rays >= 0 && n_views > 0, "bad size");
+    REQUIRE(views || n_views == 1, "views = NULL means one view (n_views = 1)");
+    REQUIRE(K_host[0] != 0.0f && K_host[4] != 0.0f, "K has a zero focal length");
+    return done(__func__, nerf::launch_ray_pose_grad(W, K_host, d_batch_rays, n_rays, pixels, views, n_views, d_pose, accumulate,
+                                                     (hipStream_t)stream));
+}
+
 int nerf_sample_coarse(const float* rays, int ray_stride, int n_rays, const float* t_vals, int n_samples,
                        int lindisp, const float* t_rand, float* z_vals, void* stream) {
     REQUIRE(rays && t_vals && z_vals, "null pointer");

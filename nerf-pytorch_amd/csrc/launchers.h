@@ -79,6 +79,12 @@ hipError_t launch_assemble_rays(const float* rays_o, const float* rays_d, long n
 hipError_t launch_sample_ray_batch(int H, int W, const float* K9, const float* pose_dev, int pose_stride, const float* image, int h0, int w0,
                                    int nh, int nw, int n_rand, unsigned key0, unsigned key1, float* rays, float* target, int* pixels,
                                    hipStream_t stream);
+hipError_t launch_sample_ray_views(int H, int W, const float* K9, const int* view_ids, int n_views, int n_table, const float* poses,
+                                   long pose_view_stride, int pose_row_stride, const float* images, long image_view_stride,
+                                   unsigned first, unsigned n_out, unsigned key0, unsigned key1, float* rays, float* target, int* pixels,
+                                   int* views, hipStream_t stream);
+hipError_t launch_ray_pose_grad(int W, const float* K9, const float* d_rays, int n_rays, const int* pixels, const int* views, int n_views,
+                                float* d_pose, int accumulate, hipStream_t stream);
 hipError_t launch_composite(const CompositeArgs& a, bool bwd, hipStream_t stream);
 hipError_t launch_sample_fine(const FineArgs& a, hipStream_t stream);
 hipError_t launch_field_fwd(const float* packed, const float* rays, int ray_stride, const float* z_vals,

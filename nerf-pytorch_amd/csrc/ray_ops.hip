@@ -201,6 +201,126 @@ hipError_t launch_sample_ray_batch(int H, int W, const float* K9, const float* p
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ multi-view ray batches (use_batching, run_nerf.py:676-726)
+// The reference builds rays_rgb [V*H*W, 3, 3] once on the host, shuffles it, and slices consecutive N_rand windows.  Here position p
+// of epoch e is perm_e(p), the same keyed bijection applied to the (view, pixel) space [0, V*H*W) and keyed per epoch; batch b is
+// positions [b*n_rand, min((b+1)*n_rand, V*H*W)).  Rays come from the pose table AS IT IS at this launch (poses may change every step).
+struct RayViewsArgs {
+    int H, W, n_views, n_table, half_bits;
+    unsigned first, n_out, total, key0, key1;
+    float fx, fy, cx, cy;
+    const int* view_ids;                    // [n_views] indices into the tables (i_train)
+    const float* poses; long pose_view_stride; int pose_row_stride;
+    const float* images; long image_view_stride;   // [.][H][W][3], views image_view_stride floats apart
+    float* rays;                            // [2][n_out][3]
+    float* target;                          // [n_out][3]
+    int* pixels;                            // [n_out] j * W + i (nullable)
+    int* views;                             // [n_out] position in view_ids (nullable)
+};
+__global__ void sample_ray_views_kernel(RayViewsArgs a) {
+    const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n_out) return;
+    const unsigned q = keyed_perm(a.first + k, a.total, a.half_bits, a.key0, a.key1);
+    const unsigned hw = (unsigned)a.H * (unsigned)a.W;
+    const unsigned v = q / hw, pix = q - v * hw;
+    const int jj = (int)(pix / (unsigned)a.W), ii = (int)(pix % (unsigned)a.W);
+    const int t = a.view_ids[v];
+    const long ko = (long)k, no = (long)a.n_out;
+    float o[3], d[3], c[3];
+    if (t >= 0 && t < a.n_table) {
+        const float* P = a.poses + (long)t * a.pose_view_stride;
+        float m[12];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) m[4 * r + cc] = P[(long)r * a.pose_row_stride + cc];
+        const float dx = ((float)ii - a.cx) / a.fx, dy = -((float)jj - a.cy) / a.fy, dz = -1.0f;
+        camera_ray(m, dx, dy, dz, o, d);
+        const float* px = a.images + (long)t * a.image_view_stride + ((long)jj * a.W + ii) * 3;
+        c[0] = px[0]; c[1] = px[1]; c[2] = px[2];
+    } else {        // a view index outside the tables: no read, NaN rays and colours
+        for (int e = 0; e < 3; ++e) o[e] = d[e] = c[e] = __int_as_float(0x7fc00000);
+    }
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        a.rays[ko * 3 + e] = o[e];
+        a.rays[(no + ko) * 3 + e] = d[e];
+        a.target[ko * 3 + e] = c[e];
+    }
+    if (a.pixels) a.pixels[k] = (int)pix;
+    if (a.views) a.views[k] = (int)v;
+}
+hipError_t launch_sample_ray_views(int H, int W, const float* K9, const int* view_ids, int n_views, int n_table, const float* poses,
+                                   long pose_view_stride, int pose_row_stride, const float* images, long image_view_stride,
+                                   unsigned first, unsigned n_out, unsigned key0, unsigned key1, float* rays, float* target, int* pixels,
+                                   int* views, hipStream_t stream) {
+    if (n_out == 0) return hipSuccess;
+    RayViewsArgs a{};
+    a.H = H; a.W = W; a.n_views = n_views; a.n_table = n_table;
+    a.total = (unsigned)((unsigned long long)n_views * (unsigned long long)H * (unsigned long long)W);
+    a.half_bits = 1;
+    while ((1ull << (2 * a.half_bits)) < (unsigned long long)a.total) ++a.half_bits;
+    a.first = first; a.n_out = n_out; a.key0 = key0; a.key1 = key1;
+    a.fx = K9[0]; a.cx = K9[2]; a.fy = K9[4]; a.cy = K9[5];
+    a.view_ids = view_ids; a.poses = poses; a.pose_view_stride = pose_view_stride; a.pose_row_stride = pose_row_stride;
+    a.images = images; a.image_view_stride = image_view_stride;
+    a.rays = rays; a.target = target; a.pixels = pixels; a.views = views;
+    hipLaunchKernelGGL(sample_ray_views_kernel, dim3((n_out + 255u) / 256u), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ adjoint of the ray set-up w.r.t. the camera poses
+// rays_o = c2w[:3, 3], rays_d[a] = sum_b dir[b] c2w[a][b]  =>  dR[a][b] = sum_k d_rd[k][a] dir_k[b], dt[a] = sum_k d_ro[k][a].
+// One block per view: every thread walks the rays k = tid, tid + 256, ... in order and keeps the 12 sums of the rays of ITS block's
+// view, then the block adds the 256 partial sums in a fixed tree: no atomics, bit-reproducible, and a view without a ray gets exact
+// zeros.  dir_k is recomputed from the pixel id with the forward's arithmetic.
+constexpr int POSE_GRAD_THREADS = 256;
+__global__ __launch_bounds__(POSE_GRAD_THREADS) void ray_pose_grad_kernel(int W, float fx, float fy, float cx, float cy,
+                                                                          const float* __restrict__ d_rays, int n_rays,
+                                                                          const int* __restrict__ pixels, const int* __restrict__ views,
+                                                                          float* __restrict__ d_pose, int accumulate) {
+    __shared__ float red[12][POSE_GRAD_THREADS];
+    const int v = blockIdx.x, tid = threadIdx.x;
+    float s[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) s[e] = 0.0f;
+    for (int k = tid; k < n_rays; k += POSE_GRAD_THREADS) {
+        if (views && views[k] != v) continue;
+        const int pix = pixels[k];
+        const int jj = pix / W, ii = pix - jj * W;
+        const float dir[3] = {((float)ii - cx) / fx, -((float)jj - cy) / fy, -1.0f};
+        const float* gro = d_rays + (long)k * 3;
+        const float* grd = d_rays + ((long)n_rays + k) * 3;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const float g = grd[r];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s[4 * r + c] += g * dir[c];
+            s[4 * r + 3] += gro[r];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 12; ++e) red[e][tid] = s[e];
+    __syncthreads();
+    for (int w = POSE_GRAD_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w)
+#pragma unroll
+            for (int e = 0; e < 12; ++e) red[e][tid] += red[e][tid + w];
+        __syncthreads();
+    }
+    if (tid < 12) {
+        float* out = d_pose + (long)v * 12 + tid;
+        *out = accumulate ? *out + red[tid][0] : red[tid][0];
+    }
+}
+hipError_t launch_ray_pose_grad(int W, const float* K9, const float* d_rays, int n_rays, const int* pixels, const int* views, int n_views,
+                                float* d_pose, int accumulate, hipStream_t stream) {
+    if (n_views <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ray_pose_grad_kernel, dim3((unsigned)n_views), dim3(POSE_GRAD_THREADS), 0, stream, W, K9[0], K9[4], K9[2], K9[5],
+                       d_rays, n_rays, pixels, views, d_pose, accumulate);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ launchers
 // ------------------------------------------------------------------ img2mse (run_nerf_helpers.py:11) and its gradient
 // mean((x - y)^2) over n elements in ONE launch, deterministic: every block sums its contiguous slice in a fixed tree, writes its

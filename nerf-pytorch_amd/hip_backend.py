@@ -81,6 +81,8 @@ def _declare(lib):
         "nerf_field_input_grad": (i, [p, p, p, i, p, i, i, p, i, p]),
         "nerf_raw2outputs_bwd_geom": (i, [p, p, p, i, i, i, p, f, i, p, p, p, p, p, p, p, p, p]),
         "nerf_embed_bwd": (i, [p, l, i, p, p, i, p]),
+        "nerf_sample_ray_views": (i, [i, i, p, p, i, i, p, l, i, p, l, i, l, ctypes.c_uint, ctypes.c_uint, p, p, p, p, p]),
+        "nerf_ray_pose_grad": (i, [i, p, p, i, p, p, i, p, i, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError here = header / library mismatch: fail loudly
@@ -99,7 +101,8 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_adam_step",
            "nerf_render_workspace_floats", "nerf_render_rays_fwd", "nerf_render_rays_bwd", "nerf_render_infer_supported",
            "nerf_render_rays_infer", "nerf_mse_scratch_floats", "nerf_mse_fwd", "nerf_mse_bwd", "nerf_build_inputs", "nerf_dense_fwd", "nerf_dense_dgrad", "nerf_dense_wgrad_scratch_floats",
-           "nerf_dense_wgrad", "nerf_range_scan", "nerf_field_input_grad", "nerf_raw2outputs_bwd_geom", "nerf_embed_bwd"]
+           "nerf_dense_wgrad", "nerf_range_scan", "nerf_field_input_grad", "nerf_raw2outputs_bwd_geom", "nerf_embed_bwd",
+           "nerf_sample_ray_views", "nerf_ray_pose_grad"]
 
 
 def lib():
@@ -374,6 +377,66 @@ def sample_ray_batch(H, W, K, pose, image, n_rand, window, key, want_pixels=Fals
                                        _ptr(rays), _ptr(target), pix.data_ptr() if pix is not None else None, _stream()),
            "nerf_sample_ray_batch")
     return (rays, target, pix) if want_pixels else (rays, target)
+
+
+def _host_K(K):
+    import numpy as np
+    return np.ascontiguousarray(np.asarray(K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else K, dtype=np.float32)[:3, :3])
+
+
+def _iptr(t, name, optional=False):
+    if t is None and optional:
+        return None
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise NerfHipError(f"{name} must be a contiguous int32 tensor on the GPU")
+    return t.data_ptr()
+
+
+def sample_ray_views(H, W, K, view_ids, poses, images, n_rand, batch, key, want_pixels=False, want_views=False):
+    """nerf_sample_ray_views: batch `batch` (B = min(n_rand, V*H*W - batch*n_rand) rays) of the epoch keyed by `key` over the
+    (view, pixel) space of view_ids (device int32 [V], indices into poses [N, 3+, 4] and images [N, H, W, 3]).
+    Returns (batch_rays [2, B, 3], target [B, 3], pixels [B] or None, views [B] or None)."""
+    Kh = _host_K(K)
+    if not (isinstance(poses, torch.Tensor) and poses.is_cuda and poses.dtype == torch.float32 and poses.dim() == 3 and poses.shape[1] >= 3
+            and poses.shape[2] >= 4 and poses.stride(2) == 1):
+        raise NerfHipError("sample_ray_views: poses must be a float32 [N, 3+, 4] device tensor with contiguous rows")
+    if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.float32 and images.dim() == 4
+            and tuple(images.shape[1:]) == (H, W, 3) and images.shape[0] == poses.shape[0] and images[0].is_contiguous()):
+        raise NerfHipError("sample_ray_views: images must be a float32 [N, H, W, 3] device tensor with contiguous views, N = len(poses)")
+    V = view_ids.numel()
+    total = V * H * W
+    n_out = min(int(n_rand), total - int(batch) * int(n_rand))
+    if n_out <= 0:
+        raise NerfHipError("sample_ray_views: batch lies past the end of the epoch")
+    dev = images.device
+    rays = torch.empty((2, n_out, 3), dtype=torch.float32, device=dev)
+    target = torch.empty((n_out, 3), dtype=torch.float32, device=dev)
+    pix = torch.empty((n_out,), dtype=torch.int32, device=dev) if want_pixels else None
+    vw = torch.empty((n_out,), dtype=torch.int32, device=dev) if want_views else None
+    _check(lib().nerf_sample_ray_views(int(H), int(W), Kh.ctypes.data_as(ctypes.c_void_p), _iptr(view_ids, "view_ids"), V, poses.shape[0],
+                                       poses.data_ptr(), int(poses.stride(0)), int(poses.stride(1)), images.data_ptr(),
+                                       int(images.stride(0)), int(n_rand), int(batch), int(key[0]) & 0xffffffff, int(key[1]) & 0xffffffff,
+                                       _ptr(rays), _ptr(target), None if pix is None else pix.data_ptr(), None if vw is None else vw.data_ptr(),
+                                       _stream()), "nerf_sample_ray_views")
+    return rays, target, pix, vw
+
+
+def ray_pose_grad(W, K, d_rays, pixels, views, n_views, d_pose=None, accumulate=False):
+    """nerf_ray_pose_grad: d_pose [n_views, 3, 4] (+)= d loss / d c2w[:3, :4] of each view from d_rays [2, B, 3] (views None: one view)."""
+    Kh = _host_K(K)
+    d_rays = d_rays.contiguous()
+    n = d_rays.shape[1]
+    if not (d_rays.dim() == 3 and d_rays.shape[0] == 2 and d_rays.shape[2] == 3 and pixels.numel() == n
+            and (views is None or views.numel() == n)):
+        raise NerfHipError("ray_pose_grad: d_rays must be [2, B, 3], pixels (and views) [B]")
+    if d_pose is None:
+        d_pose = torch.empty((n_views, 3, 4), dtype=torch.float32, device=d_rays.device)
+    elif d_pose.numel() != 12 * n_views:
+        raise NerfHipError("ray_pose_grad: d_pose must be [n_views, 3, 4]")
+    _check(lib().nerf_ray_pose_grad(int(W), Kh.ctypes.data_as(ctypes.c_void_p), _ptr(d_rays, "d_rays"), n, _iptr(pixels, "pixels"),
+                                    _iptr(views, "views", optional=True), int(n_views), _ptr(d_pose, "d_pose"), int(bool(accumulate)),
+                                    _stream()), "nerf_ray_pose_grad")
+    return d_pose
 
 
 def _dp(precision):
