@@ -386,6 +386,45 @@ int nerf_raw2outputs_bwd_geom(const float* raw, const float* z_vals, const float
  * as nerf_field_input_grad (sin / cos of the exact 2^k x). */
 int nerf_embed_bwd(const float* x, long n_pts, int n_freqs, const float* d_out, float* d_x, int accumulate, void* stream);
 
+/* ---- occupancy grid: empty-space skipping for rendering without gradients (additive in ABI v10; csrc/occupancy.hip).  The reference
+ * pushes every sample point of render_rays through the network (run_nerf.py:381-385, :397-401); with a grid only the points in
+ * occupied cells are evaluated and every other sample gets raw = (0, 0, 0, 0), i.e. relu(sigma) = 0, alpha = 0, weight 0 (:293).
+ *   The grid is an axis-aligned box in the space of the points o + d z the network sees (NDC space for ndc rays), res[0] x res[1] x
+ * res[2] cells (1..512 each), one bit per cell: cell (ix, iy, iz) has linear index c = (ix res[1] + iy) res[2] + iz, word c >> 5, bit
+ * c & 31 of `bits` (DEVICE, (cells + 31) / 32 words).  Classification of a point p, per axis a: t = (p[a] - lo[a]) * scale[a] -- one
+ * fp32 subtraction, one fp32 multiplication, not contracted --, scale[a] = fp32(res[a] / (hi[a] - lo[a])) computed by the host in
+ * double; inside iff 0 <= t < res[a] on all three axes (a NaN is outside), cell index floor(t).  A point outside the box counts as
+ * occupied (outside_skip == 0: the grid never hides what it does not cover) or as empty (outside_skip != 0). */
+typedef struct NerfOccGrid {
+    float lo[3];
+    float scale[3];
+    int res[3];
+    int outside_skip;
+    const unsigned* bits;
+} NerfOccGrid;
+/* int32 words of scratch nerf_occ_compact needs for n_points = n_rays * n_samples points (its per-block counts) */
+size_t nerf_occ_scratch_words(long n_points);
+/* Classify the n_rays * n_samples points o + d z (one fp32 multiply, one fp32 add: run_nerf.py:381) of rays[n_rays][ray_stride] /
+ * z_vals[n_rays][n_samples] and compact the occupied ones:
+ *   slot[n_rays * n_samples] (int32) = position of the point in the compacted list, or -1;
+ *   records[M][11] = (pt3, 0, 0, 0, 0, 0, viewdir3 of the owning ray) in stable ray-major, sample-minor order: n_samples = 1 ray
+ *                    records whose depth is 0, evaluated by nerf_field_fwd / nerf_field_fwd_split(n_rays = M, n_samples = 1) with M
+ *                    zero depths (o + 0 * 0 == pt exactly); the caller provides room for n_rays * n_samples records;
+ *   count[0] = M (one int32 DEVICE word).
+ * Three launches -- counts per block of 1024 points, exclusive scan, write -- no atomics: the same inputs give the same list.
+ * Moves 8 B per point (z twice) + 4 B (slot) + 44 B per occupied point.  ray_stride >= 11; fewer than 2^31 - 1024 points per call. */
+int nerf_occ_compact(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* z_vals, int n_rays, int n_samples,
+                     int* slot, float* records, int* count, int* scratch, void* stream);
+/* raw[p] = slot[p] >= 0 ? raw_c[slot[p]] : (0, 0, 0, 0) for n_points points of 4 floats (16-byte accesses; raw_c and raw 16-byte
+ * aligned; raw_c is not read when no slot is >= 0).  20 B per point + 16 B per occupied point. */
+int nerf_occ_expand(const int* slot, const float* raw_c, long n_points, float* raw, void* stream);
+/* Grid bits from densities: sigma[n_cells][samples_per_cell] (cell-major) -> bit c of words is set iff any of cell c's values
+ * exceeds threshold (a NaN does not); every word of (n_cells + 31) / 32 is written once, whole.  A slice of a grid starting at a cell
+ * index that is a multiple of 32 is marked by passing words + first_cell / 32. */
+int nerf_occ_mark(const float* sigma, long n_cells, int samples_per_cell, float threshold, unsigned* words, void* stream);
+/* bits_out = 3x3x3 OR of bits_in (neighbours beyond the faces do not exist); two different buffers of the grid's size. */
+int nerf_occ_dilate(const unsigned* bits_in, int rx, int ry, int rz, unsigned* bits_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,11 @@ def _declare(lib):
         "nerf_embed_bwd": (i, [p, l, i, p, p, i, p]),
         "nerf_sample_ray_views": (i, [i, i, p, p, i, i, p, l, i, p, l, i, l, ctypes.c_uint, ctypes.c_uint, p, p, p, p, p]),
         "nerf_ray_pose_grad": (i, [i, p, p, i, p, p, i, p, i, p]),
+        "nerf_occ_scratch_words": (sz, [l]),
+        "nerf_occ_compact": (i, [p, p, i, p, i, i, p, p, p, p, p]),
+        "nerf_occ_expand": (i, [p, p, l, p, p]),
+        "nerf_occ_mark": (i, [p, l, i, f, p, p]),
+        "nerf_occ_dilate": (i, [p, i, i, i, p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError here = header / library mismatch: fail loudly
@@ -102,7 +107,8 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_render_workspace_floats", "nerf_render_rays_fwd", "nerf_render_rays_bwd", "nerf_render_infer_supported",
            "nerf_render_rays_infer", "nerf_mse_scratch_floats", "nerf_mse_fwd", "nerf_mse_bwd", "nerf_build_inputs", "nerf_dense_fwd", "nerf_dense_dgrad", "nerf_dense_wgrad_scratch_floats",
            "nerf_dense_wgrad", "nerf_range_scan", "nerf_field_input_grad", "nerf_raw2outputs_bwd_geom", "nerf_embed_bwd",
-           "nerf_sample_ray_views", "nerf_ray_pose_grad"]
+           "nerf_sample_ray_views", "nerf_ray_pose_grad",
+           "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate"]
 
 
 def lib():
@@ -1015,6 +1021,77 @@ def _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partia
     with _timed("wgrad_reduce_kernel", 0.0, 4.0 * N_PARAMS * (n_chunks + 1)):
         _check(L.nerf_field_wgrad_phase(*args, 4, *tail), "nerf_field_wgrad_phase")
     return grad
+
+
+# ---- occupancy grid (csrc/occupancy.hip; the user-facing object is occupancy.OccupancyGrid)
+class NerfOccGrid(ctypes.Structure):
+    """include/nerf_hip.h NerfOccGrid"""
+    _fields_ = [("lo", ctypes.c_float * 3), ("scale", ctypes.c_float * 3), ("res", ctypes.c_int * 3), ("outside_skip", ctypes.c_int),
+                ("bits", ctypes.c_void_p)]
+
+
+def _words(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise NerfHipError(f"{name} must be a contiguous int32 tensor on the GPU")
+    return t.data_ptr()
+
+
+def occ_desc(lo, scale, res, outside_skip, bits):
+    """the NerfOccGrid descriptor of a grid whose bit words are the int32 device tensor `bits`"""
+    n_words = (int(res[0]) * int(res[1]) * int(res[2]) + 31) // 32
+    if bits.numel() != n_words:
+        raise NerfHipError(f"occupancy grid {tuple(res)} needs {n_words} words, got {bits.numel()}")
+    return NerfOccGrid((ctypes.c_float * 3)(*[float(v) for v in lo]), (ctypes.c_float * 3)(*[float(v) for v in scale]),
+                       (ctypes.c_int * 3)(*[int(v) for v in res]), int(bool(outside_skip)), _words(bits, "bits"))
+
+
+def occ_compact(desc, rays, z_vals, slot=None, records=None):
+    """nerf_occ_compact: (slot int32 [n * S], records fp32 [n * S, 11] of which the first M rows are written, count int32 [1] = M on
+    the device).  slot / records: flat fp32 scratch of at least n * S / 11 n * S words (hb.WORKSPACE leases) or None (allocated)."""
+    n, stride = rays.shape
+    S = z_vals.shape[1]
+    P = n * S
+    dev = rays.device
+    L = lib()
+    slot = torch.empty(max(P, 1), dtype=torch.int32, device=dev) if slot is None else slot[:max(P, 1)].view(torch.int32)
+    records = (torch.empty(max(P, 1) * 11, dtype=torch.float32, device=dev) if records is None else records[:max(P, 1) * 11]).view(-1, 11)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    scratch = WORKSPACE.take(max(L.nerf_occ_scratch_words(P), 1), dev)
+    try:
+        with _timed("occ_compact (count + scan + write)", 0.0, 12.0 * P):
+            _check(L.nerf_occ_compact(ctypes.byref(desc), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"), n, S, slot.data_ptr(),
+                                      _ptr(records, "records"), count.data_ptr(), scratch.data_ptr(), _stream()), "nerf_occ_compact")
+    finally:        # stream-ordered, like every lease
+        WORKSPACE.give(scratch)
+    return slot[:P], records, count
+
+
+def occ_expand(slot, raw_c, raw):
+    """nerf_occ_expand: raw [..., 4] (preallocated, contiguous) <- raw_c rows by slot, zeros where slot < 0"""
+    P = slot.numel()
+    if raw.numel() != 4 * P:
+        raise NerfHipError("occ_expand: raw must hold 4 floats per slot")
+    with _timed("occ_expand_kernel", 0.0, 20.0 * P):
+        _check(lib().nerf_occ_expand(_words(slot, "slot"), _ptr(raw_c, "raw_c"), P, _ptr(raw, "raw"), _stream()), "nerf_occ_expand")
+    return raw
+
+
+def occ_mark(sigma, samples_per_cell, threshold, words):
+    """nerf_occ_mark: words (int32 view of the grid's bits, or of a slice of it that starts at a multiple of 32 cells) from sigma
+    [n_cells * samples_per_cell]"""
+    n_cells = sigma.numel() // int(samples_per_cell)
+    if words.numel() != (n_cells + 31) // 32:
+        raise NerfHipError("occ_mark: one word per 32 cells")
+    _check(lib().nerf_occ_mark(_ptr(sigma, "sigma"), n_cells, int(samples_per_cell), float(threshold), _words(words, "words"), _stream()),
+           "nerf_occ_mark")
+    return words
+
+
+def occ_dilate(bits, res):
+    """nerf_occ_dilate: the 3x3x3 OR of a grid's bit words, as a new tensor"""
+    out = torch.empty_like(bits)
+    _check(lib().nerf_occ_dilate(_words(bits, "bits"), int(res[0]), int(res[1]), int(res[2]), _words(out, "out"), _stream()), "nerf_occ_dilate")
+    return out
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

@@ -1,0 +1,182 @@
+"""Occupancy grid: empty-space skipping for rendering without gradients.
+
+The reference evaluates the network at every sample point of render_rays (run_nerf.py:381-385, :397-401), the points of a trained
+scene that lie in empty space included.  ``OccupancyGrid`` is one bit per cell of an axis-aligned box; handed to
+``render_rays(..., occupancy=grid)`` (or put into ``render_kwargs_test["occupancy"]``) only the sample points in occupied cells go
+through the network, every other sample gets ``raw = (0, 0, 0, 0)`` -- ``relu(sigma) = 0``, ``alpha = 0``, weight 0 -- and nothing
+else of render_rays changes.  Device code: csrc/occupancy.hip (include/nerf_hip.h, "occupancy grid").
+"""
+import numpy as np
+import torch
+
+from . import hip_backend as hb
+
+_OUTSIDE = ("evaluate", "skip")
+_SLICE_CELLS = 1 << 20      # cells per evaluation slice of from_network (a multiple of 32: slices start on word boundaries)
+
+
+def _res3(resolution):
+    r = (resolution,) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(v) for v in resolution)
+    if len(r) != 3 or any(v < 1 or v > 512 for v in r):
+        raise ValueError(f"OccupancyGrid: resolution must be an int or three ints between 1 and 512, got {resolution!r}")
+    return tuple(int(v) for v in r)
+
+
+def _pack_bits(mask_flat):
+    """bool [n_cells] -> int32 [(n_cells + 31) // 32]: cell c is bit c & 31 of word c >> 5 (the tail of the last word stays 0)"""
+    n = mask_flat.numel()
+    pad = (-n) % 32
+    m = torch.cat([mask_flat.to(torch.int64), torch.zeros(pad, dtype=torch.int64, device=mask_flat.device)]).view(-1, 32)
+    w = (m << torch.arange(32, dtype=torch.int64, device=m.device)).sum(-1)
+    return torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
+
+
+def _unpack_bits(words, n_cells):
+    w = words.to(torch.int64) & 0xffffffff
+    return (((w[:, None] >> torch.arange(32, dtype=torch.int64, device=w.device)) & 1).reshape(-1)[:n_cells]).bool()
+
+
+class OccupancyGrid:
+    """One bit per cell of the axis-aligned box [lo, hi] at resolution (Rx, Ry, Rz) (an int means cubic; 1..512 per axis), in the
+    space of the points ``o + d z`` the network sees -- for ``ndc=True`` rays that is NDC space.
+
+    Cell (ix, iy, iz) has linear index c = (ix Ry + iy) Rz + iz and lives in bit c & 31 of the 32-bit word c >> 5 of ``bits``.
+    A point p is classified per axis by t = (p - lo) * scale in fp32 (one subtraction, one multiplication), scale = fp32(R / (hi -
+    lo)) computed once in float64; it is inside iff 0 <= t < R on all axes (a NaN is outside) and then belongs to cell floor(t).
+    ``occupied(pts)`` is that rule in plain torch and is the definition the kernels reproduce bit for bit.
+    ``outside="evaluate"`` (default): a point outside the box is evaluated -- the grid never hides what it does not cover;
+    ``outside="skip"``: it is skipped (scenes bounded by the box).  A new grid is all-occupied.
+    ``last_stats`` = {"evaluated", "total"}: sample points sent through the network / of the passes, for the last render_rays (or
+    batchify_rays / render: summed over its chunks) call that used this grid."""
+
+    def __init__(self, lo, hi, resolution, outside="evaluate", device=None):
+        if outside not in _OUTSIDE:
+            raise ValueError(f"OccupancyGrid: outside must be one of {_OUTSIDE}")
+        self.resolution = _res3(resolution)
+        self.outside = outside
+        self._set_box(lo, hi)
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        self.bits = _pack_bits(torch.ones(self.n_cells, dtype=torch.bool, device=device))
+        self.last_stats = None
+
+    def _set_box(self, lo, hi):
+        as3 = lambda v: np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float32).reshape(3)
+        self.lo, self.hi = as3(lo), as3(hi)
+        if not np.all(self.hi > self.lo):       # (also refuses NaN)
+            raise ValueError("OccupancyGrid: hi must exceed lo on every axis")
+        r = np.asarray(self.resolution, dtype=np.float64)
+        self.scale = (r / (self.hi.astype(np.float64) - self.lo.astype(np.float64))).astype(np.float32)
+
+    # ------------------------------------------------------------------ plain properties
+    @property
+    def n_cells(self):
+        return self.resolution[0] * self.resolution[1] * self.resolution[2]
+
+    @property
+    def device(self):
+        return self.bits.device
+
+    def to(self, device):
+        self.bits = self.bits.to(device)
+        return self
+
+    # ------------------------------------------------------------------ masks
+    @classmethod
+    def from_mask(cls, mask, lo, hi, outside="evaluate", device=None):
+        """grid whose cell (ix, iy, iz) is occupied iff mask[ix, iy, iz] (bool [Rx, Ry, Rz])"""
+        mask = torch.as_tensor(mask)
+        if mask.dim() != 3:
+            raise ValueError("OccupancyGrid.from_mask: mask must be [Rx, Ry, Rz]")
+        g = cls(lo, hi, tuple(mask.shape), outside, device)
+        g.bits = _pack_bits(mask.to(g.device).bool().reshape(-1))
+        return g
+
+    def to_mask(self):
+        return _unpack_bits(self.bits, self.n_cells).view(self.resolution)
+
+    def fraction_occupied(self):
+        return float(self.to_mask().float().mean())
+
+    # ------------------------------------------------------------------ the definition
+    def occupied(self, pts):
+        """bool [...] for pts [..., 3] (any device): whether a sample at that point is evaluated"""
+        dev = pts.device
+        f = lambda a: torch.tensor(a, dtype=torch.float32, device=dev)
+        t = (pts.to(torch.float32) - f(self.lo)) * f(self.scale)
+        rx, ry, rz = self.resolution
+        inside = ((t >= 0) & (t < f(np.asarray(self.resolution, dtype=np.float32)))).all(-1)
+        i = torch.floor(torch.where(inside[..., None], t, torch.zeros_like(t))).to(torch.int64)
+        c = (i[..., 0] * ry + i[..., 1]) * rz + i[..., 2]
+        bits = self.bits if self.bits.device == dev else self.bits.to(dev)
+        bit = ((bits[c >> 5].to(torch.int64) >> (c & 31)) & 1).bool()
+        return torch.where(inside, bit, torch.full_like(bit, self.outside == "evaluate"))
+
+    # ------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        return {"lo": torch.tensor(self.lo), "hi": torch.tensor(self.hi), "resolution": torch.tensor(self.resolution, dtype=torch.int64),
+                "outside": self.outside, "bits": self.bits.detach().cpu().clone()}
+
+    def load_state_dict(self, state):
+        res = _res3(tuple(int(v) for v in state["resolution"]))
+        bits = torch.as_tensor(state["bits"]).to(torch.int32)
+        if bits.numel() != (res[0] * res[1] * res[2] + 31) // 32:
+            raise ValueError("OccupancyGrid.load_state_dict: `bits` does not match `resolution`")
+        if state["outside"] not in _OUTSIDE:
+            raise ValueError(f"OccupancyGrid.load_state_dict: outside must be one of {_OUTSIDE}")
+        self.resolution, self.outside = res, state["outside"]
+        self._set_box(state["lo"], state["hi"])
+        self.bits = bits.to(self.device).contiguous().clone()
+        return self
+
+    # ------------------------------------------------------------------ building a grid from a trained network
+    def cell_points(self, first, last, samples_per_cell=1, generator=None):
+        """[last - first, K, 3] fp32 on the grid's device: sample 0 of every cell first <= c < last is its centre, the other K - 1 are
+        uniform in the cell (drawn from `generator`)"""
+        dev = self.device
+        rx, ry, rz = self.resolution
+        c = torch.arange(first, last, dtype=torch.int64, device=dev)
+        idx = torch.stack([c // (ry * rz), (c // rz) % ry, c % rz], -1).to(torch.float64)
+        K = int(samples_per_cell)
+        off = torch.full((c.numel(), K, 3), 0.5, dtype=torch.float64, device=dev)
+        if K > 1:
+            gdev = generator.device if generator is not None else dev
+            off[:, 1:] = torch.rand((c.numel(), K - 1, 3), generator=generator, device=gdev, dtype=torch.float64).to(dev)
+        lo = torch.tensor(self.lo.astype(np.float64), device=dev)
+        width = torch.tensor((self.hi.astype(np.float64) - self.lo.astype(np.float64)) / np.asarray(self.resolution, dtype=np.float64), device=dev)
+        return (lo + (idx[:, None, :] + off) * width).to(torch.float32)
+
+    @classmethod
+    def from_network(cls, model, lo, hi, resolution, sigma_threshold=0.0, samples_per_cell=1, dilate=1, generator=None):
+        """Grid of a trained network: cell c is occupied iff raw[..., 3] (the density before the ReLU) exceeds sigma_threshold at the
+        cell's centre or at one of samples_per_cell - 1 uniform points in the cell; then `dilate` rounds of the 3x3x3 OR (a margin of
+        one cell per round for what the point samples miss).  The network is evaluated through query_points in slices, with one fixed
+        view direction (the density does not depend on it: run_nerf_helpers.py:107-108).  Pass the network that renders the final image
+        (network_fine) -- or OR two grids' masks.  Fused NeRF modules only."""
+        from .field import NeRF
+        from .render import query_points
+        if not isinstance(model, NeRF):
+            raise NotImplementedError("OccupancyGrid.from_network: a fused-kernel NeRF module is required (not a DenseNeRF / other module)")
+        dev = next(model.parameters()).device
+        g = cls(lo, hi, resolution, device=dev)
+        K = int(samples_per_cell)
+        if K < 1 or dilate < 0:
+            raise ValueError("OccupancyGrid.from_network: samples_per_cell >= 1 and dilate >= 0")
+        bits = torch.empty_like(g.bits)
+        with torch.no_grad():
+            for first in range(0, g.n_cells, _SLICE_CELLS):
+                last = min(first + _SLICE_CELLS, g.n_cells)
+                pts = g.cell_points(first, last, K, generator).reshape(-1, 3)
+                vd = torch.tensor([0.0, 0.0, 1.0], device=dev).expand(pts.shape[0], 3)
+                sigma = query_points(model, pts, vd)[:, 3].contiguous()
+                hb.occ_mark(sigma, K, sigma_threshold, bits[first // 32:(last + 31) // 32])
+            for _ in range(int(dilate)):
+                bits = hb.occ_dilate(bits, g.resolution)
+        g.bits = bits
+        return g
+
+    # ------------------------------------------------------------------ what render_rays calls
+    def _desc(self):
+        if not self.bits.is_cuda:
+            raise hb.NerfHipError("OccupancyGrid: rendering needs the grid on the GPU (grid.to(device))")
+        return hb.occ_desc(self.lo, self.scale, self.resolution, self.outside == "skip", self.bits)

@@ -584,9 +584,63 @@ def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f,
     return ret
 
 
+def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw):
+    """render_rays without gradients through an occupancy grid (occupancy.OccupancyGrid): _render_rays_hooked's chain of stages with
+    device code where the hook sits.  Per pass: depths (nerf_sample_coarse / nerf_sample_fine) -> nerf_occ_compact (classify o + d z,
+    compact the occupied points into n_samples = 1 ray records) -> ONE read-back of the count M -> the field on the M records, as
+    query_points evaluates points (nerf_field_fwd / nerf_field_fwd_split; no launch when M == 0) -> nerf_occ_expand (raw, zeros for
+    skipped samples) -> nerf_raw2outputs.  One host synchronisation per pass: two per call with N_importance > 0, else one.
+    "fp16_fp8c": the compacted points run on the fp16x3 products (the fp8 correction terms' last-sample fix-up is per ray)."""
+    n_c, n_f = cfg["N_samples"], cfg["N_importance"]
+    dev = rays.device
+    n = rays.shape[0]
+    std, wb = cfg["raw_noise_std"], cfg["white_bkgd"]
+    prec = "fp16x3" if cfg["precision"] == "fp16_fp8c" else cfg["precision"]
+    desc = grid._desc()
+    stats = {"evaluated": 0, "total": 0}
+
+    def one_pass(z_vals, model, noise, want_weights):
+        S = z_vals.shape[1]
+        P = n * S
+        slot_ws, rec_ws = hb.WORKSPACE.take(P, dev), hb.WORKSPACE.take(11 * P, dev)
+        raw_ws = z0 = None
+        try:
+            slot, records, count = hb.occ_compact(desc, rays, z_vals, slot_ws, rec_ws)
+            m = int(count.item())        # the field launch needs M on the host
+            raw = torch.empty((n, S, 4), dtype=torch.float32, device=dev)
+            raw_ws = hb.WORKSPACE.take(4 * max(m, 1), dev)
+            if m > 0:
+                z0 = hb.WORKSPACE.take(m, dev)
+                z0[:m].zero_()
+                hb.field_fwd(model.packed_params(prec), records[:m], z0[:m].view(m, 1), precision=prec, raw=raw_ws[:4 * m].view(m, 1, 4))
+            hb.occ_expand(slot, raw_ws, raw)
+        finally:        # stream-ordered: the next lease is written by kernels enqueued after these
+            for t in (slot_ws, rec_ws, raw_ws, z0):
+                hb.WORKSPACE.give(t)
+        stats["evaluated"] += m
+        stats["total"] += P
+        return raw, hb.raw2outputs(raw, z_vals, rays, rays.shape[1], noise, std, wb, want_weights=want_weights, want_depth=False,
+                                   rays_d_offset=3)
+
+    z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
+    raw, (rgb, disp, acc, weights, _) = one_pass(z_c, model_c, rnd.get("noise_c"), n_f > 0)
+    ret = {}
+    if n_f > 0:
+        ret.update(rgb0=rgb, disp0=disp, acc0=acc)
+        u = rnd.get("u")
+        z_f, z_std, _ = hb.sample_fine(z_c, weights, n_f, u, None if u is not None else _linspace01(n_f, dev))
+        raw, (rgb, disp, acc, _, _) = one_pass(z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), False)
+        ret["z_std"] = z_std
+    ret.update(rgb_map=rgb, disp_map=disp, acc_map=acc)
+    if retraw:
+        ret["raw"] = raw
+    grid.last_stats = stats
+    return ret
+
+
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                *, randoms=None):
+                *, randoms=None, occupancy=None):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -596,7 +650,11 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 
     ``randoms`` (keyword-only, not in the reference) injects the random tensors
     {t_rand [N,N_samples], noise_c [N,N_samples], u [N,N_importance], noise_f [N,N_samples+N_importance]}
-    instead of drawing them: the explicit form of the reference's ``pytest=`` hook."""
+    instead of drawing them: the explicit form of the reference's ``pytest=`` hook.
+
+    ``occupancy`` (keyword-only, not in the reference): an occupancy.OccupancyGrid -- sample points in empty cells are not sent
+    through the network and get raw = 0 (_render_rays_occupancy).  Rendering without gradients on fused NeRF networks only; a grid
+    together with a needed gradient, a DenseNeRF or a user network_query_fn raises NotImplementedError.  None: nothing changes."""
     from .dense import DenseNeRF
     nets = [network_fn] + ([network_fine] if network_fine is not None else [])
     dense = all(isinstance(m, DenseNeRF) for m in nets)         # architectures outside the fused kernels: layer by layer (dense.py)
@@ -623,6 +681,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             ret['raw'] = e(N_samples + n_f, 4)
         if n_f > 0:
             ret.update(rgb0=e(3), disp0=e(), acc0=e(), z_std=e())
+        if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
+            occupancy._desc()
+            occupancy.last_stats = {"evaluated": 0, "total": 0}
         return ret
     rnd = {}
     if randoms is not None:
@@ -669,6 +730,17 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         std = 1.0       # pytest noise is pre-scaled in float64 like the reference (run_nerf.py:290)
     cfg = dict(N_samples=int(N_samples), N_importance=n_f, lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
                raw_noise_std=std, precision=_PRECISION)
+    if occupancy is not None:
+        if not _is_builtin_query(network_query_fn):
+            raise NotImplementedError("render_rays: occupancy= together with a user network_query_fn is not implemented (mask inside the "
+                                      "hook with occupancy.occupied(pts) instead)")
+        if dense:
+            raise NotImplementedError("render_rays: occupancy= together with general (DenseNeRF) networks is not implemented; the grid "
+                                      "path runs the fused NeRF architecture only")
+        if torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for m in nets for p in m.parameters())):
+            raise NotImplementedError("render_rays: occupancy= together with a needed gradient (grad mode on and parameters or rays that "
+                                      "require grad) is not implemented; render under torch.no_grad(), train without the grid")
+        return _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw)
     if not _is_builtin_query(network_query_fn):
         return _render_rays_hooked(rays, rnd, network_fn, network_query_fn, int(N_samples), n_f, network_fine if n_f > 0 else None,
                                    bool(lindisp), white_bkgd, std, retraw)
@@ -706,9 +778,10 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """run_nerf.py:54-66.  Injected ``randoms`` (one row per ray) are sliced with the rays, so a chunked call consumes
-    the same draws as an unchunked one."""
+    the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks."""
     all_ret = {}
     randoms = kwargs.pop("randoms", None)
+    occ, occ_stats = kwargs.get("occupancy"), {"evaluated": 0, "total": 0}
     if randoms is not None:
         for k, v in randoms.items():
             if v.shape[0] != rays_flat.shape[0]:
@@ -717,8 +790,12 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
         if randoms is not None:
             kwargs["randoms"] = {k: v[i:i + chunk] for k, v in randoms.items()}
         ret = render_rays(rays_flat[i:i + chunk], **kwargs)
+        if occ is not None and occ.last_stats is not None:
+            occ_stats = {k: occ_stats[k] + occ.last_stats[k] for k in occ_stats}
         for k in ret:
             all_ret.setdefault(k, []).append(ret[k])
+    if occ is not None:
+        occ.last_stats = occ_stats
     return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in all_ret.items()}
 
 
