@@ -386,7 +386,7 @@ int nerf_raw2outputs_bwd_geom(const float* raw, const float* z_vals, const float
  * as nerf_field_input_grad (sin / cos of the exact 2^k x). */
 int nerf_embed_bwd(const float* x, long n_pts, int n_freqs, const float* d_out, float* d_x, int accumulate, void* stream);
 
-/* ---- occupancy grid: empty-space skipping for rendering without gradients (additive in ABI v10; csrc/occupancy.hip).  The reference
+/* ---- occupancy grid: empty-space skipping for rendering (and, further down, training) (additive in ABI v10; csrc/occupancy.hip).  The reference
  * pushes every sample point of render_rays through the network (run_nerf.py:381-385, :397-401); with a grid only the points in
  * occupied cells are evaluated and every other sample gets raw = (0, 0, 0, 0), i.e. relu(sigma) = 0, alpha = 0, weight 0 (:293).
  *   The grid is an axis-aligned box in the space of the points o + d z the network sees (NDC space for ndc rays), res[0] x res[1] x
@@ -424,6 +424,22 @@ int nerf_occ_expand(const int* slot, const float* raw_c, long n_points, float* r
 int nerf_occ_mark(const float* sigma, long n_cells, int samples_per_cell, float threshold, unsigned* words, void* stream);
 /* bits_out = 3x3x3 OR of bits_in (neighbours beyond the faces do not exist); two different buffers of the grid's size. */
 int nerf_occ_dilate(const unsigned* bits_in, int rx, int ry, int rz, unsigned* bits_out, void* stream);
+/* ---- training through a grid (additive in ABI v10): the adjoints of the compaction and the density step of occupancy.DensityGrid.
+ * d_raw_c[slot[p]] = d_raw[p] for the points with slot[p] >= 0 (4 floats each, 16-byte accesses, both buffers 16-byte aligned): the
+ * mirror of nerf_occ_expand.  The slots >= 0 of one nerf_occ_compact call are a bijection onto 0..M-1, so every row < M of d_raw_c
+ * [M][4] is written exactly once; d_raw_c must hold M rows.  20 B per point + 16 B per occupied point. */
+int nerf_occ_gather(const int* slot, const float* d_raw, long n_points, float* d_raw_c, void* stream);
+/* Per-ray gradient of the compacted records' per-point gradient d_rec[M][11] (nerf_field_input_grad on the n_samples = 1 records:
+ * columns 0:3 = d/d pt, 8:11 = d/d viewdir).  A record's point is o + d z and its view direction the ray's, so over the samples j of
+ * ray r with s = slot[r][j] >= 0:  d_rays[r][0:3] = sum d_rec[s][0:3],  [3:6] = sum z[r][j] * d_rec[s][0:3] (one fp32 product, not
+ * contracted),  [6:8] = 0,  [8:11] = sum d_rec[s][8:11] -- nerf_field_input_grad's column contract.  accumulate != 0: added to what
+ * d_rays[n_rays][11] holds (columns 6:8 untouched).  One wavefront per ray, lanes stride the samples in ascending order, a butterfly
+ * reduction, no atomics: the same inputs give the same bits.  Reads 8 B per point + 24 B per occupied point, writes 44 B per ray. */
+int nerf_occ_fold_rays(const int* slot, const float* z_vals, const float* d_rec, int n_rays, int n_samples, float* d_rays, int accumulate,
+                       void* stream);
+/* density[c] = max(density[c] * decay, max_k sigma[c][k]) for a run of n_cells cells, in place (pass density + first_cell): one fp32
+ * multiplication and one maximum; a NaN among the samples counts as -inf; written as m > d ? m : d with d = density[c] * decay. */
+int nerf_occ_density_update(const float* sigma, long n_cells, int samples_per_cell, float decay, float* density, void* stream);
 
 #ifdef __cplusplus
 }

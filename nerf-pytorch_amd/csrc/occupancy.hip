@@ -1,8 +1,12 @@
-// Occupancy-grid empty-space skipping for no-grad rendering (include/nerf_hip.h, section "occupancy grid").
+// Occupancy-grid empty-space skipping, for rendering and for training (include/nerf_hip.h, section "occupancy grid").
 //   nerf_occ_compact : classify the sample points o + d z of one pass against a bit grid and compact the occupied ones into
 //                      n_samples = 1 ray records (pt, 0, 0, 0, 0, 0, viewdir) that nerf_field_fwd / nerf_field_fwd_split evaluate;
 //   nerf_occ_expand  : scatter the network's answers back to raw[N][S][4], exact zeros for the skipped samples;
-//   nerf_occ_mark    : densities of K samples per cell -> grid bits;   nerf_occ_dilate: 3x3x3 OR of a grid.
+//   nerf_occ_mark    : densities of K samples per cell -> grid bits;   nerf_occ_dilate: 3x3x3 OR of a grid;
+//   nerf_occ_gather  : the adjoint of nerf_occ_expand, d_raw[N][S][4] -> the M rows the delta chain runs on;
+//   nerf_occ_fold_rays : per-point input gradients [M][11] -> per-ray gradients [N][11] (the column contract of
+//                      nerf_field_input_grad), one wavefront per ray, a fixed-order reduction;
+//   nerf_occ_density_update : density[c] = max(density[c] * decay, max_k sigma[c][k]) (occupancy.DensityGrid).
 // The compaction is deterministic: a count per block of OCC_TILE points, an exclusive scan of the block counts, then the
 // write -- inside a block the position of a point is a wave ballot + popcount and a prefix over the block's wave counts, so the
 // list is in stable ray-major, sample-minor order and no atomic decides anything.
@@ -207,6 +211,77 @@ __global__ __launch_bounds__(256) void occ_dilate_kernel(const unsigned* __restr
     store_ballot_words(set, cell, (n_cells + 31) & ~31L, out);
 }
 
+// the adjoint of occ_expand_kernel: one float4 per lane; the slots >= 0 are a bijection onto 0..M-1, so every row is written once
+__global__ __launch_bounds__(256) void occ_gather_kernel(const int* __restrict__ slot, const float4* __restrict__ d_raw, long P,
+                                                         float4* __restrict__ d_raw_c) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    const int s = slot[p];
+    if (s >= 0) d_raw_c[s] = d_raw[p];
+}
+
+constexpr int FOLD_THREADS = 256;               // 4 waves = 4 rays per block
+constexpr int FOLD_RAYS = FOLD_THREADS / 64;
+
+__device__ __forceinline__ float wave_sum(float v) {
+    // butterfly: every lane ends with the same sum, the order of the additions is fixed by the lane numbers alone
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// One wavefront per ray: lane l takes samples l, l + 64, ... in ascending order, then the butterfly.  A record's point is o + d z
+// (d pt / d o = 1, d pt / d d = z) and its view direction is the ray's: columns 0:3, 3:6 and 8:11 of nerf_field_input_grad's contract.
+__global__ __launch_bounds__(FOLD_THREADS) void occ_fold_rays_kernel(const int* __restrict__ slot, const float* __restrict__ z_vals,
+                                                                      const float* __restrict__ d_rec, int n_rays, int S,
+                                                                      float* __restrict__ d_rays, int accumulate) {
+    const int ray = blockIdx.x * FOLD_RAYS + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;          // (whole waves leave: the shuffles below see full waves)
+    const int lane = threadIdx.x & 63;
+    const size_t base = (size_t)ray * S;
+    float a[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int j = lane; j < S; j += 64) {
+        const int s = slot[base + j];
+        if (s < 0) continue;
+        const float z = z_vals[base + j];
+        const float* g = d_rec + (size_t)s * 11;
+        const float gx = g[0], gy = g[1], gz = g[2];
+        a[0] += gx; a[1] += gy; a[2] += gz;
+        a[3] += z * gx; a[4] += z * gy; a[5] += z * gz;      // (one product rounding each: -ffp-contract=off)
+        a[6] += g[8]; a[7] += g[9]; a[8] += g[10];
+    }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) a[c] = wave_sum(a[c]);
+    if (lane == 0) {
+        float* o = d_rays + (size_t)ray * 11;
+        if (accumulate) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) o[c] += a[c];
+            o[8] += a[6]; o[9] += a[7]; o[10] += a[8];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) o[c] = a[c];
+            o[6] = 0.0f; o[7] = 0.0f;
+            o[8] = a[6]; o[9] = a[7]; o[10] = a[8];
+        }
+    }
+}
+
+// one thread per cell, in place: m = max_k sigma (a NaN counts as -inf), density = m > density * decay ? m : density * decay
+__global__ __launch_bounds__(256) void occ_density_update_kernel(const float* __restrict__ sigma, long n_cells, int K, float decay,
+                                                                 float* __restrict__ density) {
+    const long cell = (long)blockIdx.x * 256 + threadIdx.x;
+    if (cell >= n_cells) return;
+    const float* s = sigma + cell * K;
+    float m = -INFINITY;
+    for (int k = 0; k < K; ++k) {
+        const float v = s[k];
+        if (v > m) m = v;
+    }
+    const float d = density[cell] * decay;
+    density[cell] = m > d ? m : d;
+}
+
 int check_grid(const char* fn, const NerfOccGrid* grid, GridArgs* g) {
     if (!grid || !grid->bits) return fail_arg(fn, "null pointer");
     for (int a = 0; a < 3; ++a) {
@@ -269,6 +344,34 @@ int nerf_occ_dilate(const unsigned* bits_in, int rx, int ry, int rz, unsigned* b
     REQUIRE(rx >= 1 && rx <= 512 && ry >= 1 && ry <= 512 && rz >= 1 && rz <= 512, "grid resolution must be 1..512 per axis");
     const long n_cells = (long)rx * ry * rz;
     occ_dilate_kernel<<<(unsigned)((n_cells + 255) / 256), 256, 0, (hipStream_t)stream>>>(bits_in, rx, ry, rz, bits_out);
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_gather(const int* slot, const float* d_raw, long n_points, float* d_raw_c, void* stream) {
+    REQUIRE(slot && d_raw && d_raw_c, "null pointer");
+    REQUIRE(n_points >= 0 && n_points < (1L << 31), "bad size");
+    REQUIRE(((reinterpret_cast<uintptr_t>(d_raw) | reinterpret_cast<uintptr_t>(d_raw_c)) & 15) == 0, "d_raw and d_raw_c must be 16-byte aligned");
+    if (n_points == 0) return 0;
+    occ_gather_kernel<<<(unsigned)((n_points + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        slot, reinterpret_cast<const float4*>(d_raw), n_points, reinterpret_cast<float4*>(d_raw_c));
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_fold_rays(const int* slot, const float* z_vals, const float* d_rec, int n_rays, int n_samples, float* d_rays, int accumulate,
+                       void* stream) {
+    REQUIRE(slot && z_vals && d_rec && d_rays, "null pointer");
+    REQUIRE(n_rays >= 0 && n_samples >= 1 && (long)n_rays * n_samples < (1L << 31), "bad size");
+    if (n_rays == 0) return 0;
+    occ_fold_rays_kernel<<<(unsigned)((n_rays + FOLD_RAYS - 1) / FOLD_RAYS), FOLD_THREADS, 0, (hipStream_t)stream>>>(
+        slot, z_vals, d_rec, n_rays, n_samples, d_rays, accumulate != 0);
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_density_update(const float* sigma, long n_cells, int samples_per_cell, float decay, float* density, void* stream) {
+    REQUIRE(sigma && density, "null pointer");
+    REQUIRE(n_cells >= 0 && n_cells <= 512L * 512 * 512 && samples_per_cell >= 1, "bad size");
+    if (n_cells == 0) return 0;
+    occ_density_update_kernel<<<(unsigned)((n_cells + 255) / 256), 256, 0, (hipStream_t)stream>>>(sigma, n_cells, samples_per_cell, decay, density);
     return done(__func__, hipGetLastError());
 }
 

@@ -88,6 +88,9 @@ def _declare(lib):
         "nerf_occ_expand": (i, [p, p, l, p, p]),
         "nerf_occ_mark": (i, [p, l, i, f, p, p]),
         "nerf_occ_dilate": (i, [p, i, i, i, p, p]),
+        "nerf_occ_gather": (i, [p, p, l, p, p]),
+        "nerf_occ_fold_rays": (i, [p, p, p, i, i, p, i, p]),
+        "nerf_occ_density_update": (i, [p, l, i, f, p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError here = header / library mismatch: fail loudly
@@ -108,7 +111,8 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_render_rays_infer", "nerf_mse_scratch_floats", "nerf_mse_fwd", "nerf_mse_bwd", "nerf_build_inputs", "nerf_dense_fwd", "nerf_dense_dgrad", "nerf_dense_wgrad_scratch_floats",
            "nerf_dense_wgrad", "nerf_range_scan", "nerf_field_input_grad", "nerf_raw2outputs_bwd_geom", "nerf_embed_bwd",
            "nerf_sample_ray_views", "nerf_ray_pose_grad",
-           "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate"]
+           "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate",
+           "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update"]
 
 
 def lib():
@@ -762,8 +766,9 @@ class RangeMonitor:
         w = self.words.get(dev)
         if w is None:
             w = self.words[dev] = torch.zeros(4, dtype=torch.int32, device=dev)
-        for buf, S in bufs:
-            _check(lib().nerf_range_scan(buf.data_ptr(), int(n_rays), int(S), w.data_ptr(), _stream()), "nerf_range_scan")
+        ns = list(n_rays) if isinstance(n_rays, (list, tuple)) else [n_rays] * len(bufs)       # (one ray count per buffer, or one for all)
+        for (buf, S), n in zip(bufs, ns):
+            _check(lib().nerf_range_scan(buf.data_ptr(), int(n), int(S), w.data_ptr(), _stream()), "nerf_range_scan")
         host = torch.empty(4, dtype=torch.int32, pin_memory=True)
         host.copy_(w, non_blocking=True)
         w.zero_()                   # (stream-ordered behind the copy: the next scan starts from zero)
@@ -772,7 +777,8 @@ class RangeMonitor:
         self.inflight.append((host, ev))
 
     def after_forward(self, acts, n_rays):
-        """acts: [(act buffer, n_samples)] of one saving fp16 forward over n_rays rays"""
+        """acts: [(act buffer, n_samples)] of one saving fp16 forward over n_rays rays (a list: one count per buffer -- the compacted
+        passes of the grid path evaluate different numbers of one-sample records)"""
         self.poll()
         if self.every <= 0:
             return
@@ -818,8 +824,9 @@ class RangeMonitor:
 RANGE_MONITOR = RangeMonitor()
 
 
-def field_fwd(packed, rays, z_vals, save_act=False, precision="fp32", guard_packed=None, raw=None, next_guard=None):
-    """guard_packed (precision "fp16_fp8c"): the fp16x3 repack of the same parameters for the last-sample guard, or the string
+def field_fwd(packed, rays, z_vals, save_act=False, precision="fp32", guard_packed=None, raw=None, next_guard=None, act=None):
+    """act (with save_act): a save buffer the caller leased (at least act_floats(n, S, precision) floats) instead of a lease of that size.
+    guard_packed (precision "fp16_fp8c"): the fp16x3 repack of the same parameters for the last-sample guard, or the string
     "done" when an earlier call's next_guard has already written this pass's last samples into `raw`.
     next_guard = (fp16x3 repack of the refining pass's network, that pass's preallocated raw [n, S_next, 4]): the guard launch also
     evaluates the refining pass's last sample (its depth is this pass's last depth)."""
@@ -829,7 +836,12 @@ def field_fwd(packed, rays, z_vals, save_act=False, precision="fp32", guard_pack
         raw = torch.empty((n, S, 4), dtype=torch.float32, device=rays.device)
     elif tuple(raw.shape) != (n, S, 4) or raw.dtype != torch.float32 or not raw.is_contiguous():
         raise NerfHipError(f"field_fwd: raw= must be a contiguous float32 [{n}, {S}, 4] tensor")
-    act = WORKSPACE.take(act_floats(n, S, precision), rays.device) if save_act else None
+    if not save_act:
+        act = None
+    elif act is None:
+        act = WORKSPACE.take(act_floats(n, S, precision), rays.device)
+    elif act.numel() < act_floats(n, S, precision) or act.dtype != torch.float32 or not act.is_contiguous():
+        raise NerfHipError(f"field_fwd: act= must be a contiguous float32 buffer of at least {act_floats(n, S, precision)} floats")
     nbytes = BYTES_ACT_PER_POINT * n * S if save_act else 16.0 * n * S
     if precision in SPLIT:
         nbytes = BYTES_ACT3_PER_POINT * n * S if save_act else 16.0 * n * S
@@ -1092,6 +1104,41 @@ def occ_dilate(bits, res):
     out = torch.empty_like(bits)
     _check(lib().nerf_occ_dilate(_words(bits, "bits"), int(res[0]), int(res[1]), int(res[2]), _words(out, "out"), _stream()), "nerf_occ_dilate")
     return out
+
+
+def occ_gather(slot, d_raw, d_raw_c):
+    """nerf_occ_gather: d_raw_c [M, ..., 4] (preallocated; M = the number of slots >= 0) <- the rows of d_raw [..., 4] by slot"""
+    P = slot.numel()
+    if d_raw.numel() != 4 * P:
+        raise NerfHipError("occ_gather: d_raw must hold 4 floats per slot")
+    if d_raw_c.numel() == 0:        # M = 0: no slot is >= 0, nothing to write
+        return d_raw_c
+    with _timed("occ_gather_kernel", 0.0, 20.0 * P):
+        _check(lib().nerf_occ_gather(_words(slot, "slot"), _ptr(d_raw, "d_raw"), P, _ptr(d_raw_c, "d_raw_c"), _stream()), "nerf_occ_gather")
+    return d_raw_c
+
+
+def occ_fold_rays(slot, z_vals, d_rec, d_rays, accumulate=False):
+    """nerf_occ_fold_rays: d_rays [n, 11] (+)= the per-ray sums of the compacted records' gradient d_rec [M, 11] (slot / z_vals: [n, S])"""
+    n, S = z_vals.shape
+    if slot.numel() != n * S or tuple(d_rays.shape) != (n, 11) or d_rec.dim() != 2 or d_rec.shape[1] != 11:
+        raise NerfHipError("occ_fold_rays: slot [n * S], z_vals [n, S], d_rec [M, 11], d_rays [n, 11]")
+    if d_rec.numel() == 0:          # M = 0: never read, but the entry point refuses a null pointer
+        d_rec = torch.empty((1, 11), dtype=torch.float32, device=d_rays.device)
+    with _timed("occ_fold_rays_kernel", 0.0, 8.0 * n * S):
+        _check(lib().nerf_occ_fold_rays(_words(slot, "slot"), _ptr(z_vals, "z_vals"), _ptr(d_rec, "d_rec"), n, S, _ptr(d_rays, "d_rays"),
+                                        int(bool(accumulate)), _stream()), "nerf_occ_fold_rays")
+    return d_rays
+
+
+def occ_density_update(sigma, samples_per_cell, decay, density):
+    """nerf_occ_density_update: density (a contiguous run of a DensityGrid's cells) <- max(density * decay, max_k sigma), in place"""
+    n_cells = density.numel()
+    if sigma.numel() != n_cells * int(samples_per_cell):
+        raise NerfHipError("occ_density_update: sigma must hold samples_per_cell values per cell")
+    _check(lib().nerf_occ_density_update(_ptr(sigma, "sigma"), n_cells, int(samples_per_cell), float(decay), _ptr(density, "density"),
+                                         _stream()), "nerf_occ_density_update")
+    return density
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

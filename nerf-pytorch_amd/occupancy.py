@@ -1,11 +1,18 @@
-"""Occupancy grid: empty-space skipping for rendering without gradients.
+"""Occupancy grids: empty-space skipping for rendering (OccupancyGrid) and for training (DensityGrid).
 
 The reference evaluates the network at every sample point of render_rays (run_nerf.py:381-385, :397-401), the points of a trained
 scene that lie in empty space included.  ``OccupancyGrid`` is one bit per cell of an axis-aligned box; handed to
 ``render_rays(..., occupancy=grid)`` (or put into ``render_kwargs_test["occupancy"]``) only the sample points in occupied cells go
 through the network, every other sample gets ``raw = (0, 0, 0, 0)`` -- ``relu(sigma) = 0``, ``alpha = 0``, weight 0 -- and nothing
 else of render_rays changes.  Device code: csrc/occupancy.hip (include/nerf_hip.h, "occupancy grid").
+
+A static bit grid is built from a network that training is about to change.  ``DensityGrid`` is the grid that follows the network
+(Instant-NGP's density grid, Mueller et al. 2022, section 5 / appendix E.2): a decayed running maximum of the density per cell,
+refreshed every few steps and thresholded into the bits the renderer reads; ``render_rays(..., occupancy=density_grid)`` is
+differentiable (render._RenderRaysGrid).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -180,3 +187,132 @@ class OccupancyGrid:
         if not self.bits.is_cuda:
             raise hb.NerfHipError("OccupancyGrid: rendering needs the grid on the GPU (grid.to(device))")
         return hb.occ_desc(self.lo, self.scale, self.resolution, self.outside == "skip", self.bits)
+
+
+class DensityGrid(OccupancyGrid):
+    """The grid that follows a network in training: next to ``bits`` (all ones at first) one fp32 value per cell, ``density`` [n_cells]
+    (zeros at first), a decayed running maximum of raw[..., 3] (the density before the ReLU).
+
+    ``update(model)`` visits a run of cells: density[c] = max(density[c] * decay, max_k sigma_k) with sigma_k the network's density at
+    the cell's centre (and samples_per_cell - 1 uniform points in it); then, over the WHOLE grid, bits = `dilate` rounds of the 3x3x3 OR
+    of (density > sigma_threshold) -- recomputed from ``density`` every time, so the dilation never accumulates.
+    ``maybe_update(model, global_step)`` is the schedule of a training loop: nothing while global_step < warmup_steps (the grid stays
+    all-occupied: it must not hide geometry the network has not learnt yet), afterwards an update every `update_every` steps.
+
+    The defaults (decay 0.95, sigma_threshold 0.01, update_every 16, warmup_steps 256) are Instant-NGP's habits, not measurements made
+    with these networks: the threshold in particular is in the units of the scene's density and wants a look at ``fraction_occupied()``.
+    ``_update_reference`` / ``_bits_reference`` are the definition of the step in plain torch, as ``occupied()`` is the classifier's."""
+
+    def __init__(self, lo, hi, resolution, outside="evaluate", device=None, decay=0.95, sigma_threshold=0.01, dilate=0, update_every=16,
+                 warmup_steps=256):
+        super().__init__(lo, hi, resolution, outside, device)
+        if not (0.0 <= float(decay) <= 1.0) or int(dilate) < 0 or int(update_every) < 1 or int(warmup_steps) < 0:
+            raise ValueError("DensityGrid: 0 <= decay <= 1, dilate >= 0, update_every >= 1, warmup_steps >= 0")
+        self.decay, self.sigma_threshold = float(decay), float(sigma_threshold)
+        self.dilate, self.update_every, self.warmup_steps = int(dilate), int(update_every), int(warmup_steps)
+        self.density = torch.zeros(self.n_cells, dtype=torch.float32, device=self.bits.device)
+        self.cursor = 0             # first cell of the next update's run (a multiple of 32: runs are whole words)
+        self.n_updates = 0
+
+    def to(self, device):
+        super().to(device)
+        self.density = self.density.to(device)
+        return self
+
+    # ------------------------------------------------------------------ the definition (plain torch, any device)
+    def _update_reference(self, sigma, first, last):
+        """the density step for the cells first <= c < last from sigma [(last - first) * K] (cell-major): m = max_k sigma_k, a NaN
+        counting as -inf; density[c] = m if m > density[c] * decay else density[c] * decay (one fp32 multiplication, one maximum)"""
+        sigma = sigma.to(device=self.density.device, dtype=torch.float32).reshape(last - first, -1)
+        m = torch.where(torch.isnan(sigma), torch.full_like(sigma, float("-inf")), sigma).amax(-1)
+        d = self.density[first:last] * torch.tensor(self.decay, dtype=torch.float32, device=self.density.device)
+        self.density[first:last] = torch.where(m > d, m, d)
+
+    def _bits_reference(self):
+        """bits of the whole grid from ``density``: dilate^dilate(density > sigma_threshold)"""
+        mask = (self.density > torch.tensor(self.sigma_threshold, dtype=torch.float32, device=self.density.device)).view(self.resolution)
+        for _ in range(self.dilate):
+            mask = torch.nn.functional.max_pool3d(mask[None, None].float(), 3, 1, 1)[0, 0] > 0
+        return _pack_bits(mask.reshape(-1))
+
+    def _next_runs(self, fraction):
+        """the cells one update visits, as [(first, last)] (two runs when the visit wraps), and the cursor moved past them: `fraction`
+        of the grid's words, rounded up, from the cursor on; the first update of a grid's life visits every cell (an unvisited cell has
+        density 0 and would be emptied)"""
+        n_words = self.bits.numel()
+        if not (0.0 < float(fraction) <= 1.0):
+            raise ValueError("DensityGrid.update: 0 < fraction <= 1")
+        if self.n_updates == 0:
+            count = n_words
+        else:
+            count = min(n_words, max(1, math.ceil(float(fraction) * n_words)))
+        w0 = self.cursor // 32
+        runs = [(w0, min(w0 + count, n_words))]
+        if w0 + count > n_words:
+            runs.append((0, w0 + count - n_words))
+        self.cursor = 32 * ((w0 + count) % n_words)
+        self.n_updates += 1
+        return [(32 * a, min(32 * b, self.n_cells)) for a, b in runs]
+
+    # ------------------------------------------------------------------ following a network
+    def update(self, model, fraction=1.0, samples_per_cell=1, generator=None):
+        """one density step over `fraction` of the grid (a contiguous run of words from the cursor on, wrapping; everything on the first
+        call), then the bits of the whole grid.  The network is evaluated through query_points under no_grad in slices, with one fixed
+        view direction, exactly as OccupancyGrid.from_network does; fused NeRF modules only.  Returns self."""
+        from .field import NeRF
+        from .render import query_points
+        if not isinstance(model, NeRF):
+            raise NotImplementedError("DensityGrid.update: a fused-kernel NeRF module is required (not a DenseNeRF / other module)")
+        if not self.bits.is_cuda:
+            raise hb.NerfHipError("DensityGrid.update: the grid must be on the GPU (grid.to(device))")
+        K = int(samples_per_cell)
+        if K < 1:
+            raise ValueError("DensityGrid.update: samples_per_cell >= 1")
+        dev = self.device
+        with torch.no_grad():
+            for run_first, run_last in self._next_runs(fraction):
+                for first in range(run_first, run_last, _SLICE_CELLS):
+                    last = min(first + _SLICE_CELLS, run_last)
+                    pts = self.cell_points(first, last, K, generator).reshape(-1, 3)
+                    vd = torch.tensor([0.0, 0.0, 1.0], device=dev).expand(pts.shape[0], 3)
+                    sigma = query_points(model, pts, vd)[:, 3].contiguous()
+                    hb.occ_density_update(sigma, K, self.decay, self.density[first:last])
+            bits = hb.occ_mark(self.density, 1, self.sigma_threshold, torch.empty_like(self.bits))
+            for _ in range(self.dilate):
+                bits = hb.occ_dilate(bits, self.resolution)
+        self.bits = bits
+        return self
+
+    def maybe_update(self, model, global_step, **kw):
+        """the training loop's call, once per step: False (nothing done) while global_step < warmup_steps or when global_step is no
+        multiple of update_every, else update(model, **kw) and True"""
+        if global_step < self.warmup_steps or global_step % self.update_every != 0:
+            return False
+        self.update(model, **kw)
+        return True
+
+    # ------------------------------------------------------------------ checkpoints
+    _SCALARS = ("decay", "sigma_threshold", "dilate", "update_every", "warmup_steps")
+
+    def state_dict(self):
+        state = super().state_dict()
+        state.update(density=self.density.detach().cpu().clone(), cursor=self.cursor, n_updates=self.n_updates,
+                     **{k: getattr(self, k) for k in self._SCALARS})
+        return state
+
+    def load_state_dict(self, state):
+        missing = [k for k in ("density", "cursor", "n_updates") + self._SCALARS if k not in state]
+        if missing:
+            raise ValueError(f"DensityGrid.load_state_dict: not a DensityGrid state (no {missing})")
+        density = torch.as_tensor(state["density"]).to(torch.float32).reshape(-1)
+        res = tuple(int(v) for v in state["resolution"])
+        if density.numel() != res[0] * res[1] * res[2]:
+            raise ValueError("DensityGrid.load_state_dict: `density` does not match `resolution`")
+        if int(state["cursor"]) % 32 or not (0 <= int(state["cursor"]) < max(density.numel(), 1)):
+            raise ValueError("DensityGrid.load_state_dict: `cursor` must be a multiple of 32 inside the grid")
+        super().load_state_dict(state)
+        self.density = density.to(self.device).contiguous().clone()
+        self.cursor, self.n_updates = int(state["cursor"]), int(state["n_updates"])
+        self.decay, self.sigma_threshold = float(state["decay"]), float(state["sigma_threshold"])
+        self.dilate, self.update_every, self.warmup_steps = int(state["dilate"]), int(state["update_every"]), int(state["warmup_steps"])
+        return self

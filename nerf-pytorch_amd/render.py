@@ -638,6 +638,230 @@ def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw):
     return ret
 
 
+def _grid_pass_lease(m, P, prec):
+    """floats of the save buffer of a compacted pass of m of P points: m rounded up to the next eighth of the dense size.  M moves from
+    step to step in training and Workspace.take passes over a free buffer more than twice the request; with eight sizes per pass a
+    steady loop finds last step's buffer (or its neighbour in size) instead of allocating 4.8 KB per point every step."""
+    q = max(1, -(-P // 8))
+    return hb.act_floats(q * max(1, -(-m // q)), 1, prec)
+
+
+class _RenderRaysGrid(torch.autograd.Function):
+    """render_rays through an occupancy.DensityGrid WITH gradients, as one autograd node shaped like _RenderRays (one _grad_ready per
+    network per backward with the final flat vector, a shared network accumulated in the kernel, no weight-gradient launch for a frozen
+    network, the stale-parameter and freed-graph checks, no saved output in ctx).
+
+    Per pass, forward: depths -> nerf_occ_compact -> ONE read-back of M -> the field on the M one-sample records with saved
+    activations -> nerf_occ_expand (zeros for skipped samples) -> nerf_raw2outputs.  Backward: nerf_raw2outputs_bwd -> nerf_occ_gather
+    (d_raw of the M points) -> delta chain / weight gradient on the M records, the input gradient in point mode when the rays need one
+    -> nerf_occ_fold_rays (per-point [M, 11] -> per-ray [N, 11]) + the compositing's |d| term.  A skipped sample has raw = 0 and no
+    gradient: what a network_query_fn that evaluates only the occupied points computes.
+
+    Kept from forward to backward, per pass: slot (4 B per sample point), the saved activations of M points (leased at
+    _grid_pass_lease's size), z, raw, and the M records (44 B each) only when the rays need a gradient -- hb.WORKSPACE leases, given
+    back by the backward or freed with a dropped graph.  Calls above hb.max_saved_rays(...) rays run in equal ray sub-chunks, every
+    one resident with leases of its own M; beyond hb.SAVE_TOTAL_BYTES in total the call raises (no recompute plan on this path)."""
+
+    @staticmethod
+    def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
+        n_c, n_f = cfg["N_samples"], cfg["N_importance"]
+        prec = cfg["precision"]
+        std, wb = cfg["raw_noise_std"], cfg["white_bkgd"]
+        n = rays.shape[0]
+        dev = rays.device
+        desc = grid._desc()
+        ctx.same_net = model_f is None or model_f is model_c
+        ctx.n_params_c = len(_param_slices(model_c))
+        ctx.rays_grad = rays_grad = bool(ctx.needs_input_grad[1])
+        ctx.wgrad_c = any(ctx.needs_input_grad[6:6 + ctx.n_params_c])
+        ctx.wgrad_f = ctx.wgrad_c if ctx.same_net else any(ctx.needs_input_grad[6 + ctx.n_params_c:])
+        sub = hb.max_saved_rays(n_c, n_f, prec)
+        if n > sub:
+            ceil_div = lambda a, b: -(-a // b)
+            sub = min(sub, 64 * ceil_div(ceil_div(n, ceil_div(n, sub)), 64))        # equal sub-chunks, multiples of 64 rays
+            tiles = [(lo, min(lo + sub, n)) for lo in range(0, n, sub)]
+        else:
+            sub, tiles = n, [(0, n)]
+        global LAST_BACKWARD_PLAN
+        LAST_BACKWARD_PLAN = ("resident sub-chunks" if len(tiles) > 1 else "one launch", n, sub)
+        stats = {"evaluated": 0, "total": 0}
+        resident = [0]
+        parts = []
+
+        def one_pass(rays_t, z_vals, model, noise, want_weights):
+            nt, S = z_vals.shape
+            P = nt * S
+            p = {"z": z_vals, "slot": hb.WORKSPACE.take(P, dev), "act": None, "rec": None, "m": 0}
+            parts[-1].append(p)         # (registered first: an error below hands its leases back with the others')
+            rec_ws = hb.WORKSPACE.take(11 * P, dev)
+            try:
+                slot, records, count = hb.occ_compact(desc, rays_t, z_vals, p["slot"], rec_ws)
+                m = p["m"] = int(count.item())      # the field launch needs M on the host
+                raw = torch.empty((nt, S, 4), dtype=torch.float32, device=dev)
+                raw_c = torch.empty((max(m, 1), 1, 4), dtype=torch.float32, device=dev)
+                if m > 0:
+                    lease = _grid_pass_lease(m, P, prec)
+                    resident[0] += 4 * (lease + P + (11 * m if rays_grad else 0))
+                    if resident[0] > hb.SAVE_TOTAL_BYTES:
+                        raise RuntimeError(f"render_rays(occupancy=DensityGrid): the saved activations of this call's {n} rays exceed "
+                                           f"hip_backend.SAVE_TOTAL_BYTES = {hb.SAVE_TOTAL_BYTES} bytes (NERF_SAVE_TOTAL_GB); the grid path "
+                                           "has no recompute plan: render fewer rays per call (chunk=) or raise the budget")
+                    p["act"] = hb.WORKSPACE.take(lease, dev)
+                    p["packed"] = model.packed_params(prec)
+                    hb.field_fwd(p["packed"], records[:m], torch.zeros((m, 1), dtype=torch.float32, device=dev), save_act=True,
+                                 precision=prec, raw=raw_c[:m], act=p["act"])
+                    if rays_grad:
+                        p["rec"] = hb.WORKSPACE.take(11 * m, dev)
+                        p["rec"][:11 * m].copy_(records[:m].reshape(-1))
+                hb.occ_expand(slot, raw_c, raw)
+            finally:        # stream-ordered: the next lease is written by kernels enqueued after these
+                hb.WORKSPACE.give(rec_ws)
+            p["raw"] = raw
+            stats["evaluated"] += m
+            stats["total"] += P
+            return raw, hb.raw2outputs(raw, z_vals, rays_t, rays_t.shape[1], noise, std, wb, want_weights=want_weights, want_depth=False,
+                                       rays_d_offset=3)
+
+        outs = []
+        try:
+            for lo, hi in tiles:
+                rays_t = rays[lo:hi]
+                rnd_t = rnd if len(tiles) == 1 else {k_: v[lo:hi] for k_, v in rnd.items()}
+                parts.append([])
+                z_c = hb.sample_coarse(rays_t, _linspace01(n_c, dev), cfg["lindisp"], rnd_t.get("t_rand"))
+                raw_c, (rgb_c, disp_c, acc_c, w_c, _) = one_pass(rays_t, z_c, model_c, rnd_t.get("noise_c"), n_f > 0)
+                if n_f <= 0:
+                    outs.append((rgb_c, disp_c, acc_c, raw_c))
+                    continue
+                u = rnd_t.get("u")
+                z_f, z_std, _ = hb.sample_fine(z_c, w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
+                raw_f, (rgb_f, disp_f, acc_f, _, _) = one_pass(rays_t, z_f, model_c if ctx.same_net else model_f, rnd_t.get("noise_f"), False)
+                outs.append((rgb_f, disp_f, acc_f, raw_f, rgb_c, disp_c, acc_c, z_std))
+        except BaseException:
+            for passes in parts:
+                for p in passes:
+                    for k_ in ("slot", "act", "rec"):
+                        hb.WORKSPACE.give(p.get(k_))
+            raise
+        grid.last_stats = stats
+        if prec in ("fp16x3", "fp16x3w"):       # the fp16 split's range guard rail sees the compacted passes' saved activations
+            for passes in parts:
+                acts = [(p["act"], 1) for p in passes if p["act"] is not None]
+                if acts:
+                    hb.RANGE_MONITOR.after_forward(acts, [p["m"] for p in passes if p["act"] is not None])
+        if len(tiles) == 1:
+            out = outs[0]
+            # `raw` of the last pass is an output of this node: held through save_for_backward, never in ctx (_RenderRays.forward)
+            ctx.save_for_backward(parts[0][-1].pop("raw"))
+        else:
+            out = tuple(torch.cat([o[i] for o in outs], 0) for i in range(len(outs[0])))       # new tensors: the per-tile ones are no outputs
+        ctx.cfg, ctx.model_c, ctx.model_f, ctx.tiles, ctx.parts = cfg, model_c, model_f, tiles, parts
+        ctx.rays, ctx.rnd = rays.detach(), rnd
+        ctx.param_state = tuple(_param_state(m_) for m_ in (model_c, model_f) if m_ is not None)
+        ctx.consumed = False
+        ctx.set_materialize_grads(False)
+        if n_f > 0:
+            ctx.mark_non_differentiable(out[7])     # the reference detaches z_samples (run_nerf.py:394)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        if ctx.consumed:
+            raise RuntimeError(_FREED_MSG)
+        cfg = ctx.cfg
+        none_c = (None,) * ctx.n_params_c
+        none_all = (None,) * 6 + none_c + (() if ctx.same_net else none_c)
+        now = tuple(_param_state(m) for m in (ctx.model_c, ctx.model_f) if m is not None)
+        std, wb, prec = cfg["raw_noise_std"], cfg["white_bkgd"], cfg["precision"]
+        if prec != "fp32" and now != ctx.param_state:
+            raise RuntimeError(_STALE_MSG)
+        rays_all, rnd_all = ctx.rays, ctx.rnd
+        dev = rays_all.device
+        n_all = rays_all.shape[0]
+        fine = cfg["N_importance"] > 0
+        up_f = (gouts[0], gouts[1], gouts[2], gouts[3])
+        up_c = (gouts[4], gouts[5], gouts[6], None) if fine else None
+        if not fine:
+            up_c, up_f = up_f, None
+        has = lambda up: up is not None and any(g is not None for g in up)
+
+        def release():
+            for passes in ctx.parts:
+                for p in passes:
+                    for k_ in ("slot", "act", "rec"):
+                        hb.WORKSPACE.give(p.get(k_))
+                        p[k_] = None
+            ctx.parts = None
+            ctx.consumed = True
+
+        if not has(up_c) and not has(up_f):
+            release()
+            return none_all
+        grad_c = torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev) if ctx.wgrad_c else None
+        grad_f = None if (ctx.same_net or not fine or not ctx.wgrad_f) else torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev)
+        wrote = {"c": False, "f": False}
+        d_rays_all = torch.zeros((n_all, 11), dtype=torch.float32, device=dev) if ctx.rays_grad else None
+
+        def field_grad(rays, model, p, raw, noise, up, lo, hi, grad, key):
+            d_rgb, d_disp, d_acc, d_raw_up = (None if g is None else g[lo:hi] for g in up)
+            nt, z, m = hi - lo, p["z"], p["m"]
+            if d_rgb is None and (d_disp is not None or d_acc is not None):
+                d_rgb = torch.zeros((nt, 3), dtype=torch.float32, device=dev)
+            c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
+            d_rays = None if d_rays_all is None else d_rays_all[lo:hi]
+            d_dn = None
+            if d_rgb is None:       # only `raw` itself carries a gradient
+                d_raw = c(d_raw_up)
+            else:
+                if d_rays is not None:
+                    d_dn = torch.empty((nt, 3), dtype=torch.float32, device=dev)
+                d_raw = hb.raw2outputs_bwd(raw, z, rays, rays.shape[1], noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
+                                           rays_d_offset=3, d_rays_d=d_dn)
+                if d_raw_up is not None:
+                    d_raw += d_raw_up
+            if m == 0:          # no point of this pass was evaluated: no field launch, zero gradient from it
+                if grad is not None and not wrote[key]:
+                    grad.zero_()
+                    wrote[key] = True
+            elif grad is not None or d_rays is not None:
+                d_raw_c = hb.occ_gather(p["slot"][:nt * z.shape[1]].view(torch.int32), d_raw, torch.empty((m, 1, 4), dtype=torch.float32, device=dev))
+                d_rec = rec = None
+                if d_rays is not None:
+                    rec = p["rec"][:11 * m].view(m, 11)
+                    d_rec = torch.empty((m, 11), dtype=torch.float32, device=dev)
+                hb.field_bwd(p["packed"], p["act"], d_raw_c, grad, wrote[key], precision=prec, params=model.flat_params(),
+                             input_grad=None if d_rec is None else (rec, torch.zeros((m, 1), dtype=torch.float32, device=dev), d_rec, False))
+                if d_rec is not None:
+                    hb.occ_fold_rays(p["slot"][:nt * z.shape[1]].view(torch.int32), z, d_rec, d_rays, accumulate=True)
+                if grad is not None:
+                    wrote[key] = True
+            if d_dn is not None:
+                d_rays[:, 3:6] += d_dn          # the compositing's |d| term (dists = dz |d|)
+
+        shared = ctx.same_net and fine and has(up_f)      # the fine pass adds into the coarse network's gradient
+        raw_last = ctx.saved_tensors[0] if len(ctx.tiles) == 1 else None
+        for i, ((lo, hi), passes) in enumerate(zip(ctx.tiles, ctx.parts)):
+            last = i == len(ctx.tiles) - 1
+            rays = rays_all[lo:hi]
+            rnd = rnd_all if len(ctx.tiles) == 1 else {k: v[lo:hi] for k, v in rnd_all.items()}
+            raw_of = lambda p: p["raw"] if "raw" in p else raw_last
+            if has(up_c):
+                field_grad(rays, ctx.model_c, passes[0], raw_of(passes[0]), rnd.get("noise_c"), up_c, lo, hi, grad_c, "c")
+                if last and not shared and grad_c is not None:     # final: its all-reduce may start under the fine network's backward
+                    _grad_ready(ctx.model_c, grad_c)
+            if fine and has(up_f):
+                model, grad, key = (ctx.model_c, grad_c, "c") if ctx.same_net else (ctx.model_f, grad_f, "f")
+                field_grad(rays, model, passes[1], raw_of(passes[1]), rnd.get("noise_f"), up_f, lo, hi, grad, key)
+                if last and grad is not None:
+                    _grad_ready(model, grad)
+        release()
+        lead = (None, d_rays_all) + (None,) * 4
+        out_c = _grad_views(ctx.model_c, grad_c) if wrote["c"] else none_c
+        if ctx.same_net:
+            return lead + out_c
+        return lead + out_c + (_grad_views(ctx.model_f, grad_f) if wrote["f"] else none_c)
+
+
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
                 *, randoms=None, occupancy=None):
@@ -653,8 +877,10 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     instead of drawing them: the explicit form of the reference's ``pytest=`` hook.
 
     ``occupancy`` (keyword-only, not in the reference): an occupancy.OccupancyGrid -- sample points in empty cells are not sent
-    through the network and get raw = 0 (_render_rays_occupancy).  Rendering without gradients on fused NeRF networks only; a grid
-    together with a needed gradient, a DenseNeRF or a user network_query_fn raises NotImplementedError.  None: nothing changes."""
+    through the network and get raw = 0 (_render_rays_occupancy).  Fused NeRF networks only: a grid together with a DenseNeRF or a
+    user network_query_fn raises NotImplementedError.  With a needed gradient (grad mode on and parameters or rays that require grad)
+    an occupancy.DensityGrid renders differentiably w.r.t. both networks' parameters and the ray records (_RenderRaysGrid: skipped
+    samples get no gradient); a plain OccupancyGrid raises NotImplementedError there.  None: nothing changes."""
     from .dense import DenseNeRF
     nets = [network_fn] + ([network_fine] if network_fine is not None else [])
     dense = all(isinstance(m, DenseNeRF) for m in nets)         # architectures outside the fused kernels: layer by layer (dense.py)
@@ -738,8 +964,24 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             raise NotImplementedError("render_rays: occupancy= together with general (DenseNeRF) networks is not implemented; the grid "
                                       "path runs the fused NeRF architecture only")
         if torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for m in nets for p in m.parameters())):
-            raise NotImplementedError("render_rays: occupancy= together with a needed gradient (grad mode on and parameters or rays that "
-                                      "require grad) is not implemented; render under torch.no_grad(), train without the grid")
+            from .occupancy import DensityGrid
+            if not isinstance(occupancy, DensityGrid):
+                raise NotImplementedError("render_rays: a plain OccupancyGrid together with a needed gradient (grad mode on and parameters or "
+                                          "rays that require grad) is not implemented: a static grid would hide what the network has not "
+                                          "learnt yet.  Render under torch.no_grad(), or train through an occupancy.DensityGrid (the grid "
+                                          "that follows the network: maybe_update every step)")
+            if cfg["precision"] == "fp16_fp8c":
+                cfg["precision"] = "fp16x3"         # the reduced class is an inference form; gradients: the fp16x3 datapath
+            same = n_f <= 0 or network_fine is None or network_fine is network_fn
+            params = network_fn.param_list() + ([] if same else network_fine.param_list())
+            outs = _RenderRaysGrid.apply(cfg, rays, rnd, network_fn, None if same else network_fine, occupancy, *params)
+            ret = {}        # (keys in _render_rays_occupancy's order)
+            if n_f > 0:
+                ret.update(rgb0=outs[4], disp0=outs[5], acc0=outs[6], z_std=outs[7])
+            ret.update(rgb_map=outs[0], disp_map=outs[1], acc_map=outs[2])
+            if retraw:
+                ret['raw'] = outs[3]
+            return ret
         return _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw)
     if not _is_builtin_query(network_query_fn):
         return _render_rays_hooked(rays, rnd, network_fn, network_query_fn, int(N_samples), n_f, network_fine if n_f > 0 else None,
