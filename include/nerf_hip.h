@@ -276,6 +276,29 @@ int nerf_field_wgrad_phase(const float* act, const float* delta, const float* d_
                                            6 fp16 two-word operands (split = 5 buffers) */,
                            int phases, const float* params /* canonical parameters; may be NULL for datapath 0 */,
                            void* stream);
+/* ---- dead-tile skipping in the backward of the split datapaths (additive entry points; ABI version unchanged).
+ * A 32-point tile (points 32 t .. 32 t + 31 of the launch) is DEAD when all 128 words of its d_raw are +-0 (bits & 0x7fffffff == 0;
+ * NaN, Inf and subnormals make a tile live).  Compositing gives every sample whose density is not positive an exactly zero d_raw,
+ * the delta chain is linear in d_raw, and a zero delta adds +-0 to every weight and bias gradient: as long as the saved activations
+ * are finite, leaving the dead tiles out changes no bit of the gradient.  (With an Inf / NaN activation the dense forms produce
+ * 0 * Inf = NaN in that gradient and the sparse forms do not; the fp16 range guard has failed long before.)
+ *   nerf_live_tiles_words(n_rays, n_samples): 32-bit words of the caller-owned list buffer `live` of one pass (16-byte aligned).
+ *   nerf_field_dgrad_split_live: nerf_field_dgrad_split that also writes `live` -- [0] the count of live tiles, [1] the number of
+ * tiles, [4 + i] the live tile numbers in ascending order (then a bitmap and its prefix counts: csrc/launchers.h) -- on the device,
+ * without a read-back, in the pass over d_raw that finds its maximum plus one small launch, and runs the delta chain over the live
+ * tiles only.  CONTRACT: a dead tile's deltas are NOT WRITTEN (the buffer keeps whatever it held); readers other than
+ * nerf_field_wgrad_phase_live with the same list (nerf_field_input_grad, nerf_range_scan on the delta buffer) need the dense form.
+ *   nerf_field_wgrad_phase_live: nerf_field_wgrad_phase whose GEMM streams the live tiles only (same chunk plan, same order of
+ * summation inside every chunk: the same partial sums minus exact zeros).  datapath 0 (fp32) has no sparse form.
+ *   live = NULL in either: exactly the dense entry point.  NERF_BWD_SKIP_DEAD=0 in the environment (read once per process) makes both
+ * ignore `live` (nerf_bwd_skip_dead() returns 0 then): the A/B switch. */
+size_t nerf_live_tiles_words(int n_rays, int n_samples);
+int nerf_bwd_skip_dead(void);
+int nerf_field_dgrad_split_live(const float* packed3, const float* act, const float* d_raw, int n_rays, int n_samples,
+                                float* delta, int split, unsigned* live /* nullable */, void* stream);
+int nerf_field_wgrad_phase_live(const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
+                                float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
+                                const unsigned* live /* nullable */, void* stream);
 /* ---- render_rays in one call (run_nerf.py:308-418 and its autograd): the whole of a ray batch's forward, and the whole of
  * its backward, as ONE entry point each.  They chain the launches above in C -- coarse depths -> field -> raw2outputs
  * [-> sample_pdf + sort -> field -> raw2outputs]; raw2outputs' adjoint -> delta chain -> weight gradients per pass -- in the

@@ -1,6 +1,7 @@
 // extern "C" entry points of libnerf_hip.so (declared in include/nerf_hip.h).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <iterator>
 #include <mutex>
@@ -365,26 +366,78 @@ static int datapath_from_tags(const char* fn, const void* act, const void* delta
     return dp;
 }
 
+// NERF_BWD_SKIP_DEAD=0 in the environment (read once per process): the *_live entry points ignore their list -- the dense forms
+// everywhere, the A/B instrument of the dead-tile skipping and its fallback
+static bool skip_dead_enabled() {
+    static const bool on = [] { const char* e = getenv("NERF_BWD_SKIP_DEAD"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
+static int field_wgrad_phase(const char* fn, const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
+                             float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
+                             const unsigned* live, void* stream);
+
 int nerf_field_wgrad_phase(const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
                            float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
                            void* stream) {
-    REQUIRE(act && delta && d_raw && partial && grad, "null pointer");
-    REQUIRE(n_rays >= 0 && n_samples >= 1 && phases >= 1 && phases <= 7 && (datapath == -1 || datapath == 0 || (datapath >= 4 && datapath <= 6)), "bad size / datapath (-1, 0, 4, 5, 6)");
+    return field_wgrad_phase(__func__, act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate, datapath, phases, params, nullptr, stream);
+}
+
+size_t nerf_live_tiles_words(int n_rays, int n_samples) {
+    if (n_rays <= 0 || n_samples <= 0) return 0;
+    const size_t P = (size_t)n_rays * n_samples;
+    if (P > ((size_t)1 << 36)) return 0;
+    return nerf::live_tiles((unsigned)((P + 31) / 32)).total;
+}
+
+int nerf_bwd_skip_dead(void) { return skip_dead_enabled() ? 1 : 0; }
+
+int nerf_field_wgrad_phase_live(const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
+                                float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
+                                const unsigned* live, void* stream) {
+    REQUIRE((reinterpret_cast<uintptr_t>(live) & 15) == 0, "live must be 16-byte aligned");
+    REQUIRE(!live || datapath != 0, "the fp32 datapath has no sparse form: live must be NULL");
+    return field_wgrad_phase(__func__, act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate, datapath, phases, params,
+                             skip_dead_enabled() ? live : nullptr, stream);
+}
+
+int nerf_field_dgrad_split_live(const float* packed3, const float* act, const float* d_raw, int n_rays, int n_samples,
+                                float* delta, int split, unsigned* live, void* stream) {
+    REQUIRE(packed3 && act && d_raw && delta, "null pointer");
+    REQUIRE(n_rays >= 0 && n_samples >= 1 && (split == 0 || split == 1 || split == 5), "bad size / split (0 bf16, 1 fp16, 5 fp16 with two-word saves)");
+    REQUIRE((reinterpret_cast<uintptr_t>(packed3) & 15) == 0 && (reinterpret_cast<uintptr_t>(act) & 15) == 0 &&
+            (reinterpret_cast<uintptr_t>(d_raw) & 15) == 0 && (reinterpret_cast<uintptr_t>(delta) & 15) == 0 &&
+            (reinterpret_cast<uintptr_t>(live) & 15) == 0,
+            "packed/act/d_raw/delta/live must be 16-byte aligned");
+    if (int rc = check_act_for_dgrad(__func__, act, true, n_rays, n_samples, split == 5 ? 1 : 0)) return rc;
+    tag_record(delta, 1, split == 5 ? DELTA_TILE32_F16X2 : split ? DELTA_TILE32_F16 : DELTA_TILE32_BF16, n_rays, n_samples);
+    return done(__func__, nerf::launch_field_dgrad3r(packed3, act, d_raw, n_rays, n_samples, delta, split, (hipStream_t)stream,
+                                                     skip_dead_enabled() ? live : nullptr));
+}
+
+#define REQUIRE_FN(cond, what) do { if (!(cond)) return nerf_api::fail_arg(fn, what); } while (0)
+static int field_wgrad_phase(const char* fn, const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
+                             float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
+                             const unsigned* live, void* stream) {
+    REQUIRE_FN(act && delta && d_raw && partial && grad, "null pointer");
+    REQUIRE_FN(n_rays >= 0 && n_samples >= 1 && phases >= 1 && phases <= 7 && (datapath == -1 || datapath == 0 || (datapath >= 4 && datapath <= 6)), "bad size / datapath (-1, 0, 4, 5, 6)");
     int rc;
-    const int recorded = datapath_from_tags(__func__, act, delta, n_rays, n_samples, &rc);
+    const int recorded = datapath_from_tags(fn, act, delta, n_rays, n_samples, &rc);
     if (rc) return rc;
     if (datapath < 0) {
-        REQUIRE(recorded >= 0, "datapath = -1 (as recorded) needs act and delta written by this library's forward / dgrad entry points");
+        REQUIRE_FN(recorded >= 0, "datapath = -1 (as recorded) needs act and delta written by this library's forward / dgrad entry points");
         datapath = recorded;
     } else if (recorded >= 0 && recorded != datapath) {
         snprintf(g_err, sizeof(g_err), "%s: datapath %d requested, but act / delta were written for datapath %d (the tiling and element type of "
-                 "the saved rows and deltas follow from the forward and dgrad entry points that produced them)", __func__, datapath, recorded);
+                 "the saved rows and deltas follow from the forward and dgrad entry points that produced them)", fn, datapath, recorded);
         return NERF_E_BADARG;
     }
-    REQUIRE(datapath == 0 || params, "the split datapaths need the canonical parameters (folded feature layer)");
-    return done(__func__, nerf::launch_field_wgrad(act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate,
-                                                   datapath, phases, (hipStream_t)stream, params));
+    REQUIRE_FN(datapath == 0 || params, "the split datapaths need the canonical parameters (folded feature layer)");
+    REQUIRE_FN(!live || datapath != 0, "the fp32 datapath has no sparse form: live must be NULL");
+    return done(fn, nerf::launch_field_wgrad(act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate,
+                                                   datapath, phases, (hipStream_t)stream, params, live));
 }
+#undef REQUIRE_FN
 
 int nerf_field_dgrad_split(const float* packed3, const float* act, const float* d_raw, int n_rays, int n_samples,
                            float* delta, int split, void* stream) {

@@ -192,6 +192,9 @@ struct WgradArgs {
     // wgrad1_kernel<SP, 3> (two-word operands, round 6): bytes from any A / B operand pointer to the LO words of the same operand
     // (the mirrors of the delta / save layouts: DeltaLayout3::lo, ActLayout3::lo)
     long a_lo_bytes, b_lo_bytes;
+    // wgrad1_kernel: the live-tile list of this pass (launchers.h, LiveTiles) or null = every tile.  A workgroup streams the live
+    // tiles of its chunk only: a dead tile's deltas are exact zeros (and were never written), its products add +-0 to sums that start at +0
+    const unsigned* live;
 };
 
 __device__ inline f32x4 load_row4(const float* base, int ld, long row, bool row_ok, int col, int ncols, int vec) {
@@ -477,7 +480,29 @@ __global__ __launch_bounds__(512) void wgrad1_kernel(WgradArgs a) {
     const long p_end = min(p_begin + (long)a.chunk_pts, a.P);
     const int nrows = (int)(p_end - p_begin);
     const int n_tiles = (nrows + WG1_STAGE_PTS - 1) / WG1_STAGE_PTS;
-    const int n_st = n_tiles;                                    // one stage per 32-point tile
+    const long tile0 = p_begin >> 5;
+    // one stage per 32-point tile that the ring visits: all of the chunk's, or the slice of the live list that falls into it
+    // (scalar loads through the constant address space; the list was written by earlier launches).  A list that names every tile
+    // takes the dense path.
+    const_words lv = nullptr;
+    int n_st = n_tiles;
+    if (a.live) {
+        const_words lw = as_const_words(a.live);
+        const unsigned count = lw[0], all = lw[1];
+        if (count != all) {
+            const LiveTiles lt = live_tiles(all);
+            auto before = [&](long t) {         // live tiles before tile t <= n_tiles of the launch
+                const unsigned w = (unsigned)(t >> 5), r = (unsigned)t & 31u;
+                unsigned c = lw[lt.prefix + w];
+                if (r) c += (unsigned)__builtin_popcount(lw[lt.bitmap + w] & ((1u << r) - 1u));
+                return c;
+            };
+            const unsigned lo = before(tile0);
+            n_st = (int)(before(tile0 + n_tiles) - lo);
+            lv = lw + LIVE_HEADER + lo;
+        }
+    }
+    const bool sparse = lv != nullptr;
     constexpr int STAGE_BYTES = TERMS == 3 ? 2 * WG1_STAGE_BYTES : WG1_STAGE_BYTES;      // 64 KiB: [d_hi | X_hi | d_lo | X_lo]
     constexpr int STAGES = TERMS == 3 ? WG1_LDS_BYTES / STAGE_BYTES : WG1_STAGES;        // 2 (one in flight) / 4 (three in flight)
 
@@ -512,17 +537,22 @@ __global__ __launch_bounds__(512) void wgrad1_kernel(WgradArgs a) {
         }
     }
     const char* rbase = reinterpret_cast<const char*>(jb.B);
-    const long tile0 = p_begin >> 5;
     const unsigned lds0 = lds_addr(sm1) + (unsigned)(sop * WG1_OP_BYTES + (wave & 3) * 4096);
     const long lo_bytes = TERMS == 3 ? (sop == 0 ? a.a_lo_bytes : a.b_lo_bytes) : 0;     // this wave's operand: hi -> lo words
+    // the tile (relative to the chunk's first) that stage st streams.  issue() is called with st = 0, 1, 2, ...: the number of the
+    // NEXT stage's tile is fetched one call ahead, so that the list's indirection does not sit in front of the DMA issue.  (The word
+    // behind the chunk's slice, read by the last call and never used, is another word of the list buffer.)
+    int t_next = sparse ? (int)(lv[0] - (unsigned)tile0) : 0;
     auto issue = [&](int st) {
-        const char* src = ray_tiles > 0 ? rbase + (size_t)((tile0 + st) / ray_tiles) * (size_t)(16 * sld) : cbase + (size_t)st * tile_bytes;
+        int t = st;
+        if (sparse) { t = t_next; t_next = (int)(lv[st + 1] - (unsigned)tile0); }
+        const char* src = ray_tiles > 0 ? rbase + (size_t)((tile0 + t) / ray_tiles) * (size_t)(16 * sld) : cbase + (size_t)t * tile_bytes;
         const unsigned dst = lds0 + (unsigned)(st % STAGES) * STAGE_BYTES;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) dma_1k_s(src, doff[u] + (unsigned)st * dstep[u], dst + 1024u * u);
+        for (int u = 0; u < 4; ++u) dma_1k_s(src, doff[u] + (unsigned)t * dstep[u], dst + 1024u * u);
         if constexpr (TERMS == 3) {             // the lo words of the same pieces, behind the hi blocks of the stage
 #pragma unroll
-            for (int u = 0; u < 4; ++u) dma_1k_s(src + lo_bytes, doff[u] + (unsigned)st * dstep[u], dst + WG1_STAGE_BYTES + 1024u * u);
+            for (int u = 0; u < 4; ++u) dma_1k_s(src + lo_bytes, doff[u] + (unsigned)t * dstep[u], dst + WG1_STAGE_BYTES + 1024u * u);
         }
     };
 
@@ -557,7 +587,7 @@ __global__ __launch_bounds__(512) void wgrad1_kernel(WgradArgs a) {
         const unsigned char* stage = sm1 + (st % STAGES) * STAGE_BYTES;
         const unsigned char* sa = stage + (wave_n * 128) * 64;
         const unsigned char* sb = stage + WG1_OP_BYTES + (wave_k * 64) * 64;
-        const int left = nrows - st * WG1_STAGE_PTS;
+        const int left = nrows - (sparse ? (int)(lv[st] - (unsigned)tile0) : st) * WG1_STAGE_PTS;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             u32x4 bf[2], bl[2];
@@ -627,7 +657,9 @@ __global__ __launch_bounds__(512) void wgrad1_kernel(WgradArgs a) {
         }
     };
     const bool full_tile = wave_has_work && ni == 4 && nj == 2;                 // wave-uniform
-    const int n_full = (nrows % WG1_STAGE_PTS == 0) ? n_tiles : n_tiles - 1;     // stages whose 32 points all exist
+    // stages whose 32 points all exist: all but the ragged last tile of the launch, when this chunk visits it
+    int n_full = (nrows % WG1_STAGE_PTS == 0) ? n_tiles : n_tiles - 1;
+    if (sparse) n_full = (n_st > 0 && ((int)(lv[n_st - 1] - (unsigned)tile0) + 1) * WG1_STAGE_PTS > nrows) ? n_st - 1 : n_st;
 
     // ring: stages st+1 .. st+3 are in flight while st is consumed.  vmcnt retires in order: "at most 4 * (younger
     // stages in flight) outstanding" = this wave's pieces of st have landed.  (Two-word form: two 64-KiB stages, st+1 in flight.)
@@ -847,7 +879,7 @@ __global__ void replicate_dir_bf16_kernel(const float* __restrict__ dir_ray, u32
 // phases: bit 0 = full-width jobs, bit 1 = narrow jobs, bit 2 = chunk reduction (7 = everything)
 hipError_t launch_field_wgrad(const float* act, const float* delta, const float* d_raw, int n_rays, int S,
                               float* partial, float* grad, int accumulate, int datapath, int phases, hipStream_t stream,
-                              const float* params) {
+                              const float* params, const unsigned* live) {
     // datapath: 0 = fp32 (point-major rows); 4 = bf16 operands, rows saved by the 16-point forward (16-point tiles, row16h order),
     // deltas in 32-point tiles; 5 = the same with fp16 elements (deltas scaled by the launch's power of two, removed in the reduction);
     // 6 = fp16 TWO-WORD operands (hi and lo words saved by the SAVE = 3 forward and the TWO dgrad: three MFMAs per product)
@@ -857,6 +889,7 @@ hipError_t launch_field_wgrad(const float* act, const float* delta, const float*
     const bool split16 = datapath != 0;      // split datapaths: 16-bit operands streamed by wgrad1_kernel,
     const bool fold = split16;               //   feature layer folded into the view branch (nerf_common.h)
     if (fold && !params) return hipErrorInvalidValue;
+    if (live && !split16) return hipErrorInvalidValue;      // the fp32 anchor stays dense
     const long P = (long)n_rays * S;
     if (P <= 0) return hipSuccess;
     hipError_t e;
@@ -990,6 +1023,7 @@ hipError_t launch_field_wgrad(const float* act, const float* delta, const float*
     big.partial = small.partial = partial;
     big.a_lo_bytes = lo_a;
     big.b_lo_bytes = lo_b;
+    big.live = live;
     small.total_tiles = small_tiles;
     static bool attr_set = false;
     if (!attr_set) {

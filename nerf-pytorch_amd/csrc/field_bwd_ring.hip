@@ -21,6 +21,7 @@ struct FieldBwdRingArgs {
     const float* d_raw;     // [P][4]
     float* delta;           // delta_layout3(P): 32-point feature-major tiles
     int n_rays, S;
+    const unsigned* live;   // live-tile list (launchers.h, LiveTiles) or null: wave slot -> tile number; dead tiles are neither computed nor stored
 };
 
 // units of the transposed stream (P3B) in consumption order: W'^T 8 k-steps x 2 | (feature_linear^T 32: skipped) | L7^T .. L1^T 7 x 32
@@ -45,15 +46,46 @@ __device__ inline void apply_mask3r(float (&d)[NV], const f32x16* acc, u32x4 m) 
 // max|d_raw| over the launch (its bit pattern: non-negative floats order like unsigned integers, so the atomic maximum does not
 // depend on the order of the atomics) -> DeltaLayout3::scale word 0, zeroed by the launcher; the consumers derive the power-of-two
 // scale from it (nerf_common.h, delta_scale_bits).
-__global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restrict__ d_raw, long n4, unsigned* __restrict__ slot) {
+// LIVE: the same pass over d_raw also says which 32-point tiles carry anything.  A lane holds one point (four words), 32 consecutive
+// lanes one tile, a workgroup iteration 1024 points = 32 tiles = ONE word of the liveness bitmap (bit b = tile 32 * word + b has a
+// word with (bits & 0x7fffffff) != 0: NaN, Inf and subnormals are live, +-0 is not).  No atomics: every bitmap word has one writer.
+template <bool LIVE>
+__global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restrict__ d_raw, long n4, unsigned* __restrict__ slot,
+                                                          unsigned* __restrict__ bitmap) {
     float m = 0.0f;
-    for (long i = (long)blockIdx.x * 1024 + threadIdx.x; i < n4; i += (long)gridDim.x * 1024) {
-        const f32x4 v = d_raw[i];
-        m = fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))), m);     // (NaN: fmaxf keeps the other operand)
+    __shared__ float wm[16];
+    __shared__ unsigned wb[2][16];
+    if constexpr (LIVE) {
+        const long n_it = (n4 + 1023) / 1024;           // = bitmap words
+        int par = 0;
+        for (long it = blockIdx.x; it < n_it; it += gridDim.x, par ^= 1) {
+            const long i = it * 1024 + threadIdx.x;
+            unsigned any = 0u;
+            if (i < n4) {
+                const f32x4 v = d_raw[i];
+                m = fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))), m);
+                any = (__float_as_uint(v[0]) | __float_as_uint(v[1]) | __float_as_uint(v[2]) | __float_as_uint(v[3])) & 0x7fffffffu;
+            }
+            const unsigned long long b = __ballot(any != 0u);
+            const unsigned two = ((b & 0xffffffffull) ? 1u : 0u) | ((b >> 32) ? 2u : 0u);       // this wave's two tiles
+            if ((threadIdx.x & 63) == 0) wb[par][threadIdx.x >> 6] = two << (2 * (threadIdx.x >> 6));
+            __syncthreads();        // (wb is double-buffered by iteration parity: one barrier per iteration is enough)
+            if (threadIdx.x == 0) {
+                unsigned w = 0u;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) w |= wb[par][k];
+                bitmap[it] = w;
+            }
+        }
+        if (!slot) return;
+    } else {
+        for (long i = (long)blockIdx.x * 1024 + threadIdx.x; i < n4; i += (long)gridDim.x * 1024) {
+            const f32x4 v = d_raw[i];
+            m = fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))), m);     // (NaN: fmaxf keeps the other operand)
+        }
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    __shared__ float wm[16];
     if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x < 16) {
@@ -61,6 +93,55 @@ __global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restric
 #pragma unroll
         for (int o = 8; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
         if (threadIdx.x == 0) atomicMax(slot, __float_as_uint(m));
+    }
+}
+
+// bitmap -> the ascending list of live tile numbers, its count, and per bitmap word the number of live tiles before it (the
+// weight-gradient GEMM finds its chunk's slice of the list from those without a search).  One workgroup, a scan: the order is fixed.
+__global__ __launch_bounds__(1024) void live_scan_kernel(unsigned* __restrict__ live, unsigned n_tiles) {
+    const LiveTiles lt = live_tiles(n_tiles);
+    const unsigned* bitmap = live + lt.bitmap;
+    unsigned* prefix = live + lt.prefix;
+    unsigned* list = live + LIVE_HEADER;
+    __shared__ unsigned ws[16];
+    __shared__ unsigned carry;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry = 0u;
+    __syncthreads();
+    for (unsigned w0 = 0; w0 < lt.n_words; w0 += 1024) {
+        const unsigned w = w0 + threadIdx.x;
+        unsigned bits = w < lt.n_words ? bitmap[w] : 0u;
+        const unsigned c = __popc(bits);
+        unsigned inc = c;           // inclusive scan inside the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned t = __shfl_up(inc, o);
+            if (lane >= o) inc += t;
+        }
+        if (lane == 63) ws[wave] = inc;
+        __syncthreads();
+        unsigned base = carry;
+        for (int k = 0; k < wave; ++k) base += ws[k];
+        unsigned pos = base + inc - c;
+        if (w < lt.n_words) {
+            prefix[w] = pos;
+            while (bits) {
+                const unsigned b = __ffs(bits) - 1;
+                bits &= bits - 1;
+                list[pos++] = 32u * w + b;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 1023) carry = base + inc;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const unsigned count = carry;
+        prefix[lt.n_words] = count;
+        live[0] = count;
+        live[1] = n_tiles;
+        live[2] = 0u;
+        live[3] = 0u;
     }
 }
 
@@ -73,7 +154,17 @@ __global__ __launch_bounds__(FIELD3_WAVES * 64) void field_dgrad3r_kernel(FieldB
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5;
     const size_t P = (size_t)a.n_rays * a.S;
-    const size_t p_raw = ((size_t)blockIdx.x * FIELD3_WAVES + wave) * PTS_PER_WAVE3 + (lane & 31);
+    // this wave's tile of d_raw and of every delta region.  With a live list: the tile in slot 4 * workgroup + wave of the list; a
+    // workgroup without a first slot has nothing to do, and a wave without a slot (last populated workgroup) takes part in the ring
+    // with the tile BEHIND the padded point range: loads from point P - 1, stores to the dump tile (valid / tile_ok below)
+    size_t tile = (size_t)blockIdx.x * FIELD3_WAVES + wave;
+    if (a.live) {
+        const_words lw = as_const_words(a.live);
+        const unsigned count = lw[0];
+        if ((unsigned)blockIdx.x * FIELD3_WAVES >= count) return;
+        tile = (unsigned)tile < count ? (size_t)lw[LIVE_HEADER + tile] : pad32(P) / 32;
+    }
+    const size_t p_raw = tile * PTS_PER_WAVE3 + (lane & 31);
     const bool valid = p_raw < P;
     const size_t p = valid ? p_raw : P - 1;
 
@@ -83,7 +174,6 @@ __global__ __launch_bounds__(FIELD3_WAVES * 64) void field_dgrad3r_kernel(FieldB
 
     const ActLayout3 al = act_layout3(P, (size_t)a.n_rays, TWO);
     const DeltaLayout3 dl = delta_layout3(P, TWO);
-    const size_t tile = (size_t)blockIdx.x * FIELD3_WAVES + wave;          // this wave's tile of every delta region
     f32x4 g = *reinterpret_cast<const f32x4*>(a.d_raw + p * 4);             // (d_rgb3, d_sigma)
     if (SP::F16) {      // the whole chain is linear in d_raw: run it on s * d_raw (s = 2^k, exact), see DeltaLayout3::scale
         const float sc = __uint_as_float(delta_scale_bits(reinterpret_cast<const unsigned*>(a.delta + dl.scale)[0], false));
@@ -219,21 +309,33 @@ static hipError_t launch_dgrad_one(const FieldBwdRingArgs& ba, unsigned blocks, 
 }
 
 // split: 0 bf16, 1 fp16 parts (of the products and of the stored deltas); 5 = fp16 with two-word deltas (and a two-word save buffer)
+// live (nullable, live_tiles(P).total words): the launch writes the live-tile list there and skips the dead tiles
 hipError_t launch_field_dgrad3r(const float* packed3, const float* act, const float* d_raw, int n_rays, int S,
-                                float* delta, int split, hipStream_t stream) {
+                                float* delta, int split, hipStream_t stream, unsigned* live) {
     const long P = (long)n_rays * S;
     if (P <= 0) return hipSuccess;
-    FieldBwdRingArgs ba{packed3, act, d_raw, delta, n_rays, S};
+    FieldBwdRingArgs ba{packed3, act, d_raw, delta, n_rays, S, live};
     const unsigned blocks = (unsigned)((P + PTS_PER_WG3 - 1) / PTS_PER_WG3);
+    unsigned* slot = nullptr;
     if (split) {
         // (the scale word sits in the hi part of the layout: at the same offset in the one- and the two-word layout)
-        unsigned* slot = reinterpret_cast<unsigned*>(delta + delta_layout3((size_t)P).scale);
+        slot = reinterpret_cast<unsigned*>(delta + delta_layout3((size_t)P).scale);
         hipError_t e = hipMemsetAsync(slot, 0, 16, stream);
         if (e != hipSuccess) return e;
-        const unsigned sb = (unsigned)min((long)1024, (P + 1023) / 1024);      // one 16-byte load per thread: the launch is latency, not bytes
-        hipLaunchKernelGGL(delta_amax_kernel, dim3(sb), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot);
-        return split == 5 ? launch_dgrad_one<SplitF16, true>(ba, blocks, stream) : launch_dgrad_one<SplitF16>(ba, blocks, stream);
     }
+    if (live) {
+        // one bitmap word per 1024 points and workgroup iteration: a grid of up to 1024 workgroups strides over them
+        const LiveTiles lt = live_tiles((unsigned)((P + 31) / 32));
+        const unsigned sb = (unsigned)min((long)1024, (P + 1023) / 1024);
+        hipLaunchKernelGGL(delta_amax_kernel<true>, dim3(sb), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot, live + lt.bitmap);
+        hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, stream, live, lt.n_tiles);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    } else if (split) {
+        const unsigned sb = (unsigned)min((long)1024, (P + 1023) / 1024);      // one 16-byte load per thread: the launch is latency, not bytes
+        hipLaunchKernelGGL(delta_amax_kernel<false>, dim3(sb), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot, (unsigned*)nullptr);
+    }
+    if (split) return split == 5 ? launch_dgrad_one<SplitF16, true>(ba, blocks, stream) : launch_dgrad_one<SplitF16>(ba, blocks, stream);
     return launch_dgrad_one<SplitBF16>(ba, blocks, stream);
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 
 namespace nerf {
 
@@ -93,9 +94,11 @@ hipError_t launch_field_bwd(const float* packed, const float* act, const float* 
                             float* delta, float* partial, float* grad, int accumulate, hipStream_t stream);
 hipError_t launch_field_dgrad(const float* packed, const float* act, const float* d_raw, int n_rays, int S,
                               float* delta, hipStream_t stream);
+// live (split datapaths, nullable): the live-tile list the delta chain of the same pass wrote; the GEMM streams the live tiles only
 hipError_t launch_field_wgrad(const float* act, const float* delta, const float* d_raw, int n_rays, int S,
                               float* partial, float* grad, int accumulate, int datapath /* 0 fp32, 4 bf16 operands, 5 fp16 operands */,
-                              int phases, hipStream_t stream, const float* params);     // canonical parameters: required by the split datapaths
+                              int phases, hipStream_t stream, const float* params,      // canonical parameters: required by the split datapaths
+                              const unsigned* live = nullptr);
 size_t wgrad_partial_floats(long P);
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2, float eps, int step,
                        hipStream_t stream);
@@ -113,6 +116,27 @@ hipError_t launch_field_fwd16r_last(const float* packed3, const float* rays, int
                                     int n_rays, int S, float* raw, const float* packed3_next, float* raw_next, int S_next,
                                     hipStream_t stream);
 hipError_t launch_field_dgrad3r(const float* packed3, const float* act, const float* d_raw, int n_rays, int S,
-                                float* delta, int split, hipStream_t stream);
+                                float* delta, int split, hipStream_t stream, unsigned* live = nullptr);
+
+// The live-tile list of one backward pass (caller-owned words; written by launch_field_dgrad3r, read by the delta chain and the
+// weight-gradient GEMM).  Tile t = points 32 t .. 32 t + 31 of the launch; dead = all 128 words of its d_raw are +-0.
+//   [0] count of live tiles   [1] n_tiles   [2], [3] zero
+//   [LIVE_HEADER + i]   the live tile numbers, ascending, i < count (n_tiles words reserved)
+//   [bitmap + w]        bit b = tile 32 w + b is live (n_words words)
+//   [prefix + w]        live tiles before tile 32 w (n_words + 1 words: the last one = count)
+constexpr unsigned LIVE_HEADER = 4;
+// the kernels read the list (words an EARLIER launch wrote) through the constant address space: a uniform address becomes a scalar load
+typedef const unsigned __attribute__((address_space(4)))* const_words;
+__device__ inline const_words as_const_words(const unsigned* p) { return (const_words)(uintptr_t)p; }
+struct LiveTiles { unsigned n_tiles, n_words; size_t bitmap, prefix, total; };
+__host__ __device__ inline LiveTiles live_tiles(unsigned n_tiles) {
+    LiveTiles l;
+    l.n_tiles = n_tiles;
+    l.n_words = (n_tiles + 31) / 32;
+    l.bitmap = LIVE_HEADER + (size_t)n_tiles;
+    l.prefix = l.bitmap + l.n_words;
+    l.total = (l.prefix + l.n_words + 1 + 3) & ~(size_t)3;
+    return l;
+}
 
 }  // namespace nerf

@@ -91,6 +91,10 @@ def _declare(lib):
         "nerf_occ_gather": (i, [p, p, l, p, p]),
         "nerf_occ_fold_rays": (i, [p, p, p, i, i, p, i, p]),
         "nerf_occ_density_update": (i, [p, l, i, f, p, p]),
+        "nerf_live_tiles_words": (sz, [i, i]),
+        "nerf_bwd_skip_dead": (i, []),
+        "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
+        "nerf_field_wgrad_phase_live": (i, [p, p, p, i, i, p, p, i, i, i, p, p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)      # AttributeError here = header / library mismatch: fail loudly
@@ -112,7 +116,8 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_dense_wgrad", "nerf_range_scan", "nerf_field_input_grad", "nerf_raw2outputs_bwd_geom", "nerf_embed_bwd",
            "nerf_sample_ray_views", "nerf_ray_pose_grad",
            "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate",
-           "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update"]
+           "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update",
+           "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
 
 
 def lib():
@@ -941,6 +946,23 @@ def sample_pdf(bins, weights, n_samples, u, u_lin):
     return out
 
 
+# Dead-tile skipping in the backward of the split datapaths (include/nerf_hip.h): the delta chain and the weight-gradient GEMM leave out
+# the 32-point tiles whose d_raw is all +-0.  NERF_BWD_SKIP_DEAD=0 (read once per process, here and in the library): dense everywhere.
+BWD_SKIP_DEAD = os.environ.get("NERF_BWD_SKIP_DEAD", "1") != "0"
+_LIVE_LISTS = {}        # device -> int32 words of the live-tile list of the pass in flight (grown on demand, never per step)
+LAST_LIVE = None        # the list the last sparse field_bwd used (tools / tests read the counts back AFTER the timed region), or None
+
+
+def live_list(n_rays, n_samples, device):
+    """the cached live-tile list buffer of `device`, at least nerf_live_tiles_words(n_rays, n_samples) words (stream-ordered reuse:
+    the next pass's launches are enqueued behind this pass's readers)"""
+    words = lib().nerf_live_tiles_words(n_rays, n_samples)
+    buf = _LIVE_LISTS.get(device)
+    if buf is None or buf.numel() < words:
+        buf = _LIVE_LISTS[device] = torch.zeros(max(words, 1 << 16), dtype=torch.int32, device=device)
+    return buf
+
+
 BYTES_INPUT_GRAD_PER_POINT = 2 * (256 + 256 + 128)      # deltas the input-gradient kernel reads per point (16-bit words; x2 fp32 / hi + lo)
 
 
@@ -995,11 +1017,22 @@ def _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partia
         raise NerfHipError("field_bwd: `act` is not a save buffer this library's forward wrote (no layout record): the split "
                            "datapaths cannot guess its tiling and element type")
     P = n * S
+    # the sparse forms, unless somebody else reads this pass's deltas: the input gradient and the range monitor's delta scan would
+    # meet the tiles nobody wrote
+    global LAST_LIVE
+    live = None
+    if split is not None and BWD_SKIP_DEAD and input_grad is None and not (split in (1, 5) and RANGE_MONITOR.delta_scans_due > 0):
+        live = live_list(n, S, d_raw.device)
+    LAST_LIVE = live
     if split is not None:
         with _timed("field_dgrad3r_kernel<fp16, hi+lo>" if two else "field_dgrad3r_kernel<fp16>" if split else "field_dgrad3r_kernel<bf16 out>",
                     FLOP_DGRAD3_PER_POINT * P, BYTES_DELTA3_BF16_PER_POINT * P * (2 if two else 1)):
-            _check(L.nerf_field_dgrad_split(_ptr(packed, "packed3"), _ptr(act, "act"), _ptr(d_raw, "d_raw"), n, S, _ptr(delta), split, _stream()),
-                   "nerf_field_dgrad_split")
+            if live is not None:
+                _check(L.nerf_field_dgrad_split_live(_ptr(packed, "packed3"), _ptr(act, "act"), _ptr(d_raw, "d_raw"), n, S, _ptr(delta), split,
+                                                     live.data_ptr(), _stream()), "nerf_field_dgrad_split_live")
+            else:
+                _check(L.nerf_field_dgrad_split(_ptr(packed, "packed3"), _ptr(act, "act"), _ptr(d_raw, "d_raw"), n, S, _ptr(delta), split, _stream()),
+                       "nerf_field_dgrad_split")
     else:
         with _timed("field_dgrad_kernel", FLOP_DGRAD_PER_POINT * P, BYTES_DELTA_PER_POINT * P):
             _check(L.nerf_field_dgrad(_ptr(packed, "packed"), _ptr(act, "act"), _ptr(d_raw, "d_raw"), n, S, _ptr(delta),
@@ -1016,22 +1049,26 @@ def _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partia
     args = (_ptr(act, "act"), _ptr(delta), _ptr(d_raw, "d_raw"), n, S, _ptr(partial), _ptr(grad, "grad"),
             int(bool(accumulate)), datapath)
     tail = (_ptr(params, "params", True), _stream())
+    wgrad_phase = L.nerf_field_wgrad_phase
+    if live is not None:
+        wgrad_phase = L.nerf_field_wgrad_phase_live
+        tail = (tail[0], live.data_ptr(), tail[1])
     if TIMER is None:
-        _check(L.nerf_field_wgrad_phase(*args, 7, *tail), "nerf_field_wgrad_phase")
+        _check(wgrad_phase(*args, 7, *tail), "nerf_field_wgrad_phase")
         return grad
     if gemm16:      # all 12 jobs stream 16-bit operands straight into the MFMA
         with _timed("wgrad1_kernel<fp16, 3 terms>" if two else "wgrad1_kernel<fp16>" if split else "wgrad1_kernel", FLOP_WGRAD3_PER_POINT * P,
                     BYTES_WGRAD_MIXED_PER_POINT * P * (2 if two else 1)):
-            _check(L.nerf_field_wgrad_phase(*args, 3, *tail), "nerf_field_wgrad_phase")
+            _check(wgrad_phase(*args, 3, *tail), "nerf_field_wgrad_phase")
     else:
         with _timed("wgrad256_kernel", FLOP_WGRAD_BIG_PER_POINT * P, BYTES_WGRAD_BIG_PER_POINT * P):
-            _check(L.nerf_field_wgrad_phase(*args, 1, *tail), "nerf_field_wgrad_phase")
+            _check(wgrad_phase(*args, 1, *tail), "nerf_field_wgrad_phase")
         with _timed("wgrad_kernel(narrow jobs)", (FLOP_WGRAD_PER_POINT - FLOP_WGRAD_BIG_PER_POINT) * P, BYTES_WGRAD_SMALL_PER_POINT * P):
-            _check(L.nerf_field_wgrad_phase(*args, 2, *tail), "nerf_field_wgrad_phase")
+            _check(wgrad_phase(*args, 2, *tail), "nerf_field_wgrad_phase")
     # chunks of partial sums the reduction reads (csrc/field_bwd.hip, wgrad_chunks)
     n_chunks = min((19 if P < 400000 else 39) if gemm16 else 128, max(1, (P + 255) // 256))
     with _timed("wgrad_reduce_kernel", 0.0, 4.0 * N_PARAMS * (n_chunks + 1)):
-        _check(L.nerf_field_wgrad_phase(*args, 4, *tail), "nerf_field_wgrad_phase")
+        _check(wgrad_phase(*args, 4, *tail), "nerf_field_wgrad_phase")
     return grad
 
 

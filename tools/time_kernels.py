@@ -3,7 +3,12 @@ back-to-back launches on torch's current stream.  For A/B timing of two builds o
 
     NERF_HIP_LIB=/path/to/other/libnerf_hip.so python tools/time_kernels.py [--precision fp16x3] [--reps 20] [--rounds 3]
 
-prints one JSON line: {kernel: {"coarse_ms": .., "fine_ms": ..}}.  tools/ab.sh alternates two libraries."""
+prints one JSON line: {kernel: {"coarse_ms": .., "fine_ms": ..}}.  tools/ab.sh alternates two libraries.
+
+    --live          the sparse forms of the delta chain and the weight-gradient GEMM (nerf_field_dgrad_split_live /
+                    nerf_field_wgrad_phase_live; "dgrad" includes the liveness launches).  With the default d_raw = randn no tile is
+                    dead: what a dense batch pays for the list.
+    --dead SHARE    zero that share of d_raw's 32-point tiles, in runs of 13 tiles (with or without --live)"""
 import argparse
 import json
 import os
@@ -23,6 +28,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--rays", type=int, default=4096)
     ap.add_argument("--only", default="")
+    ap.add_argument("--live", action="store_true")
+    ap.add_argument("--dead", type=float, default=0.0)
     args = ap.parse_args()
     hb = npa.hip_backend
     L = hb.lib()
@@ -54,6 +61,10 @@ def main():
     for tag, S in (("coarse", 64), ("fine", 192)):
         z = torch.sort(torch.rand(n, S, device=dev) * 4 + 2, -1)[0]
         d_raw = torch.randn(n, S, 4, device=dev) * 1e-4
+        if args.dead > 0:
+            T = n * S // 32
+            runs = torch.rand((T + 12) // 13, device=dev) < args.dead
+            d_raw.view(T, 32, 4)[runs.repeat_interleave(13)[:T]] = 0.0
         raw = torch.empty(n, S, 4, device=dev)
         act = torch.empty(max(hb.act_floats(n, S), hb.act_floats(n, S, prec)), device=dev)
         delta = torch.empty(max(L.nerf_delta_floats(n, S), hb.delta_floats(n, S, prec)), device=dev)
@@ -73,12 +84,16 @@ def main():
         wargs = (act.data_ptr(), delta.data_ptr(), d_raw.data_ptr(), n, S, partial.data_ptr(), grad.data_ptr(), 0, -1)
         wgemm = lambda: L.nerf_field_wgrad_phase(*wargs, 3, flat.data_ptr(), s)
         wred = lambda: L.nerf_field_wgrad_phase(*wargs, 4, flat.data_ptr(), s)
+        if args.live and split is not None:
+            live = torch.zeros(L.nerf_live_tiles_words(n, S), dtype=torch.int32, device=dev)
+            dgrad = lambda: L.nerf_field_dgrad_split_live(packed.data_ptr(), act.data_ptr(), d_raw.data_ptr(), n, S, delta.data_ptr(), split, live.data_ptr(), s)
+            wgemm = lambda: L.nerf_field_wgrad_phase_live(*wargs, 3, flat.data_ptr(), live.data_ptr(), s)
         assert fwd_s() == 0 and dgrad() == 0 and wgemm() == 0 and wred() == 0, L.nerf_last_error()
         for name, fn in (("fwd_infer", fwd_i), ("fwd_save", fwd_s), ("dgrad", dgrad), ("wgrad_gemm", wgemm), ("wgrad_reduce", wred)):
             if args.only and name not in args.only.split(","):
                 continue
             out.setdefault(name, {})[tag + "_ms"] = timed(fn)
-    print(json.dumps({"lib": os.environ.get("NERF_HIP_LIB", "in-tree"), "precision": prec, "kernels": out}))
+    print(json.dumps({"lib": os.environ.get("NERF_HIP_LIB", "in-tree"), "precision": prec, "live": bool(args.live), "dead": args.dead, "kernels": out}))
 
 
 if __name__ == "__main__":
