@@ -463,6 +463,17 @@ int nerf_occ_fold_rays(const int* slot, const float* z_vals, const float* d_rec,
 /* density[c] = max(density[c] * decay, max_k sigma[c][k]) for a run of n_cells cells, in place (pass density + first_cell): one fp32
  * multiplication and one maximum; a NaN among the samples counts as -inf; written as m > d ? m : d with d = density[c] * decay. */
 int nerf_occ_density_update(const float* sigma, long n_cells, int samples_per_cell, float decay, float* density, void* stream);
+/* ---- the occupied span of a ray (additive in ABI v10): per ray (o, d, near, far) = rays[r][0:8] the first and the last occupied
+ * stretch it crosses inside [near, far] -- a stretch is one cell, or one stretch outside the box, which counts as occupied iff
+ * outside_skip == 0 -- found by two Amanatides-Woo walks over the grid's bits, one from either end:
+ *   span[r] = (max(near, t_first - pad), min(far, t_last + pad)),  pad = 2^-10 / max_a |d[a] * scale[a]| (2^-10 cell on the fastest
+ *   axis), hit[r] = 1;  or span[r] = (near, far) copied bit for bit and hit[r] = 0 when nothing occupied is crossed, near >= far, a
+ *   component of the record is NaN or infinite, or d = 0.
+ * Stretches shorter than 2^-10 cell (on the fastest axis) are not looked at: the result lies between the float64 hull of all occupied
+ * stretches and that of the stretches longer than 2^-9 cell (OccupancyGrid.ray_span_reference), and on a hit near <= near' < far' <=
+ * far.  Both walks take at most res[0] + res[1] + res[2] + 3 steps.  Reads 32 B per ray and the words of the cells walked, writes
+ * 12 B per ray; no atomics: the same inputs give the same bits.  ray_stride >= 8; span 8-byte aligned. */
+int nerf_occ_ray_span(const NerfOccGrid* grid, const float* rays, int ray_stride, int n_rays, float* span, int* hit, void* stream);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,7 @@ def _declare(lib):
         "nerf_occ_gather": (i, [p, p, l, p, p]),
         "nerf_occ_fold_rays": (i, [p, p, p, i, i, p, i, p]),
         "nerf_occ_density_update": (i, [p, l, i, f, p, p]),
+        "nerf_occ_ray_span": (i, [p, p, i, i, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -116,7 +117,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_dense_wgrad", "nerf_range_scan", "nerf_field_input_grad", "nerf_raw2outputs_bwd_geom", "nerf_embed_bwd",
            "nerf_sample_ray_views", "nerf_ray_pose_grad",
            "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate",
-           "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update",
+           "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
 
 
@@ -1176,6 +1177,22 @@ def occ_density_update(sigma, samples_per_cell, decay, density):
     _check(lib().nerf_occ_density_update(_ptr(sigma, "sigma"), n_cells, int(samples_per_cell), float(decay), _ptr(density, "density"),
                                          _stream()), "nerf_occ_density_update")
     return density
+
+
+def occ_ray_span(desc, rays):
+    """nerf_occ_ray_span: (span fp32 [n, 2], hit int32 [n]) of rays [n, >= 8] -- the ray's interval clipped to the first / last
+    occupied stretch it crosses, (near, far) unchanged and hit = 0 where it crosses none"""
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise NerfHipError("occ_ray_span: rays [n, >= 8] (o, d, near, far, ...)")
+    n, stride = rays.shape
+    span = torch.empty((n, 2), dtype=torch.float32, device=rays.device)
+    hit = torch.empty(n, dtype=torch.int32, device=rays.device)
+    if n == 0:
+        return span, hit
+    with _timed("occ_ray_span_kernel", 0.0, 44.0 * n):
+        _check(lib().nerf_occ_ray_span(ctypes.byref(desc), _ptr(rays, "rays"), stride, n, _ptr(span, "span"), hit.data_ptr(), _stream()),
+               "nerf_occ_ray_span")
+    return span, hit
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

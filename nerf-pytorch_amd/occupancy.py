@@ -54,7 +54,9 @@ class OccupancyGrid:
     ``outside="evaluate"`` (default): a point outside the box is evaluated -- the grid never hides what it does not cover;
     ``outside="skip"``: it is skipped (scenes bounded by the box).  A new grid is all-occupied.
     ``last_stats`` = {"evaluated", "total"}: sample points sent through the network / of the passes, for the last render_rays (or
-    batchify_rays / render: summed over its chunks) call that used this grid."""
+    batchify_rays / render: summed over its chunks) call that used this grid; with clip_to_occupancy=True also {"rays_hit", "rays"}.
+    ``ray_span`` / ``clip_rays`` give the grid its second use: per ray the span from the first to the last occupied cell it crosses
+    (``ray_span_reference`` is the definition), which render_rays(clip_to_occupancy=True) samples instead of [near, far]."""
 
     def __init__(self, lo, hi, resolution, outside="evaluate", device=None):
         if outside not in _OUTSIDE:
@@ -118,6 +120,71 @@ class OccupancyGrid:
         bits = self.bits if self.bits.device == dev else self.bits.to(dev)
         bit = ((bits[c >> 5].to(torch.int64) >> (c & 31)) & 1).bool()
         return torch.where(inside, bit, torch.full_like(bit, self.outside == "evaluate"))
+
+    # ------------------------------------------------------------------ the occupied span of a ray
+    def ray_span_reference(self, rays):
+        """The definition of the occupied span, in float64 plain torch: rays [N, >= 8] (o, d, near, far; any device) ->
+        (hit bool [N, 2], near_all, far_all, near_thick, far_thick), float64 [N] each.
+
+        A ray crosses the Rx + 1 / Ry + 1 / Rz + 1 cell planes of the axes at depths t (a zero direction component crosses none);
+        those inside [near, far], with near and far, cut the interval into segments: one cell each, or one stretch outside the box.
+        A segment is occupied by the rule of ``occupied()`` applied to its midpoint (inside iff 0 <= g < R on all axes, cell floor(g),
+        outside counts iff outside == "evaluate"), g = (o + d t - lo) * scale evaluated in float64.  ``*_all`` is the hull of the
+        occupied segments of positive length, ``*_thick`` that of the occupied segments longer than 2^-9 cell, a length being measured
+        in grid units along the ray's fastest axis (dt * max_a |d_a scale_a|); hit[:, 0] / hit[:, 1] say whether the all / the thick
+        hull exists, and where it does not the pair is the ray's own (near, far).  A ray with a NaN or infinite component, or with
+        near >= far, has no hull.  ``ray_span`` (the kernel) lies between the two hulls."""
+        dev = rays.device
+        if rays.shape[0] > 4096:        # (the segments of 4096 rays at 512^3 are 150 MB of float64)
+            parts = [self.ray_span_reference(rays[i:i + 4096]) for i in range(0, rays.shape[0], 4096)]
+            return tuple(torch.cat(p, 0) for p in zip(*parts))
+        r = rays.detach()[:, :8].to(torch.float64)
+        ok = torch.isfinite(r).all(-1) & (r[:, 6] < r[:, 7])
+        safe = torch.tensor([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=dev)
+        r = torch.where(ok[:, None], r, safe)
+        near, far = r[:, 6], r[:, 7]
+        f = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), device=dev)
+        res = f(self.resolution)
+        go, gd = (r[:, 0:3] - f(self.lo)) * f(self.scale), r[:, 3:6] * f(self.scale)
+        fastest = gd.abs().amax(-1)
+        cuts = [near[:, None], far[:, None]]
+        for a in range(3):
+            k = torch.arange(self.resolution[a] + 1, dtype=torch.float64, device=dev)
+            moves = gd[:, a] != 0
+            t = (k[None, :] - go[:, a:a + 1]) / torch.where(moves, gd[:, a], torch.ones_like(near))[:, None]
+            cuts.append(torch.where(moves[:, None], t, near[:, None]))
+        t = torch.minimum(torch.maximum(torch.cat(cuts, -1), near[:, None]), far[:, None]).sort(-1).values
+        t0, t1 = t[:, :-1], t[:, 1:]
+        g = go[:, None, :] + gd[:, None, :] * (0.5 * (t0 + t1))[..., None]
+        inside = ((g >= 0) & (g < res)).all(-1)
+        i = torch.floor(torch.where(inside[..., None], g, torch.zeros_like(g))).to(torch.int64)
+        c = (i[..., 0] * self.resolution[1] + i[..., 1]) * self.resolution[2] + i[..., 2]
+        bits = self.bits if self.bits.device == dev else self.bits.to(dev)
+        bit = ((bits[c >> 5].to(torch.int64) >> (c & 31)) & 1).bool()
+        occ = torch.where(inside, bit, torch.full_like(bit, self.outside == "evaluate")) & ok[:, None]
+        length = t1 - t0
+        inf = torch.full_like(t0, float("inf"))
+        out, hits = [], []
+        for keep in (occ & (length > 0), occ & (length * fastest[:, None] > 2.0 ** -9)):
+            h = keep.any(-1)
+            hits.append(h)
+            out += [torch.where(h, torch.where(keep, t0, inf).amin(-1), rays[:, 6].to(torch.float64)),
+                    torch.where(h, torch.where(keep, t1, -inf).amax(-1), rays[:, 7].to(torch.float64))]
+        return (torch.stack(hits, -1),) + tuple(out)
+
+    def ray_span(self, rays):
+        """(span fp32 [N, 2], hit bool [N]) for rays [N, >= 8] on the GPU (nerf_occ_ray_span): per ray the first and the last occupied
+        cell it crosses inside [near, far], widened by 2^-10 cell -- every sample ``occupied()`` would keep lies in [near', far'] --
+        and the ray's own (near, far), hit False, where it crosses nothing occupied.  Computed without gradients from detached values."""
+        with torch.no_grad():
+            span, hit = hb.occ_ray_span(self._desc(), rays.detach().to(torch.float32).contiguous())
+        return span, hit.bool()
+
+    def clip_rays(self, rays):
+        """(rays', hit): the ray records with columns 6:8 (near, far) replaced by ``ray_span``'s.  Columns 0:6 and 8: keep their
+        autograd history; near' / far' are constants of the graph (no gradient flows through the span, as none flows to near / far)."""
+        span, hit = self.ray_span(rays)
+        return torch.cat([rays[:, :6], span.to(rays.dtype), rays[:, 8:]], -1), hit
 
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):

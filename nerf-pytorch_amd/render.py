@@ -864,7 +864,7 @@ class _RenderRaysGrid(torch.autograd.Function):
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                *, randoms=None, occupancy=None):
+                *, randoms=None, occupancy=None, clip_to_occupancy=False):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -880,7 +880,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     through the network and get raw = 0 (_render_rays_occupancy).  Fused NeRF networks only: a grid together with a DenseNeRF or a
     user network_query_fn raises NotImplementedError.  With a needed gradient (grad mode on and parameters or rays that require grad)
     an occupancy.DensityGrid renders differentiably w.r.t. both networks' parameters and the ray records (_RenderRaysGrid: skipped
-    samples get no gradient); a plain OccupancyGrid raises NotImplementedError there.  None: nothing changes."""
+    samples get no gradient); a plain OccupancyGrid raises NotImplementedError there.  None: nothing changes.
+
+    ``clip_to_occupancy`` (keyword-only, not in the reference; needs ``occupancy``): True replaces (near, far) of every ray by the
+    span of the occupied cells it crosses (occupancy.clip_rays: nerf_occ_ray_span) before the coarse depths are drawn, so all
+    N_samples of them land where the grid lets the network be evaluated; a ray that crosses nothing occupied keeps its interval.
+    The call equals render_rays(occupancy.clip_rays(ray_batch)[0], ..., occupancy=occupancy) bit for bit, gradients included (near' /
+    far' are constants of the graph); last_stats additionally carries "rays_hit" and "rays".  False: nothing changes."""
+    if clip_to_occupancy and occupancy is None:
+        raise ValueError("render_rays: clip_to_occupancy=True needs an occupancy grid (occupancy=)")
     from .dense import DenseNeRF
     nets = [network_fn] + ([network_fine] if network_fine is not None else [])
     dense = all(isinstance(m, DenseNeRF) for m in nets)         # architectures outside the fused kernels: layer by layer (dense.py)
@@ -910,6 +918,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
             occupancy._desc()
             occupancy.last_stats = {"evaluated": 0, "total": 0}
+            if clip_to_occupancy:
+                occupancy.last_stats.update(rays_hit=0, rays=0)
         return ret
     rnd = {}
     if randoms is not None:
@@ -970,6 +980,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                                           "rays that require grad) is not implemented: a static grid would hide what the network has not "
                                           "learnt yet.  Render under torch.no_grad(), or train through an occupancy.DensityGrid (the grid "
                                           "that follows the network: maybe_update every step)")
+            grid_grad = True
+        else:
+            grid_grad = False
+        n_hit = None
+        if clip_to_occupancy:       # (after the guards: a refused call launches nothing; the draws above do not depend on near / far)
+            rays, hit = occupancy.clip_rays(rays)
+            n_hit = hit.sum()       # read back after the passes, which synchronise anyway
+        if grid_grad:
             if cfg["precision"] == "fp16_fp8c":
                 cfg["precision"] = "fp16x3"         # the reduced class is an inference form; gradients: the fp16x3 datapath
             same = n_f <= 0 or network_fine is None or network_fine is network_fn
@@ -981,8 +999,11 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             ret.update(rgb_map=outs[0], disp_map=outs[1], acc_map=outs[2])
             if retraw:
                 ret['raw'] = outs[3]
-            return ret
-        return _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw)
+        else:
+            ret = _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw)
+        if n_hit is not None:
+            occupancy.last_stats = dict(occupancy.last_stats, rays_hit=int(n_hit.item()), rays=n)
+        return ret
     if not _is_builtin_query(network_query_fn):
         return _render_rays_hooked(rays, rnd, network_fn, network_query_fn, int(N_samples), n_f, network_fine if n_f > 0 else None,
                                    bool(lindisp), white_bkgd, std, retraw)
@@ -1020,10 +1041,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """run_nerf.py:54-66.  Injected ``randoms`` (one row per ray) are sliced with the rays, so a chunked call consumes
-    the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks."""
+    the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks (with ``clip_to_occupancy``
+    its "rays_hit" / "rays" too)."""
     all_ret = {}
     randoms = kwargs.pop("randoms", None)
     occ, occ_stats = kwargs.get("occupancy"), {"evaluated": 0, "total": 0}
+    if kwargs.get("clip_to_occupancy"):
+        occ_stats.update(rays_hit=0, rays=0)
     if randoms is not None:
         for k, v in randoms.items():
             if v.shape[0] != rays_flat.shape[0]:
