@@ -474,6 +474,20 @@ int nerf_occ_density_update(const float* sigma, long n_cells, int samples_per_ce
  * far.  Both walks take at most res[0] + res[1] + res[2] + 3 steps.  Reads 32 B per ray and the words of the cells walked, writes
  * 12 B per ray; no atomics: the same inputs give the same bits.  ray_stride >= 8; span 8-byte aligned. */
 int nerf_occ_ray_span(const NerfOccGrid* grid, const float* rays, int ray_stride, int n_rays, float* span, int* hit, void* stream);
+/* ---- importance samples from a density grid (additive in ABI v10): the compositing weights of the samples o + d z (one fp32
+ * multiply, one fp32 add) of rays[n_rays][ray_stride] / z_vals[n_rays][n_samples] with the grid's own density as sigma, what
+ * render_rays(proposal="grid") hands to nerf_sample_fine in place of a coarse network's weights.  density[cells] (DEVICE) is
+ * occupancy.DensityGrid's running maximum per cell.  Lookup of a point, classified as above, no interpolation: inside the box and bit
+ * set -> density[c]; inside and bit clear -> 0; outside the box (a NaN included) -> 0 if outside_skip else outside_sigma (the caller
+ * passes the grid's sigma_threshold: the least density the grid calls occupied, so the grid still never hides what it does not cover).
+ *   weights[r][i] = alpha_i prod_{j<i} (1 - alpha_j + 1e-10),  alpha_i = 1 - expf(-max(sigma_i, 0) * dist_i),
+ *   dist_i = (z[i+1] - z[i]) * |d|, the last one 1e10 * |d|  (run_nerf.py:275-293)
+ * in the operation order, lane segments and wave scan of nerf_raw2outputs: the weights equal, bit for bit, those nerf_raw2outputs
+ * returns for raw = (0, 0, 0, sigma) without noise.  sigma[n_rays][n_samples] (optional, may be NULL) receives the looked-up densities.
+ * One wavefront per ray, no colours, no ray integrals, no atomics: the same inputs give the same bits.  Reads 24 B per ray, 4 B per
+ * point and one bit word plus one density word per point; writes 4 B (8 B with sigma) per point.  ray_stride >= 6; 1 <= n_samples <= 4096. */
+int nerf_occ_proposal_weights(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride,
+                              const float* z_vals, int n_rays, int n_samples, float* weights, float* sigma, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,8 @@
 //   nerf_occ_density_update : density[c] = max(density[c] * decay, max_k sigma[c][k]) (occupancy.DensityGrid).
 //   nerf_occ_ray_span : per ray the first and the last occupied cell it crosses inside [near, far] (two walks over the bits), the
 //                      interval render_rays(clip_to_occupancy=True) samples instead of [near, far].
+//   nerf_occ_proposal_weights : the compositing weights of a ray's samples with the DensityGrid's own density per cell as sigma --
+//                      what render_rays(proposal="grid") draws its importance samples from instead of a coarse network's weights.
 // The compaction is deterministic: a count per block of OCC_TILE points, an exclusive scan of the block counts, then the
 // write -- inside a block the position of a point is a wave ballot + popcount and a prefix over the block's wave counts, so the
 // list is in stable ray-major, sample-minor order and no atomic decides anything.
@@ -17,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "api_util.h"
+#include "ray_device.h"
 
 using namespace nerf_api;
 
@@ -448,6 +451,60 @@ __global__ __launch_bounds__(SPAN_THREADS) void occ_ray_span_kernel(GridArgs g, 
     }
 }
 
+// ---- nerf_occ_proposal_weights (DensityGrid.proposal_sigma is the definition of the lookup)
+// One wavefront per ray, the launch shape and the arithmetic of composite_ray<false> (ray_device.h) with sigma_i looked up in the grid:
+// lane l owns the C = ceil(S / 64) consecutive samples from l C on, multiplies their 1 - alpha + 1e-10 into a segment product, the
+// wave scans the products, and the lane walks its segment again for w_i = alpha_i T_i.  Same operations in the same order, so the
+// weights are those nerf_raw2outputs gives for raw = (0, 0, 0, sigma) without noise, bit for bit.  No colours, no ray integrals.
+// LDS: 2 S floats (alpha_i, 1 - alpha_i + 1e-10); each lane touches only its own segment: no synchronisation.
+__device__ __forceinline__ float proposal_sigma(const GridArgs& g, const float* __restrict__ density, float outside_sigma, const Pt& p) {
+    const float tx = (p.x - g.lo[0]) * g.scale[0];
+    const float ty = (p.y - g.lo[1]) * g.scale[1];
+    const float tz = (p.z - g.lo[2]) * g.scale[2];
+    // (a NaN fails every comparison: outside)
+    const bool inside = tx >= 0.0f && tx < (float)g.res[0] && ty >= 0.0f && ty < (float)g.res[1] && tz >= 0.0f && tz < (float)g.res[2];
+    if (!inside) return g.outside_skip ? 0.0f : outside_sigma;
+    const int ix = (int)floorf(tx), iy = (int)floorf(ty), iz = (int)floorf(tz);
+    const unsigned c = ((unsigned)ix * (unsigned)g.res[1] + (unsigned)iy) * (unsigned)g.res[2] + (unsigned)iz;
+    return ((g.bits[c >> 5] >> (c & 31u)) & 1u) ? density[c] : 0.0f;
+}
+
+__global__ __launch_bounds__(64) void occ_proposal_weights_kernel(GridArgs g, const float* __restrict__ density, float outside_sigma,
+                                                                   const float* __restrict__ rays, int ray_stride,
+                                                                   const float* __restrict__ z_vals, int S, float* __restrict__ weights,
+                                                                   float* __restrict__ sigma_out) {
+    extern __shared__ float sm[];
+    const int ray = blockIdx.x, lane = threadIdx.x;
+    const int C = (S + 63) >> 6;
+    const int lo = lane * C, hi = min(lo + C, S);
+    const float* r = rays + (size_t)ray * ray_stride;
+    const float* z = z_vals + (size_t)ray * S;
+    const float dn = sqrtf(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+    float* s_alpha = sm;            // alpha_i
+    float* s_t = sm + S;            // 1 - alpha_i + 1e-10
+    float seg = 1.0f;
+    for (int i = lo; i < hi; ++i) {
+        const float zi = z[i];
+        float dist = (i + 1 < S) ? (z[i + 1] - zi) : 1e10f;
+        dist = dist * dn;
+        const float sg = proposal_sigma(g, density, outside_sigma, sample_point(r, zi));
+        if (sigma_out) sigma_out[(size_t)ray * S + i] = sg;
+        const float ex = expf(-fmaxf(sg, 0.0f) * dist);
+        const float al = 1.0f - ex;
+        const float t = 1.0f - al + 1e-10f;
+        s_alpha[i] = al;
+        s_t[i] = t;
+        seg *= t;
+    }
+    const float incl = nerf::wave_incl_scan_mul(seg, lane);
+    float T = __shfl_up(incl, 1);
+    if (lane == 0) T = 1.0f;
+    for (int i = lo; i < hi; ++i) {
+        weights[(size_t)ray * S + i] = s_alpha[i] * T;
+        T *= s_t[i];
+    }
+}
+
 int check_grid(const char* fn, const NerfOccGrid* grid, GridArgs* g) {
     if (!grid || !grid->bits) return fail_arg(fn, "null pointer");
     for (int a = 0; a < 3; ++a) {
@@ -550,6 +607,18 @@ int nerf_occ_ray_span(const NerfOccGrid* grid, const float* rays, int ray_stride
     if (n_rays == 0) return 0;
     const unsigned lanes = 2u * (unsigned)n_rays;
     occ_ray_span_kernel<<<(lanes + SPAN_THREADS - 1) / SPAN_THREADS, SPAN_THREADS, 0, (hipStream_t)stream>>>(g, rays, ray_stride, n_rays, span, hit);
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_proposal_weights(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride,
+                              const float* z_vals, int n_rays, int n_samples, float* weights, float* sigma, void* stream) {
+    GridArgs g;
+    if (int rc = check_grid(__func__, grid, &g)) return rc;
+    REQUIRE(density && rays && z_vals && weights, "null pointer");
+    REQUIRE(ray_stride >= 6 && n_rays >= 0 && n_samples >= 1 && n_samples <= 4096, "bad size (ray records need 6 columns, 1..4096 samples)");
+    if (n_rays == 0) return 0;
+    occ_proposal_weights_kernel<<<(unsigned)n_rays, 64, 2 * (size_t)n_samples * sizeof(float), (hipStream_t)stream>>>(
+        g, density, outside_sigma, rays, ray_stride, z_vals, n_samples, weights, sigma);
     return done(__func__, hipGetLastError());
 }
 

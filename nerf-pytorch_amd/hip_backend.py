@@ -92,6 +92,7 @@ def _declare(lib):
         "nerf_occ_fold_rays": (i, [p, p, p, i, i, p, i, p]),
         "nerf_occ_density_update": (i, [p, l, i, f, p, p]),
         "nerf_occ_ray_span": (i, [p, p, i, i, p, p, p]),
+        "nerf_occ_proposal_weights": (i, [p, p, f, p, i, p, i, i, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -117,7 +118,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_dense_wgrad", "nerf_range_scan", "nerf_field_input_grad", "nerf_raw2outputs_bwd_geom", "nerf_embed_bwd",
            "nerf_sample_ray_views", "nerf_ray_pose_grad",
            "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate",
-           "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span",
+           "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span", "nerf_occ_proposal_weights",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
 
 
@@ -1193,6 +1194,26 @@ def occ_ray_span(desc, rays):
         _check(lib().nerf_occ_ray_span(ctypes.byref(desc), _ptr(rays, "rays"), stride, n, _ptr(span, "span"), hit.data_ptr(), _stream()),
                "nerf_occ_ray_span")
     return span, hit
+
+
+def occ_proposal_weights(desc, density, outside_sigma, rays, z_vals, want_sigma=False):
+    """nerf_occ_proposal_weights: (weights fp32 [n, S], sigma fp32 [n, S] or None) of rays [n, >= 6] / z_vals [n, S] -- the compositing
+    weights with the grid's density per cell (fp32 [cells]) as sigma; outside the box outside_sigma (0 for a grid that skips there)"""
+    if rays.dim() != 2 or rays.shape[1] < 6 or z_vals.dim() != 2 or z_vals.shape[0] != rays.shape[0]:
+        raise NerfHipError("occ_proposal_weights: rays [n, >= 6] (o, d, ...), z_vals [n, S]")
+    n, stride = rays.shape
+    S = z_vals.shape[1]
+    if density.numel() != desc.res[0] * desc.res[1] * desc.res[2]:
+        raise NerfHipError("occ_proposal_weights: one density per cell of the grid")
+    weights = torch.empty((n, S), dtype=torch.float32, device=rays.device)
+    sigma = torch.empty((n, S), dtype=torch.float32, device=rays.device) if want_sigma else None
+    if n == 0:
+        return weights, sigma
+    with _timed("occ_proposal_weights_kernel", 0.0, (16.0 if want_sigma else 12.0) * n * S):
+        _check(lib().nerf_occ_proposal_weights(ctypes.byref(desc), _ptr(density, "density"), float(outside_sigma), _ptr(rays, "rays"), stride,
+                                               _ptr(z_vals, "z_vals"), n, S, _ptr(weights), _ptr(sigma, "sigma", True), _stream()),
+               "nerf_occ_proposal_weights")
+    return weights, sigma
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

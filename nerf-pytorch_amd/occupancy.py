@@ -108,8 +108,8 @@ class OccupancyGrid:
         return float(self.to_mask().float().mean())
 
     # ------------------------------------------------------------------ the definition
-    def occupied(self, pts):
-        """bool [...] for pts [..., 3] (any device): whether a sample at that point is evaluated"""
+    def _classify(self, pts):
+        """(inside bool [...], cell int64 [...] -- 0 where outside --, bit bool [...]) for pts [..., 3]: the rule of the class docstring"""
         dev = pts.device
         f = lambda a: torch.tensor(a, dtype=torch.float32, device=dev)
         t = (pts.to(torch.float32) - f(self.lo)) * f(self.scale)
@@ -119,6 +119,11 @@ class OccupancyGrid:
         c = (i[..., 0] * ry + i[..., 1]) * rz + i[..., 2]
         bits = self.bits if self.bits.device == dev else self.bits.to(dev)
         bit = ((bits[c >> 5].to(torch.int64) >> (c & 31)) & 1).bool()
+        return inside, c, bit
+
+    def occupied(self, pts):
+        """bool [...] for pts [..., 3] (any device): whether a sample at that point is evaluated"""
+        inside, _, bit = self._classify(pts)
         return torch.where(inside, bit, torch.full_like(bit, self.outside == "evaluate"))
 
     # ------------------------------------------------------------------ the occupied span of a ray
@@ -268,7 +273,10 @@ class DensityGrid(OccupancyGrid):
 
     The defaults (decay 0.95, sigma_threshold 0.01, update_every 16, warmup_steps 256) are Instant-NGP's habits, not measurements made
     with these networks: the threshold in particular is in the units of the scene's density and wants a look at ``fraction_occupied()``.
-    ``_update_reference`` / ``_bits_reference`` are the definition of the step in plain torch, as ``occupied()`` is the classifier's."""
+    ``_update_reference`` / ``_bits_reference`` are the definition of the step in plain torch, as ``occupied()`` is the classifier's.
+
+    The densities have a second reader: render_rays(..., occupancy=grid, proposal="grid") draws its importance samples from the
+    compositing weights of ``proposal_sigma`` at the coarse depths (``proposal_weights``) and evaluates one network only."""
 
     def __init__(self, lo, hi, resolution, outside="evaluate", device=None, decay=0.95, sigma_threshold=0.01, dilate=0, update_every=16,
                  warmup_steps=256):
@@ -357,6 +365,30 @@ class DensityGrid(OccupancyGrid):
             return False
         self.update(model, **kw)
         return True
+
+    # ------------------------------------------------------------------ importance samples from the grid
+    def proposal_sigma(self, pts):
+        """fp32 [...] for pts [..., 3] (any device): the density render_rays(proposal="grid") composites at a sample point, the
+        definition nerf_occ_proposal_weights reproduces bit for bit (as ``occupied()`` is the classifier's).  The point is classified
+        exactly as ``occupied()`` does; inside the box it is density[c] where the cell's bit is set and 0 where it is clear; outside
+        the box (a NaN included) it is 0 with outside="skip" and fp32(sigma_threshold) with outside="evaluate" -- the least density
+        the grid calls occupied, so the grid still never hides what it does not cover.  No interpolation."""
+        inside, c, bit = self._classify(pts)
+        density = self.density if self.density.device == pts.device else self.density.to(pts.device)
+        zero = torch.zeros((), dtype=torch.float32, device=pts.device)
+        out = torch.tensor(self.sigma_threshold if self.outside == "evaluate" else 0.0, dtype=torch.float32, device=pts.device)
+        return torch.where(inside, torch.where(bit, density[c], zero), out)
+
+    def proposal_weights(self, rays, z_vals, want_sigma=False):
+        """fp32 [N, S] for rays [N, >= 6] / z_vals [N, S] on the GPU (nerf_occ_proposal_weights): the compositing weights of the samples
+        o + d z with ``proposal_sigma`` as their density -- bit for bit the weights raw2outputs gives for raw = (0, 0, 0, sigma) without
+        noise.  A grid that was never updated has density 0 everywhere: every sample inside the box has a weight of exactly 0, which
+        sample_pdf's 1e-5 floor turns into a uniform pdf.  Constants of the graph (computed without gradients from detached values).  want_sigma: (weights, sigma)."""
+        with torch.no_grad():
+            w, sigma = hb.occ_proposal_weights(self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0,
+                                               rays.detach().to(torch.float32).contiguous(), z_vals.detach().to(torch.float32).contiguous(),
+                                               want_sigma)
+        return (w, sigma) if want_sigma else w
 
     # ------------------------------------------------------------------ checkpoints
     _SCALARS = ("decay", "sigma_threshold", "dilate", "update_every", "warmup_steps")

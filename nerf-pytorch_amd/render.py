@@ -584,13 +584,15 @@ def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f,
     return ret
 
 
-def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw):
+def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, proposal=None):
     """render_rays without gradients through an occupancy grid (occupancy.OccupancyGrid): _render_rays_hooked's chain of stages with
     device code where the hook sits.  Per pass: depths (nerf_sample_coarse / nerf_sample_fine) -> nerf_occ_compact (classify o + d z,
     compact the occupied points into n_samples = 1 ray records) -> ONE read-back of the count M -> the field on the M records, as
     query_points evaluates points (nerf_field_fwd / nerf_field_fwd_split; no launch when M == 0) -> nerf_occ_expand (raw, zeros for
     skipped samples) -> nerf_raw2outputs.  One host synchronisation per pass: two per call with N_importance > 0, else one.
-    "fp16_fp8c": the compacted points run on the fp16x3 products (the fp8 correction terms' last-sample fix-up is per ray)."""
+    "fp16_fp8c": the compacted points run on the fp16x3 products (the fp8 correction terms' last-sample fix-up is per ray).
+    proposal="grid": the coarse pass is replaced by the grid's own weights at the coarse depths (DensityGrid.proposal_weights: one
+    launch, no network, no read-back) and only the refining pass -- model_f, or model_c without one -- runs: one synchronisation."""
     n_c, n_f = cfg["N_samples"], cfg["N_importance"]
     dev = rays.device
     n = rays.shape[0]
@@ -623,10 +625,14 @@ def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw):
                                    rays_d_offset=3)
 
     z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
-    raw, (rgb, disp, acc, weights, _) = one_pass(z_c, model_c, rnd.get("noise_c"), n_f > 0)
     ret = {}
+    if proposal is not None:
+        weights = grid.proposal_weights(rays, z_c)
+    else:
+        raw, (rgb, disp, acc, weights, _) = one_pass(z_c, model_c, rnd.get("noise_c"), n_f > 0)
     if n_f > 0:
-        ret.update(rgb0=rgb, disp0=disp, acc0=acc)
+        if proposal is None:
+            ret.update(rgb0=rgb, disp0=disp, acc0=acc)
         u = rnd.get("u")
         z_f, z_std, _ = hb.sample_fine(z_c, weights, n_f, u, None if u is not None else _linspace01(n_f, dev))
         raw, (rgb, disp, acc, _, _) = one_pass(z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), False)
@@ -660,7 +666,11 @@ class _RenderRaysGrid(torch.autograd.Function):
     Kept from forward to backward, per pass: slot (4 B per sample point), the saved activations of M points (leased at
     _grid_pass_lease's size), z, raw, and the M records (44 B each) only when the rays need a gradient -- hb.WORKSPACE leases, given
     back by the backward or freed with a dropped graph.  Calls above hb.max_saved_rays(...) rays run in equal ray sub-chunks, every
-    one resident with leases of its own M; beyond hb.SAVE_TOTAL_BYTES in total the call raises (no recompute plan on this path)."""
+    one resident with leases of its own M; beyond hb.SAVE_TOTAL_BYTES in total the call raises (no recompute plan on this path).
+
+    cfg["proposal"] == "grid" (render_rays(proposal="grid")): the coarse pass is DensityGrid.proposal_weights -- a constant of the graph,
+    nothing saved -- and the node has ONE pass, the refining one on model_c (the caller hands the evaluated network as model_c, model_f =
+    None); outputs (rgb, disp, acc, raw, z_std)."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
@@ -670,6 +680,7 @@ class _RenderRaysGrid(torch.autograd.Function):
         n = rays.shape[0]
         dev = rays.device
         desc = grid._desc()
+        ctx.proposal = proposal = cfg.get("proposal") is not None
         ctx.same_net = model_f is None or model_f is model_c
         ctx.n_params_c = len(_param_slices(model_c))
         ctx.rays_grad = rays_grad = bool(ctx.needs_input_grad[1])
@@ -729,14 +740,17 @@ class _RenderRaysGrid(torch.autograd.Function):
                 rnd_t = rnd if len(tiles) == 1 else {k_: v[lo:hi] for k_, v in rnd.items()}
                 parts.append([])
                 z_c = hb.sample_coarse(rays_t, _linspace01(n_c, dev), cfg["lindisp"], rnd_t.get("t_rand"))
-                raw_c, (rgb_c, disp_c, acc_c, w_c, _) = one_pass(rays_t, z_c, model_c, rnd_t.get("noise_c"), n_f > 0)
-                if n_f <= 0:
-                    outs.append((rgb_c, disp_c, acc_c, raw_c))
-                    continue
+                if proposal:
+                    w_c = grid.proposal_weights(rays_t, z_c)
+                else:
+                    raw_c, (rgb_c, disp_c, acc_c, w_c, _) = one_pass(rays_t, z_c, model_c, rnd_t.get("noise_c"), n_f > 0)
+                    if n_f <= 0:
+                        outs.append((rgb_c, disp_c, acc_c, raw_c))
+                        continue
                 u = rnd_t.get("u")
                 z_f, z_std, _ = hb.sample_fine(z_c, w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
                 raw_f, (rgb_f, disp_f, acc_f, _, _) = one_pass(rays_t, z_f, model_c if ctx.same_net else model_f, rnd_t.get("noise_f"), False)
-                outs.append((rgb_f, disp_f, acc_f, raw_f, rgb_c, disp_c, acc_c, z_std))
+                outs.append((rgb_f, disp_f, acc_f, raw_f, z_std) if proposal else (rgb_f, disp_f, acc_f, raw_f, rgb_c, disp_c, acc_c, z_std))
         except BaseException:
             for passes in parts:
                 for p in passes:
@@ -761,7 +775,7 @@ class _RenderRaysGrid(torch.autograd.Function):
         ctx.consumed = False
         ctx.set_materialize_grads(False)
         if n_f > 0:
-            ctx.mark_non_differentiable(out[7])     # the reference detaches z_samples (run_nerf.py:394)
+            ctx.mark_non_differentiable(out[-1])    # z_std: the reference detaches z_samples (run_nerf.py:394)
         return tuple(out)
 
     @staticmethod
@@ -780,7 +794,10 @@ class _RenderRaysGrid(torch.autograd.Function):
         n_all = rays_all.shape[0]
         fine = cfg["N_importance"] > 0
         up_f = (gouts[0], gouts[1], gouts[2], gouts[3])
-        up_c = (gouts[4], gouts[5], gouts[6], None) if fine else None
+        if ctx.proposal:        # one pass, the refining one: there is no coarse image
+            up_c = None
+        else:
+            up_c = (gouts[4], gouts[5], gouts[6], None) if fine else None
         if not fine:
             up_c, up_f = up_f, None
         has = lambda up: up is not None and any(g is not None for g in up)
@@ -851,7 +868,7 @@ class _RenderRaysGrid(torch.autograd.Function):
                     _grad_ready(ctx.model_c, grad_c)
             if fine and has(up_f):
                 model, grad, key = (ctx.model_c, grad_c, "c") if ctx.same_net else (ctx.model_f, grad_f, "f")
-                field_grad(rays, model, passes[1], raw_of(passes[1]), rnd.get("noise_f"), up_f, lo, hi, grad, key)
+                field_grad(rays, model, passes[-1], raw_of(passes[-1]), rnd.get("noise_f"), up_f, lo, hi, grad, key)
                 if last and grad is not None:
                     _grad_ready(model, grad)
         release()
@@ -864,7 +881,7 @@ class _RenderRaysGrid(torch.autograd.Function):
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                *, randoms=None, occupancy=None, clip_to_occupancy=False):
+                *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -886,9 +903,33 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     span of the occupied cells it crosses (occupancy.clip_rays: nerf_occ_ray_span) before the coarse depths are drawn, so all
     N_samples of them land where the grid lets the network be evaluated; a ray that crosses nothing occupied keeps its interval.
     The call equals render_rays(occupancy.clip_rays(ray_batch)[0], ..., occupancy=occupancy) bit for bit, gradients included (near' /
-    far' are constants of the graph); last_stats additionally carries "rays_hit" and "rays".  False: nothing changes."""
+    far' are constants of the graph); last_stats additionally carries "rays_hit" and "rays".  False: nothing changes.
+
+    ``proposal`` (keyword-only, not in the reference; needs an occupancy.DensityGrid as ``occupancy`` and N_importance > 0): "grid"
+    draws the importance samples from the grid instead of a coarse network.  The coarse depths are drawn as always (after
+    clip_to_occupancy if that is on); their weights are the compositing weights of the grid's own density per cell
+    (DensityGrid.proposal_sigma is the definition, nerf_occ_proposal_weights the kernel: no network, no interpolation);
+    nerf_sample_fine turns them into the sorted N_samples + N_importance depths, and ONE network -- network_fine if given, else
+    network_fn -- is evaluated on those through the compacted grid pass, with gradients to its parameters and the ray records as
+    without the option.  The other network is never touched: no launch, no gradient (.grad stays None), no _grad_ready.  The dict
+    holds rgb_map, disp_map, acc_map, z_std (and raw with retraw) and NO rgb0 / disp0 / acc0: there is no coarse image (the reference's
+    train() guards its coarse loss with ``if 'rgb0' in extras``).  last_stats counts the one pass: total = N * (N_samples +
+    N_importance).  Random draws: t_rand, u, noise_f in that order; noise_c is not drawn and is ignored in ``randoms`` -- the generator
+    stream therefore differs from the two-network render's, by design.  Before the grid's first update its densities are 0 and all
+    bits are set: the weights of the samples inside the box are exactly 0 (beyond a box with outside="evaluate" they carry
+    sigma_threshold), sample_pdf's 1e-5 floor makes the pdf uniform, and the network sees the stratified plus uniformly drawn depths
+    -- nothing is hidden during the warm-up.  None: nothing changes."""
     if clip_to_occupancy and occupancy is None:
         raise ValueError("render_rays: clip_to_occupancy=True needs an occupancy grid (occupancy=)")
+    if proposal not in (None, "grid"):
+        raise ValueError(f"render_rays: proposal must be None or \"grid\", got {proposal!r}")
+    if proposal is not None:
+        from .occupancy import DensityGrid
+        if not isinstance(occupancy, DensityGrid):
+            raise ValueError("render_rays: proposal=\"grid\" reads the densities of an occupancy.DensityGrid (occupancy=); "
+                             + ("none was given" if occupancy is None else "a plain OccupancyGrid has none"))
+        if int(N_importance) <= 0:
+            raise ValueError("render_rays: proposal=\"grid\" draws importance samples: N_importance must be > 0")
     from .dense import DenseNeRF
     nets = [network_fn] + ([network_fine] if network_fine is not None else [])
     dense = all(isinstance(m, DenseNeRF) for m in nets)         # architectures outside the fused kernels: layer by layer (dense.py)
@@ -914,7 +955,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         if retraw:
             ret['raw'] = e(N_samples + n_f, 4)
         if n_f > 0:
-            ret.update(rgb0=e(3), disp0=e(), acc0=e(), z_std=e())
+            if proposal is None:
+                ret.update(rgb0=e(3), disp0=e(), acc0=e())
+            ret.update(z_std=e())
         if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
             occupancy._desc()
             occupancy.last_stats = {"evaluated": 0, "total": 0}
@@ -923,7 +966,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         return ret
     rnd = {}
     if randoms is not None:
-        keys = (["t_rand"] if perturb > 0. else []) + (["noise_c"] if raw_noise_std > 0. else [])
+        keys = (["t_rand"] if perturb > 0. else []) + (["noise_c"] if raw_noise_std > 0. and proposal is None else [])
         if n_f > 0:
             keys += (["u"] if perturb > 0. else []) + (["noise_f"] if raw_noise_std > 0. else [])
         rnd = {k: randoms[k].to(device=dev, dtype=torch.float32).contiguous() for k in keys}
@@ -947,7 +990,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             np.random.seed(0)
             nz = torch.Tensor(np.random.rand(n, S) * raw_noise_std).to(dev)
         return nz.contiguous()
-    if raw_noise_std > 0. and randoms is None:
+    if raw_noise_std > 0. and randoms is None and proposal is None:
         rnd["noise_c"] = draw_noise(N_samples)
     if n_f > 0:
         if perturb_draw > 0.:
@@ -973,7 +1016,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         if dense:
             raise NotImplementedError("render_rays: occupancy= together with general (DenseNeRF) networks is not implemented; the grid "
                                       "path runs the fused NeRF architecture only")
-        if torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for m in nets for p in m.parameters())):
+        evaluated = nets if proposal is None else nets[-1:]        # (proposal: network_fine if given, else network_fn)
+        if torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for m in evaluated for p in m.parameters())):
             from .occupancy import DensityGrid
             if not isinstance(occupancy, DensityGrid):
                 raise NotImplementedError("render_rays: a plain OccupancyGrid together with a needed gradient (grad mode on and parameters or "
@@ -990,17 +1034,22 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         if grid_grad:
             if cfg["precision"] == "fp16_fp8c":
                 cfg["precision"] = "fp16x3"         # the reduced class is an inference form; gradients: the fp16x3 datapath
-            same = n_f <= 0 or network_fine is None or network_fine is network_fn
-            params = network_fn.param_list() + ([] if same else network_fine.param_list())
-            outs = _RenderRaysGrid.apply(cfg, rays, rnd, network_fn, None if same else network_fine, occupancy, *params)
             ret = {}        # (keys in _render_rays_occupancy's order)
-            if n_f > 0:
-                ret.update(rgb0=outs[4], disp0=outs[5], acc0=outs[6], z_std=outs[7])
+            if proposal is not None:
+                cfg["proposal"] = proposal
+                outs = _RenderRaysGrid.apply(cfg, rays, rnd, evaluated[0], None, occupancy, *evaluated[0].param_list())
+                ret.update(z_std=outs[4])
+            else:
+                same = n_f <= 0 or network_fine is None or network_fine is network_fn
+                params = network_fn.param_list() + ([] if same else network_fine.param_list())
+                outs = _RenderRaysGrid.apply(cfg, rays, rnd, network_fn, None if same else network_fine, occupancy, *params)
+                if n_f > 0:
+                    ret.update(rgb0=outs[4], disp0=outs[5], acc0=outs[6], z_std=outs[7])
             ret.update(rgb_map=outs[0], disp_map=outs[1], acc_map=outs[2])
             if retraw:
                 ret['raw'] = outs[3]
         else:
-            ret = _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw)
+            ret = _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw, proposal)
         if n_hit is not None:
             occupancy.last_stats = dict(occupancy.last_stats, rays_hit=int(n_hit.item()), rays=n)
         return ret
