@@ -488,6 +488,26 @@ int nerf_occ_ray_span(const NerfOccGrid* grid, const float* rays, int ray_stride
  * point and one bit word plus one density word per point; writes 4 B (8 B with sigma) per point.  ray_stride >= 6; 1 <= n_samples <= 4096. */
 int nerf_occ_proposal_weights(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride,
                               const float* z_vals, int n_rays, int n_samples, float* weights, float* sigma, void* stream);
+/* ---- early ray termination for the grid paths (additive in ABI v10): render_rays(early_stop_eps=eps) stops a ray of the refining pass
+ * where the COARSE pass's estimate of its transmittance has fallen below eps.  weights[r][i] (nerf_raw2outputs' or
+ * nerf_occ_proposal_weights') belongs to the interval [z_i, z_{i+1}] and the sum of the weights up to sample i is 1 - T behind it.
+ * Per ray: a = 0; for i = 0 .. n_samples - 1: a = a + weights[r][i] -- one fp32 addition each, strictly left to right (the order is the
+ * contract: np.cumsum(weights, axis=1, dtype=float32) is a bit-exact reference) --; i* = the first i with a >= threshold (a NaN never
+ * satisfies the comparison and poisons a: such a ray never stops);
+ *   z_stop[r] = z_vals[r][i* + 1] if there is an i* and i* + 1 < n_samples, else +inf
+ * (the last interval is the reference's 1e10 one: nothing lies behind it).  threshold = fp32(1 - eps), computed by the host in double.
+ * The stop is an approximation: what is dropped from the refined image is the REFINING pass's transmittance at z_stop, which is close to
+ * eps but not bounded by it.  Weights staged through LDS in tiles of 64 rays x 64 samples (coalesced reads, one lane sums one ray); a
+ * block leaves once all of its rays have crossed.  Reads at most 4 B per point (weights) and one z per ray, writes 4 B per ray; no
+ * atomics: the same inputs give the same bits.  1 <= n_samples <= 4096. */
+int nerf_occ_stop_depth(const float* z_vals, const float* weights, int n_rays, int n_samples, float threshold, float* z_stop, void* stream);
+/* nerf_occ_compact with a stop depth per ray (z_stop[n_rays], DEVICE): a point is kept iff it is occupied by nerf_occ_compact's rule AND
+ * !(z >= z_stop[ray]) -- a NaN z_stop or a NaN z stops nothing, +inf stops nothing, -inf stops everything.  The comparison comes before
+ * the grid lookup: a stopped point reads no bit word.  slot, records, count, scratch, the three launches and the ordering are those of
+ * nerf_occ_compact (the same kernels, instantiated with the extra predicate); with z_stop all +inf the results are bit-identical to
+ * it.  Moves what nerf_occ_compact moves + 8 B per point (z_stop of the owning ray, twice; cached: 4 B per ray reach HBM). */
+int nerf_occ_compact_stop(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* z_vals, const float* z_stop, int n_rays,
+                          int n_samples, int* slot, float* records, int* count, int* scratch, void* stream);
 
 #ifdef __cplusplus
 }

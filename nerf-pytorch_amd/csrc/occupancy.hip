@@ -11,6 +11,9 @@
 //                      interval render_rays(clip_to_occupancy=True) samples instead of [near, far].
 //   nerf_occ_proposal_weights : the compositing weights of a ray's samples with the DensityGrid's own density per cell as sigma --
 //                      what render_rays(proposal="grid") draws its importance samples from instead of a coarse network's weights.
+//   nerf_occ_stop_depth : per ray the depth behind which the transmittance the coarse weights imply has fallen below eps -- a strictly
+//                      left-to-right fp32 running sum of the weights against 1 - eps -- and nerf_occ_compact_stop, the compaction that
+//                      also drops the samples at or behind it: render_rays(early_stop_eps=eps).
 // The compaction is deterministic: a count per block of OCC_TILE points, an exclusive scan of the block counts, then the
 // write -- inside a block the position of a point is a wave ballot + popcount and a prefix over the block's wave counts, so the
 // list is in stable ray-major, sample-minor order and no atomic decides anything.
@@ -71,9 +74,18 @@ __device__ __forceinline__ int lanes_below(unsigned long long m) {
 // (32-bit: a call holds fewer than 2^31 - OCC_TILE points, and p / S stays a 32-bit division)
 __device__ __forceinline__ unsigned point_of(unsigned b, int it, int tid) { return b * OCC_TILE + it * OCC_THREADS + tid; }
 
+// STOP (nerf_occ_compact_stop): a sample at or behind its ray's stop depth is dropped before the grid is looked at -- it reads no bit
+// word.  !(z >= z_stop): a NaN on either side stops nothing.
+template <bool STOP>
+__device__ __forceinline__ bool in_front(const float* __restrict__ z_stop, unsigned ray, float z) {
+    if (!STOP) return true;
+    return !(z >= z_stop[ray]);
+}
+
+template <bool STOP>
 __global__ __launch_bounds__(OCC_THREADS) void occ_count_kernel(GridArgs g, const float* __restrict__ rays, int ray_stride,
-                                                                const float* __restrict__ z_vals, unsigned P, unsigned S,
-                                                                int* __restrict__ block_count) {
+                                                                const float* __restrict__ z_vals, const float* __restrict__ z_stop,
+                                                                unsigned P, unsigned S, int* __restrict__ block_count) {
     __shared__ int wave_n[OCC_WAVES];
     const int tid = threadIdx.x;
     int n = 0;
@@ -81,7 +93,11 @@ __global__ __launch_bounds__(OCC_THREADS) void occ_count_kernel(GridArgs g, cons
     for (int it = 0; it < OCC_ITERS; ++it) {
         const unsigned p = point_of(blockIdx.x, it, tid);
         bool occ = false;
-        if (p < P) occ = occupied(g, sample_point(rays + (size_t)(p / S) * ray_stride, z_vals[p]));
+        if (p < P) {
+            const unsigned ray = p / S;
+            const float z = z_vals[p];
+            occ = in_front<STOP>(z_stop, ray, z) && occupied(g, sample_point(rays + (size_t)ray * ray_stride, z));
+        }
         n += __popcll(__ballot(occ));
     }
     if ((tid & 63) == 0) wave_n[tid >> 6] = n;
@@ -122,10 +138,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void occ_scan_kernel(int* __restrict_
     if (tid == 0) count[0] = carry_s;
 }
 
+template <bool STOP>
 __global__ __launch_bounds__(OCC_THREADS) void occ_write_kernel(GridArgs g, const float* __restrict__ rays, int ray_stride,
-                                                                const float* __restrict__ z_vals, unsigned P, unsigned S,
-                                                                const int* __restrict__ block_offset, int* __restrict__ slot,
-                                                                float* __restrict__ records) {
+                                                                const float* __restrict__ z_vals, const float* __restrict__ z_stop,
+                                                                unsigned P, unsigned S, const int* __restrict__ block_offset,
+                                                                int* __restrict__ slot, float* __restrict__ records) {
     __shared__ int wave_n[OCC_ITERS][OCC_WAVES];
     const int tid = threadIdx.x, wave = tid >> 6;
     bool occ[OCC_ITERS];
@@ -137,8 +154,10 @@ __global__ __launch_bounds__(OCC_THREADS) void occ_write_kernel(GridArgs g, cons
         occ[it] = false;
         pt[it] = Pt{0.0f, 0.0f, 0.0f};
         if (p < P) {
-            pt[it] = sample_point(rays + (size_t)(p / S) * ray_stride, z_vals[p]);
-            occ[it] = occupied(g, pt[it]);
+            const unsigned ray = p / S;
+            const float z = z_vals[p];
+            pt[it] = sample_point(rays + (size_t)ray * ray_stride, z);
+            occ[it] = in_front<STOP>(z_stop, ray, z) && occupied(g, pt[it]);
         }
         const unsigned long long m = __ballot(occ[it]);
         below[it] = lanes_below(m);
@@ -505,6 +524,49 @@ __global__ __launch_bounds__(64) void occ_proposal_weights_kernel(GridArgs g, co
     }
 }
 
+// ---- nerf_occ_stop_depth (occupancy.stop_depth_reference is the definition)
+// A block takes STOP_RAYS rays and walks their weights in tiles of STOP_RAYS x STOP_COLS through LDS.  Loading: consecutive lanes take
+// consecutive samples of one ray (a wave reads one 256-byte run per ray: coalesced).  Summing: lane r of wave 0 owns ray r and adds its
+// row left to right, one fp32 addition per sample -- the contract, which is what makes np.cumsum(dtype=float32) a bit-exact reference;
+// a row is STOP_COLS + 1 words long, so the 32 lanes of a half-wave read 32 different banks.  The other three waves only load.  z_vals
+// is touched once per ray, at the sample behind the crossing (4 B per ray; staging the whole array would move S times as much).  The
+// block leaves as soon as every one of its rays has crossed.
+constexpr int STOP_RAYS = 64;
+constexpr int STOP_COLS = 64;
+constexpr int STOP_THREADS = 256;
+
+__global__ __launch_bounds__(STOP_THREADS) void occ_stop_depth_kernel(const float* __restrict__ z_vals, const float* __restrict__ weights,
+                                                                      int n_rays, int S, float threshold, float* __restrict__ z_stop) {
+    __shared__ float tile[STOP_RAYS][STOP_COLS + 1];
+    const int tid = threadIdx.x;
+    const int ray0 = blockIdx.x * STOP_RAYS;
+    const int col = tid & (STOP_COLS - 1);
+    const int my_ray = ray0 + tid;              // (meaningful for wave 0 only)
+    const bool walker = tid < STOP_RAYS && my_ray < n_rays;
+    float a = 0.0f;
+    int crossed = -1;
+    for (int c0 = 0; c0 < S; c0 += STOP_COLS) {
+#pragma unroll 4
+        for (int row = tid / STOP_COLS; row < STOP_RAYS; row += STOP_THREADS / STOP_COLS) {
+            const int r = ray0 + row, c = c0 + col;
+            tile[row][col] = (r < n_rays && c < S) ? weights[(size_t)r * S + c] : 0.0f;
+        }
+        __syncthreads();
+        if (walker && crossed < 0) {
+            const int n = min(STOP_COLS, S - c0);
+            for (int j = 0; j < n; ++j) {
+                a = a + tile[tid][j];
+                if (a >= threshold) {           // (a NaN never is, and poisons a: such a ray never stops)
+                    crossed = c0 + j;
+                    break;
+                }
+            }
+        }
+        if (__syncthreads_and(!walker || crossed >= 0)) break;      // (also the barrier in front of the next tile's stores)
+    }
+    if (walker) z_stop[my_ray] = (crossed >= 0 && crossed + 1 < S) ? z_vals[(size_t)my_ray * S + crossed + 1] : INFINITY;
+}
+
 int check_grid(const char* fn, const NerfOccGrid* grid, GridArgs* g) {
     if (!grid || !grid->bits) return fail_arg(fn, "null pointer");
     for (int a = 0; a < 3; ++a) {
@@ -537,9 +599,37 @@ int nerf_occ_compact(const NerfOccGrid* grid, const float* rays, int ray_stride,
     hipStream_t st = (hipStream_t)stream;
     if (P == 0) return done(__func__, hipMemsetAsync(count, 0, sizeof(int), st));
     const int nb = (int)occ_blocks(P);
-    occ_count_kernel<<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, (unsigned)P, (unsigned)n_samples, scratch);
+    occ_count_kernel<false><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, nullptr, (unsigned)P, (unsigned)n_samples, scratch);
     occ_scan_kernel<<<1, SCAN_THREADS, 0, st>>>(scratch, nb, count);
-    occ_write_kernel<<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, (unsigned)P, (unsigned)n_samples, scratch, slot, records);
+    occ_write_kernel<false><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, nullptr, (unsigned)P, (unsigned)n_samples, scratch, slot,
+                                                        records);
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_compact_stop(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* z_vals, const float* z_stop, int n_rays,
+                          int n_samples, int* slot, float* records, int* count, int* scratch, void* stream) {
+    GridArgs g;
+    if (int rc = check_grid(__func__, grid, &g)) return rc;
+    REQUIRE(rays && z_vals && z_stop && slot && records && count && scratch, "null pointer");
+    REQUIRE(ray_stride >= 11 && n_rays >= 0 && n_samples >= 1, "bad size (ray records need 11 columns)");
+    const long P = (long)n_rays * n_samples;
+    REQUIRE(P < (1L << 31) - OCC_TILE, "too many points for one call");
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 0) return done(__func__, hipMemsetAsync(count, 0, sizeof(int), st));
+    const int nb = (int)occ_blocks(P);
+    occ_count_kernel<true><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, z_stop, (unsigned)P, (unsigned)n_samples, scratch);
+    occ_scan_kernel<<<1, SCAN_THREADS, 0, st>>>(scratch, nb, count);
+    occ_write_kernel<true><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, z_stop, (unsigned)P, (unsigned)n_samples, scratch, slot,
+                                                       records);
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_stop_depth(const float* z_vals, const float* weights, int n_rays, int n_samples, float threshold, float* z_stop, void* stream) {
+    REQUIRE(z_vals && weights && z_stop, "null pointer");
+    REQUIRE(n_rays >= 0 && n_samples >= 1 && n_samples <= 4096, "bad size (1..4096 samples)");
+    if (n_rays == 0) return 0;
+    occ_stop_depth_kernel<<<(unsigned)((n_rays + STOP_RAYS - 1) / STOP_RAYS), STOP_THREADS, 0, (hipStream_t)stream>>>(
+        z_vals, weights, n_rays, n_samples, threshold, z_stop);
     return done(__func__, hipGetLastError());
 }
 

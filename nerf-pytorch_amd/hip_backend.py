@@ -93,6 +93,8 @@ def _declare(lib):
         "nerf_occ_density_update": (i, [p, l, i, f, p, p]),
         "nerf_occ_ray_span": (i, [p, p, i, i, p, p, p]),
         "nerf_occ_proposal_weights": (i, [p, p, f, p, i, p, i, i, p, p, p]),
+        "nerf_occ_stop_depth": (i, [p, p, i, i, f, p, p]),
+        "nerf_occ_compact_stop": (i, [p, p, i, p, p, i, i, p, p, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -119,6 +121,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_sample_ray_views", "nerf_ray_pose_grad",
            "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate",
            "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span", "nerf_occ_proposal_weights",
+           "nerf_occ_stop_depth", "nerf_occ_compact_stop",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
 
 
@@ -1096,9 +1099,11 @@ def occ_desc(lo, scale, res, outside_skip, bits):
                        (ctypes.c_int * 3)(*[int(v) for v in res]), int(bool(outside_skip)), _words(bits, "bits"))
 
 
-def occ_compact(desc, rays, z_vals, slot=None, records=None):
+def occ_compact(desc, rays, z_vals, slot=None, records=None, z_stop=None):
     """nerf_occ_compact: (slot int32 [n * S], records fp32 [n * S, 11] of which the first M rows are written, count int32 [1] = M on
-    the device).  slot / records: flat fp32 scratch of at least n * S / 11 n * S words (hb.WORKSPACE leases) or None (allocated)."""
+    the device).  slot / records: flat fp32 scratch of at least n * S / 11 n * S words (hb.WORKSPACE leases) or None (allocated).
+    z_stop (fp32 [n], occ_stop_depth's): nerf_occ_compact_stop -- the samples with z >= z_stop[ray] are dropped as well; None: the
+    entry point without a stop."""
     n, stride = rays.shape
     S = z_vals.shape[1]
     P = n * S
@@ -1108,10 +1113,18 @@ def occ_compact(desc, rays, z_vals, slot=None, records=None):
     records = (torch.empty(max(P, 1) * 11, dtype=torch.float32, device=dev) if records is None else records[:max(P, 1) * 11]).view(-1, 11)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     scratch = WORKSPACE.take(max(L.nerf_occ_scratch_words(P), 1), dev)
+    if z_stop is not None and tuple(z_stop.shape) != (n,):
+        raise NerfHipError("occ_compact: z_stop must hold one depth per ray")
     try:
-        with _timed("occ_compact (count + scan + write)", 0.0, 12.0 * P):
-            _check(L.nerf_occ_compact(ctypes.byref(desc), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"), n, S, slot.data_ptr(),
-                                      _ptr(records, "records"), count.data_ptr(), scratch.data_ptr(), _stream()), "nerf_occ_compact")
+        if z_stop is None:
+            with _timed("occ_compact (count + scan + write)", 0.0, 12.0 * P):
+                _check(L.nerf_occ_compact(ctypes.byref(desc), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"), n, S, slot.data_ptr(),
+                                          _ptr(records, "records"), count.data_ptr(), scratch.data_ptr(), _stream()), "nerf_occ_compact")
+        else:
+            with _timed("occ_compact_stop (count + scan + write)", 0.0, 12.0 * P + 4.0 * n):
+                _check(L.nerf_occ_compact_stop(ctypes.byref(desc), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"), _ptr(z_stop, "z_stop"),
+                                               n, S, slot.data_ptr(), _ptr(records, "records"), count.data_ptr(), scratch.data_ptr(),
+                                               _stream()), "nerf_occ_compact_stop")
     finally:        # stream-ordered, like every lease
         WORKSPACE.give(scratch)
     return slot[:P], records, count
@@ -1214,6 +1227,27 @@ def occ_proposal_weights(desc, density, outside_sigma, rays, z_vals, want_sigma=
                                                _ptr(z_vals, "z_vals"), n, S, _ptr(weights), _ptr(sigma, "sigma", True), _stream()),
                "nerf_occ_proposal_weights")
     return weights, sigma
+
+
+def stop_threshold(eps):
+    """fp32(1 - eps), computed in double: what the running sum of the coarse weights is compared with (include/nerf_hip.h)"""
+    import numpy as np
+    return float(np.float32(1.0 - float(eps)))
+
+
+def occ_stop_depth(z_vals, weights, eps):
+    """nerf_occ_stop_depth: z_stop fp32 [n] of z_vals / weights [n, S] -- per ray the depth of the sample behind the first one at which
+    the left-to-right fp32 sum of the weights reaches fp32(1 - eps), +inf where it never does or nothing lies behind"""
+    if z_vals.dim() != 2 or tuple(weights.shape) != tuple(z_vals.shape):
+        raise NerfHipError("occ_stop_depth: z_vals and weights [n, S]")
+    n, S = z_vals.shape
+    z_stop = torch.empty(n, dtype=torch.float32, device=z_vals.device)
+    if n == 0:
+        return z_stop
+    with _timed("occ_stop_depth_kernel", 0.0, 4.0 * n * S + 8.0 * n):
+        _check(lib().nerf_occ_stop_depth(_ptr(z_vals, "z_vals"), _ptr(weights, "weights"), n, S, stop_threshold(eps), _ptr(z_stop), _stream()),
+               "nerf_occ_stop_depth")
+    return z_stop
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

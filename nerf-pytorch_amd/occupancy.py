@@ -43,6 +43,46 @@ def _unpack_bits(words, n_cells):
     return (((w[:, None] >> torch.arange(32, dtype=torch.int64, device=w.device)) & 1).reshape(-1)[:n_cells]).bool()
 
 
+def _check_eps(eps, who):
+    e = float(eps)
+    if not (0.0 < e < 1.0):         # (also refuses NaN)
+        raise ValueError(f"{who}: early_stop_eps must satisfy 0 < eps < 1, got {eps!r}")
+    return e
+
+
+def stop_depth_reference(z_vals, weights, eps):
+    """The definition of the stop depth of render_rays(early_stop_eps=eps), in numpy (tensors of any device; fp32 [N] on z_vals' device).
+
+    weights[r, i] are the compositing weights of the coarse depths z_vals[r, i] -- the weight i belongs to the interval [z_i, z_{i+1}]
+    -- and their sum up to sample i is 1 - T, T the transmittance behind that interval.  Per ray: a = 0; a = a + weights[i] for i = 0,
+    1, ... -- one fp32 addition each, strictly left to right --; i* = the first i with a >= fp32(1 - eps) (the threshold is computed in
+    float64 and rounded once; a NaN weight never satisfies the comparison and poisons a: such a ray never stops);
+    z_stop = z_vals[i* + 1], or +inf when there is no i* or i* is the last sample (its interval is the reference's 1e10 one: nothing
+    lies behind it).  Behind z_stop the COARSE estimate of the transmittance is below eps."""
+    eps = _check_eps(eps, "stop_depth_reference")
+    z = np.asarray(z_vals.detach().cpu().numpy(), dtype=np.float32)
+    w = np.asarray(weights.detach().cpu().numpy(), dtype=np.float32)
+    if z.ndim != 2 or z.shape != w.shape:
+        raise ValueError("stop_depth_reference: z_vals and weights [N, S]")
+    n, S = z.shape
+    out = np.full(n, np.inf, dtype=np.float32)
+    if n > 0:
+        with np.errstate(invalid="ignore"):         # (inf - inf among the weights: a NaN, which never crosses)
+            crossed = np.cumsum(w, axis=1, dtype=np.float32) >= np.float32(hb.stop_threshold(eps))      # (sequential per row)
+        first = np.argmax(crossed, axis=1)
+        behind = crossed.any(axis=1) & (first + 1 < S)
+        out[behind] = z[behind, first[behind] + 1]
+    return torch.from_numpy(out).to(z_vals.device)
+
+
+def stop_depth(z_vals, weights, eps):
+    """fp32 [N] for z_vals / weights [N, S] on the GPU (nerf_occ_stop_depth): ``stop_depth_reference`` bit for bit.  A constant of the
+    graph (computed without gradients from detached values)."""
+    eps = _check_eps(eps, "stop_depth")
+    with torch.no_grad():
+        return hb.occ_stop_depth(z_vals.detach().to(torch.float32).contiguous(), weights.detach().to(torch.float32).contiguous(), eps)
+
+
 class OccupancyGrid:
     """One bit per cell of the axis-aligned box [lo, hi] at resolution (Rx, Ry, Rz) (an int means cubic; 1..512 per axis), in the
     space of the points ``o + d z`` the network sees -- for ``ndc=True`` rays that is NDC space.
@@ -54,7 +94,8 @@ class OccupancyGrid:
     ``outside="evaluate"`` (default): a point outside the box is evaluated -- the grid never hides what it does not cover;
     ``outside="skip"``: it is skipped (scenes bounded by the box).  A new grid is all-occupied.
     ``last_stats`` = {"evaluated", "total"}: sample points sent through the network / of the passes, for the last render_rays (or
-    batchify_rays / render: summed over its chunks) call that used this grid; with clip_to_occupancy=True also {"rays_hit", "rays"}.
+    batchify_rays / render: summed over its chunks) call that used this grid; with clip_to_occupancy=True also {"rays_hit", "rays"},
+    with early_stop_eps also {"rays_stopped"} (rays with a finite stop depth; "evaluated" then counts what survived grid and stop).
     ``ray_span`` / ``clip_rays`` give the grid its second use: per ray the span from the first to the last occupied cell it crosses
     (``ray_span_reference`` is the definition), which render_rays(clip_to_occupancy=True) samples instead of [near, far]."""
 

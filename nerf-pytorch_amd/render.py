@@ -584,7 +584,7 @@ def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f,
     return ret
 
 
-def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, proposal=None):
+def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, proposal=None, early_stop_eps=None):
     """render_rays without gradients through an occupancy grid (occupancy.OccupancyGrid): _render_rays_hooked's chain of stages with
     device code where the hook sits.  Per pass: depths (nerf_sample_coarse / nerf_sample_fine) -> nerf_occ_compact (classify o + d z,
     compact the occupied points into n_samples = 1 ray records) -> ONE read-back of the count M -> the field on the M records, as
@@ -592,7 +592,9 @@ def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, propo
     skipped samples) -> nerf_raw2outputs.  One host synchronisation per pass: two per call with N_importance > 0, else one.
     "fp16_fp8c": the compacted points run on the fp16x3 products (the fp8 correction terms' last-sample fix-up is per ray).
     proposal="grid": the coarse pass is replaced by the grid's own weights at the coarse depths (DensityGrid.proposal_weights: one
-    launch, no network, no read-back) and only the refining pass -- model_f, or model_c without one -- runs: one synchronisation."""
+    launch, no network, no read-back) and only the refining pass -- model_f, or model_c without one -- runs: one synchronisation.
+    early_stop_eps: the coarse weights give one stop depth per ray (nerf_occ_stop_depth) and the refining pass compacts with it
+    (nerf_occ_compact_stop); one more launch, no more synchronisations per pass."""
     n_c, n_f = cfg["N_samples"], cfg["N_importance"]
     dev = rays.device
     n = rays.shape[0]
@@ -601,13 +603,13 @@ def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, propo
     desc = grid._desc()
     stats = {"evaluated": 0, "total": 0}
 
-    def one_pass(z_vals, model, noise, want_weights):
+    def one_pass(z_vals, model, noise, want_weights, z_stop=None):
         S = z_vals.shape[1]
         P = n * S
         slot_ws, rec_ws = hb.WORKSPACE.take(P, dev), hb.WORKSPACE.take(11 * P, dev)
         raw_ws = z0 = None
         try:
-            slot, records, count = hb.occ_compact(desc, rays, z_vals, slot_ws, rec_ws)
+            slot, records, count = hb.occ_compact(desc, rays, z_vals, slot_ws, rec_ws, z_stop)
             m = int(count.item())        # the field launch needs M on the host
             raw = torch.empty((n, S, 4), dtype=torch.float32, device=dev)
             raw_ws = hb.WORKSPACE.take(4 * max(m, 1), dev)
@@ -634,9 +636,15 @@ def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, propo
         if proposal is None:
             ret.update(rgb0=rgb, disp0=disp, acc0=acc)
         u = rnd.get("u")
+        z_stop = n_stopped = None
+        if early_stop_eps is not None:
+            z_stop = hb.occ_stop_depth(z_c, weights, early_stop_eps)
+            n_stopped = torch.isfinite(z_stop).sum()        # read back after the passes, which synchronise anyway
         z_f, z_std, _ = hb.sample_fine(z_c, weights, n_f, u, None if u is not None else _linspace01(n_f, dev))
-        raw, (rgb, disp, acc, _, _) = one_pass(z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), False)
+        raw, (rgb, disp, acc, _, _) = one_pass(z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), False, z_stop)
         ret["z_std"] = z_std
+        if n_stopped is not None:
+            stats["rays_stopped"] = int(n_stopped.item())
     ret.update(rgb_map=rgb, disp_map=disp, acc_map=acc)
     if retraw:
         ret["raw"] = raw
@@ -670,7 +678,11 @@ class _RenderRaysGrid(torch.autograd.Function):
 
     cfg["proposal"] == "grid" (render_rays(proposal="grid")): the coarse pass is DensityGrid.proposal_weights -- a constant of the graph,
     nothing saved -- and the node has ONE pass, the refining one on model_c (the caller hands the evaluated network as model_c, model_f =
-    None); outputs (rgb, disp, acc, raw, z_std)."""
+    None); outputs (rgb, disp, acc, raw, z_std).
+
+    cfg["early_stop_eps"] (render_rays(early_stop_eps=)): per sub-chunk the coarse weights give one stop depth per ray
+    (nerf_occ_stop_depth) and the refining pass compacts with it (nerf_occ_compact_stop).  z_stop is a constant of the graph; a stopped
+    sample has slot -1 like a skipped one -- raw = 0, no gradient -- so nothing beyond slot is kept for it and the backward is unchanged."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
@@ -696,17 +708,19 @@ class _RenderRaysGrid(torch.autograd.Function):
         global LAST_BACKWARD_PLAN
         LAST_BACKWARD_PLAN = ("resident sub-chunks" if len(tiles) > 1 else "one launch", n, sub)
         stats = {"evaluated": 0, "total": 0}
+        eps = cfg.get("early_stop_eps")
+        n_stopped = []
         resident = [0]
         parts = []
 
-        def one_pass(rays_t, z_vals, model, noise, want_weights):
+        def one_pass(rays_t, z_vals, model, noise, want_weights, z_stop=None):
             nt, S = z_vals.shape
             P = nt * S
             p = {"z": z_vals, "slot": hb.WORKSPACE.take(P, dev), "act": None, "rec": None, "m": 0}
             parts[-1].append(p)         # (registered first: an error below hands its leases back with the others')
             rec_ws = hb.WORKSPACE.take(11 * P, dev)
             try:
-                slot, records, count = hb.occ_compact(desc, rays_t, z_vals, p["slot"], rec_ws)
+                slot, records, count = hb.occ_compact(desc, rays_t, z_vals, p["slot"], rec_ws, z_stop)
                 m = p["m"] = int(count.item())      # the field launch needs M on the host
                 raw = torch.empty((nt, S, 4), dtype=torch.float32, device=dev)
                 raw_c = torch.empty((max(m, 1), 1, 4), dtype=torch.float32, device=dev)
@@ -748,8 +762,13 @@ class _RenderRaysGrid(torch.autograd.Function):
                         outs.append((rgb_c, disp_c, acc_c, raw_c))
                         continue
                 u = rnd_t.get("u")
+                z_stop = None
+                if eps is not None:
+                    z_stop = hb.occ_stop_depth(z_c, w_c, eps)
+                    n_stopped.append(torch.isfinite(z_stop).sum())
                 z_f, z_std, _ = hb.sample_fine(z_c, w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
-                raw_f, (rgb_f, disp_f, acc_f, _, _) = one_pass(rays_t, z_f, model_c if ctx.same_net else model_f, rnd_t.get("noise_f"), False)
+                raw_f, (rgb_f, disp_f, acc_f, _, _) = one_pass(rays_t, z_f, model_c if ctx.same_net else model_f, rnd_t.get("noise_f"), False,
+                                                               z_stop)
                 outs.append((rgb_f, disp_f, acc_f, raw_f, z_std) if proposal else (rgb_f, disp_f, acc_f, raw_f, rgb_c, disp_c, acc_c, z_std))
         except BaseException:
             for passes in parts:
@@ -757,6 +776,8 @@ class _RenderRaysGrid(torch.autograd.Function):
                     for k_ in ("slot", "act", "rec"):
                         hb.WORKSPACE.give(p.get(k_))
             raise
+        if eps is not None:         # read back after the passes, which synchronised anyway
+            stats["rays_stopped"] = int(torch.stack(n_stopped).sum().item())
         grid.last_stats = stats
         if prec in ("fp16x3", "fp16x3w"):       # the fp16 split's range guard rail sees the compacted passes' saved activations
             for passes in parts:
@@ -881,7 +902,7 @@ class _RenderRaysGrid(torch.autograd.Function):
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None):
+                *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -918,9 +939,30 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     stream therefore differs from the two-network render's, by design.  Before the grid's first update its densities are 0 and all
     bits are set: the weights of the samples inside the box are exactly 0 (beyond a box with outside="evaluate" they carry
     sigma_threshold), sample_pdf's 1e-5 floor makes the pdf uniform, and the network sees the stratified plus uniformly drawn depths
-    -- nothing is hidden during the warm-up.  None: nothing changes."""
+    -- nothing is hidden during the warm-up.  None: nothing changes.
+
+    ``early_stop_eps`` (keyword-only, not in the reference; a float with 0 < eps < 1; needs ``occupancy`` and N_importance > 0): early
+    ray termination for the refining pass.  The coarse pass -- untouched -- has just returned its compositing weights (the coarse
+    network's, or the grid's under proposal="grid"); their running sum up to sample i is 1 - T, so one launch (nerf_occ_stop_depth;
+    occupancy.stop_depth_reference is the definition) finds per ray the coarse depth z_stop behind which that estimate of the
+    transmittance is below eps, and the refining pass's compaction (nerf_occ_compact_stop) drops every sample with z >= z_stop next to
+    the ones in empty cells: raw = 0, no network evaluation, no gradient, no saved activations.  Order inside a call: coarse depths
+    (after clip_to_occupancy) -> coarse weights -> z_stop -> nerf_sample_fine as before -> the refining pass.  rgb0 / disp0 / acc0, z_std
+    and the random draws are those of the call without the option.  AN APPROXIMATION: what is dropped from the refined image is the
+    REFINING pass's own transmittance at z_stop, which is close to eps where the two passes agree but is not bounded by it (a coarse
+    network that sees a surface the fine one does not cuts visible geometry) -- hence opt-in.  z_stop is a constant of the graph.
+    last_stats additionally carries "rays_stopped" (rays with a finite z_stop); "evaluated" counts what survived grid and stop.
+    None: nothing changes -- same launches, same bits, same draws."""
     if clip_to_occupancy and occupancy is None:
         raise ValueError("render_rays: clip_to_occupancy=True needs an occupancy grid (occupancy=)")
+    if early_stop_eps is not None:
+        early_stop_eps = float(early_stop_eps)
+        if not (0.0 < early_stop_eps < 1.0):        # (also refuses NaN)
+            raise ValueError(f"render_rays: early_stop_eps must be None or a float with 0 < eps < 1, got {early_stop_eps!r}")
+        if occupancy is None:
+            raise ValueError("render_rays: early_stop_eps needs an occupancy grid (occupancy=): the stop is applied by the grid's compaction")
+        if int(N_importance) <= 0:
+            raise ValueError("render_rays: early_stop_eps stops the refining pass from the coarse pass's weights: N_importance must be > 0")
     if proposal not in (None, "grid"):
         raise ValueError(f"render_rays: proposal must be None or \"grid\", got {proposal!r}")
     if proposal is not None:
@@ -963,6 +1005,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             occupancy.last_stats = {"evaluated": 0, "total": 0}
             if clip_to_occupancy:
                 occupancy.last_stats.update(rays_hit=0, rays=0)
+            if early_stop_eps is not None:
+                occupancy.last_stats.update(rays_stopped=0)
         return ret
     rnd = {}
     if randoms is not None:
@@ -1035,6 +1079,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             if cfg["precision"] == "fp16_fp8c":
                 cfg["precision"] = "fp16x3"         # the reduced class is an inference form; gradients: the fp16x3 datapath
             ret = {}        # (keys in _render_rays_occupancy's order)
+            if early_stop_eps is not None:
+                cfg["early_stop_eps"] = early_stop_eps
             if proposal is not None:
                 cfg["proposal"] = proposal
                 outs = _RenderRaysGrid.apply(cfg, rays, rnd, evaluated[0], None, occupancy, *evaluated[0].param_list())
@@ -1049,7 +1095,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             if retraw:
                 ret['raw'] = outs[3]
         else:
-            ret = _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw, proposal)
+            ret = _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw, proposal,
+                                         early_stop_eps)
         if n_hit is not None:
             occupancy.last_stats = dict(occupancy.last_stats, rays_hit=int(n_hit.item()), rays=n)
         return ret
@@ -1091,12 +1138,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """run_nerf.py:54-66.  Injected ``randoms`` (one row per ray) are sliced with the rays, so a chunked call consumes
     the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks (with ``clip_to_occupancy``
-    its "rays_hit" / "rays" too)."""
+    its "rays_hit" / "rays" too, with ``early_stop_eps`` its "rays_stopped")."""
     all_ret = {}
     randoms = kwargs.pop("randoms", None)
     occ, occ_stats = kwargs.get("occupancy"), {"evaluated": 0, "total": 0}
     if kwargs.get("clip_to_occupancy"):
         occ_stats.update(rays_hit=0, rays=0)
+    if kwargs.get("early_stop_eps") is not None:
+        occ_stats.update(rays_stopped=0)
     if randoms is not None:
         for k, v in randoms.items():
             if v.shape[0] != rays_flat.shape[0]:
