@@ -508,6 +508,25 @@ int nerf_occ_stop_depth(const float* z_vals, const float* weights, int n_rays, i
  * it.  Moves what nerf_occ_compact moves + 8 B per point (z_stop of the owning ray, twice; cached: 4 B per ray reach HBM). */
 int nerf_occ_compact_stop(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* z_vals, const float* z_stop, int n_rays,
                           int n_samples, int* slot, float* records, int* count, int* scratch, void* stream);
+/* ---- grid ray marching (additive in ABI v10): render_rays(proposal="march") places the depths of a ray itself instead of thinning
+ * out the reference's -- n_steps = M equal steps over [near, far], of which only the ones in occupied cells (and one closing step behind
+ * every occupied run) are emitted into n_slots = S slots.  OccupancyGrid.march_reference is the definition.  Per ray (o, d, near, far) =
+ * rays[r][0:8], with u[r] in [0, 1) (u == NULL: 0.5 for every ray), for k = 0 .. M - 1:
+ *   t_k = (fp32(k) + u) / fp32(M)              one fp32 addition, one correctly rounded fp32 division
+ *   z_k = near * (1 - t_k) + far * t_k         run_nerf.py:360's expression: one subtraction, two multiplications, one addition
+ *   keep_k  = the point o + d * z_k (one multiply, one add per axis) is occupied by nerf_occ_compact's rule
+ *   close_k = !keep_k && k > 0 && keep_{k-1}   the first empty candidate behind an occupied run: it is skipped by the compaction
+ *                                              (raw = 0) and owns the gap, so an evaluated sample's interval never reaches across one
+ * The emitted candidates are those with keep_k || close_k, in order of k, E of them.  The first n = min(E, S - 1) fill
+ * z_vals[r][0 .. n); E > S - 1: truncated[r] = 1 and z_stop[r] = the depth of emitted candidate S - 1 (the first that did not fit);
+ * else truncated[r] = 0 and z_stop[r] = far.  z_vals[r][n .. S) = z_stop[r]: nerf_occ_compact_stop's !(z >= z_stop) drops the padding,
+ * the last slot (the reference's 1e10 interval) included.  Rows are nondecreasing.  A ray whose first eight components are not all
+ * finite, or with near >= far, emits nothing: z_vals[r][:] = its own far (copied bit for bit), z_stop[r] = -inf, truncated[r] = 0.
+ * One wavefront per ray, 64 candidates per round (ballots and lane ranks); a wave leaves its loop once S slots are spoken for, so the
+ * cost follows what is emitted.  Plain stores, no atomics: the same inputs give the same bits.  Reads 32 B (+ 4 B of u) per ray and
+ * one bit word per candidate looked at; writes 4 S + 8 B per ray.  ray_stride >= 8; 1 <= n_steps <= 16384; 1 <= n_slots <= 4096. */
+int nerf_occ_march(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* u /* nullable: 0.5 */,
+                   int n_rays, int n_steps, int n_slots, float* z_vals, float* z_stop, int* truncated, void* stream);
 
 #ifdef __cplusplus
 }

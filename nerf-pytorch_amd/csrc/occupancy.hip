@@ -14,6 +14,9 @@
 //   nerf_occ_stop_depth : per ray the depth behind which the transmittance the coarse weights imply has fallen below eps -- a strictly
 //                      left-to-right fp32 running sum of the weights against 1 - eps -- and nerf_occ_compact_stop, the compaction that
 //                      also drops the samples at or behind it: render_rays(early_stop_eps=eps).
+//   nerf_occ_march   : per ray M equal steps over [near, far], the ones in occupied cells (and one closing step behind every occupied
+//                      run) emitted into S slots, with the stop depth that makes nerf_occ_compact_stop drop the padding:
+//                      render_rays(proposal="march").
 // The compaction is deterministic: a count per block of OCC_TILE points, an exclusive scan of the block counts, then the
 // write -- inside a block the position of a point is a wave ballot + popcount and a prefix over the block's wave counts, so the
 // list is in stable ray-major, sample-minor order and no atomic decides anything.
@@ -567,6 +570,69 @@ __global__ __launch_bounds__(STOP_THREADS) void occ_stop_depth_kernel(const floa
     if (walker) z_stop[my_ray] = (crossed >= 0 && crossed + 1 < S) ? z_vals[(size_t)my_ray * S + crossed + 1] : INFINITY;
 }
 
+// ---- nerf_occ_march (OccupancyGrid.march_reference is the definition)
+// One wavefront per ray, MARCH_RAYS rays per block.  A round takes 64 candidates: lane l builds z_k of k = k0 + l and classifies it
+// with sample_point / occupied -- the compaction's own functions, so the compaction sees the bits this kernel saw.  The keep mask is
+// a ballot; the closing candidates are (keep << 1 | carry) & ~keep, carry being lane 63's keep bit of the round before; a lane's rank
+// is the emitted lanes below it plus the running base.  Ranks below S - 1 store their depth, rank S - 1 is the stop depth (one
+// shuffle hands it to every lane), and the wave leaves once the base has passed S - 1: a ray that fills its slots in the first rounds
+// never looks at the rest of its M candidates.  Then the lanes pad the row with the stop depth.  Everything the wave branches on is
+// wave-uniform.
+constexpr int MARCH_THREADS = 256;
+constexpr int MARCH_RAYS = MARCH_THREADS / 64;
+
+__global__ __launch_bounds__(MARCH_THREADS) void occ_march_kernel(GridArgs g, const float* __restrict__ rays, int ray_stride,
+                                                                  const float* __restrict__ u, int n_rays, int M, int S,
+                                                                  float* __restrict__ z_vals, float* __restrict__ z_stop,
+                                                                  int* __restrict__ truncated) {
+    const int ray = blockIdx.x * MARCH_RAYS + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;          // (whole waves leave: the ballots below see full waves)
+    const int lane = threadIdx.x & 63;
+    const float* r = rays + (size_t)ray * ray_stride;
+    float* zrow = z_vals + (size_t)ray * S;
+    const float near = r[6], far = r[7];
+    bool ok = near < far;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) ok = ok && fabsf(r[c]) < INFINITY;      // (a NaN fails the comparison)
+    if (!ok) {
+        for (int j = lane; j < S; j += 64) zrow[j] = far;
+        if (lane == 0) {
+            z_stop[ray] = -INFINITY;
+            truncated[ray] = 0;
+        }
+        return;
+    }
+    const float uu = u ? u[ray] : 0.5f;
+    const float Mf = (float)M;
+    const int last = S - 1;
+    int base = 0, trunc = 0;
+    unsigned long long carry = 0ull;
+    float stop = far;
+    for (int k0 = 0; k0 < M && base <= last; k0 += 64) {
+        const int k = k0 + lane;
+        const float t = ((float)k + uu) / Mf;               // (IEEE division: hipcc's default for fp32)
+        const float z = near * (1.0f - t) + far * t;        // run_nerf.py:360 (no contraction)
+        const bool keep = k < M && occupied(g, sample_point(r, z));
+        const unsigned long long km = __ballot(keep);
+        const unsigned long long em = km | (((km << 1) | carry) & ~km & __ballot(k < M));
+        carry = km >> 63;
+        const int rank = base + lanes_below(em);
+        const bool emit = (em >> lane) & 1ull;
+        if (emit && rank < last) zrow[rank] = z;
+        const unsigned long long hit = __ballot(emit && rank == last);
+        if (hit) {
+            stop = __shfl(z, __ffsll((long long)hit) - 1);
+            trunc = 1;
+        }
+        base += __popcll(em);
+    }
+    for (int j = min(base, last) + lane; j < S; j += 64) zrow[j] = stop;
+    if (lane == 0) {
+        z_stop[ray] = stop;
+        truncated[ray] = trunc;
+    }
+}
+
 int check_grid(const char* fn, const NerfOccGrid* grid, GridArgs* g) {
     if (!grid || !grid->bits) return fail_arg(fn, "null pointer");
     for (int a = 0; a < 3; ++a) {
@@ -630,6 +696,19 @@ int nerf_occ_stop_depth(const float* z_vals, const float* weights, int n_rays, i
     if (n_rays == 0) return 0;
     occ_stop_depth_kernel<<<(unsigned)((n_rays + STOP_RAYS - 1) / STOP_RAYS), STOP_THREADS, 0, (hipStream_t)stream>>>(
         z_vals, weights, n_rays, n_samples, threshold, z_stop);
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_march(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* u, int n_rays, int n_steps, int n_slots,
+                   float* z_vals, float* z_stop, int* truncated, void* stream) {
+    GridArgs g;
+    if (int rc = check_grid(__func__, grid, &g)) return rc;
+    REQUIRE(rays && z_vals && z_stop && truncated, "null pointer");
+    REQUIRE(ray_stride >= 8 && n_rays >= 0 && n_steps >= 1 && n_steps <= 16384 && n_slots >= 1 && n_slots <= 4096,
+            "bad size (ray records need 8 columns, 1..16384 steps, 1..4096 slots)");
+    if (n_rays == 0) return 0;
+    occ_march_kernel<<<(unsigned)((n_rays + MARCH_RAYS - 1) / MARCH_RAYS), MARCH_THREADS, 0, (hipStream_t)stream>>>(
+        g, rays, ray_stride, u, n_rays, n_steps, n_slots, z_vals, z_stop, truncated);
     return done(__func__, hipGetLastError());
 }
 

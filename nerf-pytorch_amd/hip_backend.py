@@ -95,6 +95,7 @@ def _declare(lib):
         "nerf_occ_proposal_weights": (i, [p, p, f, p, i, p, i, i, p, p, p]),
         "nerf_occ_stop_depth": (i, [p, p, i, i, f, p, p]),
         "nerf_occ_compact_stop": (i, [p, p, i, p, p, i, i, p, p, p, p, p]),
+        "nerf_occ_march": (i, [p, p, i, p, i, i, i, p, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -121,7 +122,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_sample_ray_views", "nerf_ray_pose_grad",
            "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate",
            "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span", "nerf_occ_proposal_weights",
-           "nerf_occ_stop_depth", "nerf_occ_compact_stop",
+           "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
 
 
@@ -1248,6 +1249,25 @@ def occ_stop_depth(z_vals, weights, eps):
         _check(lib().nerf_occ_stop_depth(_ptr(z_vals, "z_vals"), _ptr(weights, "weights"), n, S, stop_threshold(eps), _ptr(z_stop), _stream()),
                "nerf_occ_stop_depth")
     return z_stop
+
+
+def occ_march(desc, rays, u, n_steps, n_slots):
+    """nerf_occ_march: (z_vals fp32 [n, n_slots], z_stop fp32 [n], truncated int32 [n]) of rays [n, >= 8] -- per ray the n_steps equal
+    steps over [near, far] that fall in occupied cells (plus one closing step behind every occupied run), padded with the stop depth
+    that nerf_occ_compact_stop drops; u: fp32 [n] in [0, 1), the offset of the ray's steps, or None (0.5)"""
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise NerfHipError("occ_march: rays [n, >= 8] (o, d, near, far, ...)")
+    n, stride = rays.shape
+    M, S = int(n_steps), int(n_slots)
+    if u is not None and tuple(u.shape) != (n,):
+        raise NerfHipError("occ_march: u must hold one offset per ray")
+    z_vals = torch.empty((n, S), dtype=torch.float32, device=rays.device)
+    z_stop = torch.empty(n, dtype=torch.float32, device=rays.device)
+    truncated = torch.empty(n, dtype=torch.int32, device=rays.device)
+    with _timed("occ_march_kernel", 0.0, (4.0 * S + 44.0) * n):
+        _check(lib().nerf_occ_march(ctypes.byref(desc), _ptr(rays, "rays"), stride, _ptr(u, "u", True), n, M, S, _ptr(z_vals), _ptr(z_stop),
+                                    truncated.data_ptr(), _stream()), "nerf_occ_march")
+    return z_vals, z_stop, truncated
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

@@ -97,7 +97,9 @@ class OccupancyGrid:
     batchify_rays / render: summed over its chunks) call that used this grid; with clip_to_occupancy=True also {"rays_hit", "rays"},
     with early_stop_eps also {"rays_stopped"} (rays with a finite stop depth; "evaluated" then counts what survived grid and stop).
     ``ray_span`` / ``clip_rays`` give the grid its second use: per ray the span from the first to the last occupied cell it crosses
-    (``ray_span_reference`` is the definition), which render_rays(clip_to_occupancy=True) samples instead of [near, far]."""
+    (``ray_span_reference`` is the definition), which render_rays(clip_to_occupancy=True) samples instead of [near, far].
+    ``march`` gives it a third: the depths themselves, per ray the equal steps over [near, far] that fall in occupied cells
+    (``march_reference`` is the definition) -- render_rays(proposal="march"), whose last_stats carry {"rays_truncated"}."""
 
     def __init__(self, lo, hi, resolution, outside="evaluate", device=None):
         if outside not in _OUTSIDE:
@@ -231,6 +233,63 @@ class OccupancyGrid:
         autograd history; near' / far' are constants of the graph (no gradient flows through the span, as none flows to near / far)."""
         span, hit = self.ray_span(rays)
         return torch.cat([rays[:, :6], span.to(rays.dtype), rays[:, 8:]], -1), hit
+
+    # ------------------------------------------------------------------ ray marching
+    def march_reference(self, rays, u, n_steps, n_slots):
+        """The definition of the depths of render_rays(proposal="march"), in plain torch (any device): rays [N, >= 8] (o, d, near, far),
+        u fp32 [N] in [0, 1) or None (0.5 for every ray) -> (z_vals fp32 [N, S], z_stop fp32 [N], truncated bool [N]), M = n_steps,
+        S = n_slots.
+
+        Candidates, k = 0 .. M - 1: t_k = (fp32(k) + u) / fp32(M) (one addition, one correctly rounded division);
+        z_k = near * (1 - t_k) + far * t_k (run_nerf.py:360's expression, no contraction).  keep_k = occupied(o + d * z_k) (one multiply,
+        one add per axis: run_nerf.py:381); close_k = not keep_k and k > 0 and keep_{k-1}, the first empty candidate behind an occupied
+        run.  The emitted candidates are those with keep_k or close_k, in order of k, E of them: the first n = min(E, S - 1) fill
+        z_vals[r, 0:n]; with E > S - 1 the ray is truncated and z_stop is the depth of emitted candidate S - 1 (the first that did not
+        fit), else z_stop = far; the slots n .. S - 1 hold z_stop.  A ray whose first eight components are not all finite, or with
+        near >= far, emits nothing: its row is its own far, its z_stop -inf ("stops everything"), and it is not truncated.
+
+        A closing sample lies in an empty cell: the compaction skips it (raw = 0, alpha = 0) and it owns the gap behind its run, so an
+        evaluated sample's interval z[i + 1] - z[i] reaches exactly to the next candidate and never across a gap.  Padding and
+        truncation ride on z_stop: nerf_occ_compact_stop's not (z >= z_stop) drops every slot at or behind it, the last one -- the
+        reference's 1e10 interval -- included.  Rows are nondecreasing: nothing is sorted."""
+        M, S = int(n_steps), int(n_slots)
+        if M < 1 or S < 1:
+            raise ValueError("march_reference: n_steps >= 1 and n_slots >= 1")
+        if rays.dim() != 2 or rays.shape[1] < 8:
+            raise ValueError("march_reference: rays [N, >= 8] (o, d, near, far, ...)")
+        dev = rays.device
+        r = rays.detach()[:, :8].to(torch.float32)
+        N = r.shape[0]
+        ok = torch.isfinite(r).all(-1) & (r[:, 6] < r[:, 7])
+        near, far = r[:, 6:7], r[:, 7:8]
+        uu = torch.full((N, 1), 0.5, dtype=torch.float32, device=dev) if u is None else u.detach().to(device=dev, dtype=torch.float32).reshape(N, 1)
+        k = torch.arange(M, dtype=torch.float32, device=dev)[None, :]
+        t = (k + uu) / torch.tensor(float(M), dtype=torch.float32, device=dev)
+        z = near * (1.0 - t) + far * t
+        keep = self.occupied(r[:, None, 0:3] + r[:, None, 3:6] * z[:, :, None]) & ok[:, None]
+        before = torch.cat([torch.zeros_like(keep[:, :1]), keep[:, :-1]], -1)
+        emit = keep | (before & ~keep)
+        rank = torch.cumsum(emit.to(torch.int64), -1) - 1
+        truncated = emit.sum(-1) > S - 1
+        first_out = emit & (rank == S - 1)          # (at most one per row)
+        z_stop = torch.where(truncated, z.gather(1, first_out.to(torch.uint8).argmax(-1, keepdim=True))[:, 0], r[:, 7])
+        z_stop = torch.where(ok, z_stop, torch.full_like(z_stop, float("-inf")))
+        z_vals = torch.where(ok, z_stop, r[:, 7])[:, None].repeat(1, S)
+        rows, cols = (emit & (rank < S - 1)).nonzero(as_tuple=True)
+        z_vals[rows, rank[rows, cols]] = z[rows, cols]
+        return z_vals, z_stop, truncated
+
+    def march(self, rays, n_steps, n_slots, u=None):
+        """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N]) for rays [N, >= 8] on the GPU (nerf_occ_march):
+        ``march_reference`` bit for bit.  Constants of the graph (computed without gradients from detached values, as the reference
+        detaches z_samples)."""
+        M, S = int(n_steps), int(n_slots)
+        if not (1 <= M <= 16384) or not (1 <= S <= 4096):
+            raise ValueError(f"OccupancyGrid.march: 1 <= n_steps <= 16384 and 1 <= n_slots <= 4096, got {n_steps!r}, {n_slots!r}")
+        with torch.no_grad():
+            z_vals, z_stop, truncated = hb.occ_march(self._desc(), rays.detach().to(torch.float32).contiguous(),
+                                                     None if u is None else u.detach().to(torch.float32).contiguous(), M, S)
+        return z_vals, z_stop, truncated.bool()
 
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):

@@ -584,7 +584,7 @@ def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f,
     return ret
 
 
-def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, proposal=None, early_stop_eps=None):
+def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, proposal=None, early_stop_eps=None, march_steps=None):
     """render_rays without gradients through an occupancy grid (occupancy.OccupancyGrid): _render_rays_hooked's chain of stages with
     device code where the hook sits.  Per pass: depths (nerf_sample_coarse / nerf_sample_fine) -> nerf_occ_compact (classify o + d z,
     compact the occupied points into n_samples = 1 ray records) -> ONE read-back of the count M -> the field on the M records, as
@@ -594,7 +594,10 @@ def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, propo
     proposal="grid": the coarse pass is replaced by the grid's own weights at the coarse depths (DensityGrid.proposal_weights: one
     launch, no network, no read-back) and only the refining pass -- model_f, or model_c without one -- runs: one synchronisation.
     early_stop_eps: the coarse weights give one stop depth per ray (nerf_occ_stop_depth) and the refining pass compacts with it
-    (nerf_occ_compact_stop); one more launch, no more synchronisations per pass."""
+    (nerf_occ_compact_stop); one more launch, no more synchronisations per pass.
+    march_steps (render_rays(proposal="march")): the depths are the grid's own (nerf_occ_march: march_steps candidates, N_samples slots)
+    and the call is ONE pass of model_c on them, compacted with the march's stop depth (the caller hands the evaluated network as
+    model_c, N_importance = 0 and the pass's noise as noise_c): one more launch than a coarse-only call, one synchronisation."""
     n_c, n_f = cfg["N_samples"], cfg["N_importance"]
     dev = rays.device
     n = rays.shape[0]
@@ -626,12 +629,18 @@ def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, propo
         return raw, hb.raw2outputs(raw, z_vals, rays, rays.shape[1], noise, std, wb, want_weights=want_weights, want_depth=False,
                                    rays_d_offset=3)
 
-    z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
     ret = {}
-    if proposal is not None:
-        weights = grid.proposal_weights(rays, z_c)
+    if march_steps is not None:
+        z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), march_steps, n_c)
+        n_truncated = truncated.sum()       # read back after the pass, which synchronises anyway
+        raw, (rgb, disp, acc, _, _) = one_pass(z_m, model_c, rnd.get("noise_c"), False, z_stop)
+        stats["rays_truncated"] = int(n_truncated.item())
     else:
-        raw, (rgb, disp, acc, weights, _) = one_pass(z_c, model_c, rnd.get("noise_c"), n_f > 0)
+        z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
+        if proposal is not None:
+            weights = grid.proposal_weights(rays, z_c)
+        else:
+            raw, (rgb, disp, acc, weights, _) = one_pass(z_c, model_c, rnd.get("noise_c"), n_f > 0)
     if n_f > 0:
         if proposal is None:
             ret.update(rgb0=rgb, disp0=disp, acc0=acc)
@@ -682,7 +691,12 @@ class _RenderRaysGrid(torch.autograd.Function):
 
     cfg["early_stop_eps"] (render_rays(early_stop_eps=)): per sub-chunk the coarse weights give one stop depth per ray
     (nerf_occ_stop_depth) and the refining pass compacts with it (nerf_occ_compact_stop).  z_stop is a constant of the graph; a stopped
-    sample has slot -1 like a skipped one -- raw = 0, no gradient -- so nothing beyond slot is kept for it and the backward is unchanged."""
+    sample has slot -1 like a skipped one -- raw = 0, no gradient -- so nothing beyond slot is kept for it and the backward is unchanged.
+
+    cfg["march_steps"] (render_rays(proposal="march")): per sub-chunk the depths are nerf_occ_march's (march_steps candidates, N_samples
+    slots) and the node's single pass compacts with the march's stop depth.  The caller hands the evaluated network as model_c, model_f =
+    None, N_importance = 0 and the pass's noise as noise_c, so the backward is the coarse-only one; depths and stop depth are constants of
+    the graph; outputs (rgb, disp, acc, raw)."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
@@ -709,7 +723,8 @@ class _RenderRaysGrid(torch.autograd.Function):
         LAST_BACKWARD_PLAN = ("resident sub-chunks" if len(tiles) > 1 else "one launch", n, sub)
         stats = {"evaluated": 0, "total": 0}
         eps = cfg.get("early_stop_eps")
-        n_stopped = []
+        march_steps = cfg.get("march_steps")
+        n_stopped, n_truncated = [], []
         resident = [0]
         parts = []
 
@@ -753,6 +768,12 @@ class _RenderRaysGrid(torch.autograd.Function):
                 rays_t = rays[lo:hi]
                 rnd_t = rnd if len(tiles) == 1 else {k_: v[lo:hi] for k_, v in rnd.items()}
                 parts.append([])
+                if march_steps is not None:
+                    z_m, z_stop, truncated = hb.occ_march(desc, rays_t, rnd_t.get("u_march"), march_steps, n_c)
+                    n_truncated.append(truncated.sum())
+                    raw_c, (rgb_c, disp_c, acc_c, _, _) = one_pass(rays_t, z_m, model_c, rnd_t.get("noise_c"), False, z_stop)
+                    outs.append((rgb_c, disp_c, acc_c, raw_c))
+                    continue
                 z_c = hb.sample_coarse(rays_t, _linspace01(n_c, dev), cfg["lindisp"], rnd_t.get("t_rand"))
                 if proposal:
                     w_c = grid.proposal_weights(rays_t, z_c)
@@ -778,6 +799,8 @@ class _RenderRaysGrid(torch.autograd.Function):
             raise
         if eps is not None:         # read back after the passes, which synchronised anyway
             stats["rays_stopped"] = int(torch.stack(n_stopped).sum().item())
+        if march_steps is not None:
+            stats["rays_truncated"] = int(torch.stack(n_truncated).sum().item())
         grid.last_stats = stats
         if prec in ("fp16x3", "fp16x3w"):       # the fp16 split's range guard rail sees the compacted passes' saved activations
             for passes in parts:
@@ -902,7 +925,7 @@ class _RenderRaysGrid(torch.autograd.Function):
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None):
+                *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None, march_steps=None):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -952,9 +975,41 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     REFINING pass's own transmittance at z_stop, which is close to eps where the two passes agree but is not bounded by it (a coarse
     network that sees a surface the fine one does not cuts visible geometry) -- hence opt-in.  z_stop is a constant of the graph.
     last_stats additionally carries "rays_stopped" (rays with a finite z_stop); "evaluated" counts what survived grid and stop.
-    None: nothing changes -- same launches, same bits, same draws."""
+    None: nothing changes -- same launches, same bits, same draws.
+
+    ``proposal="march"`` with ``march_steps=M`` (keyword-only, not in the reference; needs ``occupancy``, a plain OccupancyGrid under
+    no_grad or a DensityGrid with gradients): grid ray marching.  The depths are no longer the reference's thinned out: every ray is
+    walked in M equal steps over [near, far] (after clip_to_occupancy if that is on: the steps then span the occupied hull) and only
+    the steps in occupied cells, plus one closing step behind every occupied run, are written into S = N_samples + max(N_importance, 0)
+    slots (occupancy.OccupancyGrid.march_reference is the definition, nerf_occ_march the kernel; no coarse pass, no sample_pdf, no
+    sort).  ONE network -- network_fine if given, else network_fn -- is evaluated on them through the compacted grid pass; the closing
+    steps lie in empty cells and get raw = 0, so a sample's interval never reaches across a gap; the padding behind the last emitted
+    step, and whatever did not fit into S slots, is dropped by the compaction's stop depth.  The other network is never touched: no
+    launch, .grad stays None, no _grad_ready.  The dict holds rgb_map, disp_map, acc_map (and raw [N, S, 4] with retraw): no rgb0 /
+    disp0 / acc0 and no z_std.  Random draws: with perturb > 0 one offset per ray, u_march [N] (all steps of a ray move together; 0.5
+    without), then with raw_noise_std > 0 noise_f [N, S] -- these are the ``randoms`` keys; t_rand, u and noise_c are neither drawn nor
+    read.  last_stats = {"evaluated", "total" = N * S, "rays_truncated"} (rays whose emitted steps did not fit: raise N_samples +
+    N_importance, or lower march_steps).  1 <= march_steps <= 16384, S <= 4096; lindisp and early_stop_eps (there are no coarse weights to
+    stop on) are refused.  ``march_steps`` without proposal="march" is refused."""
     if clip_to_occupancy and occupancy is None:
         raise ValueError("render_rays: clip_to_occupancy=True needs an occupancy grid (occupancy=)")
+    march = isinstance(proposal, str) and proposal == "march"
+    if march_steps is not None and not march:
+        raise ValueError("render_rays: march_steps belongs to proposal=\"march\"")
+    if march:
+        if occupancy is None:
+            raise ValueError("render_rays: proposal=\"march\" walks an occupancy grid (occupancy=): none was given")
+        if isinstance(march_steps, bool) or not isinstance(march_steps, (int, np.integer)) or not (1 <= int(march_steps) <= 16384):
+            raise ValueError(f"render_rays: proposal=\"march\" needs march_steps, an int with 1 <= march_steps <= 16384, got {march_steps!r}")
+        if early_stop_eps is not None:
+            raise ValueError("render_rays: early_stop_eps together with proposal=\"march\": there are no coarse weights to stop on")
+        if int(N_samples) + max(int(N_importance), 0) > 4096:
+            raise ValueError("render_rays: proposal=\"march\" fills at most 4096 slots per ray (N_samples + N_importance)")
+        if int(N_samples) + max(int(N_importance), 0) < 1:
+            raise ValueError("render_rays: proposal=\"march\" needs at least one slot per ray (N_samples + N_importance)")
+        if lindisp:
+            raise NotImplementedError("render_rays: proposal=\"march\" with lindisp=True is not implemented (the steps are equal in depth)")
+        march_steps = int(march_steps)
     if early_stop_eps is not None:
         early_stop_eps = float(early_stop_eps)
         if not (0.0 < early_stop_eps < 1.0):        # (also refuses NaN)
@@ -963,9 +1018,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             raise ValueError("render_rays: early_stop_eps needs an occupancy grid (occupancy=): the stop is applied by the grid's compaction")
         if int(N_importance) <= 0:
             raise ValueError("render_rays: early_stop_eps stops the refining pass from the coarse pass's weights: N_importance must be > 0")
-    if proposal not in (None, "grid"):
-        raise ValueError(f"render_rays: proposal must be None or \"grid\", got {proposal!r}")
-    if proposal is not None:
+    if not march and proposal not in (None, "grid"):
+        raise ValueError(f"render_rays: proposal must be None, \"grid\" or \"march\", got {proposal!r}")
+    if proposal is not None and not march:
         from .occupancy import DensityGrid
         if not isinstance(occupancy, DensityGrid):
             raise ValueError("render_rays: proposal=\"grid\" reads the densities of an occupancy.DensityGrid (occupancy=); "
@@ -995,8 +1050,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         e = lambda *tail: torch.zeros((0,) + tail, dtype=torch.float32, device=dev)
         ret = {'rgb_map': e(3), 'disp_map': e(), 'acc_map': e()}
         if retraw:
-            ret['raw'] = e(N_samples + n_f, 4)
-        if n_f > 0:
+            ret['raw'] = e(N_samples + max(n_f, 0) if march else N_samples + n_f, 4)
+        if n_f > 0 and not march:
             if proposal is None:
                 ret.update(rgb0=e(3), disp0=e(), acc0=e())
             ret.update(z_std=e())
@@ -1007,12 +1062,16 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                 occupancy.last_stats.update(rays_hit=0, rays=0)
             if early_stop_eps is not None:
                 occupancy.last_stats.update(rays_stopped=0)
+            if march:
+                occupancy.last_stats.update(rays_truncated=0)
         return ret
     rnd = {}
     if randoms is not None:
         keys = (["t_rand"] if perturb > 0. else []) + (["noise_c"] if raw_noise_std > 0. and proposal is None else [])
         if n_f > 0:
             keys += (["u"] if perturb > 0. else []) + (["noise_f"] if raw_noise_std > 0. else [])
+        if march:
+            keys = (["u_march"] if perturb > 0. else []) + (["noise_f"] if raw_noise_std > 0. else [])
         rnd = {k: randoms[k].to(device=dev, dtype=torch.float32).contiguous() for k in keys}
         for k, v in rnd.items():
             if v.shape[0] != n:
@@ -1021,7 +1080,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     else:
         perturb_draw = perturb
     # draw order of the reference: t_rand (:371) -> noise coarse (:285) -> u (helpers:208) -> noise fine (:285)
-    if perturb_draw > 0.:
+    if perturb_draw > 0. and not march:
         rnd["t_rand"] = torch.rand((n, N_samples), device=dev)
         if pytest:
             np.random.seed(0)
@@ -1036,7 +1095,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         return nz.contiguous()
     if raw_noise_std > 0. and randoms is None and proposal is None:
         rnd["noise_c"] = draw_noise(N_samples)
-    if n_f > 0:
+    if march:       # draw order: u_march (one offset per ray) -> noise of the one pass
+        if perturb_draw > 0.:
+            rnd["u_march"] = torch.rand(n, device=dev)
+            if pytest:
+                np.random.seed(0)
+                rnd["u_march"] = torch.Tensor(np.random.rand(n)).to(dev)
+        if raw_noise_std > 0. and randoms is None:
+            rnd["noise_f"] = draw_noise(N_samples + max(n_f, 0))
+    elif n_f > 0:
         if perturb_draw > 0.:
             rnd["u"] = torch.rand((n, n_f), device=dev)
             if pytest:
@@ -1071,6 +1138,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             grid_grad = True
         else:
             grid_grad = False
+        if march:       # ONE pass over all the slots: what the two paths below run as a coarse-only call on the march's depths
+            cfg.update(N_samples=int(N_samples) + max(n_f, 0), N_importance=0, march_steps=march_steps)
+            rnd = {k_: v for k_, v in (("u_march", rnd.get("u_march")), ("noise_c", rnd.get("noise_f"))) if v is not None}
         n_hit = None
         if clip_to_occupancy:       # (after the guards: a refused call launches nothing; the draws above do not depend on near / far)
             rays, hit = occupancy.clip_rays(rays)
@@ -1081,7 +1151,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             ret = {}        # (keys in _render_rays_occupancy's order)
             if early_stop_eps is not None:
                 cfg["early_stop_eps"] = early_stop_eps
-            if proposal is not None:
+            if march:
+                outs = _RenderRaysGrid.apply(cfg, rays, rnd, evaluated[0], None, occupancy, *evaluated[0].param_list())
+            elif proposal is not None:
                 cfg["proposal"] = proposal
                 outs = _RenderRaysGrid.apply(cfg, rays, rnd, evaluated[0], None, occupancy, *evaluated[0].param_list())
                 ret.update(z_std=outs[4])
@@ -1094,6 +1166,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             ret.update(rgb_map=outs[0], disp_map=outs[1], acc_map=outs[2])
             if retraw:
                 ret['raw'] = outs[3]
+        elif march:
+            ret = _render_rays_occupancy(cfg, rays, rnd, evaluated[0], None, occupancy, retraw, march_steps=march_steps)
         else:
             ret = _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw, proposal,
                                          early_stop_eps)
@@ -1138,7 +1212,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """run_nerf.py:54-66.  Injected ``randoms`` (one row per ray) are sliced with the rays, so a chunked call consumes
     the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks (with ``clip_to_occupancy``
-    its "rays_hit" / "rays" too, with ``early_stop_eps`` its "rays_stopped")."""
+    its "rays_hit" / "rays" too, with ``early_stop_eps`` its "rays_stopped", with ``proposal="march"`` its "rays_truncated")."""
     all_ret = {}
     randoms = kwargs.pop("randoms", None)
     occ, occ_stats = kwargs.get("occupancy"), {"evaluated": 0, "total": 0}
@@ -1146,6 +1220,8 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
         occ_stats.update(rays_hit=0, rays=0)
     if kwargs.get("early_stop_eps") is not None:
         occ_stats.update(rays_stopped=0)
+    if isinstance(kwargs.get("proposal"), str) and kwargs["proposal"] == "march":
+        occ_stats.update(rays_truncated=0)
     if randoms is not None:
         for k, v in randoms.items():
             if v.shape[0] != rays_flat.shape[0]:
