@@ -9,7 +9,7 @@ else of render_rays changes.  Device code: csrc/occupancy.hip (include/nerf_hip.
 A static bit grid is built from a network that training is about to change.  ``DensityGrid`` is the grid that follows the network
 (Instant-NGP's density grid, Mueller et al. 2022, section 5 / appendix E.2): a decayed running maximum of the density per cell,
 refreshed every few steps and thresholded into the bits the renderer reads; ``render_rays(..., occupancy=density_grid)`` is
-differentiable (render._RenderRaysGrid).
+differentiable (render._RenderRaysGrid; its forward is render._grid_chain, the stages of the no-grad grid render).
 """
 import math
 

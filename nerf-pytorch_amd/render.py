@@ -7,6 +7,8 @@ Random draws (stratified jitter, density noise, CDF samples) are made here with
 torch, in the reference's order and shapes, and handed to the
 kernels, so a seeded run consumes the generator exactly like the reference.
 """
+from functools import partial
+
 import numpy as np
 import torch
 
@@ -584,83 +586,6 @@ def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f,
     return ret
 
 
-def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid, retraw, proposal=None, early_stop_eps=None, march_steps=None):
-    """render_rays without gradients through an occupancy grid (occupancy.OccupancyGrid): _render_rays_hooked's chain of stages with
-    device code where the hook sits.  Per pass: depths (nerf_sample_coarse / nerf_sample_fine) -> nerf_occ_compact (classify o + d z,
-    compact the occupied points into n_samples = 1 ray records) -> ONE read-back of the count M -> the field on the M records, as
-    query_points evaluates points (nerf_field_fwd / nerf_field_fwd_split; no launch when M == 0) -> nerf_occ_expand (raw, zeros for
-    skipped samples) -> nerf_raw2outputs.  One host synchronisation per pass: two per call with N_importance > 0, else one.
-    "fp16_fp8c": the compacted points run on the fp16x3 products (the fp8 correction terms' last-sample fix-up is per ray).
-    proposal="grid": the coarse pass is replaced by the grid's own weights at the coarse depths (DensityGrid.proposal_weights: one
-    launch, no network, no read-back) and only the refining pass -- model_f, or model_c without one -- runs: one synchronisation.
-    early_stop_eps: the coarse weights give one stop depth per ray (nerf_occ_stop_depth) and the refining pass compacts with it
-    (nerf_occ_compact_stop); one more launch, no more synchronisations per pass.
-    march_steps (render_rays(proposal="march")): the depths are the grid's own (nerf_occ_march: march_steps candidates, N_samples slots)
-    and the call is ONE pass of model_c on them, compacted with the march's stop depth (the caller hands the evaluated network as
-    model_c, N_importance = 0 and the pass's noise as noise_c): one more launch than a coarse-only call, one synchronisation."""
-    n_c, n_f = cfg["N_samples"], cfg["N_importance"]
-    dev = rays.device
-    n = rays.shape[0]
-    std, wb = cfg["raw_noise_std"], cfg["white_bkgd"]
-    prec = "fp16x3" if cfg["precision"] == "fp16_fp8c" else cfg["precision"]
-    desc = grid._desc()
-    stats = {"evaluated": 0, "total": 0}
-
-    def one_pass(z_vals, model, noise, want_weights, z_stop=None):
-        S = z_vals.shape[1]
-        P = n * S
-        slot_ws, rec_ws = hb.WORKSPACE.take(P, dev), hb.WORKSPACE.take(11 * P, dev)
-        raw_ws = z0 = None
-        try:
-            slot, records, count = hb.occ_compact(desc, rays, z_vals, slot_ws, rec_ws, z_stop)
-            m = int(count.item())        # the field launch needs M on the host
-            raw = torch.empty((n, S, 4), dtype=torch.float32, device=dev)
-            raw_ws = hb.WORKSPACE.take(4 * max(m, 1), dev)
-            if m > 0:
-                z0 = hb.WORKSPACE.take(m, dev)
-                z0[:m].zero_()
-                hb.field_fwd(model.packed_params(prec), records[:m], z0[:m].view(m, 1), precision=prec, raw=raw_ws[:4 * m].view(m, 1, 4))
-            hb.occ_expand(slot, raw_ws, raw)
-        finally:        # stream-ordered: the next lease is written by kernels enqueued after these
-            for t in (slot_ws, rec_ws, raw_ws, z0):
-                hb.WORKSPACE.give(t)
-        stats["evaluated"] += m
-        stats["total"] += P
-        return raw, hb.raw2outputs(raw, z_vals, rays, rays.shape[1], noise, std, wb, want_weights=want_weights, want_depth=False,
-                                   rays_d_offset=3)
-
-    ret = {}
-    if march_steps is not None:
-        z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), march_steps, n_c)
-        n_truncated = truncated.sum()       # read back after the pass, which synchronises anyway
-        raw, (rgb, disp, acc, _, _) = one_pass(z_m, model_c, rnd.get("noise_c"), False, z_stop)
-        stats["rays_truncated"] = int(n_truncated.item())
-    else:
-        z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
-        if proposal is not None:
-            weights = grid.proposal_weights(rays, z_c)
-        else:
-            raw, (rgb, disp, acc, weights, _) = one_pass(z_c, model_c, rnd.get("noise_c"), n_f > 0)
-    if n_f > 0:
-        if proposal is None:
-            ret.update(rgb0=rgb, disp0=disp, acc0=acc)
-        u = rnd.get("u")
-        z_stop = n_stopped = None
-        if early_stop_eps is not None:
-            z_stop = hb.occ_stop_depth(z_c, weights, early_stop_eps)
-            n_stopped = torch.isfinite(z_stop).sum()        # read back after the passes, which synchronise anyway
-        z_f, z_std, _ = hb.sample_fine(z_c, weights, n_f, u, None if u is not None else _linspace01(n_f, dev))
-        raw, (rgb, disp, acc, _, _) = one_pass(z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), False, z_stop)
-        ret["z_std"] = z_std
-        if n_stopped is not None:
-            stats["rays_stopped"] = int(n_stopped.item())
-    ret.update(rgb_map=rgb, disp_map=disp, acc_map=acc)
-    if retraw:
-        ret["raw"] = raw
-    grid.last_stats = stats
-    return ret
-
-
 def _grid_pass_lease(m, P, prec):
     """floats of the save buffer of a compacted pass of m of P points: m rounded up to the next eighth of the dense size.  M moves from
     step to step in training and Workspace.take passes over a free buffer more than twice the request; with eight sizes per pass a
@@ -669,13 +594,127 @@ def _grid_pass_lease(m, P, prec):
     return hb.act_floats(q * max(1, -(-m // q)), 1, prec)
 
 
+def _grid_pass(cfg, desc, rays, z_vals, model, noise, want_weights, z_stop=None, *, stats, passes=None, budget=None):
+    """THE compacted pass of both grid paths: depths -> nerf_occ_compact[_stop] (classify o + d z, drop what lies at or behind z_stop,
+    compact the rest into n_samples = 1 ray records) -> ONE read-back of the count M -> the field on the M records, as query_points
+    evaluates points (no launch when M == 0) -> nerf_occ_expand (raw, zeros for skipped samples) -> nerf_raw2outputs.  Returns
+    (raw, raw2outputs' tuple) and adds the pass to stats["evaluated" / "total"].
+    passes None (no backward follows): slot and records are hb.WORKSPACE leases handed back before the compositing -- stream-ordered: the
+    next lease is written by kernels enqueued after these.
+    passes = the list of the current ray sub-chunk's pass records (_RenderRaysGrid.forward): the field saves its activations into a lease
+    of _grid_pass_lease's size, and the record the backward reads -- z, slot, act, rec (the M records, only when the rays need a
+    gradient), m, packed, raw -- is appended to `passes` BEFORE anything can fail, so that the node hands its leases back with the
+    others' on an error.  budget = {"rays_grad": bool, "resident": bytes the call keeps so far, "rays": rays of the whole call} goes with
+    it: beyond hb.SAVE_TOTAL_BYTES in total the pass raises.
+    The compacted raw and the M zero depths live inside the pass and are plain torch allocations on both paths."""
+    n, S = z_vals.shape
+    P = n * S
+    dev, prec = rays.device, cfg["precision"]
+    p = {"z": z_vals, "slot": hb.WORKSPACE.take(P, dev), "act": None, "rec": None, "m": 0}
+    if passes is not None:
+        passes.append(p)
+    rec_ws = hb.WORKSPACE.take(11 * P, dev)
+    try:
+        slot, records, count = hb.occ_compact(desc, rays, z_vals, p["slot"], rec_ws, z_stop)
+        m = p["m"] = int(count.item())      # the field launch needs M on the host
+        raw = torch.empty((n, S, 4), dtype=torch.float32, device=dev)
+        raw_c = torch.empty((max(m, 1), 1, 4), dtype=torch.float32, device=dev)
+        if m > 0:
+            if passes is not None:
+                lease = _grid_pass_lease(m, P, prec)
+                budget["resident"] += 4 * (lease + P + (11 * m if budget["rays_grad"] else 0))
+                if budget["resident"] > hb.SAVE_TOTAL_BYTES:
+                    raise RuntimeError(f"render_rays(occupancy=DensityGrid): the saved activations of this call's {budget['rays']} rays exceed "
+                                       f"hip_backend.SAVE_TOTAL_BYTES = {hb.SAVE_TOTAL_BYTES} bytes (NERF_SAVE_TOTAL_GB); the grid path "
+                                       "has no recompute plan: render fewer rays per call (chunk=) or raise the budget")
+                p["act"] = hb.WORKSPACE.take(lease, dev)
+            p["packed"] = model.packed_params(prec)
+            hb.field_fwd(p["packed"], records[:m], torch.zeros((m, 1), dtype=torch.float32, device=dev), save_act=passes is not None,
+                         precision=prec, raw=raw_c[:m], act=p["act"])
+            if passes is not None and budget["rays_grad"]:
+                p["rec"] = hb.WORKSPACE.take(11 * m, dev)
+                p["rec"][:11 * m].copy_(records[:m].reshape(-1))
+        hb.occ_expand(slot, raw_c, raw)
+    finally:
+        hb.WORKSPACE.give(rec_ws)
+        if passes is None:
+            hb.WORKSPACE.give(p["slot"])
+    p["raw"] = raw
+    stats["evaluated"] += m
+    stats["total"] += P
+    return raw, hb.raw2outputs(raw, z_vals, rays, rays.shape[1], noise, cfg["raw_noise_std"], cfg["white_bkgd"], want_weights=want_weights,
+                               want_depth=False, rays_d_offset=3)
+
+
+def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
+    """THE stages of a grid render on one ray chunk or sub-chunk -- _render_rays_hooked's chain with device code where the hook sits --
+    with run_pass(rays, z_vals, model, noise, want_weights, z_stop) = _grid_pass bound to the caller's cfg, desc and bookkeeping.
+    Everything option-dependent is read from cfg, which render_rays fills once for both paths:
+      cfg["march_steps"] (proposal="march"): the depths are the grid's own (nerf_occ_march: march_steps candidates, N_samples slots) and
+        the chunk is ONE pass of model_c on them, compacted with the march's stop depth (the caller hands the evaluated network as
+        model_c, N_importance = 0 and the pass's noise as noise_c);
+      else coarse depths (nerf_sample_coarse) and their weights: cfg["proposal"] ("grid") takes the grid's own
+        (DensityGrid.proposal_weights: one launch, no network, no read-back; the evaluated network is model_c), otherwise a pass of
+        model_c, which is the whole chunk when N_importance = 0;
+      cfg["early_stop_eps"]: the coarse weights give one stop depth per ray (nerf_occ_stop_depth), with which the refining pass compacts;
+      nerf_sample_fine, and the refining pass on model_f (model_c without one).
+    One host synchronisation per pass and none of its own.  Returns the output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std])
+    and the device counters (stopped rays, truncated rays; None without the option), which the caller reads back after its passes."""
+    n_c, n_f = cfg["N_samples"], cfg["N_importance"]
+    dev = rays.device
+    if cfg["march_steps"] is not None:
+        z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), cfg["march_steps"], n_c)
+        n_truncated = truncated.sum()
+        raw, (rgb, disp, acc, _, _) = run_pass(rays, z_m, model_c, rnd.get("noise_c"), False, z_stop)
+        return (rgb, disp, acc, raw), None, n_truncated
+    z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
+    coarse = ()
+    if cfg["proposal"] is not None:
+        w_c = grid.proposal_weights(rays, z_c)
+    else:
+        raw_c, (rgb_c, disp_c, acc_c, w_c, _) = run_pass(rays, z_c, model_c, rnd.get("noise_c"), n_f > 0, None)
+        if n_f <= 0:
+            return (rgb_c, disp_c, acc_c, raw_c), None, None
+        coarse = (rgb_c, disp_c, acc_c)
+    z_stop = n_stopped = None
+    if cfg["early_stop_eps"] is not None:
+        z_stop = hb.occ_stop_depth(z_c, w_c, cfg["early_stop_eps"])
+        n_stopped = torch.isfinite(z_stop).sum()
+    u = rnd.get("u")
+    z_f, z_std, _ = hb.sample_fine(z_c, w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
+    raw_f, (rgb_f, disp_f, acc_f, _, _) = run_pass(rays, z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), False, z_stop)
+    return (rgb_f, disp_f, acc_f, raw_f) + coarse + (z_std,), n_stopped, None
+
+
+def _grid_stats(grid, stats, n_stopped, n_truncated):
+    """grid.last_stats of one call: the passes' counts and the chain's device counters (None without the option), read back here -- after
+    the passes, which synchronised anyway -- once per call"""
+    if n_stopped is not None:
+        stats["rays_stopped"] = int(n_stopped.item())
+    if n_truncated is not None:
+        stats["rays_truncated"] = int(n_truncated.item())
+    grid.last_stats = stats
+
+
+def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid):
+    """render_rays without gradients through an occupancy grid (occupancy.OccupancyGrid): _grid_chain once over the whole chunk, nothing
+    kept.  One host synchronisation per pass: two per call with N_importance > 0, one under a proposal or without a refining pass.
+    Returns the chain's output tuple."""
+    desc = grid._desc()
+    stats = {"evaluated": 0, "total": 0}
+    outs, n_stopped, n_truncated = _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, partial(_grid_pass, cfg, desc, stats=stats))
+    _grid_stats(grid, stats, n_stopped, n_truncated)
+    return outs
+
+
 class _RenderRaysGrid(torch.autograd.Function):
     """render_rays through an occupancy.DensityGrid WITH gradients, as one autograd node shaped like _RenderRays (one _grad_ready per
     network per backward with the final flat vector, a shared network accumulated in the kernel, no weight-gradient launch for a frozen
     network, the stale-parameter and freed-graph checks, no saved output in ctx).
 
-    Per pass, forward: depths -> nerf_occ_compact -> ONE read-back of M -> the field on the M one-sample records with saved
-    activations -> nerf_occ_expand (zeros for skipped samples) -> nerf_raw2outputs.  Backward: nerf_raw2outputs_bwd -> nerf_occ_gather
+    Forward: _grid_chain -- the stages of the no-grad grid render -- per ray sub-chunk, every pass a saving _grid_pass (depths ->
+    nerf_occ_compact -> ONE read-back of M -> the field on the M one-sample records with saved activations -> nerf_occ_expand, zeros for
+    skipped samples -> nerf_raw2outputs).  Backward, per pass: nerf_raw2outputs_bwd -> nerf_occ_gather
     (d_raw of the M points) -> delta chain / weight gradient on the M records, the input gradient in point mode when the rays need one
     -> nerf_occ_fold_rays (per-point [M, 11] -> per-ray [N, 11]) + the compositing's |d| term.  A skipped sample has raw = 0 and no
     gradient: what a network_query_fn that evaluates only the occupied points computes.
@@ -685,28 +724,19 @@ class _RenderRaysGrid(torch.autograd.Function):
     back by the backward or freed with a dropped graph.  Calls above hb.max_saved_rays(...) rays run in equal ray sub-chunks, every
     one resident with leases of its own M; beyond hb.SAVE_TOTAL_BYTES in total the call raises (no recompute plan on this path).
 
-    cfg["proposal"] == "grid" (render_rays(proposal="grid")): the coarse pass is DensityGrid.proposal_weights -- a constant of the graph,
-    nothing saved -- and the node has ONE pass, the refining one on model_c (the caller hands the evaluated network as model_c, model_f =
-    None); outputs (rgb, disp, acc, raw, z_std).
-
-    cfg["early_stop_eps"] (render_rays(early_stop_eps=)): per sub-chunk the coarse weights give one stop depth per ray
-    (nerf_occ_stop_depth) and the refining pass compacts with it (nerf_occ_compact_stop).  z_stop is a constant of the graph; a stopped
-    sample has slot -1 like a skipped one -- raw = 0, no gradient -- so nothing beyond slot is kept for it and the backward is unchanged.
-
-    cfg["march_steps"] (render_rays(proposal="march")): per sub-chunk the depths are nerf_occ_march's (march_steps candidates, N_samples
-    slots) and the node's single pass compacts with the march's stop depth.  The caller hands the evaluated network as model_c, model_f =
-    None, N_importance = 0 and the pass's noise as noise_c, so the backward is the coarse-only one; depths and stop depth are constants of
-    the graph; outputs (rgb, disp, acc, raw)."""
+    The options of _grid_chain as the backward sees them.  cfg["proposal"] ("grid"): the coarse weights are a constant of the graph,
+    nothing saved, and the node has ONE pass, the refining one on model_c; outputs (rgb, disp, acc, raw, z_std).  cfg["early_stop_eps"]:
+    z_stop is a constant of the graph, computed per sub-chunk; a stopped sample has slot -1 like a skipped one -- raw = 0, no gradient
+    -- so nothing beyond slot is kept for it and the backward is unchanged.  cfg["march_steps"]: depths and stop depth are constants of
+    the graph, computed per sub-chunk; with N_importance = 0 the backward is the coarse-only one; outputs (rgb, disp, acc, raw)."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
         n_c, n_f = cfg["N_samples"], cfg["N_importance"]
         prec = cfg["precision"]
-        std, wb = cfg["raw_noise_std"], cfg["white_bkgd"]
         n = rays.shape[0]
-        dev = rays.device
         desc = grid._desc()
-        ctx.proposal = proposal = cfg.get("proposal") is not None
+        ctx.proposal = cfg["proposal"] is not None
         ctx.same_net = model_f is None or model_f is model_c
         ctx.n_params_c = len(_param_slices(model_c))
         ctx.rays_grad = rays_grad = bool(ctx.needs_input_grad[1])
@@ -722,86 +752,25 @@ class _RenderRaysGrid(torch.autograd.Function):
         global LAST_BACKWARD_PLAN
         LAST_BACKWARD_PLAN = ("resident sub-chunks" if len(tiles) > 1 else "one launch", n, sub)
         stats = {"evaluated": 0, "total": 0}
-        eps = cfg.get("early_stop_eps")
-        march_steps = cfg.get("march_steps")
+        budget = {"rays_grad": rays_grad, "resident": 0, "rays": n}
         n_stopped, n_truncated = [], []
-        resident = [0]
-        parts = []
-
-        def one_pass(rays_t, z_vals, model, noise, want_weights, z_stop=None):
-            nt, S = z_vals.shape
-            P = nt * S
-            p = {"z": z_vals, "slot": hb.WORKSPACE.take(P, dev), "act": None, "rec": None, "m": 0}
-            parts[-1].append(p)         # (registered first: an error below hands its leases back with the others')
-            rec_ws = hb.WORKSPACE.take(11 * P, dev)
-            try:
-                slot, records, count = hb.occ_compact(desc, rays_t, z_vals, p["slot"], rec_ws, z_stop)
-                m = p["m"] = int(count.item())      # the field launch needs M on the host
-                raw = torch.empty((nt, S, 4), dtype=torch.float32, device=dev)
-                raw_c = torch.empty((max(m, 1), 1, 4), dtype=torch.float32, device=dev)
-                if m > 0:
-                    lease = _grid_pass_lease(m, P, prec)
-                    resident[0] += 4 * (lease + P + (11 * m if rays_grad else 0))
-                    if resident[0] > hb.SAVE_TOTAL_BYTES:
-                        raise RuntimeError(f"render_rays(occupancy=DensityGrid): the saved activations of this call's {n} rays exceed "
-                                           f"hip_backend.SAVE_TOTAL_BYTES = {hb.SAVE_TOTAL_BYTES} bytes (NERF_SAVE_TOTAL_GB); the grid path "
-                                           "has no recompute plan: render fewer rays per call (chunk=) or raise the budget")
-                    p["act"] = hb.WORKSPACE.take(lease, dev)
-                    p["packed"] = model.packed_params(prec)
-                    hb.field_fwd(p["packed"], records[:m], torch.zeros((m, 1), dtype=torch.float32, device=dev), save_act=True,
-                                 precision=prec, raw=raw_c[:m], act=p["act"])
-                    if rays_grad:
-                        p["rec"] = hb.WORKSPACE.take(11 * m, dev)
-                        p["rec"][:11 * m].copy_(records[:m].reshape(-1))
-                hb.occ_expand(slot, raw_c, raw)
-            finally:        # stream-ordered: the next lease is written by kernels enqueued after these
-                hb.WORKSPACE.give(rec_ws)
-            p["raw"] = raw
-            stats["evaluated"] += m
-            stats["total"] += P
-            return raw, hb.raw2outputs(raw, z_vals, rays_t, rays_t.shape[1], noise, std, wb, want_weights=want_weights, want_depth=False,
-                                       rays_d_offset=3)
-
-        outs = []
+        parts, outs = [], []
         try:
             for lo, hi in tiles:
-                rays_t = rays[lo:hi]
                 rnd_t = rnd if len(tiles) == 1 else {k_: v[lo:hi] for k_, v in rnd.items()}
                 parts.append([])
-                if march_steps is not None:
-                    z_m, z_stop, truncated = hb.occ_march(desc, rays_t, rnd_t.get("u_march"), march_steps, n_c)
-                    n_truncated.append(truncated.sum())
-                    raw_c, (rgb_c, disp_c, acc_c, _, _) = one_pass(rays_t, z_m, model_c, rnd_t.get("noise_c"), False, z_stop)
-                    outs.append((rgb_c, disp_c, acc_c, raw_c))
-                    continue
-                z_c = hb.sample_coarse(rays_t, _linspace01(n_c, dev), cfg["lindisp"], rnd_t.get("t_rand"))
-                if proposal:
-                    w_c = grid.proposal_weights(rays_t, z_c)
-                else:
-                    raw_c, (rgb_c, disp_c, acc_c, w_c, _) = one_pass(rays_t, z_c, model_c, rnd_t.get("noise_c"), n_f > 0)
-                    if n_f <= 0:
-                        outs.append((rgb_c, disp_c, acc_c, raw_c))
-                        continue
-                u = rnd_t.get("u")
-                z_stop = None
-                if eps is not None:
-                    z_stop = hb.occ_stop_depth(z_c, w_c, eps)
-                    n_stopped.append(torch.isfinite(z_stop).sum())
-                z_f, z_std, _ = hb.sample_fine(z_c, w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
-                raw_f, (rgb_f, disp_f, acc_f, _, _) = one_pass(rays_t, z_f, model_c if ctx.same_net else model_f, rnd_t.get("noise_f"), False,
-                                                               z_stop)
-                outs.append((rgb_f, disp_f, acc_f, raw_f, z_std) if proposal else (rgb_f, disp_f, acc_f, raw_f, rgb_c, disp_c, acc_c, z_std))
+                out, stopped, truncated = _grid_chain(cfg, desc, grid, rays[lo:hi], rnd_t, model_c, model_f,
+                                                      partial(_grid_pass, cfg, desc, stats=stats, passes=parts[-1], budget=budget))
+                outs.append(out)
+                n_stopped += [] if stopped is None else [stopped]
+                n_truncated += [] if truncated is None else [truncated]
         except BaseException:
             for passes in parts:
                 for p in passes:
                     for k_ in ("slot", "act", "rec"):
                         hb.WORKSPACE.give(p.get(k_))
             raise
-        if eps is not None:         # read back after the passes, which synchronised anyway
-            stats["rays_stopped"] = int(torch.stack(n_stopped).sum().item())
-        if march_steps is not None:
-            stats["rays_truncated"] = int(torch.stack(n_truncated).sum().item())
-        grid.last_stats = stats
+        _grid_stats(grid, stats, torch.stack(n_stopped).sum() if n_stopped else None, torch.stack(n_truncated).sum() if n_truncated else None)
         if prec in ("fp16x3", "fp16x3w"):       # the fp16 split's range guard rail sees the compacted passes' saved activations
             for passes in parts:
                 acts = [(p["act"], 1) for p in passes if p["act"] is not None]
@@ -923,74 +892,9 @@ class _RenderRaysGrid(torch.autograd.Function):
         return lead + out_c + (_grad_views(ctx.model_f, grad_f) if wrote["f"] else none_c)
 
 
-def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
-                N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None, march_steps=None):
-    """run_nerf.py:308-418.  Same arguments, same returned dict.
-
-    ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
-    for every pass with (pts, viewdirs, network) like the reference does (_render_rays_hooked).  ``verbose`` is accepted and prints
-    nothing (run_nerf.py:414-416's DEBUG-gated NaN check: see render.check_range()); the reference's ``netchunk`` has no counterpart
-    (the kernels tile the points themselves).
-
-    ``randoms`` (keyword-only, not in the reference) injects the random tensors
-    {t_rand [N,N_samples], noise_c [N,N_samples], u [N,N_importance], noise_f [N,N_samples+N_importance]}
-    instead of drawing them: the explicit form of the reference's ``pytest=`` hook.
-
-    ``occupancy`` (keyword-only, not in the reference): an occupancy.OccupancyGrid -- sample points in empty cells are not sent
-    through the network and get raw = 0 (_render_rays_occupancy).  Fused NeRF networks only: a grid together with a DenseNeRF or a
-    user network_query_fn raises NotImplementedError.  With a needed gradient (grad mode on and parameters or rays that require grad)
-    an occupancy.DensityGrid renders differentiably w.r.t. both networks' parameters and the ray records (_RenderRaysGrid: skipped
-    samples get no gradient); a plain OccupancyGrid raises NotImplementedError there.  None: nothing changes.
-
-    ``clip_to_occupancy`` (keyword-only, not in the reference; needs ``occupancy``): True replaces (near, far) of every ray by the
-    span of the occupied cells it crosses (occupancy.clip_rays: nerf_occ_ray_span) before the coarse depths are drawn, so all
-    N_samples of them land where the grid lets the network be evaluated; a ray that crosses nothing occupied keeps its interval.
-    The call equals render_rays(occupancy.clip_rays(ray_batch)[0], ..., occupancy=occupancy) bit for bit, gradients included (near' /
-    far' are constants of the graph); last_stats additionally carries "rays_hit" and "rays".  False: nothing changes.
-
-    ``proposal`` (keyword-only, not in the reference; needs an occupancy.DensityGrid as ``occupancy`` and N_importance > 0): "grid"
-    draws the importance samples from the grid instead of a coarse network.  The coarse depths are drawn as always (after
-    clip_to_occupancy if that is on); their weights are the compositing weights of the grid's own density per cell
-    (DensityGrid.proposal_sigma is the definition, nerf_occ_proposal_weights the kernel: no network, no interpolation);
-    nerf_sample_fine turns them into the sorted N_samples + N_importance depths, and ONE network -- network_fine if given, else
-    network_fn -- is evaluated on those through the compacted grid pass, with gradients to its parameters and the ray records as
-    without the option.  The other network is never touched: no launch, no gradient (.grad stays None), no _grad_ready.  The dict
-    holds rgb_map, disp_map, acc_map, z_std (and raw with retraw) and NO rgb0 / disp0 / acc0: there is no coarse image (the reference's
-    train() guards its coarse loss with ``if 'rgb0' in extras``).  last_stats counts the one pass: total = N * (N_samples +
-    N_importance).  Random draws: t_rand, u, noise_f in that order; noise_c is not drawn and is ignored in ``randoms`` -- the generator
-    stream therefore differs from the two-network render's, by design.  Before the grid's first update its densities are 0 and all
-    bits are set: the weights of the samples inside the box are exactly 0 (beyond a box with outside="evaluate" they carry
-    sigma_threshold), sample_pdf's 1e-5 floor makes the pdf uniform, and the network sees the stratified plus uniformly drawn depths
-    -- nothing is hidden during the warm-up.  None: nothing changes.
-
-    ``early_stop_eps`` (keyword-only, not in the reference; a float with 0 < eps < 1; needs ``occupancy`` and N_importance > 0): early
-    ray termination for the refining pass.  The coarse pass -- untouched -- has just returned its compositing weights (the coarse
-    network's, or the grid's under proposal="grid"); their running sum up to sample i is 1 - T, so one launch (nerf_occ_stop_depth;
-    occupancy.stop_depth_reference is the definition) finds per ray the coarse depth z_stop behind which that estimate of the
-    transmittance is below eps, and the refining pass's compaction (nerf_occ_compact_stop) drops every sample with z >= z_stop next to
-    the ones in empty cells: raw = 0, no network evaluation, no gradient, no saved activations.  Order inside a call: coarse depths
-    (after clip_to_occupancy) -> coarse weights -> z_stop -> nerf_sample_fine as before -> the refining pass.  rgb0 / disp0 / acc0, z_std
-    and the random draws are those of the call without the option.  AN APPROXIMATION: what is dropped from the refined image is the
-    REFINING pass's own transmittance at z_stop, which is close to eps where the two passes agree but is not bounded by it (a coarse
-    network that sees a surface the fine one does not cuts visible geometry) -- hence opt-in.  z_stop is a constant of the graph.
-    last_stats additionally carries "rays_stopped" (rays with a finite z_stop); "evaluated" counts what survived grid and stop.
-    None: nothing changes -- same launches, same bits, same draws.
-
-    ``proposal="march"`` with ``march_steps=M`` (keyword-only, not in the reference; needs ``occupancy``, a plain OccupancyGrid under
-    no_grad or a DensityGrid with gradients): grid ray marching.  The depths are no longer the reference's thinned out: every ray is
-    walked in M equal steps over [near, far] (after clip_to_occupancy if that is on: the steps then span the occupied hull) and only
-    the steps in occupied cells, plus one closing step behind every occupied run, are written into S = N_samples + max(N_importance, 0)
-    slots (occupancy.OccupancyGrid.march_reference is the definition, nerf_occ_march the kernel; no coarse pass, no sample_pdf, no
-    sort).  ONE network -- network_fine if given, else network_fn -- is evaluated on them through the compacted grid pass; the closing
-    steps lie in empty cells and get raw = 0, so a sample's interval never reaches across a gap; the padding behind the last emitted
-    step, and whatever did not fit into S slots, is dropped by the compaction's stop depth.  The other network is never touched: no
-    launch, .grad stays None, no _grad_ready.  The dict holds rgb_map, disp_map, acc_map (and raw [N, S, 4] with retraw): no rgb0 /
-    disp0 / acc0 and no z_std.  Random draws: with perturb > 0 one offset per ray, u_march [N] (all steps of a ray move together; 0.5
-    without), then with raw_noise_std > 0 noise_f [N, S] -- these are the ``randoms`` keys; t_rand, u and noise_c are neither drawn nor
-    read.  last_stats = {"evaluated", "total" = N * S, "rays_truncated"} (rays whose emitted steps did not fit: raise N_samples +
-    N_importance, or lower march_steps).  1 <= march_steps <= 16384, S <= 4096; lindisp and early_stop_eps (there are no coarse weights to
-    stop on) are refused.  ``march_steps`` without proposal="march" is refused."""
+def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal, early_stop_eps, march_steps):
+    """render_rays' checks of its grid options, in front of everything else (a refused call launches nothing, not even hb.lib()).
+    Returns (march, early_stop_eps as a float or None, march_steps as an int or None)."""
     if clip_to_occupancy and occupancy is None:
         raise ValueError("render_rays: clip_to_occupancy=True needs an occupancy grid (occupancy=)")
     march = isinstance(proposal, str) and proposal == "march"
@@ -1027,44 +931,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                              + ("none was given" if occupancy is None else "a plain OccupancyGrid has none"))
         if int(N_importance) <= 0:
             raise ValueError("render_rays: proposal=\"grid\" draws importance samples: N_importance must be > 0")
-    from .dense import DenseNeRF
-    nets = [network_fn] + ([network_fine] if network_fine is not None else [])
-    dense = all(isinstance(m, DenseNeRF) for m in nets)         # architectures outside the fused kernels: layer by layer (dense.py)
-    if not dense and not all(isinstance(m, NeRF) for m in nets):
-        raise NotImplementedError("render_rays: network_fn / network_fine must both be fused-kernel NeRF modules (D=8, W=256, 10 / 4 "
-                                  "frequencies, view directions) or both general ones (nerf_pytorch_amd.NeRF builds either)")
-    if not dense and ray_batch.shape[-1] <= 8:
-        raise ValueError("render_rays: these networks use view directions; the ray records need 11 columns (render(use_viewdirs=True))")
-    rays_grad = torch.is_grad_enabled() and ray_batch.requires_grad
-    if rays_grad and dense:
-        raise NotImplementedError("render_rays: gradients to rays / sample points / camera poses are implemented for the fused "
-                                  "NeRF architecture only, not for general (DenseNeRF) networks")
-    # rays that require grad stay in the graph (d loss / d ray records: nerf_field_input_grad + the compositing's |d| term)
-    rays = ray_batch.to(torch.float32).contiguous()
-    if not rays_grad:
-        rays = rays.detach()
-    n = rays.shape[0]
-    dev = rays.device
-    n_f = int(N_importance)
-    if n == 0:      # empty batch: the reference returns empty tensors of the right trailing shapes
-        e = lambda *tail: torch.zeros((0,) + tail, dtype=torch.float32, device=dev)
-        ret = {'rgb_map': e(3), 'disp_map': e(), 'acc_map': e()}
-        if retraw:
-            ret['raw'] = e(N_samples + max(n_f, 0) if march else N_samples + n_f, 4)
-        if n_f > 0 and not march:
-            if proposal is None:
-                ret.update(rgb0=e(3), disp0=e(), acc0=e())
-            ret.update(z_std=e())
-        if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
-            occupancy._desc()
-            occupancy.last_stats = {"evaluated": 0, "total": 0}
-            if clip_to_occupancy:
-                occupancy.last_stats.update(rays_hit=0, rays=0)
-            if early_stop_eps is not None:
-                occupancy.last_stats.update(rays_stopped=0)
-            if march:
-                occupancy.last_stats.update(rays_truncated=0)
-        return ret
+    return march, early_stop_eps, march_steps
+
+
+def _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march):
+    """render_rays' random tensors for n rays, injected (``randoms``: the keys the options read, checked for their row count) or drawn in
+    the reference's order and shapes.  Returns (rnd, the noise scale the kernels apply)."""
     rnd = {}
     if randoms is not None:
         keys = (["t_rand"] if perturb > 0. else []) + (["noise_c"] if raw_noise_std > 0. and proposal is None else [])
@@ -1118,6 +990,126 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             rnd["noise_f"] = draw_noise(N_samples + n_f)
     if pytest and raw_noise_std > 0. and randoms is None:
         std = 1.0       # pytest noise is pre-scaled in float64 like the reference (run_nerf.py:290)
+    return rnd, std
+
+
+def _result_dict(outs, retraw, coarse_first):
+    """the returned dict of an output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std]).  coarse_first: the key order of
+    _render_rays_hooked, which the grid paths share (the coarse image and z_std in front); else the fused dense path's, which the empty
+    batch has always had"""
+    fine = dict(rgb_map=outs[0], disp_map=outs[1], acc_map=outs[2], **({"raw": outs[3]} if retraw else {}))
+    coarse = dict(zip(("rgb0", "disp0", "acc0"), outs[4:7])) if len(outs) == 8 else {}
+    if len(outs) > 4:
+        coarse["z_std"] = outs[-1]
+    return {**coarse, **fine} if coarse_first else {**fine, **coarse}
+
+
+def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal):
+    """the last_stats keys the grid options add to "evaluated" and "total" (render_rays' keyword arguments, checked or not)"""
+    march = isinstance(proposal, str) and proposal == "march"
+    return ((("rays_hit", "rays") if clip_to_occupancy else ()) + (("rays_stopped",) if early_stop_eps is not None else ())
+            + (("rays_truncated",) if march else ()))
+
+
+def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
+                N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
+                *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None, march_steps=None):
+    """run_nerf.py:308-418.  Same arguments, same returned dict.
+
+    ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
+    for every pass with (pts, viewdirs, network) like the reference does (_render_rays_hooked).  ``verbose`` is accepted and prints
+    nothing (run_nerf.py:414-416's DEBUG-gated NaN check: see render.check_range()); the reference's ``netchunk`` has no counterpart
+    (the kernels tile the points themselves).
+
+    ``randoms`` (keyword-only, not in the reference) injects the random tensors
+    {t_rand [N,N_samples], noise_c [N,N_samples], u [N,N_importance], noise_f [N,N_samples+N_importance]}
+    instead of drawing them: the explicit form of the reference's ``pytest=`` hook.
+
+    ``occupancy`` (keyword-only, not in the reference): an occupancy.OccupancyGrid -- sample points in empty cells are not sent
+    through the network and get raw = 0 (_grid_chain / _grid_pass).  Fused NeRF networks only: a grid together with a DenseNeRF or a
+    user network_query_fn raises NotImplementedError.  With a needed gradient (grad mode on and parameters or rays that require grad)
+    an occupancy.DensityGrid renders differentiably w.r.t. both networks' parameters and the ray records (_RenderRaysGrid: skipped
+    samples get no gradient); a plain OccupancyGrid raises NotImplementedError there.  None: nothing changes.
+
+    ``clip_to_occupancy`` (keyword-only, not in the reference; needs ``occupancy``): True replaces (near, far) of every ray by the
+    span of the occupied cells it crosses (occupancy.clip_rays: nerf_occ_ray_span) before the coarse depths are drawn, so all
+    N_samples of them land where the grid lets the network be evaluated; a ray that crosses nothing occupied keeps its interval.
+    The call equals render_rays(occupancy.clip_rays(ray_batch)[0], ..., occupancy=occupancy) bit for bit, gradients included (near' /
+    far' are constants of the graph); last_stats additionally carries "rays_hit" and "rays".  False: nothing changes.
+
+    ``proposal`` (keyword-only, not in the reference; needs an occupancy.DensityGrid as ``occupancy`` and N_importance > 0): "grid"
+    draws the importance samples from the grid instead of a coarse network.  The coarse depths are drawn as always (after
+    clip_to_occupancy if that is on); their weights are the compositing weights of the grid's own density per cell
+    (DensityGrid.proposal_sigma is the definition, nerf_occ_proposal_weights the kernel: no network, no interpolation);
+    nerf_sample_fine turns them into the sorted N_samples + N_importance depths, and ONE network -- network_fine if given, else
+    network_fn -- is evaluated on those through the compacted grid pass, with gradients to its parameters and the ray records as
+    without the option.  The other network is never touched: no launch, no gradient (.grad stays None), no _grad_ready.  The dict
+    holds rgb_map, disp_map, acc_map, z_std (and raw with retraw) and NO rgb0 / disp0 / acc0: there is no coarse image (the reference's
+    train() guards its coarse loss with ``if 'rgb0' in extras``).  last_stats counts the one pass: total = N * (N_samples +
+    N_importance).  Random draws: t_rand, u, noise_f in that order; noise_c is not drawn and is ignored in ``randoms`` -- the generator
+    stream therefore differs from the two-network render's, by design.  Before the grid's first update its densities are 0 and all
+    bits are set: the weights of the samples inside the box are exactly 0 (beyond a box with outside="evaluate" they carry
+    sigma_threshold), sample_pdf's 1e-5 floor makes the pdf uniform, and the network sees the stratified plus uniformly drawn depths
+    -- nothing is hidden during the warm-up.  None: nothing changes.
+
+    ``early_stop_eps`` (keyword-only, not in the reference; a float with 0 < eps < 1; needs ``occupancy`` and N_importance > 0): early
+    ray termination for the refining pass.  The coarse pass -- untouched -- has just returned its compositing weights (the coarse
+    network's, or the grid's under proposal="grid"); their running sum up to sample i is 1 - T, so one launch (nerf_occ_stop_depth;
+    occupancy.stop_depth_reference is the definition) finds per ray the coarse depth z_stop behind which that estimate of the
+    transmittance is below eps, and the refining pass's compaction (nerf_occ_compact_stop) drops every sample with z >= z_stop next to
+    the ones in empty cells: raw = 0, no network evaluation, no gradient, no saved activations.  Order inside a call: coarse depths
+    (after clip_to_occupancy) -> coarse weights -> z_stop -> nerf_sample_fine as before -> the refining pass.  rgb0 / disp0 / acc0, z_std
+    and the random draws are those of the call without the option.  AN APPROXIMATION: what is dropped from the refined image is the
+    REFINING pass's own transmittance at z_stop, which is close to eps where the two passes agree but is not bounded by it (a coarse
+    network that sees a surface the fine one does not cuts visible geometry) -- hence opt-in.  z_stop is a constant of the graph.
+    last_stats additionally carries "rays_stopped" (rays with a finite z_stop); "evaluated" counts what survived grid and stop.
+    None: nothing changes -- same launches, same bits, same draws.
+
+    ``proposal="march"`` with ``march_steps=M`` (keyword-only, not in the reference; needs ``occupancy``, a plain OccupancyGrid under
+    no_grad or a DensityGrid with gradients): grid ray marching.  The depths are no longer the reference's thinned out: every ray is
+    walked in M equal steps over [near, far] (after clip_to_occupancy if that is on: the steps then span the occupied hull) and only
+    the steps in occupied cells, plus one closing step behind every occupied run, are written into S = N_samples + max(N_importance, 0)
+    slots (occupancy.OccupancyGrid.march_reference is the definition, nerf_occ_march the kernel; no coarse pass, no sample_pdf, no
+    sort).  ONE network -- network_fine if given, else network_fn -- is evaluated on them through the compacted grid pass; the closing
+    steps lie in empty cells and get raw = 0, so a sample's interval never reaches across a gap; the padding behind the last emitted
+    step, and whatever did not fit into S slots, is dropped by the compaction's stop depth.  The other network is never touched: no
+    launch, .grad stays None, no _grad_ready.  The dict holds rgb_map, disp_map, acc_map (and raw [N, S, 4] with retraw): no rgb0 /
+    disp0 / acc0 and no z_std.  Random draws: with perturb > 0 one offset per ray, u_march [N] (all steps of a ray move together; 0.5
+    without), then with raw_noise_std > 0 noise_f [N, S] -- these are the ``randoms`` keys; t_rand, u and noise_c are neither drawn nor
+    read.  last_stats = {"evaluated", "total" = N * S, "rays_truncated"} (rays whose emitted steps did not fit: raise N_samples +
+    N_importance, or lower march_steps).  1 <= march_steps <= 16384, S <= 4096; lindisp and early_stop_eps (there are no coarse weights to
+    stop on) are refused.  ``march_steps`` without proposal="march" is refused."""
+    march, early_stop_eps, march_steps = _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal,
+                                                             early_stop_eps, march_steps)
+    from .dense import DenseNeRF
+    nets = [network_fn] + ([network_fine] if network_fine is not None else [])
+    dense = all(isinstance(m, DenseNeRF) for m in nets)         # architectures outside the fused kernels: layer by layer (dense.py)
+    if not dense and not all(isinstance(m, NeRF) for m in nets):
+        raise NotImplementedError("render_rays: network_fn / network_fine must both be fused-kernel NeRF modules (D=8, W=256, 10 / 4 "
+                                  "frequencies, view directions) or both general ones (nerf_pytorch_amd.NeRF builds either)")
+    if not dense and ray_batch.shape[-1] <= 8:
+        raise ValueError("render_rays: these networks use view directions; the ray records need 11 columns (render(use_viewdirs=True))")
+    rays_grad = torch.is_grad_enabled() and ray_batch.requires_grad
+    if rays_grad and dense:
+        raise NotImplementedError("render_rays: gradients to rays / sample points / camera poses are implemented for the fused "
+                                  "NeRF architecture only, not for general (DenseNeRF) networks")
+    # rays that require grad stay in the graph (d loss / d ray records: nerf_field_input_grad + the compositing's |d| term)
+    rays = ray_batch.to(torch.float32).contiguous()
+    if not rays_grad:
+        rays = rays.detach()
+    n = rays.shape[0]
+    dev = rays.device
+    n_f = int(N_importance)
+    if n == 0:      # empty batch: the reference returns empty tensors of the right trailing shapes
+        e = lambda *tail: torch.zeros((0,) + tail, dtype=torch.float32, device=dev)
+        outs = (e(3), e(), e(), e(N_samples + max(n_f, 0) if march else N_samples + n_f, 4))
+        if n_f > 0 and not march:
+            outs += ((e(3), e(), e()) if proposal is None else ()) + (e(),)
+        if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
+            occupancy._desc()
+            occupancy.last_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal), 0)
+        return _result_dict(outs, retraw, coarse_first=False)
+    rnd, std = _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march)
     cfg = dict(N_samples=int(N_samples), N_importance=n_f, lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
                raw_noise_std=std, precision=_PRECISION)
     if occupancy is not None:
@@ -1138,39 +1130,29 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             grid_grad = True
         else:
             grid_grad = False
+        # what _grid_chain reads, set once for both paths; the reduced class is an inference form whose last-sample fix-up is per ray: the
+        # compacted points, and gradients anyway, run on the fp16x3 products
+        cfg.update(proposal=None if march else proposal, early_stop_eps=early_stop_eps, march_steps=march_steps)
+        if cfg["precision"] == "fp16_fp8c":
+            cfg["precision"] = "fp16x3"
         if march:       # ONE pass over all the slots: what the two paths below run as a coarse-only call on the march's depths
-            cfg.update(N_samples=int(N_samples) + max(n_f, 0), N_importance=0, march_steps=march_steps)
+            cfg.update(N_samples=int(N_samples) + max(n_f, 0), N_importance=0)
             rnd = {k_: v for k_, v in (("u_march", rnd.get("u_march")), ("noise_c", rnd.get("noise_f"))) if v is not None}
         n_hit = None
         if clip_to_occupancy:       # (after the guards: a refused call launches nothing; the draws above do not depend on near / far)
             rays, hit = occupancy.clip_rays(rays)
             n_hit = hit.sum()       # read back after the passes, which synchronise anyway
-        if grid_grad:
-            if cfg["precision"] == "fp16_fp8c":
-                cfg["precision"] = "fp16x3"         # the reduced class is an inference form; gradients: the fp16x3 datapath
-            ret = {}        # (keys in _render_rays_occupancy's order)
-            if early_stop_eps is not None:
-                cfg["early_stop_eps"] = early_stop_eps
-            if march:
-                outs = _RenderRaysGrid.apply(cfg, rays, rnd, evaluated[0], None, occupancy, *evaluated[0].param_list())
-            elif proposal is not None:
-                cfg["proposal"] = proposal
-                outs = _RenderRaysGrid.apply(cfg, rays, rnd, evaluated[0], None, occupancy, *evaluated[0].param_list())
-                ret.update(z_std=outs[4])
-            else:
-                same = n_f <= 0 or network_fine is None or network_fine is network_fn
-                params = network_fn.param_list() + ([] if same else network_fine.param_list())
-                outs = _RenderRaysGrid.apply(cfg, rays, rnd, network_fn, None if same else network_fine, occupancy, *params)
-                if n_f > 0:
-                    ret.update(rgb0=outs[4], disp0=outs[5], acc0=outs[6], z_std=outs[7])
-            ret.update(rgb_map=outs[0], disp_map=outs[1], acc_map=outs[2])
-            if retraw:
-                ret['raw'] = outs[3]
-        elif march:
-            ret = _render_rays_occupancy(cfg, rays, rnd, evaluated[0], None, occupancy, retraw, march_steps=march_steps)
+        if proposal is not None:        # one network, handed on as model_c
+            model_c, model_f = evaluated[0], None
         else:
-            ret = _render_rays_occupancy(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None, occupancy, retraw, proposal,
-                                         early_stop_eps)
+            same = n_f <= 0 or network_fine is None or network_fine is network_fn
+            model_c, model_f = network_fn, None if same else network_fine
+        if grid_grad:
+            params = model_c.param_list() + ([] if model_f is None else model_f.param_list())
+            outs = _RenderRaysGrid.apply(cfg, rays, rnd, model_c, model_f, occupancy, *params)
+        else:
+            outs = _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, occupancy)
+        ret = _result_dict(outs, retraw, coarse_first=True)
         if n_hit is not None:
             occupancy.last_stats = dict(occupancy.last_stats, rays_hit=int(n_hit.item()), rays=n)
         return ret
@@ -1215,13 +1197,9 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     its "rays_hit" / "rays" too, with ``early_stop_eps`` its "rays_stopped", with ``proposal="march"`` its "rays_truncated")."""
     all_ret = {}
     randoms = kwargs.pop("randoms", None)
-    occ, occ_stats = kwargs.get("occupancy"), {"evaluated": 0, "total": 0}
-    if kwargs.get("clip_to_occupancy"):
-        occ_stats.update(rays_hit=0, rays=0)
-    if kwargs.get("early_stop_eps") is not None:
-        occ_stats.update(rays_stopped=0)
-    if isinstance(kwargs.get("proposal"), str) and kwargs["proposal"] == "march":
-        occ_stats.update(rays_truncated=0)
+    occ = kwargs.get("occupancy")
+    occ_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(kwargs.get("clip_to_occupancy"), kwargs.get("early_stop_eps"),
+                                                                          kwargs.get("proposal")), 0)
     if randoms is not None:
         for k, v in randoms.items():
             if v.shape[0] != rays_flat.shape[0]:
