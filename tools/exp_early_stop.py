@@ -14,78 +14,39 @@ And nerf_occ_stop_depth / nerf_occ_compact_stop alone (HIP events around 100 lau
     python tools/exp_early_stop.py --out profiles/r13_exp_early_stop.json
     python tools/exp_early_stop.py --root <checkout of the parent commit> --label "parent commit" --out ...      # its rows with the option off
 """
-import argparse
 import inspect
-import json
-import math
-import os
-import statistics
-import sys
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ap.add_argument("--label", default="this commit", help="what --root is, for the record")
-ap.add_argument("--out", default=None)
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--steps", type=int, default=10, help="training steps / renders between two HIP events")
+import grid_exp as gx
+
+ap = gx.parser(__doc__, steps="training steps / renders between two HIP events")
 ap.add_argument("--radius", type=float, default=1.0, help="radius of the opaque ball")
 ap.add_argument("--opaque", type=float, default=60.0, help="constant added to both networks' density-head bias")
 args = ap.parse_args()
-sys.path.insert(0, os.path.abspath(args.root))
-import torch  # noqa: E402
-import workloads as wl  # noqa: E402
-import nerf_pytorch_amd as npa  # noqa: E402
-
-if not torch.cuda.is_available():
-    raise SystemExit("exp_early_stop: needs the GPU (no timing without one)")
-hb = npa.hip_backend
-dev = torch.device("cuda", 0)
+torch, wl, npa, hb, dev = gx.load(args, "exp_early_stop")
 HAVE_STOP = "early_stop_eps" in inspect.signature(npa.render_rays).parameters
-Pc, Pf = wl.scene_params()
-kwn = dict(D=8, W=256, input_ch=63, output_ch=5, skips=[4], input_ch_views=27, use_viewdirs=True)
-nc, nf = npa.NeRF(**kwn).to(dev), npa.NeRF(**kwn).to(dev)
-nc.load_state_dict(Pc)
-nf.load_state_dict(Pf)
+S = gx.Scene(wl, npa, dev, perturb=1., target=True, records=True)
+LO, HI, R, N_RAYS, nc, nf = S.LO, S.HI, S.R, S.N_RAYS, S.nc, S.nf
+N_C, N_F = 64, 128
 with torch.no_grad():
     nc.alpha_linear.bias += args.opaque
     nf.alpha_linear.bias += args.opaque
-npa.set_precision("fp16x3")
-LO, HI, R = (-2.0, -2.0, -2.0), (2.0, 2.0, 2.0), 128
-N_RAYS, N_C, N_F = 4096, 64, 128
-KW = dict(network_fn=nc, network_query_fn=None, N_samples=N_C, N_importance=N_F, network_fine=nf, perturb=1., white_bkgd=True, raw_noise_std=0.)
-H = W = 800
-K = wl.intrinsics(dict(H=H, W=W, focal=1111.0))
-GEO = dict(chunk=32768, ndc=False, near=2., far=6., use_viewdirs=True)
-rays = wl.lego_batch(N_RAYS, seed=1).to(dev)
-target = torch.rand(N_RAYS, 3, generator=torch.Generator().manual_seed(2)).to(dev)
-opt_two = npa.FlatAdam(list(nc.parameters()) + list(nf.parameters()), lr=0.0)
-opt_one = npa.FlatAdam(list(nf.parameters()), lr=0.0)
+opt_two, opt_one = S.adam(nc, nf), S.adam(nf)
 
-c = LO[0] + (torch.arange(R, dtype=torch.float64) + 0.5) * (HI[0] - LO[0]) / R
-x, y, z = torch.meshgrid(c, c, c, indexing="ij")
-grid = npa.DensityGrid.from_mask((x * x + y * y + z * z) <= args.radius ** 2, LO, HI, outside="skip", device=dev)
+grid = S.ball(npa.DensityGrid, args.radius)
 with torch.no_grad():
     grid.density = npa.DensityGrid(LO, HI, R, device=dev).update(nf).density
 
 
 def render(eps, proposal, **over):
-    kw = dict(KW, occupancy=grid, **over)
     if proposal:
-        kw["proposal"] = "grid"
+        over["proposal"] = "grid"
     if eps is not None:
-        kw["early_stop_eps"] = eps
-    return npa.render(H, W, K, rays=rays, **GEO, **kw)
+        over["early_stop_eps"] = eps
+    return S.render(occupancy=grid, **over)
 
 
 def step(eps, proposal):
-    rgb, _, _, extras = render(eps, proposal)
-    loss = npa.img2mse(rgb, target)
-    if not proposal:
-        loss = loss + npa.img2mse(extras["rgb0"], target)
-    opt = opt_one if proposal else opt_two
-    opt.zero_grad()
-    loss.backward()
-    opt.step()
+    S.fit(render(eps, proposal), opt_one if proposal else opt_two, rgb0=not proposal)
 
 
 def infer(eps, proposal):
@@ -95,39 +56,18 @@ def infer(eps, proposal):
 
 def time_all(fn, configs, k, reps):
     """alternate the configurations inside every repetition; HIP events around k calls each"""
-    times = {name: [] for name, _, _ in configs}
-    for _, eps, proposal in configs:
-        for _ in range(3):
-            fn(eps, proposal)
-    torch.cuda.synchronize()
-    for _ in range(reps):
-        for name, eps, proposal in configs:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(k):
-                fn(eps, proposal)
-            e1.record()
-            torch.cuda.synchronize()
-            times[name].append(e0.elapsed_time(e1) / k)
+    times = gx.time_alternating([(name, lambda e=e, p=p: fn(e, p)) for name, e, p in configs], k, reps, warmup=3)
     rows = {}
     for name, eps, proposal in configs:
-        ms = statistics.median(times[name])
-        rows[name] = {"ms_median": ms, "ms_min": min(times[name]), "ms_max": max(times[name]), "rays_per_s": N_RAYS / ms * 1e3}
-        timer = hb.TIMER
-        hb.TIMER = hb.KernelTimer()         # a separate call with HIP events around every launch
-        try:
-            fn(eps, proposal)
-            summ = hb.TIMER.summary()
-        finally:
-            hb.TIMER = timer
+        rows[name] = gx.row_stats(times[name], N_RAYS)
+        summ = gx.kernel_summary(hb, lambda: fn(eps, proposal))      # a separate call with HIP events around every launch
         with torch.no_grad():       # the counts at perturb = 0, where the coarse pass's own count is known (coarse_evaluated)
             render(eps, proposal, perturb=0.)
         refine = grid.last_stats["evaluated"] - (0 if proposal else coarse_evaluated[0])
         rows[name].update(evaluated=grid.last_stats["evaluated"], total=grid.last_stats["total"], rays_stopped=grid.last_stats.get("rays_stopped"),
                           refining_pass_evaluated=refine, refining_pass_share=refine / (N_RAYS * (N_C + N_F)),
-                          occ_kernels_ms=sum(v["ms"] for kname, v in summ.items() if kname.startswith("occ_")),
-                          stop_depth_ms=sum(v["ms"] for kname, v in summ.items() if kname.startswith("occ_stop_depth")),
-                          field_ms=sum(v["ms"] for kname, v in summ.items() if kname.startswith(("field_", "wgrad"))))
+                          occ_kernels_ms=gx.kernel_ms(summ, "occ_"), stop_depth_ms=gx.kernel_ms(summ, "occ_stop_depth"),
+                          field_ms=gx.kernel_ms(summ, ("field_", "wgrad")))
     return rows
 
 
@@ -135,13 +75,12 @@ def psnr_vs_unstopped(eps, proposal):
     with torch.no_grad():
         a = render(eps, proposal, perturb=0.)[0]
         b = render(None, proposal, perturb=0.)[0]
-    mse = float(((a.double() - b.double()) ** 2).mean())
-    return {"psnr_db": None if mse == 0.0 else -10.0 * math.log10(mse), "max_abs_difference": float((a - b).abs().max())}
+    return {"psnr_db": gx.psnr_db(a, b), "max_abs_difference": float((a - b).abs().max())}
 
 
 # the coarse pass's evaluated points (the stop never touches it): the two-network render with N_importance = 0
 with torch.no_grad():
-    npa.render(H, W, K, rays=rays, **GEO, **dict(KW, occupancy=grid, N_importance=0, network_fine=None, perturb=0.))
+    S.render(occupancy=grid, N_importance=0, network_fine=None, perturb=0.)
 coarse_evaluated = [grid.last_stats["evaluated"]]
 
 result = {"precision": "fp16x3", "rays": N_RAYS, "samples": "64 + 128", "grid_resolution": R, "tree": args.label, "have_early_stop": HAVE_STOP,
@@ -159,7 +98,7 @@ result["train_step_4096_rays"] = time_all(step, configs, args.steps, args.reps)
 if HAVE_STOP:
     result["image_vs_unstopped_perturb_0"] = {name: psnr_vs_unstopped(eps, proposal) for name, eps, proposal in configs if eps is not None}
     # the two new launches alone, on the refining pass's own inputs
-    rec = wl.synthetic_rays(N_RAYS, 1).to(dev).contiguous()
+    rec = S.records
     z_c = hb.sample_coarse(rec, torch.linspace(0., 1., N_C, device=dev), False, None)
     w = grid.proposal_weights(rec, z_c)
     z_f = hb.sample_fine(z_c, w, N_F, None, torch.linspace(0., 1., N_F, device=dev))[0]
@@ -169,26 +108,8 @@ if HAVE_STOP:
     launches = {"nerf_occ_stop_depth (4096 x 64)": lambda: hb.occ_stop_depth(z_c, w, 1e-3),
                 "nerf_occ_compact (4096 x 192)": lambda: hb.occ_compact(desc, rec, z_f, slot_ws, rec_ws),
                 "nerf_occ_compact_stop (4096 x 192)": lambda: hb.occ_compact(desc, rec, z_f, slot_ws, rec_ws, z_stop)}
-    alone = {}
-    for name, fn in launches.items():
-        for _ in range(3):
-            fn()
-        ts = []
-        for _ in range(args.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(100):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1) / 100 * 1e3)
-        alone[name] = {"us_median": statistics.median(ts), "us_min": min(ts), "us_max": max(ts),
-                       "note": "host-timed back-to-back calls (allocation of the small outputs included)"}
+    alone = {name: dict(gx.time_launches(fn, args.reps), note="host-timed back-to-back calls (allocation of the small outputs included)")
+             for name, fn in launches.items()}
     alone["rays_stopped_at_1e-3"] = int(torch.isfinite(z_stop).sum())
     result["launches_alone"] = alone
-text = json.dumps(result, indent=1)
-print(text)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+gx.emit(result, args.out)

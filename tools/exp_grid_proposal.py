@@ -12,67 +12,30 @@ The learning rate is 0 (the optimizer does all of its work; the scene and every 
     python tools/exp_grid_proposal.py --root <checkout of the parent commit> --label "parent commit" --out ...   # its rows without the option
     python tools/exp_grid_proposal.py --psnr-run 2000 --out profiles/r12_exp_grid_proposal_run.json              # a record, not a gate
 """
-import argparse
 import inspect
-import json
-import os
-import statistics
-import sys
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ap.add_argument("--label", default="this commit", help="what --root is, for the record")
-ap.add_argument("--out", default=None)
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--steps", type=int, default=10, help="training steps / renders between two HIP events")
+import grid_exp as gx
+
+ap = gx.parser(__doc__, steps="training steps / renders between two HIP events")
 ap.add_argument("--psnr-run", type=int, default=0, metavar="STEPS",
                 help="instead of the timing: fit a student to a teacher scene for STEPS steps through a DensityGrid (class defaults, "
                      "maybe_update every step) once with two networks and once with proposal=\"grid\"; report held-out PSNR")
 args = ap.parse_args()
-sys.path.insert(0, os.path.abspath(args.root))
-import torch  # noqa: E402
-import workloads as wl  # noqa: E402
-import nerf_pytorch_amd as npa  # noqa: E402
-
-if not torch.cuda.is_available():
-    raise SystemExit("exp_grid_proposal: needs the GPU (no timing without one)")
-hb = npa.hip_backend
-dev = torch.device("cuda", 0)
+torch, wl, npa, hb, dev = gx.load(args, "exp_grid_proposal")
 HAVE_PROPOSAL = "proposal" in inspect.signature(npa.render_rays).parameters
-Pc, Pf = wl.scene_params()
-kwn = dict(D=8, W=256, input_ch=63, output_ch=5, skips=[4], input_ch_views=27, use_viewdirs=True)
-nc, nf = npa.NeRF(**kwn).to(dev), npa.NeRF(**kwn).to(dev)
-nc.load_state_dict(Pc)
-nf.load_state_dict(Pf)
-npa.set_precision("fp16x3")
-LO, HI, R = (-2.0, -2.0, -2.0), (2.0, 2.0, 2.0), 128
-N_RAYS = 4096
-KW = dict(network_fn=nc, network_query_fn=None, N_samples=64, N_importance=128, network_fine=nf, perturb=1., white_bkgd=True, raw_noise_std=0.)
-H = W = 800
-K = wl.intrinsics(dict(H=H, W=W, focal=1111.0))
-GEO = dict(chunk=32768, ndc=False, near=2., far=6., use_viewdirs=True)
-rays = wl.lego_batch(N_RAYS, seed=1).to(dev)
-target = torch.rand(N_RAYS, 3, generator=torch.Generator().manual_seed(2)).to(dev)
-opt_two = npa.FlatAdam(list(nc.parameters()) + list(nf.parameters()), lr=0.0)
-opt_one = npa.FlatAdam(list(nf.parameters()), lr=0.0)
+S = gx.Scene(wl, npa, dev, perturb=1., target=True, records=True)
+LO, HI, R, N_RAYS, nc, nf = S.LO, S.HI, S.R, S.N_RAYS, S.nc, S.nf
+opt_two, opt_one = S.adam(nc, nf), S.adam(nf)
 
 
-def render(grid, proposal, batch=rays, **over):
-    kw = dict(KW, occupancy=grid, **over)
+def render(grid, proposal, batch=None, **over):
     if proposal:
-        kw["proposal"] = "grid"
-    return npa.render(H, W, K, rays=batch, **GEO, **kw)
+        over["proposal"] = "grid"
+    return S.render(batch, occupancy=grid, **over)
 
 
 def step(grid, proposal):
-    rgb, _, _, extras = render(grid, proposal)
-    loss = npa.img2mse(rgb, target)
-    if not proposal:
-        loss = loss + npa.img2mse(extras["rgb0"], target)
-    opt = opt_one if proposal else opt_two
-    opt.zero_grad()
-    loss.backward()
-    opt.step()
+    S.fit(render(grid, proposal), opt_one if proposal else opt_two, rgb0=not proposal)
 
 
 def infer(grid, proposal):
@@ -80,59 +43,21 @@ def infer(grid, proposal):
         render(grid, proposal)
 
 
-def ball(radius):
-    c = LO[0] + (torch.arange(R, dtype=torch.float64) + 0.5) * (HI[0] - LO[0]) / R
-    x, y, z = torch.meshgrid(c, c, c, indexing="ij")
-    return npa.DensityGrid.from_mask((x * x + y * y + z * z) <= radius * radius, LO, HI, outside="skip", device=dev)
-
-
-def share_of(grid, proposal=False):
+def share_of(grid):
     torch.manual_seed(0)
-    infer(grid, proposal)
-    return grid.last_stats["evaluated"] / grid.last_stats["total"]
-
-
-def ball_with_share(want):
-    lo, hi = 0.0, 4.0
-    for _ in range(14):
-        mid = 0.5 * (lo + hi)
-        if share_of(ball(mid)) < want:
-            lo = mid
-        else:
-            hi = mid
-    return ball(hi), hi
+    infer(grid, False)
+    return gx.evaluated_share(grid)
 
 
 def time_all(fn, configs, k, reps):
     """alternate the configurations inside every repetition; HIP events around k calls each"""
-    times = {name: [] for name, _, _ in configs}
-    for _, grid, proposal in configs:
-        for _ in range(3):
-            fn(grid, proposal)
-    torch.cuda.synchronize()
-    for _ in range(reps):
-        for name, grid, proposal in configs:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(k):
-                fn(grid, proposal)
-            e1.record()
-            torch.cuda.synchronize()
-            times[name].append(e0.elapsed_time(e1) / k)
+    times = gx.time_alternating([(name, lambda g=g, p=p: fn(g, p)) for name, g, p in configs], k, reps, warmup=3)
     rows = {}
     for name, grid, proposal in configs:
-        ms = statistics.median(times[name])
-        rows[name] = {"ms_median": ms, "ms_min": min(times[name]), "ms_max": max(times[name]), "rays_per_s": N_RAYS / ms * 1e3}
-        timer = hb.TIMER
-        hb.TIMER = hb.KernelTimer()         # a separate call with HIP events around every launch
-        try:
-            fn(grid, proposal)
-            summ = hb.TIMER.summary()
-        finally:
-            hb.TIMER = timer
+        rows[name] = gx.row_stats(times[name], N_RAYS)
+        summ = gx.kernel_summary(hb, lambda: fn(grid, proposal))      # a separate call with HIP events around every launch
         rows[name].update(evaluated=grid.last_stats["evaluated"], total=grid.last_stats["total"],
-                          occ_kernels_ms=sum(v["ms"] for kname, v in summ.items() if kname.startswith("occ_")),
-                          field_ms=sum(v["ms"] for kname, v in summ.items() if kname.startswith(("field_", "wgrad"))))
+                          occ_kernels_ms=gx.kernel_ms(summ, "occ_"), field_ms=gx.kernel_ms(summ, ("field_", "wgrad")))
     return rows
 
 
@@ -140,22 +65,14 @@ if args.psnr_run > 0:
     # the converging pair of bench.py --long (tools/exp_occupancy_train.py --psnr-run): a student that starts as scene_params(seed=6) is
     # fitted to the scene of scene_params(seed=5); fresh batches every step, targets = the teacher's no_grad render of the same rays,
     # Adam 5e-4; held out: a batch never trained on, rendered the way the run trains
-    Tc, Tf = wl.scene_params(seed=5)
-    Sc, Sf = wl.scene_params(seed=6)
-    tc, tf = npa.NeRF(**kwn).to(dev), npa.NeRF(**kwn).to(dev)
-    tc.load_state_dict(Tc)
-    tf.load_state_dict(Tf)
-    tkw = dict(KW, network_fn=tc, network_fine=tf, perturb=0.)
-    held = wl.lego_batch(N_RAYS, seed=10 ** 6).to(dev)
-    with torch.no_grad():
-        held_target = npa.render(H, W, K, rays=held, **GEO, **tkw)[0]
+    tkw, (Sc, Sf), held, held_target = S.teacher_and_held_out()
     runs = {}
     for label, proposal in (("two networks through the DensityGrid", False), ("proposal=\"grid\": the fine network alone", True)):
         if proposal and not HAVE_PROPOSAL:
             continue
         nc.load_state_dict(Sc)
         nf.load_state_dict(Sf)
-        adam = npa.FlatAdam(list(nf.parameters()) + ([] if proposal else list(nc.parameters())), lr=5e-4)
+        adam = S.adam(nf, *([] if proposal else [nc]), lr=5e-4)
         grid = npa.DensityGrid(LO, HI, R, device=dev)
         torch.manual_seed(7)
         log = []
@@ -167,12 +84,12 @@ if args.psnr_run > 0:
                     rgb = render(grid, proposal, held, perturb=0.)[0]
                 log.append({"step": it, "held_out_psnr_db": float(wl.psnr(npa.img2mse(rgb, held_target))),
                             "fraction_occupied": grid.fraction_occupied(),
-                            "evaluated_share": grid.last_stats["evaluated"] / grid.last_stats["total"]})
+                            "evaluated_share": gx.evaluated_share(grid)})
             if it == args.psnr_run:
                 break
             batch = wl.lego_batch(N_RAYS, seed=it).to(dev)
             with torch.no_grad():
-                tgt = npa.render(H, W, K, rays=batch, **GEO, **tkw)[0]
+                tgt = S.render(batch, **tkw)[0]
             grid.maybe_update(nf, it)
             rgb, _, _, extras = render(grid, proposal, batch)
             loss = npa.img2mse(rgb, tgt)
@@ -196,7 +113,7 @@ else:
         density = npa.DensityGrid(LO, HI, R, device=dev).update(nf).density
     grids = [("share 1.0 (all occupied)", npa.DensityGrid(LO, HI, R, device=dev))]
     for want in (0.5, 0.25, 0.1):
-        g, radius = ball_with_share(want)
+        g, radius = S.ball_with_share(npa.DensityGrid, share_of, want)
         grids.append((f"share {want} (ball r = {radius:.3f}, outside skipped)", g))
     configs = []
     for name, g in grids:
@@ -208,27 +125,11 @@ else:
     result["no_grad_render_4096_rays"] = time_all(infer, configs, args.steps, args.reps)
     if HAVE_PROPOSAL:
         g = grids[2][1]
-        rays_rec = wl.synthetic_rays(N_RAYS, 1).to(dev).contiguous()       # (the records render() makes of `rays`)
+        rays_rec = S.records
         z = hb.sample_coarse(rays_rec, torch.linspace(0., 1., 64, device=dev), False, None)
-        ts = []
-        for _ in range(3):
-            g.proposal_weights(rays_rec, z)
-        for _ in range(args.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(100):
-                g.proposal_weights(rays_rec, z)
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1) / 100 * 1e3)
         P = N_RAYS * 64
-        us = statistics.median(ts)
-        result["proposal_weights_kernel_128_cubed"] = {"us_median": us, "us_min": min(ts), "us_max": max(ts), "rays": N_RAYS, "samples": 64,
-                                                       "bytes_model": 24 * N_RAYS + 16 * P, "gbytes_per_s_model": (24 * N_RAYS + 16 * P) / us / 1e3,
-                                                       "note": "host-timed back-to-back launches (allocation of the output included)"}
-text = json.dumps(result, indent=1)
-print(text)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+        us = gx.time_launches(lambda: g.proposal_weights(rays_rec, z), args.reps)
+        result["proposal_weights_kernel_128_cubed"] = dict(us, rays=N_RAYS, samples=64, bytes_model=24 * N_RAYS + 16 * P,
+                                                           gbytes_per_s_model=(24 * N_RAYS + 16 * P) / us["us_median"] / 1e3,
+                                                           note="host-timed back-to-back launches (allocation of the output included)")
+gx.emit(result, args.out)

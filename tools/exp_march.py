@@ -11,66 +11,28 @@ The learning rate is 0 (the optimizer does all of its work; the scene and every 
 
     python tools/exp_march.py --out profiles/r14_exp_march.json
 """
-import argparse
-import json
-import os
-import statistics
-import sys
+import grid_exp as gx
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ap.add_argument("--label", default="this commit", help="what --root is, for the record")
-ap.add_argument("--out", default=None)
-ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--steps", type=int, default=10, help="training steps / renders between two HIP events")
-args = ap.parse_args()
-sys.path.insert(0, os.path.abspath(args.root))
-import torch  # noqa: E402
-import workloads as wl  # noqa: E402
-import nerf_pytorch_amd as npa  # noqa: E402
-
-if not torch.cuda.is_available():
-    raise SystemExit("exp_march: needs the GPU (no timing without one)")
-hb = npa.hip_backend
-dev = torch.device("cuda", 0)
-Pc, Pf = wl.scene_params()
-kwn = dict(D=8, W=256, input_ch=63, output_ch=5, skips=[4], input_ch_views=27, use_viewdirs=True)
-nc, nf = npa.NeRF(**kwn).to(dev), npa.NeRF(**kwn).to(dev)
-nc.load_state_dict(Pc)
-nf.load_state_dict(Pf)
-npa.set_precision("fp16x3")
-LO, HI, R = (-2.0, -2.0, -2.0), (2.0, 2.0, 2.0), 128
-N_RAYS, N_C, N_F = 4096, 64, 128
+args = gx.parser(__doc__, steps="training steps / renders between two HIP events").parse_args()
+torch, wl, npa, hb, dev = gx.load(args, "exp_march")
+S = gx.Scene(wl, npa, dev, perturb=1., target=True, records=True)
+LO, HI, R, N_RAYS, nc, nf = S.LO, S.HI, S.R, S.N_RAYS, S.nc, S.nf
+N_C, N_F = 64, 128
 MARCH_STEPS = (256, 512, 1024)
-KW = dict(network_fn=nc, network_query_fn=None, N_samples=N_C, N_importance=N_F, network_fine=nf, perturb=1., white_bkgd=True, raw_noise_std=0.)
-H = W = 800
-K = wl.intrinsics(dict(H=H, W=W, focal=1111.0))
-GEO = dict(chunk=32768, ndc=False, near=2., far=6., use_viewdirs=True)
-rays = wl.lego_batch(N_RAYS, seed=1).to(dev)
-target = torch.rand(N_RAYS, 3, generator=torch.Generator().manual_seed(2)).to(dev)
-opt_two = npa.FlatAdam(list(nc.parameters()) + list(nf.parameters()), lr=0.0)
-opt_one = npa.FlatAdam(list(nf.parameters()), lr=0.0)
+opt_two, opt_one = S.adam(nc, nf), S.adam(nf)
 
 
 def render(grid, mode):
     """mode: None (two networks), "grid", or the march's step count"""
-    kw = dict(KW, occupancy=grid)
     if mode == "grid":
-        kw["proposal"] = "grid"
-    elif mode is not None:
-        kw.update(proposal="march", march_steps=mode)
-    return npa.render(H, W, K, rays=rays, **GEO, **kw)
+        return S.render(occupancy=grid, proposal="grid")
+    if mode is not None:
+        return S.render(occupancy=grid, proposal="march", march_steps=mode)
+    return S.render(occupancy=grid)
 
 
 def step(grid, mode):
-    rgb, _, _, extras = render(grid, mode)
-    loss = npa.img2mse(rgb, target)
-    if mode is None:
-        loss = loss + npa.img2mse(extras["rgb0"], target)
-    opt = opt_two if mode is None else opt_one
-    opt.zero_grad()
-    loss.backward()
-    opt.step()
+    S.fit(render(grid, mode), opt_two if mode is None else opt_one, rgb0=mode is None)
 
 
 def infer(grid, mode):
@@ -78,60 +40,22 @@ def infer(grid, mode):
         render(grid, mode)
 
 
-def ball(radius):
-    c = LO[0] + (torch.arange(R, dtype=torch.float64) + 0.5) * (HI[0] - LO[0]) / R
-    x, y, z = torch.meshgrid(c, c, c, indexing="ij")
-    return npa.DensityGrid.from_mask((x * x + y * y + z * z) <= radius * radius, LO, HI, outside="skip", device=dev)
-
-
 def share_of(grid):
     torch.manual_seed(0)
     infer(grid, None)
-    return grid.last_stats["evaluated"] / grid.last_stats["total"]
-
-
-def ball_with_share(want):
-    lo, hi = 0.0, 4.0
-    for _ in range(14):
-        mid = 0.5 * (lo + hi)
-        if share_of(ball(mid)) < want:
-            lo = mid
-        else:
-            hi = mid
-    return ball(hi), hi
+    return gx.evaluated_share(grid)
 
 
 def time_all(fn, configs, k, reps):
     """alternate the configurations inside every repetition; HIP events around k calls each"""
-    times = {name: [] for name, _, _ in configs}
-    for _, grid, mode in configs:
-        for _ in range(3):
-            fn(grid, mode)
-    torch.cuda.synchronize()
-    for _ in range(reps):
-        for name, grid, mode in configs:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(k):
-                fn(grid, mode)
-            e1.record()
-            torch.cuda.synchronize()
-            times[name].append(e0.elapsed_time(e1) / k)
+    times = gx.time_alternating([(name, lambda g=g, m=m: fn(g, m)) for name, g, m in configs], k, reps, warmup=3)
     rows = {}
     for name, grid, mode in configs:
-        ms = statistics.median(times[name])
-        rows[name] = {"ms_median": ms, "ms_min": min(times[name]), "ms_max": max(times[name]), "rays_per_s": N_RAYS / ms * 1e3}
-        timer = hb.TIMER
-        hb.TIMER = hb.KernelTimer()         # a separate call with HIP events around every launch
-        try:
-            fn(grid, mode)
-            summ = hb.TIMER.summary()
-        finally:
-            hb.TIMER = timer
+        rows[name] = gx.row_stats(times[name], N_RAYS)
+        summ = gx.kernel_summary(hb, lambda: fn(grid, mode))      # a separate call with HIP events around every launch
         stats = grid.last_stats
         rows[name].update(evaluated=stats["evaluated"], total=stats["total"], evaluated_per_ray=stats["evaluated"] / N_RAYS,
-                          occ_kernels_ms=sum(v["ms"] for kname, v in summ.items() if kname.startswith("occ_")),
-                          field_ms=sum(v["ms"] for kname, v in summ.items() if kname.startswith(("field_", "wgrad"))))
+                          occ_kernels_ms=gx.kernel_ms(summ, "occ_"), field_ms=gx.kernel_ms(summ, ("field_", "wgrad")))
         if "rays_truncated" in stats:
             rows[name]["rays_truncated"] = stats["rays_truncated"]
     return rows
@@ -144,7 +68,7 @@ with torch.no_grad():
 configs = []
 grids = []
 for want in (0.5, 0.25, 0.1):
-    g, radius = ball_with_share(want)
+    g, radius = S.ball_with_share(npa.DensityGrid, share_of, want)
     g.density = density.clone()
     grids.append(g)
     name = f"share {want} (ball r = {radius:.3f}, outside skipped)"
@@ -155,30 +79,14 @@ for want in (0.5, 0.25, 0.1):
 result["train_step_4096_rays"] = time_all(step, configs, args.steps, args.reps)
 result["no_grad_render_4096_rays"] = time_all(infer, configs, args.steps, args.reps)
 g = grids[1]
-rays_rec = wl.synthetic_rays(N_RAYS, 1).to(dev).contiguous()       # (the records render() makes of `rays`)
-S = N_C + N_F
+rays_rec = S.records
+SLOTS = N_C + N_F
 kernel = {}
 for M in MARCH_STEPS:
-    ts = []
-    for _ in range(3):
-        g.march(rays_rec, M, S)
-    for _ in range(args.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(100):
-            g.march(rays_rec, M, S)
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / 100 * 1e3)
-    us = statistics.median(ts)
-    nbytes = (32 + 4 * S + 8) * N_RAYS
-    kernel[f"M={M}"] = {"us_median": us, "us_min": min(ts), "us_max": max(ts), "rays": N_RAYS, "slots": S, "bytes_model": nbytes,
-                        "gbytes_per_s_model": nbytes / us / 1e3, "rays_truncated": int(g.march(rays_rec, M, S)[2].sum())}
+    us = gx.time_launches(lambda: g.march(rays_rec, M, SLOTS), args.reps)
+    nbytes = (32 + 4 * SLOTS + 8) * N_RAYS
+    kernel[f"M={M}"] = dict(us, rays=N_RAYS, slots=SLOTS, bytes_model=nbytes, gbytes_per_s_model=nbytes / us["us_median"] / 1e3,
+                            rays_truncated=int(g.march(rays_rec, M, SLOTS)[2].sum()))
 kernel["note"] = "host-timed back-to-back launches (allocation of the outputs included)"
 result["march_kernel_128_cubed"] = kernel
-text = json.dumps(result, indent=1)
-print(text)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+gx.emit(result, args.out)
