@@ -527,6 +527,30 @@ int nerf_occ_compact_stop(const NerfOccGrid* grid, const float* rays, int ray_st
  * one bit word per candidate looked at; writes 4 S + 8 B per ray.  ray_stride >= 8; 1 <= n_steps <= 16384; 1 <= n_slots <= 4096. */
 int nerf_occ_march(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* u /* nullable: 0.5 */,
                    int n_rays, int n_steps, int n_slots, float* z_vals, float* z_stop, int* truncated, void* stream);
+/* ---- the march with a stop on the grid's own transmittance (additive in ABI v10): render_rays(proposal="march", march_stop_eps=eps).
+ * nerf_occ_march over a DensityGrid (density[cells], outside_sigma: nerf_occ_proposal_weights' arguments) with one more rule;
+ * DensityGrid.march_stop_reference is the definition.  Candidates, t_k, z_k, keep_k and close_k are nerf_occ_march's.  Per candidate
+ *   sigma_k = nerf_occ_proposal_weights' lookup at the point o + d * z_k, taken as 0 unless sigma_k > 0 (a NaN counts as 0)
+ *   c_k     = sigma_k * ((z_{k+1} - z_k) * |d|) where keep_k, exactly 0 elsewhere; z_{k+1} is built from fp32(k + 1) by z_k's
+ *             expression, and is far for k = M - 1; |d| = sqrt(dx dx + dy dy + dz dz) added left to right; no contraction
+ *   A_k     = the exclusive prefix sum of c in fp32 in THIS order: rounds of 64 candidates; inside a round the inclusive scan with
+ *             strides 1, 2, 4, 8, 16, 32 (lane l >= stride adds the previous step's value of lane l - stride); A_k = base + incl_{l-1}
+ *             (+ 0 for lane 0); base starts at 0 and grows by incl_63 after every round
+ *   k_stop  = the first k < M with A_k >= tau (a NaN never satisfies this: a poisoned sum never stops); tau = fp32(-ln(eps)), computed
+ *             by the host in double
+ * The emitted candidates are those with (keep_k || close_k) && k < k_stop, E of them.  E > S - 1: truncated as by nerf_occ_march,
+ * stopped[r] = 0 (the slot limit bit first).  Else, with a k_stop: z_stop[r] = z_{k_stop}, stopped[r] = 1, z_vals[r][E .. S) = z_stop[r].
+ * Else everything is nerf_occ_march's, stopped[r] = 0.  Invalid rays: as nerf_occ_march, stopped[r] = 0.  With density all zero the
+ * first three outputs are nerf_occ_march's bit for bit.  c >= 0 grows only at kept candidates, so candidate k_stop - 1 is a kept one
+ * and its interval ends exactly at z_stop.  AN APPROXIMATION of the render: what is dropped is the network's own transmittance behind
+ * z_stop; the grid's densities are a decayed running maximum and overestimate, so that is close to eps where grid and network agree but
+ * not bounded by it.  One wavefront per ray, 64 candidates per round (one scan, one more ballot); the wave leaves once the slots are
+ * full or the cut has been seen.  Plain stores, no atomics, no LDS: the same inputs give the same bits.  Reads what nerf_occ_march
+ * reads and one density word per kept candidate; writes 4 S + 12 B per ray.  ray_stride >= 8; 1 <= n_steps <= 16384;
+ * 1 <= n_slots <= 4096; tau > 0. */
+int nerf_occ_march_stop(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride,
+                        const float* u /* nullable: 0.5 */, int n_rays, int n_steps, int n_slots, float tau, float* z_vals,
+                        float* z_stop, int* truncated, int* stopped, void* stream);
 
 #ifdef __cplusplus
 }

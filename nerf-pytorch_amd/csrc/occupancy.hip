@@ -17,6 +17,8 @@
 //   nerf_occ_march   : per ray M equal steps over [near, far], the ones in occupied cells (and one closing step behind every occupied
 //                      run) emitted into S slots, with the stop depth that makes nerf_occ_compact_stop drop the padding:
 //                      render_rays(proposal="march").
+//   nerf_occ_march_stop : the same walk over a DensityGrid, which also adds up the grid's own optical depth and stops emitting where the
+//                      grid's transmittance has fallen to eps: render_rays(proposal="march", march_stop_eps=eps).
 // The compaction is deterministic: a count per block of OCC_TILE points, an exclusive scan of the block counts, then the
 // write -- inside a block the position of a point is a wave ballot + popcount and a prefix over the block's wave counts, so the
 // list is in stable ray-major, sample-minor order and no atomic decides anything.
@@ -633,6 +635,91 @@ __global__ __launch_bounds__(MARCH_THREADS) void occ_march_kernel(GridArgs g, co
     }
 }
 
+// ---- nerf_occ_march_stop (DensityGrid.march_stop_reference is the definition)
+// occ_march_kernel with one more rule: the ray stops emitting at the first candidate in front of which the grid's own optical depth
+// A_k = sum_{j < k} c_j has reached tau = -ln(eps).  Per round the lane builds c of its candidate -- proposal_sigma at the point it
+// classified (0 where the candidate is not kept, where sigma <= 0 and where sigma is a NaN) times the interval up to the NEXT candidate
+// (built from k + 1 by the same expression; far behind the last one) times |d|, occ_proposal_weights_kernel's order of operations --,
+// the wave scans c (nerf::wave_incl_scan_add: the order of the additions is the definition's), A = base + the inclusive sum of the lane
+// below, and one ballot of A >= tau (k < M) finds the cut lane.  The emit mask keeps the lanes below the cut; a truncation hit inside
+// what is left wins (the slot limit bit first), otherwise the stop depth is the cut lane's z.  The wave leaves once the slots are full
+// or the cut has been seen.  A NaN in A fails the comparison and poisons every later A: such a ray never stops.  Everything the wave
+// branches on is wave-uniform; no LDS, no atomics.
+__global__ __launch_bounds__(MARCH_THREADS) void occ_march_stop_kernel(GridArgs g, const float* __restrict__ density, float outside_sigma,
+                                                                       const float* __restrict__ rays, int ray_stride,
+                                                                       const float* __restrict__ u, int n_rays, int M, int S, float tau,
+                                                                       float* __restrict__ z_vals, float* __restrict__ z_stop,
+                                                                       int* __restrict__ truncated, int* __restrict__ stopped) {
+    const int ray = blockIdx.x * MARCH_RAYS + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;          // (whole waves leave: the ballots and shuffles below see full waves)
+    const int lane = threadIdx.x & 63;
+    const float* r = rays + (size_t)ray * ray_stride;
+    float* zrow = z_vals + (size_t)ray * S;
+    const float near = r[6], far = r[7];
+    bool ok = near < far;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) ok = ok && fabsf(r[c]) < INFINITY;      // (a NaN fails the comparison)
+    if (!ok) {
+        for (int j = lane; j < S; j += 64) zrow[j] = far;
+        if (lane == 0) {
+            z_stop[ray] = -INFINITY;
+            truncated[ray] = 0;
+            stopped[ray] = 0;
+        }
+        return;
+    }
+    const float uu = u ? u[ray] : 0.5f;
+    const float Mf = (float)M;
+    const float dn = sqrtf(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+    const int last = S - 1;
+    int base = 0, trunc = 0, stp = 0;
+    unsigned long long carry = 0ull;
+    float stop = far, depth = 0.0f;     // depth: A in front of the round's first candidate
+    for (int k0 = 0; k0 < M && base <= last && !stp; k0 += 64) {
+        const int k = k0 + lane;
+        const float t = ((float)k + uu) / Mf;               // (IEEE division: hipcc's default for fp32)
+        const float z = near * (1.0f - t) + far * t;        // run_nerf.py:360 (no contraction)
+        const Pt p = sample_point(r, z);
+        const bool keep = k < M && occupied(g, p);
+        float c = 0.0f;
+        if (keep) {
+            const float t1 = ((float)(k + 1) + uu) / Mf;
+            const float z1 = k + 1 < M ? near * (1.0f - t1) + far * t1 : far;
+            const float sg = proposal_sigma(g, density, outside_sigma, p);
+            const float dist = (z1 - z) * dn;
+            c = (sg > 0.0f ? sg : 0.0f) * dist;             // (a NaN sigma fails the comparison: 0)
+        }
+        const float incl = nerf::wave_incl_scan_add(c, lane);
+        float below = __shfl_up(incl, 1);
+        if (lane == 0) below = 0.0f;
+        const unsigned long long cut = __ballot(k < M && depth + below >= tau);
+        const unsigned long long km = __ballot(keep);
+        unsigned long long em = km | (((km << 1) | carry) & ~km & __ballot(k < M));
+        carry = km >> 63;
+        const int cut_lane = cut ? __ffsll((long long)cut) - 1 : 64;
+        if (cut) em &= (1ull << cut_lane) - 1ull;
+        const int rank = base + lanes_below(em);
+        const bool emit = (em >> lane) & 1ull;
+        if (emit && rank < last) zrow[rank] = z;
+        const unsigned long long hit = __ballot(emit && rank == last);
+        if (hit) {
+            stop = __shfl(z, __ffsll((long long)hit) - 1);
+            trunc = 1;
+        } else if (cut) {
+            stop = __shfl(z, cut_lane);
+            stp = 1;
+        }
+        base += __popcll(em);
+        depth = depth + __shfl(incl, 63);
+    }
+    for (int j = min(base, last) + lane; j < S; j += 64) zrow[j] = stop;
+    if (lane == 0) {
+        z_stop[ray] = stop;
+        truncated[ray] = trunc;
+        stopped[ray] = stp;
+    }
+}
+
 int check_grid(const char* fn, const NerfOccGrid* grid, GridArgs* g) {
     if (!grid || !grid->bits) return fail_arg(fn, "null pointer");
     for (int a = 0; a < 3; ++a) {
@@ -709,6 +796,21 @@ int nerf_occ_march(const NerfOccGrid* grid, const float* rays, int ray_stride, c
     if (n_rays == 0) return 0;
     occ_march_kernel<<<(unsigned)((n_rays + MARCH_RAYS - 1) / MARCH_RAYS), MARCH_THREADS, 0, (hipStream_t)stream>>>(
         g, rays, ray_stride, u, n_rays, n_steps, n_slots, z_vals, z_stop, truncated);
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_march_stop(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride, const float* u,
+                        int n_rays, int n_steps, int n_slots, float tau, float* z_vals, float* z_stop, int* truncated, int* stopped,
+                        void* stream) {
+    GridArgs g;
+    if (int rc = check_grid(__func__, grid, &g)) return rc;
+    REQUIRE(density && rays && z_vals && z_stop && truncated && stopped, "null pointer");
+    REQUIRE(ray_stride >= 8 && n_rays >= 0 && n_steps >= 1 && n_steps <= 16384 && n_slots >= 1 && n_slots <= 4096,
+            "bad size (ray records need 8 columns, 1..16384 steps, 1..4096 slots)");
+    REQUIRE(tau > 0.0f, "bad threshold (tau = -ln(eps) must be > 0)");        // (a NaN fails the comparison)
+    if (n_rays == 0) return 0;
+    occ_march_stop_kernel<<<(unsigned)((n_rays + MARCH_RAYS - 1) / MARCH_RAYS), MARCH_THREADS, 0, (hipStream_t)stream>>>(
+        g, density, outside_sigma, rays, ray_stride, u, n_rays, n_steps, n_slots, tau, z_vals, z_stop, truncated, stopped);
     return done(__func__, hipGetLastError());
 }
 

@@ -96,6 +96,7 @@ def _declare(lib):
         "nerf_occ_stop_depth": (i, [p, p, i, i, f, p, p]),
         "nerf_occ_compact_stop": (i, [p, p, i, p, p, i, i, p, p, p, p, p]),
         "nerf_occ_march": (i, [p, p, i, p, i, i, i, p, p, p, p]),
+        "nerf_occ_march_stop": (i, [p, p, f, p, i, p, i, i, i, f, p, p, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -122,7 +123,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_sample_ray_views", "nerf_ray_pose_grad",
            "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate",
            "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span", "nerf_occ_proposal_weights",
-           "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march",
+           "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march", "nerf_occ_march_stop",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
 
 
@@ -1268,6 +1269,37 @@ def occ_march(desc, rays, u, n_steps, n_slots):
         _check(lib().nerf_occ_march(ctypes.byref(desc), _ptr(rays, "rays"), stride, _ptr(u, "u", True), n, M, S, _ptr(z_vals), _ptr(z_stop),
                                     truncated.data_ptr(), _stream()), "nerf_occ_march")
     return z_vals, z_stop, truncated
+
+
+def march_stop_threshold(eps):
+    """tau = fp32(-ln(eps)), computed in double: what the grid's accumulated optical depth is compared with (include/nerf_hip.h)"""
+    import math
+    import numpy as np
+    return float(np.float32(-math.log(float(eps))))
+
+
+def occ_march_stop(desc, density, outside_sigma, rays, u, n_steps, n_slots, eps):
+    """nerf_occ_march_stop: (z_vals fp32 [n, n_slots], z_stop fp32 [n], truncated int32 [n], stopped int32 [n]) of rays [n, >= 8] --
+    occ_march over a DensityGrid's densities (fp32 [cells]; outside the box outside_sigma, as occ_proposal_weights takes them) that stops
+    emitting where the grid's own transmittance has fallen to eps (0 < eps < 1); a stopped ray's stop depth is the first candidate not
+    emitted"""
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise NerfHipError("occ_march_stop: rays [n, >= 8] (o, d, near, far, ...)")
+    n, stride = rays.shape
+    M, S = int(n_steps), int(n_slots)
+    if u is not None and tuple(u.shape) != (n,):
+        raise NerfHipError("occ_march_stop: u must hold one offset per ray")
+    if density.numel() != desc.res[0] * desc.res[1] * desc.res[2]:
+        raise NerfHipError("occ_march_stop: one density per cell of the grid")
+    z_vals = torch.empty((n, S), dtype=torch.float32, device=rays.device)
+    z_stop = torch.empty(n, dtype=torch.float32, device=rays.device)
+    truncated = torch.empty(n, dtype=torch.int32, device=rays.device)
+    stopped = torch.empty(n, dtype=torch.int32, device=rays.device)
+    with _timed("occ_march_stop_kernel", 0.0, (4.0 * S + 48.0) * n):
+        _check(lib().nerf_occ_march_stop(ctypes.byref(desc), _ptr(density, "density"), float(outside_sigma), _ptr(rays, "rays"), stride,
+                                         _ptr(u, "u", True), n, M, S, march_stop_threshold(eps), _ptr(z_vals), _ptr(z_stop),
+                                         truncated.data_ptr(), stopped.data_ptr(), _stream()), "nerf_occ_march_stop")
+    return z_vals, z_stop, truncated, stopped
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

@@ -50,6 +50,12 @@ def _check_eps(eps, who):
     return e
 
 
+def _check_march_eps(eps, who):
+    if isinstance(eps, bool) or not isinstance(eps, (float, np.floating)) or not (0.0 < float(eps) < 1.0):      # (also refuses NaN)
+        raise ValueError(f"{who}: march_stop_eps must be a float with 0 < eps < 1, got {eps!r}")
+    return float(eps)
+
+
 def stop_depth_reference(z_vals, weights, eps):
     """The definition of the stop depth of render_rays(early_stop_eps=eps), in numpy (tensors of any device; fp32 [N] on z_vals' device).
 
@@ -99,7 +105,8 @@ class OccupancyGrid:
     ``ray_span`` / ``clip_rays`` give the grid its second use: per ray the span from the first to the last occupied cell it crosses
     (``ray_span_reference`` is the definition), which render_rays(clip_to_occupancy=True) samples instead of [near, far].
     ``march`` gives it a third: the depths themselves, per ray the equal steps over [near, far] that fall in occupied cells
-    (``march_reference`` is the definition) -- render_rays(proposal="march"), whose last_stats carry {"rays_truncated"}."""
+    (``march_reference`` is the definition) -- render_rays(proposal="march"), whose last_stats carry {"rays_truncated"} (and, with
+    march_stop_eps over a DensityGrid, {"rays_stopped"})."""
 
     def __init__(self, lo, hi, resolution, outside="evaluate", device=None):
         if outside not in _OUTSIDE:
@@ -376,7 +383,9 @@ class DensityGrid(OccupancyGrid):
     ``_update_reference`` / ``_bits_reference`` are the definition of the step in plain torch, as ``occupied()`` is the classifier's.
 
     The densities have a second reader: render_rays(..., occupancy=grid, proposal="grid") draws its importance samples from the
-    compositing weights of ``proposal_sigma`` at the coarse depths (``proposal_weights``) and evaluates one network only."""
+    compositing weights of ``proposal_sigma`` at the coarse depths (``proposal_weights``) and evaluates one network only.
+    And a third: ``march_stop`` is ``march`` that adds the densities up as it walks and stops emitting where the grid's own
+    transmittance has fallen to eps (``march_stop_reference`` is the definition) -- render_rays(proposal="march", march_stop_eps=eps)."""
 
     def __init__(self, lo, hi, resolution, outside="evaluate", device=None, decay=0.95, sigma_threshold=0.01, dilate=0, update_every=16,
                  warmup_steps=256):
@@ -489,6 +498,94 @@ class DensityGrid(OccupancyGrid):
                                                rays.detach().to(torch.float32).contiguous(), z_vals.detach().to(torch.float32).contiguous(),
                                                want_sigma)
         return (w, sigma) if want_sigma else w
+
+    # ------------------------------------------------------------------ the march that stops on the grid's own transmittance
+    def march_stop_reference(self, rays, u, n_steps, n_slots, eps):
+        """The definition of the depths of render_rays(proposal="march", march_stop_eps=eps), in plain torch (any device): rays
+        [N, >= 8], u fp32 [N] or None -> (z_vals fp32 [N, S], z_stop fp32 [N], truncated bool [N], stopped bool [N]).
+
+        ``march_reference`` with one more rule.  The candidates k = 0 .. M - 1, t_k, z_k, keep_k and close_k are exactly its own (an
+        invalid ray keeps nothing).  Density of a candidate: sigma_k = proposal_sigma(o + d * z_k) at the same fp32 point, taken where
+        sigma_k > 0, else 0 (a NaN counts as 0).  Its optical depth: c_k = sigma_k * ((z_{k+1} - z_k) * |d|) where keep_k holds and
+        exactly 0 elsewhere; z_{k+1} comes from t_{k+1} = (fp32(k + 1) + u) / fp32(M) by z_k's expression and is `far` for k = M - 1;
+        |d| = sqrt(dx dx + dy dy + dz dz), added left to right -- nerf_occ_proposal_weights' order of operations, no contraction: the
+        interval the compositing gives an evaluated marched sample, whose next slot is always the next candidate.
+        A_k is the exclusive prefix sum of c in fp32 in a FIXED order that is part of the definition: rounds of 64 candidates (k0 = 0,
+        64, ...; lanes with k >= M contribute 0); inside a round the inclusive scan for d = 1, 2, 4, 8, 16, 32 in which every lane
+        l >= d adds the previous step's value of lane l - d; A_k = base + incl_{l-1} (0 is added for lane 0); base starts at 0 and
+        grows by incl_63 after each round.
+        tau = fp32(-ln(float64(eps))); k_stop = the first k with A_k >= tau (a NaN never satisfies this: a poisoned sum never stops).
+        The emitted candidates are those with (keep_k or close_k) and k < k_stop, E of them.  E > S - 1: the ray is truncated exactly
+        as in march_reference and stopped = False -- the slot limit bit first.  Else, with a k_stop: z_stop = z_{k_stop}, stopped =
+        True, slots E .. S - 1 hold z_stop.  Else everything is march_reference's.  Invalid rays: row = own far, z_stop = -inf, neither
+        flag.
+
+        A only grows at kept candidates, so k_stop - 1 is always a kept candidate, and its interval ends exactly at z_stop, as every
+        marched sample's does.  A grid that was never updated (density == 0) never stops: z_vals, z_stop and truncated then equal
+        march_reference's bit for bit."""
+        M, S = int(n_steps), int(n_slots)
+        if M < 1 or S < 1:
+            raise ValueError("march_stop_reference: n_steps >= 1 and n_slots >= 1")
+        if rays.dim() != 2 or rays.shape[1] < 8:
+            raise ValueError("march_stop_reference: rays [N, >= 8] (o, d, near, far, ...)")
+        tau = torch.tensor(hb.march_stop_threshold(_check_march_eps(eps, "march_stop_reference")), dtype=torch.float32, device=rays.device)
+        dev = rays.device
+        r = rays.detach()[:, :8].to(torch.float32)
+        N = r.shape[0]
+        ok = torch.isfinite(r).all(-1) & (r[:, 6] < r[:, 7])
+        near, far = r[:, 6:7], r[:, 7:8]
+        uu = torch.full((N, 1), 0.5, dtype=torch.float32, device=dev) if u is None else u.detach().to(device=dev, dtype=torch.float32).reshape(N, 1)
+        k = torch.arange(M, dtype=torch.float32, device=dev)[None, :]
+        t = (k + uu) / torch.tensor(float(M), dtype=torch.float32, device=dev)
+        z = near * (1.0 - t) + far * t
+        z_next = torch.cat([z[:, 1:], far], -1)
+        pts = r[:, None, 0:3] + r[:, None, 3:6] * z[:, :, None]
+        keep = self.occupied(pts) & ok[:, None]
+        # the optical depth of every candidate
+        sigma = self.proposal_sigma(pts)
+        sigma = torch.where(sigma > 0, sigma, torch.zeros_like(sigma))
+        d = r[:, 3:6]
+        dn = torch.sqrt(d[:, 0:1] * d[:, 0:1] + d[:, 1:2] * d[:, 1:2] + d[:, 2:3] * d[:, 2:3])
+        c = torch.where(keep, sigma * ((z_next - z) * dn), torch.zeros_like(z))
+        # its exclusive prefix sum, in the order of the kernel's wave scan
+        rounds = (M + 63) // 64
+        incl = torch.cat([c, torch.zeros((N, rounds * 64 - M), dtype=torch.float32, device=dev)], -1).view(N, rounds, 64)
+        for s in (1, 2, 4, 8, 16, 32):
+            incl = torch.cat([incl[..., :s], incl[..., s:] + incl[..., :-s]], -1)
+        base = torch.zeros((N, rounds), dtype=torch.float32, device=dev)
+        for j in range(1, rounds):
+            base[:, j] = base[:, j - 1] + incl[:, j - 1, 63]
+        A = (base[:, :, None] + torch.cat([torch.zeros_like(incl[..., :1]), incl[..., :-1]], -1)).view(N, rounds * 64)[:, :M]
+        cut = A >= tau                                  # (a NaN never is)
+        has_cut = cut.any(-1)
+        k_stop = torch.where(has_cut, cut.to(torch.uint8).argmax(-1), torch.full((N,), M, dtype=torch.int64, device=dev))
+        before = torch.cat([torch.zeros_like(keep[:, :1]), keep[:, :-1]], -1)
+        emit = (keep | (before & ~keep)) & (torch.arange(M, device=dev)[None, :] < k_stop[:, None])
+        rank = torch.cumsum(emit.to(torch.int64), -1) - 1
+        truncated = emit.sum(-1) > S - 1
+        stopped = has_cut & ~truncated
+        first_out = emit & (rank == S - 1)          # (at most one per row)
+        z_stop = torch.where(truncated, z.gather(1, first_out.to(torch.uint8).argmax(-1, keepdim=True))[:, 0], r[:, 7])
+        z_stop = torch.where(stopped, z.gather(1, k_stop.clamp(max=M - 1)[:, None])[:, 0], z_stop)
+        z_stop = torch.where(ok, z_stop, torch.full_like(z_stop, float("-inf")))
+        z_vals = torch.where(ok, z_stop, r[:, 7])[:, None].repeat(1, S)
+        rows, cols = (emit & (rank < S - 1)).nonzero(as_tuple=True)
+        z_vals[rows, rank[rows, cols]] = z[rows, cols]
+        return z_vals, z_stop, truncated, stopped
+
+    def march_stop(self, rays, n_steps, n_slots, eps, u=None):
+        """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N], stopped bool [N]) for rays [N, >= 8] on the GPU
+        (nerf_occ_march_stop): ``march_stop_reference`` bit for bit.  Constants of the graph (computed without gradients from detached
+        values, like ``march``)."""
+        M, S = int(n_steps), int(n_slots)
+        if not (1 <= M <= 16384) or not (1 <= S <= 4096):
+            raise ValueError(f"DensityGrid.march_stop: 1 <= n_steps <= 16384 and 1 <= n_slots <= 4096, got {n_steps!r}, {n_slots!r}")
+        eps = _check_march_eps(eps, "DensityGrid.march_stop")
+        with torch.no_grad():
+            z_vals, z_stop, truncated, stopped = hb.occ_march_stop(
+                self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0,
+                rays.detach().to(torch.float32).contiguous(), None if u is None else u.detach().to(torch.float32).contiguous(), M, S, eps)
+        return z_vals, z_stop, truncated.bool(), stopped.bool()
 
     # ------------------------------------------------------------------ checkpoints
     _SCALARS = ("decay", "sigma_threshold", "dilate", "update_every", "warmup_steps")

@@ -652,7 +652,8 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
     Everything option-dependent is read from cfg, which render_rays fills once for both paths:
       cfg["march_steps"] (proposal="march"): the depths are the grid's own (nerf_occ_march: march_steps candidates, N_samples slots) and
         the chunk is ONE pass of model_c on them, compacted with the march's stop depth (the caller hands the evaluated network as
-        model_c, N_importance = 0 and the pass's noise as noise_c);
+        model_c, N_importance = 0 and the pass's noise as noise_c); with cfg["march_stop_eps"] the depths are nerf_occ_march_stop's, the
+        march that also stops on the DensityGrid's own transmittance -- nothing else of the chunk changes;
       else coarse depths (nerf_sample_coarse) and their weights: cfg["proposal"] ("grid") takes the grid's own
         (DensityGrid.proposal_weights: one launch, no network, no read-back; the evaluated network is model_c), otherwise a pass of
         model_c, which is the whole chunk when N_importance = 0;
@@ -663,10 +664,16 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
     n_c, n_f = cfg["N_samples"], cfg["N_importance"]
     dev = rays.device
     if cfg["march_steps"] is not None:
-        z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), cfg["march_steps"], n_c)
+        n_stopped = None
+        if cfg["march_stop_eps"] is not None:
+            z_m, z_stop, truncated, stopped = hb.occ_march_stop(desc, grid.density, grid.sigma_threshold if grid.outside == "evaluate" else 0.0,
+                                                                rays, rnd.get("u_march"), cfg["march_steps"], n_c, cfg["march_stop_eps"])
+            n_stopped = stopped.sum()
+        else:
+            z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), cfg["march_steps"], n_c)
         n_truncated = truncated.sum()
         raw, (rgb, disp, acc, _, _) = run_pass(rays, z_m, model_c, rnd.get("noise_c"), False, z_stop)
-        return (rgb, disp, acc, raw), None, n_truncated
+        return (rgb, disp, acc, raw), n_stopped, n_truncated
     z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
     coarse = ()
     if cfg["proposal"] is not None:
@@ -688,10 +695,12 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
 
 def _grid_stats(grid, stats, n_stopped, n_truncated):
     """grid.last_stats of one call: the passes' counts and the chain's device counters (None without the option), read back here -- after
-    the passes, which synchronised anyway -- once per call"""
-    if n_stopped is not None:
+    the passes, which synchronised anyway -- once per call (the march with a stop has both counters: one stacked read-back)"""
+    if n_stopped is not None and n_truncated is not None:
+        stats["rays_stopped"], stats["rays_truncated"] = (int(v) for v in torch.stack([n_stopped, n_truncated]).tolist())
+    elif n_stopped is not None:
         stats["rays_stopped"] = int(n_stopped.item())
-    if n_truncated is not None:
+    elif n_truncated is not None:
         stats["rays_truncated"] = int(n_truncated.item())
     grid.last_stats = stats
 
@@ -728,7 +737,8 @@ class _RenderRaysGrid(torch.autograd.Function):
     nothing saved, and the node has ONE pass, the refining one on model_c; outputs (rgb, disp, acc, raw, z_std).  cfg["early_stop_eps"]:
     z_stop is a constant of the graph, computed per sub-chunk; a stopped sample has slot -1 like a skipped one -- raw = 0, no gradient
     -- so nothing beyond slot is kept for it and the backward is unchanged.  cfg["march_steps"]: depths and stop depth are constants of
-    the graph, computed per sub-chunk; with N_importance = 0 the backward is the coarse-only one; outputs (rgb, disp, acc, raw)."""
+    the graph, computed per sub-chunk; with N_importance = 0 the backward is the coarse-only one; outputs (rgb, disp, acc, raw) --
+    cfg["march_stop_eps"] changes which kernel computes those constants and nothing of the backward."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
@@ -892,14 +902,17 @@ class _RenderRaysGrid(torch.autograd.Function):
         return lead + out_c + (_grad_views(ctx.model_f, grad_f) if wrote["f"] else none_c)
 
 
-def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal, early_stop_eps, march_steps):
+def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal, early_stop_eps, march_steps,
+                        march_stop_eps=None):
     """render_rays' checks of its grid options, in front of everything else (a refused call launches nothing, not even hb.lib()).
-    Returns (march, early_stop_eps as a float or None, march_steps as an int or None)."""
+    Returns (march, early_stop_eps as a float or None, march_steps as an int or None, march_stop_eps as a float or None)."""
     if clip_to_occupancy and occupancy is None:
         raise ValueError("render_rays: clip_to_occupancy=True needs an occupancy grid (occupancy=)")
     march = isinstance(proposal, str) and proposal == "march"
     if march_steps is not None and not march:
         raise ValueError("render_rays: march_steps belongs to proposal=\"march\"")
+    if march_stop_eps is not None and not march:
+        raise ValueError("render_rays: march_stop_eps belongs to proposal=\"march\"")
     if march:
         if occupancy is None:
             raise ValueError("render_rays: proposal=\"march\" walks an occupancy grid (occupancy=): none was given")
@@ -914,6 +927,12 @@ def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occ
         if lindisp:
             raise NotImplementedError("render_rays: proposal=\"march\" with lindisp=True is not implemented (the steps are equal in depth)")
         march_steps = int(march_steps)
+        if march_stop_eps is not None:
+            from .occupancy import DensityGrid, _check_march_eps
+            march_stop_eps = _check_march_eps(march_stop_eps, "render_rays")
+            if not isinstance(occupancy, DensityGrid):
+                raise ValueError("render_rays: march_stop_eps reads the densities of an occupancy.DensityGrid (occupancy=); "
+                                 "a plain OccupancyGrid has none")
     if early_stop_eps is not None:
         early_stop_eps = float(early_stop_eps)
         if not (0.0 < early_stop_eps < 1.0):        # (also refuses NaN)
@@ -931,7 +950,7 @@ def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occ
                              + ("none was given" if occupancy is None else "a plain OccupancyGrid has none"))
         if int(N_importance) <= 0:
             raise ValueError("render_rays: proposal=\"grid\" draws importance samples: N_importance must be > 0")
-    return march, early_stop_eps, march_steps
+    return march, early_stop_eps, march_steps, march_stop_eps
 
 
 def _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march):
@@ -1004,16 +1023,17 @@ def _result_dict(outs, retraw, coarse_first):
     return {**coarse, **fine} if coarse_first else {**fine, **coarse}
 
 
-def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal):
+def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal, march_stop_eps=None):
     """the last_stats keys the grid options add to "evaluated" and "total" (render_rays' keyword arguments, checked or not)"""
     march = isinstance(proposal, str) and proposal == "march"
     return ((("rays_hit", "rays") if clip_to_occupancy else ()) + (("rays_stopped",) if early_stop_eps is not None else ())
-            + (("rays_truncated",) if march else ()))
+            + (("rays_truncated",) if march else ()) + (("rays_stopped",) if march and march_stop_eps is not None else ()))
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None, march_steps=None):
+                *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None, march_steps=None,
+                march_stop_eps=None):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -1078,9 +1098,25 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     without), then with raw_noise_std > 0 noise_f [N, S] -- these are the ``randoms`` keys; t_rand, u and noise_c are neither drawn nor
     read.  last_stats = {"evaluated", "total" = N * S, "rays_truncated"} (rays whose emitted steps did not fit: raise N_samples +
     N_importance, or lower march_steps).  1 <= march_steps <= 16384, S <= 4096; lindisp and early_stop_eps (there are no coarse weights to
-    stop on) are refused.  ``march_steps`` without proposal="march" is refused."""
-    march, early_stop_eps, march_steps = _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal,
-                                                             early_stop_eps, march_steps)
+    stop on) are refused.  ``march_steps`` without proposal="march" is refused.
+
+    ``march_stop_eps`` (keyword-only, not in the reference; a float with 0 < eps < 1; needs proposal="march" and an
+    occupancy.DensityGrid as ``occupancy``): the march's own termination rule.  The marcher adds up the grid's densities as it walks --
+    per kept step sigma * (the step's interval) * |d|, the optical depth the compositing would give that sample if the network
+    answered what the grid holds -- and once the grid's own transmittance exp(-sum) has fallen to eps the ray stops emitting: no slot,
+    no field evaluation, no saved activation, no gradient (occupancy.DensityGrid.march_stop_reference is the definition,
+    nerf_occ_march_stop the kernel, which replaces nerf_occ_march in the call).  The slots a stop frees go to nobody; a ray that would
+    have been truncated behind its stop no longer is.  The single compacted pass with the march's z_stop, the backward (depths and
+    z_stop are constants of the graph), the draws (u_march, then noise_f) and the output keys are those of the march without the
+    option.  AN APPROXIMATION: what is dropped from the image is the NETWORK's own transmittance behind the stop.  The grid's
+    densities are a decayed running maximum per cell, so they overestimate and the grid stops early rather than late: the dropped
+    transmittance is close to eps where grid and network agree, but it is not bounded by eps (a cell whose maximum came from a thin
+    structure stops rays that pass beside it) -- hence opt-in.  A grid that was never updated has density 0 and stops nothing.
+    last_stats additionally carries "rays_stopped" (a truncated ray does not count: the slot limit bit first).  Refused: the option
+    without proposal="march", a value that is not a float in (0, 1) (bools included), a plain OccupancyGrid (it has no densities).
+    None: nothing changes -- same launches, same bits, same draws."""
+    march, early_stop_eps, march_steps, march_stop_eps = _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occupancy,
+                                                                             proposal, early_stop_eps, march_steps, march_stop_eps)
     from .dense import DenseNeRF
     nets = [network_fn] + ([network_fine] if network_fine is not None else [])
     dense = all(isinstance(m, DenseNeRF) for m in nets)         # architectures outside the fused kernels: layer by layer (dense.py)
@@ -1107,7 +1143,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             outs += ((e(3), e(), e()) if proposal is None else ()) + (e(),)
         if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
             occupancy._desc()
-            occupancy.last_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal), 0)
+            occupancy.last_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal,
+                                                                                             march_stop_eps), 0)
         return _result_dict(outs, retraw, coarse_first=False)
     rnd, std = _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march)
     cfg = dict(N_samples=int(N_samples), N_importance=n_f, lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
@@ -1132,7 +1169,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             grid_grad = False
         # what _grid_chain reads, set once for both paths; the reduced class is an inference form whose last-sample fix-up is per ray: the
         # compacted points, and gradients anyway, run on the fp16x3 products
-        cfg.update(proposal=None if march else proposal, early_stop_eps=early_stop_eps, march_steps=march_steps)
+        cfg.update(proposal=None if march else proposal, early_stop_eps=early_stop_eps, march_steps=march_steps, march_stop_eps=march_stop_eps)
         if cfg["precision"] == "fp16_fp8c":
             cfg["precision"] = "fp16x3"
         if march:       # ONE pass over all the slots: what the two paths below run as a coarse-only call on the march's depths
@@ -1194,12 +1231,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """run_nerf.py:54-66.  Injected ``randoms`` (one row per ray) are sliced with the rays, so a chunked call consumes
     the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks (with ``clip_to_occupancy``
-    its "rays_hit" / "rays" too, with ``early_stop_eps`` its "rays_stopped", with ``proposal="march"`` its "rays_truncated")."""
+    its "rays_hit" / "rays" too, with ``early_stop_eps`` its "rays_stopped", with ``proposal="march"`` its "rays_truncated" and with
+    ``march_stop_eps`` its "rays_stopped")."""
     all_ret = {}
     randoms = kwargs.pop("randoms", None)
     occ = kwargs.get("occupancy")
     occ_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(kwargs.get("clip_to_occupancy"), kwargs.get("early_stop_eps"),
-                                                                          kwargs.get("proposal")), 0)
+                                                                          kwargs.get("proposal"), kwargs.get("march_stop_eps")), 0)
     if randoms is not None:
         for k, v in randoms.items():
             if v.shape[0] != rays_flat.shape[0]:

@@ -5,27 +5,40 @@ S = 64 + 128 = 192 slots):
     tools/exp_grid_proposal.py (evaluated shares of about 0.5 / 0.25 / 0.1 of the two-network render, outside skipped), the march at
     M = 256, 512 and 1024 steps;
   * per march row the evaluated points per ray and rays_truncated (last_stats): what the sample budget is spent on;
-  * nerf_occ_march alone at 128^3 for the three M (HIP events around 100 launches).
+  * the march with march_stop_eps = 1e-3 and 1e-2 (the stop on the grid's own transmittance) at the same M, next to the
+    march_stop_eps=None rows of the same run: ms, evaluated points per ray, rays truncated and rays stopped (left out when the tree
+    under --root has no such option); with --density-scale F, because the fixture scene is a fog on which next to nothing stops,
+    the eps = 1e-2 rows once more on a copy of every grid whose densities are multiplied by F -- a stand-in for surfaces that says
+    what a stop saves in TIME only: the network is not scaled with the grid, so the image of those rows means nothing;
+  * nerf_occ_march alone at 128^3 for the three M (HIP events around 100 launches), and nerf_occ_march_stop next to it.
 Per row: ms (median of --reps alternating repetitions, min and max = the spread), the evaluated points, field and occupancy kernel ms.
 The learning rate is 0 (the optimizer does all of its work; the scene and every share stay put).
 
     python tools/exp_march.py --out profiles/r14_exp_march.json
+    python tools/exp_march.py --density-scale 16 --out profiles/r17_exp_march.json
 """
 import grid_exp as gx
 
-args = gx.parser(__doc__, steps="training steps / renders between two HIP events").parse_args()
+ap = gx.parser(__doc__, steps="training steps / renders between two HIP events")
+ap.add_argument("--density-scale", type=float, default=None,
+                help="also time march_stop_eps = 1e-2 on a copy of every grid with its densities multiplied by this (time and counts only)")
+args = ap.parse_args()
 torch, wl, npa, hb, dev = gx.load(args, "exp_march")
 S = gx.Scene(wl, npa, dev, perturb=1., target=True, records=True)
 LO, HI, R, N_RAYS, nc, nf = S.LO, S.HI, S.R, S.N_RAYS, S.nc, S.nf
 N_C, N_F = 64, 128
 MARCH_STEPS = (256, 512, 1024)
+STOP_EPS = (1e-3, 1e-2)
+HAVE_STOP = hasattr(npa.DensityGrid, "march_stop")      # (--root of a tree without the option: the rows of that tree only)
 opt_two, opt_one = S.adam(nc, nf), S.adam(nf)
 
 
 def render(grid, mode):
-    """mode: None (two networks), "grid", or the march's step count"""
+    """mode: None (two networks), "grid", the march's step count, or (step count, march_stop_eps)"""
     if mode == "grid":
         return S.render(occupancy=grid, proposal="grid")
+    if isinstance(mode, tuple):
+        return S.render(occupancy=grid, proposal="march", march_steps=mode[0], march_stop_eps=mode[1])
     if mode is not None:
         return S.render(occupancy=grid, proposal="march", march_steps=mode)
     return S.render(occupancy=grid)
@@ -56,8 +69,9 @@ def time_all(fn, configs, k, reps):
         stats = grid.last_stats
         rows[name].update(evaluated=stats["evaluated"], total=stats["total"], evaluated_per_ray=stats["evaluated"] / N_RAYS,
                           occ_kernels_ms=gx.kernel_ms(summ, "occ_"), field_ms=gx.kernel_ms(summ, ("field_", "wgrad")))
-        if "rays_truncated" in stats:
-            rows[name]["rays_truncated"] = stats["rays_truncated"]
+        for key in ("rays_truncated", "rays_stopped"):
+            if key in stats:
+                rows[name][key] = stats[key]
     return rows
 
 
@@ -76,6 +90,16 @@ for want in (0.5, 0.25, 0.1):
     configs.append((name + ", proposal=grid", g, "grid"))
     for M in MARCH_STEPS:
         configs.append((name + f", proposal=march M={M}", g, M))
+    if not HAVE_STOP:
+        continue
+    for M in MARCH_STEPS:
+        for eps in STOP_EPS:
+            configs.append((name + f", proposal=march M={M} march_stop_eps={eps:g}", g, (M, eps)))
+    if args.density_scale is not None:
+        dense = S.ball(npa.DensityGrid, radius)
+        dense.density = density * args.density_scale
+        for M in MARCH_STEPS:
+            configs.append((name + f", proposal=march M={M} march_stop_eps=0.01, grid density x {args.density_scale:g}", dense, (M, 1e-2)))
 result["train_step_4096_rays"] = time_all(step, configs, args.steps, args.reps)
 result["no_grad_render_4096_rays"] = time_all(infer, configs, args.steps, args.reps)
 g = grids[1]
@@ -89,4 +113,13 @@ for M in MARCH_STEPS:
                             rays_truncated=int(g.march(rays_rec, M, SLOTS)[2].sum()))
 kernel["note"] = "host-timed back-to-back launches (allocation of the outputs included)"
 result["march_kernel_128_cubed"] = kernel
+kernel = {}
+for M in MARCH_STEPS if HAVE_STOP else ():
+    for eps in STOP_EPS:
+        us = gx.time_launches(lambda: g.march_stop(rays_rec, M, SLOTS, eps), args.reps)
+        out = g.march_stop(rays_rec, M, SLOTS, eps)
+        kernel[f"M={M} eps={eps:g}"] = dict(us, rays=N_RAYS, slots=SLOTS, rays_truncated=int(out[2].sum()), rays_stopped=int(out[3].sum()))
+if HAVE_STOP:
+    kernel["note"] = "host-timed back-to-back launches (allocation of the outputs included)"
+    result["march_stop_kernel_128_cubed"] = kernel
 gx.emit(result, args.out)
