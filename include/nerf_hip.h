@@ -551,6 +551,30 @@ int nerf_occ_march(const NerfOccGrid* grid, const float* rays, int ray_stride, c
 int nerf_occ_march_stop(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride,
                         const float* u /* nullable: 0.5 */, int n_rays, int n_steps, int n_slots, float tau, float* z_vals,
                         float* z_stop, int* truncated, int* stopped, void* stream);
+/* ---- the march in world-space steps with a per-ray fit to the slots (additive in ABI v10):
+ * render_rays(proposal="march", march_step_size=ds, march_fit=J).  OccupancyGrid.march_step_reference (density == NULL) and
+ * DensityGrid.march_step_stop_reference (density != NULL) are the definition.  Per ray: |d| = sqrt(dx dx + dy dy + dz dz) added left to
+ * right, dz0 = step_size / |d| (one correctly rounded division).  A ray is invalid when its first eight components are not all finite,
+ * when near >= far, or when dz0 is not a finite number > 0 (d = 0): z_vals[r][:] = its own far, z_stop[r] = -inf, no flag, level[r] = 0.
+ * Level j = 0 .. fit walks with dz_j = dz0 * 2^j, for k = 0 .. n_steps - 1 (n_steps = M is the cap on candidates):
+ *   z_k     = near + (fp32(k) + u) * dz_j      one addition, one multiplication, one addition; not contracted; u == NULL: 0.5
+ *   valid_k = z_k < far                        z_k is nondecreasing in k: the valid candidates are a prefix
+ *   keep_k  = valid_k && the point o + d * z_k is occupied by nerf_occ_compact's rule
+ *   close_k = valid_k && !keep_k && k > 0 && keep_{k-1}
+ * and from there on everything is nerf_occ_march's with "k < M" read as valid_k: emission in order of k, the first min(E, S - 1) fill
+ * the row, E > S - 1 truncates with z_stop = the first candidate that did not fit, else z_stop = far, the padding holds z_stop.
+ * With a density, level j also applies nerf_occ_march_stop's rule: c_k = max(sigma_k, 0) * ((z_{k+1} - z_k) * |d|) at kept candidates,
+ * z_{k+1} = far where candidate k + 1 is not valid (or k + 1 == M); the same fixed-order prefix sum; k_stop = the first VALID k with
+ * A_k >= tau; emission is cut at k_stop; the slot limit bites first.
+ * level[r] = the smallest j at which the ray is not truncated, and the outputs are that level's; if no level fits, level[r] = fit and
+ * the ray is truncated with that level's outputs.  u is the same at every level.
+ * One wavefront per ray, rounds of 64 candidates; a ray that overflows at level j < fit starts again at j + 1 and the plain stores of the
+ * later level overwrite its row.  A wave leaves a level once its slots are full, its candidates run out or it stops.  Plain stores, no
+ * atomics: the same inputs give the same bits.  stopped must be non-NULL exactly when density is.  ray_stride >= 8;
+ * 1 <= n_steps <= 16384; 1 <= n_slots <= 4096; 0 <= fit <= 8; step_size finite and > 0; with a density tau > 0. */
+int nerf_occ_march_step(const NerfOccGrid* grid, const float* density /* nullable */, float outside_sigma, const float* rays, int ray_stride,
+                        const float* u /* nullable: 0.5 */, int n_rays, float step_size, int n_steps, int n_slots, int fit, float tau,
+                        float* z_vals, float* z_stop, int* truncated, int* level, int* stopped /* non-NULL iff density */, void* stream);
 
 #ifdef __cplusplus
 }

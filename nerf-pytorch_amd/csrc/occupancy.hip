@@ -19,6 +19,9 @@
 //                      render_rays(proposal="march").
 //   nerf_occ_march_stop : the same walk over a DensityGrid, which also adds up the grid's own optical depth and stops emitting where the
 //                      grid's transmittance has fallen to eps: render_rays(proposal="march", march_stop_eps=eps).
+//   nerf_occ_march_step : either walk in steps of one world-space length along the ray, capped at M candidates, with a per-ray fit: a
+//                      ray whose emitted steps overflow its slots walks again with the step doubled, up to `fit` times:
+//                      render_rays(proposal="march", march_step_size=ds, march_fit=J).
 // The compaction is deterministic: a count per block of OCC_TILE points, an exclusive scan of the block counts, then the
 // write -- inside a block the position of a point is a wave ballot + popcount and a prefix over the block's wave counts, so the
 // list is in stable ray-major, sample-minor order and no atomic decides anything.
@@ -720,6 +723,114 @@ __global__ __launch_bounds__(MARCH_THREADS) void occ_march_stop_kernel(GridArgs 
     }
 }
 
+// ---- nerf_occ_march_step (OccupancyGrid.march_step_reference / DensityGrid.march_step_stop_reference are the definition)
+// The march in world-space steps with a per-ray fit to the slots.  The walk of a level is occ_march_kernel's (STOP: occ_march_stop_kernel's)
+// with two differences: the candidates are z_k = near + (k + u) * dz, dz = (ds / |d|) * 2^level -- one addition, one multiplication, one
+// addition --, and a candidate counts only while z_k < far (`valid`, a ballot: z_k is nondecreasing in k, so the valid candidates are a
+// prefix and a round whose lane 63 is not valid is the ray's last).  The fit: a ray whose emitted candidates overflow its slots at a level
+// below `fit` starts again with the doubled step; the plain stores of the later level overwrite its row (ranks 0 .. S - 2 that the later
+// level does not reach are covered by the padding loop, which starts at min(base, S - 1) of the LAST level).  A ray leaves a level as
+// soon as its slots are full, its candidates run out or it stops; it leaves the kernel at the first level that fits.  Everything the
+// wave branches on is wave-uniform (ballots, the level, the round); no atomics, no LDS of its own.
+template <bool STOP>
+__global__ __launch_bounds__(MARCH_THREADS) void occ_march_step_kernel(GridArgs g, const float* __restrict__ density, float outside_sigma,
+                                                                       const float* __restrict__ rays, int ray_stride,
+                                                                       const float* __restrict__ u, int n_rays, float ds, int M, int S,
+                                                                       int fit, float tau, float* __restrict__ z_vals,
+                                                                       float* __restrict__ z_stop, int* __restrict__ truncated,
+                                                                       int* __restrict__ level, int* __restrict__ stopped) {
+    const int ray = blockIdx.x * MARCH_RAYS + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;          // (whole waves leave: the ballots and shuffles below see full waves)
+    const int lane = threadIdx.x & 63;
+    const float* r = rays + (size_t)ray * ray_stride;
+    float* zrow = z_vals + (size_t)ray * S;
+    const float near = r[6], far = r[7];
+    bool ok = near < far;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) ok = ok && fabsf(r[c]) < INFINITY;      // (a NaN fails the comparison)
+    const float dn = sqrtf(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+    const float dz0 = ds / dn;                                          // (IEEE division: hipcc's default for fp32)
+    ok = ok && dz0 > 0.0f && dz0 < INFINITY;                            // (d = 0, an overflowing |d|, a NaN: no step)
+    if (!ok) {
+        for (int j = lane; j < S; j += 64) zrow[j] = far;
+        if (lane == 0) {
+            z_stop[ray] = -INFINITY;
+            truncated[ray] = 0;
+            level[ray] = 0;
+            if (STOP) stopped[ray] = 0;
+        }
+        return;
+    }
+    const float uu = u ? u[ray] : 0.5f;
+    const int last = S - 1;
+    int lvl = 0, base, trunc, stp;
+    float stop;
+    for (;; ++lvl) {
+        const float dz = dz0 * (float)(1 << lvl);           // (exact, or +inf: then no candidate is valid)
+        base = 0; trunc = 0; stp = 0;
+        stop = far;
+        unsigned long long carry = 0ull;
+        float depth = 0.0f;             // STOP: A in front of the round's first candidate
+        bool more = true;
+        for (int k0 = 0; k0 < M && base <= last && !stp && more; k0 += 64) {
+            const int k = k0 + lane;
+            const float z = near + ((float)k + uu) * dz;    // (no contraction)
+            const bool valid = k < M && z < far;            // (a NaN fails the comparison)
+            const unsigned long long vm = __ballot(valid);
+            more = (vm >> 63) & 1ull;
+            const Pt p = sample_point(r, z);
+            const bool keep = valid && occupied(g, p);
+            const unsigned long long km = __ballot(keep);
+            unsigned long long em = km | (((km << 1) | carry) & ~km & vm);
+            carry = km >> 63;
+            unsigned long long cut = 0ull;
+            int cut_lane = 64;
+            if (STOP) {
+                float c = 0.0f;
+                if (keep) {
+                    const float z1 = near + ((float)(k + 1) + uu) * dz;
+                    const float zn = (k + 1 < M && z1 < far) ? z1 : far;
+                    const float sg = proposal_sigma(g, density, outside_sigma, p);
+                    const float dist = (zn - z) * dn;
+                    c = (sg > 0.0f ? sg : 0.0f) * dist;     // (a NaN sigma fails the comparison: 0)
+                }
+                const float incl = nerf::wave_incl_scan_add(c, lane);
+                float below = __shfl_up(incl, 1);
+                if (lane == 0) below = 0.0f;
+                cut = __ballot(valid && depth + below >= tau);
+                if (cut) {
+                    cut_lane = __ffsll((long long)cut) - 1;
+                    em &= (1ull << cut_lane) - 1ull;
+                }
+                depth = depth + __shfl(incl, 63);
+            }
+            const int rank = base + lanes_below(em);
+            const bool emit = (em >> lane) & 1ull;
+            if (emit && rank < last) zrow[rank] = z;
+            const unsigned long long hit = __ballot(emit && rank == last);
+            if (hit) {
+                stop = __shfl(z, __ffsll((long long)hit) - 1);
+                trunc = 1;
+            } else if (cut) {
+                stop = __shfl(z, cut_lane);
+                stp = 1;
+            }
+            base += __popcll(em);
+        }
+        if (!trunc || lvl >= fit) break;
+        // the next level's stores land on this level's, from other lanes of the same wave: a wave's vector stores are performed in
+        // issue order, which is what wavefront scope asks for (no instruction, the compiler keeps the order)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    }
+    for (int j = min(base, last) + lane; j < S; j += 64) zrow[j] = stop;
+    if (lane == 0) {
+        z_stop[ray] = stop;
+        truncated[ray] = trunc;
+        level[ray] = lvl;
+        if (STOP) stopped[ray] = stp;
+    }
+}
+
 int check_grid(const char* fn, const NerfOccGrid* grid, GridArgs* g) {
     if (!grid || !grid->bits) return fail_arg(fn, "null pointer");
     for (int a = 0; a < 3; ++a) {
@@ -811,6 +922,29 @@ int nerf_occ_march_stop(const NerfOccGrid* grid, const float* density, float out
     if (n_rays == 0) return 0;
     occ_march_stop_kernel<<<(unsigned)((n_rays + MARCH_RAYS - 1) / MARCH_RAYS), MARCH_THREADS, 0, (hipStream_t)stream>>>(
         g, density, outside_sigma, rays, ray_stride, u, n_rays, n_steps, n_slots, tau, z_vals, z_stop, truncated, stopped);
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_march_step(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride, const float* u,
+                        int n_rays, float step_size, int n_steps, int n_slots, int fit, float tau, float* z_vals, float* z_stop,
+                        int* truncated, int* level, int* stopped, void* stream) {
+    GridArgs g;
+    if (int rc = check_grid(__func__, grid, &g)) return rc;
+    REQUIRE(rays && z_vals && z_stop && truncated && level, "null pointer");
+    REQUIRE((density != nullptr) == (stopped != nullptr), "null pointer (density and stopped come together: the stop form, or neither)");
+    REQUIRE(ray_stride >= 8 && n_rays >= 0 && n_steps >= 1 && n_steps <= 16384 && n_slots >= 1 && n_slots <= 4096,
+            "bad size (ray records need 8 columns, 1..16384 steps, 1..4096 slots)");
+    REQUIRE(fit >= 0 && fit <= 8, "bad fit (0..8 doublings of the step)");
+    REQUIRE(step_size > 0.0f && step_size < INFINITY, "bad step_size (finite and > 0)");        // (a NaN fails the comparison)
+    if (density) REQUIRE(tau > 0.0f, "bad threshold (tau = -ln(eps) must be > 0)");
+    if (n_rays == 0) return 0;
+    const unsigned blocks = (unsigned)((n_rays + MARCH_RAYS - 1) / MARCH_RAYS);
+    if (density)
+        occ_march_step_kernel<true><<<blocks, MARCH_THREADS, 0, (hipStream_t)stream>>>(
+            g, density, outside_sigma, rays, ray_stride, u, n_rays, step_size, n_steps, n_slots, fit, tau, z_vals, z_stop, truncated, level, stopped);
+    else
+        occ_march_step_kernel<false><<<blocks, MARCH_THREADS, 0, (hipStream_t)stream>>>(
+            g, nullptr, 0.0f, rays, ray_stride, u, n_rays, step_size, n_steps, n_slots, fit, 0.0f, z_vals, z_stop, truncated, level, nullptr);
     return done(__func__, hipGetLastError());
 }
 

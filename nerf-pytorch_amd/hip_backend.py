@@ -97,6 +97,7 @@ def _declare(lib):
         "nerf_occ_compact_stop": (i, [p, p, i, p, p, i, i, p, p, p, p, p]),
         "nerf_occ_march": (i, [p, p, i, p, i, i, i, p, p, p, p]),
         "nerf_occ_march_stop": (i, [p, p, f, p, i, p, i, i, i, f, p, p, p, p, p]),
+        "nerf_occ_march_step": (i, [p, p, f, p, i, p, i, f, i, i, i, f, p, p, p, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -123,7 +124,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_sample_ray_views", "nerf_ray_pose_grad",
            "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate",
            "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span", "nerf_occ_proposal_weights",
-           "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march", "nerf_occ_march_stop",
+           "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march", "nerf_occ_march_stop", "nerf_occ_march_step",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
 
 
@@ -1300,6 +1301,35 @@ def occ_march_stop(desc, density, outside_sigma, rays, u, n_steps, n_slots, eps)
                                          _ptr(u, "u", True), n, M, S, march_stop_threshold(eps), _ptr(z_vals), _ptr(z_stop),
                                          truncated.data_ptr(), stopped.data_ptr(), _stream()), "nerf_occ_march_stop")
     return z_vals, z_stop, truncated, stopped
+
+
+def occ_march_step(desc, density, outside_sigma, rays, u, step_size, n_steps, n_slots, fit=0, eps=None):
+    """nerf_occ_march_step: (z_vals fp32 [n, n_slots], z_stop fp32 [n], truncated int32 [n], level int32 [n], stopped int32 [n] or None) of
+    rays [n, >= 8] -- the march in steps of step_size along the ray (a length in the scene: the depth step is step_size / |d|), at most
+    n_steps candidates in front of far, and per ray the step doubled up to `fit` times until the emitted steps fit the slots (level: how
+    often).  density None (eps None): occ_march's rule per level, stopped is None; density fp32 [cells] with eps: occ_march_stop's"""
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise NerfHipError("occ_march_step: rays [n, >= 8] (o, d, near, far, ...)")
+    n, stride = rays.shape
+    M, S = int(n_steps), int(n_slots)
+    if u is not None and tuple(u.shape) != (n,):
+        raise NerfHipError("occ_march_step: u must hold one offset per ray")
+    if (density is None) != (eps is None):
+        raise NerfHipError("occ_march_step: density and eps come together (the stop form) or not at all")
+    if density is not None and density.numel() != desc.res[0] * desc.res[1] * desc.res[2]:
+        raise NerfHipError("occ_march_step: one density per cell of the grid")
+    z_vals = torch.empty((n, S), dtype=torch.float32, device=rays.device)
+    z_stop = torch.empty(n, dtype=torch.float32, device=rays.device)
+    truncated = torch.empty(n, dtype=torch.int32, device=rays.device)
+    level = torch.empty(n, dtype=torch.int32, device=rays.device)
+    stopped = None if density is None else torch.empty(n, dtype=torch.int32, device=rays.device)
+    with _timed("occ_march_step_kernel", 0.0, (4.0 * S + (52.0 if stopped is not None else 48.0)) * n):
+        _check(lib().nerf_occ_march_step(ctypes.byref(desc), _ptr(density, "density", True), float(outside_sigma), _ptr(rays, "rays"), stride,
+                                         _ptr(u, "u", True), n, float(step_size), M, S, int(fit),
+                                         0.0 if eps is None else march_stop_threshold(eps), _ptr(z_vals), _ptr(z_stop),
+                                         truncated.data_ptr(), level.data_ptr(), None if stopped is None else stopped.data_ptr(), _stream()),
+               "nerf_occ_march_step")
+    return z_vals, z_stop, truncated, level, stopped
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

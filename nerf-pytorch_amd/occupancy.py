@@ -56,6 +56,22 @@ def _check_march_eps(eps, who):
     return float(eps)
 
 
+def _check_march_step(step_size, fit, who):
+    """(step_size as a float, fit as an int) of the world-space march: a finite real number > 0 and an int in 0..8, bools refused"""
+    real = not isinstance(step_size, (bool, np.bool_)) and isinstance(step_size, (int, float, np.integer, np.floating))
+    if real:
+        try:
+            with np.errstate(all="ignore"):
+                real = 0.0 < float(np.float32(step_size)) < float("inf")       # (the kernel's step is fp32(step_size); also refuses NaN)
+        except OverflowError:
+            real = False
+    if not real:
+        raise ValueError(f"{who}: march_step_size must be a finite real number > 0 (as an fp32 value), got {step_size!r}")
+    if isinstance(fit, (bool, np.bool_)) or not isinstance(fit, (int, np.integer)) or not (0 <= int(fit) <= 8):
+        raise ValueError(f"{who}: march_fit must be an int with 0 <= march_fit <= 8, got {fit!r}")
+    return float(step_size), int(fit)
+
+
 def stop_depth_reference(z_vals, weights, eps):
     """The definition of the stop depth of render_rays(early_stop_eps=eps), in numpy (tensors of any device; fp32 [N] on z_vals' device).
 
@@ -106,7 +122,9 @@ class OccupancyGrid:
     (``ray_span_reference`` is the definition), which render_rays(clip_to_occupancy=True) samples instead of [near, far].
     ``march`` gives it a third: the depths themselves, per ray the equal steps over [near, far] that fall in occupied cells
     (``march_reference`` is the definition) -- render_rays(proposal="march"), whose last_stats carry {"rays_truncated"} (and, with
-    march_stop_eps over a DensityGrid, {"rays_stopped"})."""
+    march_stop_eps over a DensityGrid, {"rays_stopped"}).  ``march_step`` is the march in steps of one length in the scene, with the
+    step doubled per ray until its emitted steps fit the slots (``march_step_reference`` is the definition) --
+    render_rays(proposal="march", march_step_size=ds, march_fit=J), whose last_stats carry {"rays_refit"} when J > 0."""
 
     def __init__(self, lo, hi, resolution, outside="evaluate", device=None):
         if outside not in _OUTSIDE:
@@ -298,6 +316,122 @@ class OccupancyGrid:
                                                      None if u is None else u.detach().to(torch.float32).contiguous(), M, S)
         return z_vals, z_stop, truncated.bool()
 
+    # ------------------------------------------------------------------ ray marching in world-space steps, fitted to the slots
+    def _march_step_level(self, r, ok, uu, dz, dn, M, S, tau):
+        """one level of the world-space march for the valid rays' step dz [N, 1] (plain torch): (z_vals, z_stop, truncated, stopped).
+        tau None: the plain rule; else a DensityGrid's stop rule on top.  Candidates behind the last one that is valid on ANY ray are
+        not built: they emit nothing, add nothing to an optical depth and cut nothing."""
+        dev = r.device
+        N = r.shape[0]
+        near, far = r[:, 6:7], r[:, 7:8]
+        kf = torch.arange(M, dtype=torch.float32, device=dev)[None, :]
+        z = near + (kf + uu) * dz
+        valid = (z < far) & ok[:, None]
+        cols = valid.any(0).nonzero()
+        K = min(M, (int(cols.max()) + 2) if cols.numel() else 1)       # (one column more: the candidate behind the last valid one)
+        z, valid = z[:, :K], valid[:, :K]
+        pts = r[:, None, 0:3] + r[:, None, 3:6] * z[:, :, None]
+        keep = self.occupied(pts) & valid
+        before = torch.cat([torch.zeros_like(keep[:, :1]), keep[:, :-1]], -1)
+        emit = keep | (before & ~keep & valid)
+        has_cut = torch.zeros(N, dtype=torch.bool, device=dev)
+        k_stop = torch.full((N,), K, dtype=torch.int64, device=dev)
+        if tau is not None:
+            valid_next = torch.cat([valid[:, 1:], torch.zeros_like(valid[:, :1])], -1)
+            z_next = torch.where(valid_next, torch.cat([z[:, 1:], far], -1), far.expand(-1, K))
+            sigma = self.proposal_sigma(pts)
+            sigma = torch.where(sigma > 0, sigma, torch.zeros_like(sigma))
+            c = torch.where(keep, sigma * ((z_next - z) * dn), torch.zeros_like(z))
+            rounds = (K + 63) // 64         # the exclusive prefix sum in the order of the kernel's wave scan
+            incl = torch.cat([c, torch.zeros((N, rounds * 64 - K), dtype=torch.float32, device=dev)], -1).view(N, rounds, 64)
+            for s in (1, 2, 4, 8, 16, 32):
+                incl = torch.cat([incl[..., :s], incl[..., s:] + incl[..., :-s]], -1)
+            base = torch.zeros((N, rounds), dtype=torch.float32, device=dev)
+            for j in range(1, rounds):
+                base[:, j] = base[:, j - 1] + incl[:, j - 1, 63]
+            A = (base[:, :, None] + torch.cat([torch.zeros_like(incl[..., :1]), incl[..., :-1]], -1)).view(N, rounds * 64)[:, :K]
+            cut = (A >= tau) & valid                        # (a NaN never is)
+            has_cut = cut.any(-1)
+            k_stop = torch.where(has_cut, cut.to(torch.uint8).argmax(-1), k_stop)
+            emit = emit & (torch.arange(K, device=dev)[None, :] < k_stop[:, None])
+        rank = torch.cumsum(emit.to(torch.int64), -1) - 1
+        truncated = emit.sum(-1) > S - 1
+        stopped = has_cut & ~truncated
+        first_out = emit & (rank == S - 1)          # (at most one per row)
+        z_stop = torch.where(truncated, z.gather(1, first_out.to(torch.uint8).argmax(-1, keepdim=True))[:, 0], r[:, 7])
+        z_stop = torch.where(stopped, z.gather(1, k_stop.clamp(max=K - 1)[:, None])[:, 0], z_stop)
+        z_stop = torch.where(ok, z_stop, torch.full_like(z_stop, float("-inf")))
+        z_vals = torch.where(ok, z_stop, r[:, 7])[:, None].repeat(1, S)
+        rows, cols = (emit & (rank < S - 1)).nonzero(as_tuple=True)
+        z_vals[rows, rank[rows, cols]] = z[rows, cols]
+        return z_vals, z_stop, truncated, stopped
+
+    def _march_step_levels(self, who, rays, u, step_size, n_steps, n_slots, fit, tau):
+        M, S = int(n_steps), int(n_slots)
+        if M < 1 or S < 1:
+            raise ValueError(f"{who}: n_steps >= 1 and n_slots >= 1")
+        if rays.dim() != 2 or rays.shape[1] < 8:
+            raise ValueError(f"{who}: rays [N, >= 8] (o, d, near, far, ...)")
+        step_size, fit = _check_march_step(step_size, fit, who)
+        dev = rays.device
+        r = rays.detach()[:, :8].to(torch.float32)
+        N = r.shape[0]
+        d = r[:, 3:6]
+        # the correctly rounded fp32 square root, taken through float64 (53 >= 2 * 24 + 2 bits: rounding twice is rounding once): a torch
+        # build's own fp32 sqrt may be a vector-library routine that is an ulp off on some CPUs, and the step, unlike an optical depth,
+        # puts that ulp into every depth
+        dn = torch.sqrt((d[:, 0:1] * d[:, 0:1] + d[:, 1:2] * d[:, 1:2] + d[:, 2:3] * d[:, 2:3]).to(torch.float64)).to(torch.float32)
+        dz0 = torch.tensor(step_size, dtype=torch.float32, device=dev) / dn
+        ok = torch.isfinite(r).all(-1) & (r[:, 6] < r[:, 7]) & (dz0[:, 0] > 0) & torch.isfinite(dz0[:, 0])
+        uu = torch.full((N, 1), 0.5, dtype=torch.float32, device=dev) if u is None else u.detach().to(device=dev, dtype=torch.float32).reshape(N, 1)
+        out = list(self._march_step_level(r, ok, uu, dz0, dn, M, S, tau))
+        level = torch.zeros(N, dtype=torch.int32, device=dev)
+        for j in range(1, fit + 1):
+            again = out[2].nonzero()[:, 0]          # the rays still truncated walk again with the step doubled
+            if again.numel() == 0:
+                break
+            dz = dz0[again] * torch.tensor(float(1 << j), dtype=torch.float32, device=dev)
+            nxt = self._march_step_level(r[again], ok[again], uu[again], dz, dn[again], M, S, tau)
+            for a, b in zip(out, nxt):
+                a[again] = b
+            level[again] = j
+        return out[0], out[1], out[2], level, out[3]
+
+    def march_step_reference(self, rays, u, step_size, n_steps, n_slots, fit=0):
+        """The definition of the depths of render_rays(proposal="march", march_step_size=ds, march_fit=J), in plain torch (any device):
+        rays [N, >= 8], u fp32 [N] in [0, 1) or None (0.5) -> (z_vals fp32 [N, S], z_stop fp32 [N], truncated bool [N], level int32 [N]);
+        M = n_steps is the cap on candidates per ray, S = n_slots, ds = fp32(step_size) a length in the scene, J = fit.
+
+        Per ray: dn = sqrt(dx dx + dy dy + dz dz), added left to right (march_stop_reference's expression); dz0 = ds / dn, one correctly
+        rounded division.  The ray is invalid when its first eight components are not all finite, when near >= far, or when dz0 is not a
+        finite number > 0 (d = 0 among them); an invalid ray emits nothing: its row is its own far, z_stop = -inf, no flag, level 0.
+        Level j = 0 .. J: dz_j = dz0 * 2^j; candidates k = 0 .. M - 1 at z_k = near + (fp32(k) + u) * dz_j (one addition, one
+        multiplication, one addition, not contracted); valid_k = z_k < far (z_k is nondecreasing in k: a prefix); keep_k = valid_k and
+        occupied(o + d * z_k); close_k = valid_k and not keep_k and k > 0 and keep_{k-1}.  From here on everything is march_reference's
+        with "k < M" read as valid_k: the emitted candidates in order of k, the first min(E, S - 1) of them fill the row, E > S - 1
+        means truncated with z_stop the first candidate that did not fit, else z_stop = far; padding slots hold z_stop.
+        The ray's level is the smallest j at which it is not truncated and its outputs are that level's; if no level fits, the level
+        is J and the ray is truncated.  u is the same at every level.
+
+        With |d| = 1, near = 0 and a power-of-two geometry (ds * M = far, all of them powers of two) the level-0 depths equal
+        march_reference's bit for bit: (k + u) * ds and (k + u) / M * far are then the same exact scalings."""
+        z, z_stop, tr, level, _ = self._march_step_levels("march_step_reference", rays, u, step_size, n_steps, n_slots, fit, None)
+        return z, z_stop, tr, level
+
+    def march_step(self, rays, step_size, n_steps, n_slots, fit=0, u=None):
+        """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N], level int32 [N]) for rays [N, >= 8] on the GPU
+        (nerf_occ_march_step): ``march_step_reference`` bit for bit.  Constants of the graph (computed without gradients from detached
+        values, like ``march``)."""
+        M, S = int(n_steps), int(n_slots)
+        if not (1 <= M <= 16384) or not (1 <= S <= 4096):
+            raise ValueError(f"OccupancyGrid.march_step: 1 <= n_steps <= 16384 and 1 <= n_slots <= 4096, got {n_steps!r}, {n_slots!r}")
+        step_size, fit = _check_march_step(step_size, fit, "OccupancyGrid.march_step")
+        with torch.no_grad():
+            z_vals, z_stop, truncated, level, _ = hb.occ_march_step(self._desc(), None, 0.0, rays.detach().to(torch.float32).contiguous(),
+                                                                    None if u is None else u.detach().to(torch.float32).contiguous(),
+                                                                    step_size, M, S, fit)
+        return z_vals, z_stop, truncated.bool(), level
+
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):
         return {"lo": torch.tensor(self.lo), "hi": torch.tensor(self.hi), "resolution": torch.tensor(self.resolution, dtype=torch.int64),
@@ -385,7 +519,8 @@ class DensityGrid(OccupancyGrid):
     The densities have a second reader: render_rays(..., occupancy=grid, proposal="grid") draws its importance samples from the
     compositing weights of ``proposal_sigma`` at the coarse depths (``proposal_weights``) and evaluates one network only.
     And a third: ``march_stop`` is ``march`` that adds the densities up as it walks and stops emitting where the grid's own
-    transmittance has fallen to eps (``march_stop_reference`` is the definition) -- render_rays(proposal="march", march_stop_eps=eps)."""
+    transmittance has fallen to eps (``march_stop_reference`` is the definition) -- render_rays(proposal="march", march_stop_eps=eps);
+    ``march_step_stop`` is the same rule on the world-space march (``march_step_stop_reference``)."""
 
     def __init__(self, lo, hi, resolution, outside="evaluate", device=None, decay=0.95, sigma_threshold=0.01, dilate=0, update_every=16,
                  warmup_steps=256):
@@ -586,6 +721,35 @@ class DensityGrid(OccupancyGrid):
                 self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0,
                 rays.detach().to(torch.float32).contiguous(), None if u is None else u.detach().to(torch.float32).contiguous(), M, S, eps)
         return z_vals, z_stop, truncated.bool(), stopped.bool()
+
+    # ------------------------------------------------------------------ the world-space march with the stop
+    def march_step_stop_reference(self, rays, u, step_size, n_steps, n_slots, eps, fit=0):
+        """The definition of the depths of render_rays(proposal="march", march_step_size=ds, march_stop_eps=eps, march_fit=J), in plain
+        torch (any device): ``march_step_reference``'s outputs plus stopped bool [N].
+
+        Every level of ``march_step_reference`` also applies ``march_stop_reference``'s rule unchanged: c_k = max(sigma_k, 0) *
+        ((z_{k+1} - z_k) * dn) at kept candidates, z_{k+1} = far where candidate k + 1 is not valid; the exclusive prefix sum A in the
+        fixed wave order (rounds of 64, the Hillis-Steele inclusive scan over d = 1 .. 32, a running base); k_stop = the first valid k
+        with A_k >= tau; emission is cut at k_stop; the slot limit bites first.  The level is the smallest at which the ray is not
+        truncated, so a stop can spare a ray a doubling.  With an all-zero density the first four outputs are march_step_reference's and
+        nothing stops."""
+        tau = torch.tensor(hb.march_stop_threshold(_check_march_eps(eps, "march_step_stop_reference")), dtype=torch.float32, device=rays.device)
+        return self._march_step_levels("march_step_stop_reference", rays, u, step_size, n_steps, n_slots, fit, tau)
+
+    def march_step_stop(self, rays, step_size, n_steps, n_slots, eps, fit=0, u=None):
+        """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N], level int32 [N], stopped bool [N]) for rays [N, >= 8] on the
+        GPU (nerf_occ_march_step with the densities): ``march_step_stop_reference`` bit for bit.  Constants of the graph."""
+        M, S = int(n_steps), int(n_slots)
+        if not (1 <= M <= 16384) or not (1 <= S <= 4096):
+            raise ValueError(f"DensityGrid.march_step_stop: 1 <= n_steps <= 16384 and 1 <= n_slots <= 4096, got {n_steps!r}, {n_slots!r}")
+        step_size, fit = _check_march_step(step_size, fit, "DensityGrid.march_step_stop")
+        eps = _check_march_eps(eps, "DensityGrid.march_step_stop")
+        with torch.no_grad():
+            z_vals, z_stop, truncated, level, stopped = hb.occ_march_step(
+                self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0,
+                rays.detach().to(torch.float32).contiguous(), None if u is None else u.detach().to(torch.float32).contiguous(),
+                step_size, M, S, fit, eps)
+        return z_vals, z_stop, truncated.bool(), level, stopped.bool()
 
     # ------------------------------------------------------------------ checkpoints
     _SCALARS = ("decay", "sigma_threshold", "dilate", "update_every", "warmup_steps")

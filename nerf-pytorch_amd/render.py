@@ -653,19 +653,30 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
       cfg["march_steps"] (proposal="march"): the depths are the grid's own (nerf_occ_march: march_steps candidates, N_samples slots) and
         the chunk is ONE pass of model_c on them, compacted with the march's stop depth (the caller hands the evaluated network as
         model_c, N_importance = 0 and the pass's noise as noise_c); with cfg["march_stop_eps"] the depths are nerf_occ_march_stop's, the
-        march that also stops on the DensityGrid's own transmittance -- nothing else of the chunk changes;
+        march that also stops on the DensityGrid's own transmittance -- nothing else of the chunk changes (cfg["march_step_size"]: below);
       else coarse depths (nerf_sample_coarse) and their weights: cfg["proposal"] ("grid") takes the grid's own
         (DensityGrid.proposal_weights: one launch, no network, no read-back; the evaluated network is model_c), otherwise a pass of
         model_c, which is the whole chunk when N_importance = 0;
       cfg["early_stop_eps"]: the coarse weights give one stop depth per ray (nerf_occ_stop_depth), with which the refining pass compacts;
       nerf_sample_fine, and the refining pass on model_f (model_c without one).
     One host synchronisation per pass and none of its own.  Returns the output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std])
-    and the device counters (stopped rays, truncated rays; None without the option), which the caller reads back after its passes."""
+    and the device counters (stopped rays, truncated rays, refit rays; None without the option), which the caller reads back after its
+    passes.  cfg["march_step_size"] (with cfg["march_fit"]): the march's depths are nerf_occ_march_step's -- steps of one length in the
+    scene, march_steps the cap on candidates, the step doubled per ray until it fits the slots -- and nothing else of the chunk changes."""
     n_c, n_f = cfg["N_samples"], cfg["N_importance"]
     dev = rays.device
     if cfg["march_steps"] is not None:
-        n_stopped = None
-        if cfg["march_stop_eps"] is not None:
+        n_stopped = n_refit = None
+        if cfg["march_step_size"] is not None:      # world-space steps, march_steps is the cap: one kernel for both forms
+            dens = cfg["march_stop_eps"] is not None
+            z_m, z_stop, truncated, level, stopped = hb.occ_march_step(
+                desc, grid.density if dens else None, grid.sigma_threshold if dens and grid.outside == "evaluate" else 0.0, rays,
+                rnd.get("u_march"), cfg["march_step_size"], cfg["march_steps"], n_c, cfg["march_fit"], cfg["march_stop_eps"])
+            if dens:
+                n_stopped = stopped.sum()
+            if cfg["march_fit"] > 0:
+                n_refit = (level > 0).sum()
+        elif cfg["march_stop_eps"] is not None:
             z_m, z_stop, truncated, stopped = hb.occ_march_stop(desc, grid.density, grid.sigma_threshold if grid.outside == "evaluate" else 0.0,
                                                                 rays, rnd.get("u_march"), cfg["march_steps"], n_c, cfg["march_stop_eps"])
             n_stopped = stopped.sum()
@@ -673,7 +684,7 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
             z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), cfg["march_steps"], n_c)
         n_truncated = truncated.sum()
         raw, (rgb, disp, acc, _, _) = run_pass(rays, z_m, model_c, rnd.get("noise_c"), False, z_stop)
-        return (rgb, disp, acc, raw), n_stopped, n_truncated
+        return (rgb, disp, acc, raw), n_stopped, n_truncated, n_refit
     z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
     coarse = ()
     if cfg["proposal"] is not None:
@@ -681,7 +692,7 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
     else:
         raw_c, (rgb_c, disp_c, acc_c, w_c, _) = run_pass(rays, z_c, model_c, rnd.get("noise_c"), n_f > 0, None)
         if n_f <= 0:
-            return (rgb_c, disp_c, acc_c, raw_c), None, None
+            return (rgb_c, disp_c, acc_c, raw_c), None, None, None
         coarse = (rgb_c, disp_c, acc_c)
     z_stop = n_stopped = None
     if cfg["early_stop_eps"] is not None:
@@ -690,18 +701,18 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
     u = rnd.get("u")
     z_f, z_std, _ = hb.sample_fine(z_c, w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
     raw_f, (rgb_f, disp_f, acc_f, _, _) = run_pass(rays, z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), False, z_stop)
-    return (rgb_f, disp_f, acc_f, raw_f) + coarse + (z_std,), n_stopped, None
+    return (rgb_f, disp_f, acc_f, raw_f) + coarse + (z_std,), n_stopped, None, None
 
 
-def _grid_stats(grid, stats, n_stopped, n_truncated):
+def _grid_stats(grid, stats, n_stopped, n_truncated, n_refit=None):
     """grid.last_stats of one call: the passes' counts and the chain's device counters (None without the option), read back here -- after
-    the passes, which synchronised anyway -- once per call (the march with a stop has both counters: one stacked read-back)"""
-    if n_stopped is not None and n_truncated is not None:
-        stats["rays_stopped"], stats["rays_truncated"] = (int(v) for v in torch.stack([n_stopped, n_truncated]).tolist())
-    elif n_stopped is not None:
-        stats["rays_stopped"] = int(n_stopped.item())
-    elif n_truncated is not None:
-        stats["rays_truncated"] = int(n_truncated.item())
+    the passes, which synchronised anyway -- once per call (a march with a stop or a fit has several counters: one stacked read-back)"""
+    counters = [(k_, v) for k_, v in (("rays_stopped", n_stopped), ("rays_truncated", n_truncated), ("rays_refit", n_refit)) if v is not None]
+    if len(counters) == 1:
+        stats[counters[0][0]] = int(counters[0][1].item())
+    elif counters:
+        for (k_, _), v in zip(counters, torch.stack([v for _, v in counters]).tolist()):
+            stats[k_] = int(v)
     grid.last_stats = stats
 
 
@@ -711,8 +722,8 @@ def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid):
     Returns the chain's output tuple."""
     desc = grid._desc()
     stats = {"evaluated": 0, "total": 0}
-    outs, n_stopped, n_truncated = _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, partial(_grid_pass, cfg, desc, stats=stats))
-    _grid_stats(grid, stats, n_stopped, n_truncated)
+    outs, *counters = _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, partial(_grid_pass, cfg, desc, stats=stats))
+    _grid_stats(grid, stats, *counters)
     return outs
 
 
@@ -738,7 +749,8 @@ class _RenderRaysGrid(torch.autograd.Function):
     z_stop is a constant of the graph, computed per sub-chunk; a stopped sample has slot -1 like a skipped one -- raw = 0, no gradient
     -- so nothing beyond slot is kept for it and the backward is unchanged.  cfg["march_steps"]: depths and stop depth are constants of
     the graph, computed per sub-chunk; with N_importance = 0 the backward is the coarse-only one; outputs (rgb, disp, acc, raw) --
-    cfg["march_stop_eps"] changes which kernel computes those constants and nothing of the backward."""
+    cfg["march_stop_eps"], cfg["march_step_size"] and cfg["march_fit"] change which kernel computes those constants and nothing of the
+    backward."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
@@ -763,24 +775,26 @@ class _RenderRaysGrid(torch.autograd.Function):
         LAST_BACKWARD_PLAN = ("resident sub-chunks" if len(tiles) > 1 else "one launch", n, sub)
         stats = {"evaluated": 0, "total": 0}
         budget = {"rays_grad": rays_grad, "resident": 0, "rays": n}
-        n_stopped, n_truncated = [], []
+        n_stopped, n_truncated, n_refit = [], [], []
         parts, outs = [], []
         try:
             for lo, hi in tiles:
                 rnd_t = rnd if len(tiles) == 1 else {k_: v[lo:hi] for k_, v in rnd.items()}
                 parts.append([])
-                out, stopped, truncated = _grid_chain(cfg, desc, grid, rays[lo:hi], rnd_t, model_c, model_f,
-                                                      partial(_grid_pass, cfg, desc, stats=stats, passes=parts[-1], budget=budget))
+                out, stopped, truncated, refit = _grid_chain(cfg, desc, grid, rays[lo:hi], rnd_t, model_c, model_f,
+                                                             partial(_grid_pass, cfg, desc, stats=stats, passes=parts[-1], budget=budget))
                 outs.append(out)
                 n_stopped += [] if stopped is None else [stopped]
                 n_truncated += [] if truncated is None else [truncated]
+                n_refit += [] if refit is None else [refit]
         except BaseException:
             for passes in parts:
                 for p in passes:
                     for k_ in ("slot", "act", "rec"):
                         hb.WORKSPACE.give(p.get(k_))
             raise
-        _grid_stats(grid, stats, torch.stack(n_stopped).sum() if n_stopped else None, torch.stack(n_truncated).sum() if n_truncated else None)
+        _grid_stats(grid, stats, torch.stack(n_stopped).sum() if n_stopped else None, torch.stack(n_truncated).sum() if n_truncated else None,
+                    torch.stack(n_refit).sum() if n_refit else None)
         if prec in ("fp16x3", "fp16x3w"):       # the fp16 split's range guard rail sees the compacted passes' saved activations
             for passes in parts:
                 acts = [(p["act"], 1) for p in passes if p["act"] is not None]
@@ -903,9 +917,10 @@ class _RenderRaysGrid(torch.autograd.Function):
 
 
 def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal, early_stop_eps, march_steps,
-                        march_stop_eps=None):
+                        march_stop_eps=None, march_step_size=None, march_fit=0):
     """render_rays' checks of its grid options, in front of everything else (a refused call launches nothing, not even hb.lib()).
-    Returns (march, early_stop_eps as a float or None, march_steps as an int or None, march_stop_eps as a float or None)."""
+    Returns (march, early_stop_eps as a float or None, march_steps as an int or None, march_stop_eps as a float or None,
+    march_step_size as a float or None, march_fit as an int)."""
     if clip_to_occupancy and occupancy is None:
         raise ValueError("render_rays: clip_to_occupancy=True needs an occupancy grid (occupancy=)")
     march = isinstance(proposal, str) and proposal == "march"
@@ -913,6 +928,11 @@ def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occ
         raise ValueError("render_rays: march_steps belongs to proposal=\"march\"")
     if march_stop_eps is not None and not march:
         raise ValueError("render_rays: march_stop_eps belongs to proposal=\"march\"")
+    if march_step_size is not None and not march:
+        raise ValueError("render_rays: march_step_size belongs to proposal=\"march\"")
+    fit_off = march_fit is None or (not isinstance(march_fit, (bool, np.bool_)) and isinstance(march_fit, (int, np.integer)) and int(march_fit) == 0)
+    if not fit_off and not march:
+        raise ValueError("render_rays: march_fit belongs to proposal=\"march\"")
     if march:
         if occupancy is None:
             raise ValueError("render_rays: proposal=\"march\" walks an occupancy grid (occupancy=): none was given")
@@ -927,6 +947,12 @@ def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occ
         if lindisp:
             raise NotImplementedError("render_rays: proposal=\"march\" with lindisp=True is not implemented (the steps are equal in depth)")
         march_steps = int(march_steps)
+        if march_step_size is not None or not fit_off:
+            from .occupancy import _check_march_step
+            if march_step_size is None:
+                _check_march_step(1.0, march_fit, "render_rays")
+                raise ValueError("render_rays: march_fit doubles the world-space step of a ray: it needs march_step_size")
+            march_step_size, march_fit = _check_march_step(march_step_size, march_fit, "render_rays")
         if march_stop_eps is not None:
             from .occupancy import DensityGrid, _check_march_eps
             march_stop_eps = _check_march_eps(march_stop_eps, "render_rays")
@@ -950,7 +976,7 @@ def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occ
                              + ("none was given" if occupancy is None else "a plain OccupancyGrid has none"))
         if int(N_importance) <= 0:
             raise ValueError("render_rays: proposal=\"grid\" draws importance samples: N_importance must be > 0")
-    return march, early_stop_eps, march_steps, march_stop_eps
+    return march, early_stop_eps, march_steps, march_stop_eps, march_step_size, 0 if fit_off else int(march_fit)
 
 
 def _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march):
@@ -1023,17 +1049,19 @@ def _result_dict(outs, retraw, coarse_first):
     return {**coarse, **fine} if coarse_first else {**fine, **coarse}
 
 
-def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal, march_stop_eps=None):
+def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal, march_stop_eps=None, march_fit=0):
     """the last_stats keys the grid options add to "evaluated" and "total" (render_rays' keyword arguments, checked or not)"""
     march = isinstance(proposal, str) and proposal == "march"
+    refit = march and not isinstance(march_fit, (bool, np.bool_)) and isinstance(march_fit, (int, np.integer)) and march_fit > 0
     return ((("rays_hit", "rays") if clip_to_occupancy else ()) + (("rays_stopped",) if early_stop_eps is not None else ())
-            + (("rays_truncated",) if march else ()) + (("rays_stopped",) if march and march_stop_eps is not None else ()))
+            + (("rays_truncated",) if march else ()) + (("rays_stopped",) if march and march_stop_eps is not None else ())
+            + (("rays_refit",) if refit else ()))
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
                 *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None, march_steps=None,
-                march_stop_eps=None):
+                march_stop_eps=None, march_step_size=None, march_fit=0):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -1114,9 +1142,26 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     structure stops rays that pass beside it) -- hence opt-in.  A grid that was never updated has density 0 and stops nothing.
     last_stats additionally carries "rays_stopped" (a truncated ray does not count: the slot limit bit first).  Refused: the option
     without proposal="march", a value that is not a float in (0, 1) (bools included), a plain OccupancyGrid (it has no densities).
-    None: nothing changes -- same launches, same bits, same draws."""
-    march, early_stop_eps, march_steps, march_stop_eps = _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occupancy,
-                                                                             proposal, early_stop_eps, march_steps, march_stop_eps)
+    None: nothing changes -- same launches, same bits, same draws.
+
+    ``march_step_size`` (keyword-only, not in the reference; a finite real number > 0; needs proposal="march") with ``march_fit``
+    (keyword-only; an int in 0..8, default 0): the march in steps of ONE LENGTH IN THE SCENE, fitted per ray to the slots.  Without it
+    a ray's step is (far - near) / march_steps in depth: its length in the scene changes with |d| (rays_d is not normalised), with near
+    / far and with clip_to_occupancy.  With march_step_size=ds every ray steps ds along its direction -- dz = ds / |d| in depth, from
+    near + u dz on, while z < far -- and march_steps, still required, is the cap on candidates per ray; "half a cell of a 128^3 grid"
+    is said once.  march_fit=J lets a ray whose emitted steps do not fit its S slots walk again with the step doubled, up to J times:
+    the slot limit then coarsens a ray instead of cutting off what lies behind its first cells; a ray that fits at no level keeps level
+    J's depths and stays truncated (occupancy.OccupancyGrid.march_step_reference is the definition, with march_stop_eps
+    DensityGrid.march_step_stop_reference -- every level applies the stop rule, so a stop can spare a doubling; nerf_occ_march_step is
+    the kernel of both and replaces nerf_occ_march / nerf_occ_march_stop in the call).  A ray with d = 0 has no step and emits nothing.
+    Nothing else of the call changes: the single compacted pass with the march's z_stop, the backward (depths and z_stop are constants
+    of the graph), the draws (u_march, then noise_f), the output keys, clip_to_occupancy before the march.  last_stats additionally
+    carries "rays_refit" (rays whose step was doubled at least once) when march_fit > 0.  Refused: either option without
+    proposal="march", a step that is not a finite real number > 0 or a fit that is not an int in 0..8 (bools included), march_fit > 0
+    without march_step_size; lindisp stays NotImplementedError.  None / 0: nothing changes -- same launches, same bits, same draws."""
+    march, early_stop_eps, march_steps, march_stop_eps, march_step_size, march_fit = _check_grid_options(
+        N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal, early_stop_eps, march_steps, march_stop_eps, march_step_size,
+        march_fit)
     from .dense import DenseNeRF
     nets = [network_fn] + ([network_fine] if network_fine is not None else [])
     dense = all(isinstance(m, DenseNeRF) for m in nets)         # architectures outside the fused kernels: layer by layer (dense.py)
@@ -1144,7 +1189,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
             occupancy._desc()
             occupancy.last_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal,
-                                                                                             march_stop_eps), 0)
+                                                                                             march_stop_eps, march_fit), 0)
         return _result_dict(outs, retraw, coarse_first=False)
     rnd, std = _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march)
     cfg = dict(N_samples=int(N_samples), N_importance=n_f, lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
@@ -1169,7 +1214,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             grid_grad = False
         # what _grid_chain reads, set once for both paths; the reduced class is an inference form whose last-sample fix-up is per ray: the
         # compacted points, and gradients anyway, run on the fp16x3 products
-        cfg.update(proposal=None if march else proposal, early_stop_eps=early_stop_eps, march_steps=march_steps, march_stop_eps=march_stop_eps)
+        cfg.update(proposal=None if march else proposal, early_stop_eps=early_stop_eps, march_steps=march_steps, march_stop_eps=march_stop_eps,
+                   march_step_size=march_step_size, march_fit=march_fit)
         if cfg["precision"] == "fp16_fp8c":
             cfg["precision"] = "fp16x3"
         if march:       # ONE pass over all the slots: what the two paths below run as a coarse-only call on the march's depths
@@ -1232,12 +1278,13 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """run_nerf.py:54-66.  Injected ``randoms`` (one row per ray) are sliced with the rays, so a chunked call consumes
     the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks (with ``clip_to_occupancy``
     its "rays_hit" / "rays" too, with ``early_stop_eps`` its "rays_stopped", with ``proposal="march"`` its "rays_truncated" and with
-    ``march_stop_eps`` its "rays_stopped")."""
+    ``march_stop_eps`` its "rays_stopped", with ``march_fit`` > 0 its "rays_refit")."""
     all_ret = {}
     randoms = kwargs.pop("randoms", None)
     occ = kwargs.get("occupancy")
     occ_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(kwargs.get("clip_to_occupancy"), kwargs.get("early_stop_eps"),
-                                                                          kwargs.get("proposal"), kwargs.get("march_stop_eps")), 0)
+                                                                          kwargs.get("proposal"), kwargs.get("march_stop_eps"),
+                                                                          kwargs.get("march_fit", 0)), 0)
     if randoms is not None:
         for k, v in randoms.items():
             if v.shape[0] != rays_flat.shape[0]:

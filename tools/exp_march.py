@@ -10,18 +10,24 @@ S = 64 + 128 = 192 slots):
     under --root has no such option); with --density-scale F, because the fixture scene is a fog on which next to nothing stops,
     the eps = 1e-2 rows once more on a copy of every grid whose densities are multiplied by F -- a stand-in for surfaces that says
     what a stop saves in TIME only: the network is not scaled with the grid, so the image of those rows means nothing;
-  * nerf_occ_march alone at 128^3 for the three M (HIP events around 100 launches), and nerf_occ_march_stop next to it.
+  * nerf_occ_march alone at 128^3 for the three M (HIP events around 100 launches), and nerf_occ_march_stop next to it;
+  * with --step-size DS, next to the fixed-M rows of the same run, the march in world-space steps of DS (march_step_size=DS, the cap
+    march_steps = 1024) at march_fit = 0 and 3, and at march_fit = 3 with march_stop_eps = 1e-2: ms, evaluated points per ray, rays
+    truncated, refit and stopped; and nerf_occ_march_step alone.  Half a cell of the 128^3 grid over [-2, 2]^3 is 1 / 64.
 Per row: ms (median of --reps alternating repetitions, min and max = the spread), the evaluated points, field and occupancy kernel ms.
 The learning rate is 0 (the optimizer does all of its work; the scene and every share stay put).
 
     python tools/exp_march.py --out profiles/r14_exp_march.json
     python tools/exp_march.py --density-scale 16 --out profiles/r17_exp_march.json
+    python tools/exp_march.py --step-size 0.015625 --out profiles/r18_exp_march_step.json
 """
 import grid_exp as gx
 
 ap = gx.parser(__doc__, steps="training steps / renders between two HIP events")
 ap.add_argument("--density-scale", type=float, default=None,
                 help="also time march_stop_eps = 1e-2 on a copy of every grid with its densities multiplied by this (time and counts only)")
+ap.add_argument("--step-size", type=float, default=None,
+                help="also time the march in world-space steps of this length (march_step_size, cap 1024) at march_fit 0 and 3")
 args = ap.parse_args()
 torch, wl, npa, hb, dev = gx.load(args, "exp_march")
 S = gx.Scene(wl, npa, dev, perturb=1., target=True, records=True)
@@ -29,12 +35,15 @@ LO, HI, R, N_RAYS, nc, nf = S.LO, S.HI, S.R, S.N_RAYS, S.nc, S.nf
 N_C, N_F = 64, 128
 MARCH_STEPS = (256, 512, 1024)
 STOP_EPS = (1e-3, 1e-2)
+STEP_CAP, STEP_FITS = 1024, (0, 3)
 HAVE_STOP = hasattr(npa.DensityGrid, "march_stop")      # (--root of a tree without the option: the rows of that tree only)
 opt_two, opt_one = S.adam(nc, nf), S.adam(nf)
 
 
 def render(grid, mode):
-    """mode: None (two networks), "grid", the march's step count, or (step count, march_stop_eps)"""
+    """mode: None (two networks), "grid", the march's step count, (step count, march_stop_eps), or a dict of march keywords"""
+    if isinstance(mode, dict):
+        return S.render(occupancy=grid, proposal="march", **mode)
     if mode == "grid":
         return S.render(occupancy=grid, proposal="grid")
     if isinstance(mode, tuple):
@@ -69,7 +78,7 @@ def time_all(fn, configs, k, reps):
         stats = grid.last_stats
         rows[name].update(evaluated=stats["evaluated"], total=stats["total"], evaluated_per_ray=stats["evaluated"] / N_RAYS,
                           occ_kernels_ms=gx.kernel_ms(summ, "occ_"), field_ms=gx.kernel_ms(summ, ("field_", "wgrad")))
-        for key in ("rays_truncated", "rays_stopped"):
+        for key in ("rays_truncated", "rays_stopped", "rays_refit"):
             if key in stats:
                 rows[name][key] = stats[key]
     return rows
@@ -90,6 +99,12 @@ for want in (0.5, 0.25, 0.1):
     configs.append((name + ", proposal=grid", g, "grid"))
     for M in MARCH_STEPS:
         configs.append((name + f", proposal=march M={M}", g, M))
+    if args.step_size is not None:
+        for fit in STEP_FITS:
+            configs.append((name + f", proposal=march M={STEP_CAP} march_step_size={args.step_size:g} march_fit={fit}", g,
+                            dict(march_steps=STEP_CAP, march_step_size=args.step_size, march_fit=fit)))
+        configs.append((name + f", proposal=march M={STEP_CAP} march_step_size={args.step_size:g} march_fit={STEP_FITS[-1]} march_stop_eps=0.01", g,
+                        dict(march_steps=STEP_CAP, march_step_size=args.step_size, march_fit=STEP_FITS[-1], march_stop_eps=1e-2)))
     if not HAVE_STOP:
         continue
     for M in MARCH_STEPS:
@@ -122,4 +137,17 @@ for M in MARCH_STEPS if HAVE_STOP else ():
 if HAVE_STOP:
     kernel["note"] = "host-timed back-to-back launches (allocation of the outputs included)"
     result["march_stop_kernel_128_cubed"] = kernel
+if args.step_size is not None:
+    kernel = {}
+    for fit in STEP_FITS:
+        us = gx.time_launches(lambda: g.march_step(rays_rec, args.step_size, STEP_CAP, SLOTS, fit), args.reps)
+        out = g.march_step(rays_rec, args.step_size, STEP_CAP, SLOTS, fit)
+        kernel[f"ds={args.step_size:g} M={STEP_CAP} fit={fit}"] = dict(us, rays=N_RAYS, slots=SLOTS, rays_truncated=int(out[2].sum()),
+                                                                     rays_refit=int((out[3] > 0).sum()))
+    us = gx.time_launches(lambda: g.march_step_stop(rays_rec, args.step_size, STEP_CAP, SLOTS, 1e-2, STEP_FITS[-1]), args.reps)
+    out = g.march_step_stop(rays_rec, args.step_size, STEP_CAP, SLOTS, 1e-2, STEP_FITS[-1])
+    kernel[f"ds={args.step_size:g} M={STEP_CAP} fit={STEP_FITS[-1]} eps=0.01"] = dict(
+        us, rays=N_RAYS, slots=SLOTS, rays_truncated=int(out[2].sum()), rays_refit=int((out[3] > 0).sum()), rays_stopped=int(out[4].sum()))
+    kernel["note"] = "host-timed back-to-back launches (allocation of the outputs included)"
+    result["march_step_kernel_128_cubed"] = kernel
 gx.emit(result, args.out)
