@@ -22,6 +22,8 @@
 //   nerf_occ_march_step : either walk in steps of one world-space length along the ray, capped at M candidates, with a per-ray fit: a
 //                      ray whose emitted steps overflow its slots walks again with the step doubled, up to `fit` times:
 //                      render_rays(proposal="march", march_step_size=ds, march_fit=J).
+//                      The three are one kernel, occ_march_walk_kernel<Steps, STOP>: Steps (EqualSteps, WorldSteps) says how a candidate
+//                      becomes a depth, when it counts and whether there are levels; STOP adds the stop on the optical depth.
 // The compaction is deterministic: a count per block of OCC_TILE points, an exclusive scan of the block counts, then the
 // write -- inside a block the position of a point is a wave ballot + popcount and a prefix over the block's wave counts, so the
 // list is in stable ray-major, sample-minor order and no atomic decides anything.
@@ -60,16 +62,25 @@ __device__ __forceinline__ Pt sample_point(const float* __restrict__ ray, float 
     return p;
 }
 
-__device__ __forceinline__ bool occupied(const GridArgs& g, const Pt& p) {
+// The classification of a point, shared by occupied() and proposal_sigma(): false outside the box, else true and the point's cell in *c
+__device__ __forceinline__ bool cell_of(const GridArgs& g, const Pt& p, unsigned* c) {
     const float tx = (p.x - g.lo[0]) * g.scale[0];
     const float ty = (p.y - g.lo[1]) * g.scale[1];
     const float tz = (p.z - g.lo[2]) * g.scale[2];
     // (a NaN fails every comparison: outside)
     const bool inside = tx >= 0.0f && tx < (float)g.res[0] && ty >= 0.0f && ty < (float)g.res[1] && tz >= 0.0f && tz < (float)g.res[2];
-    if (!inside) return g.outside_skip == 0;
+    if (!inside) return false;
     const int ix = (int)floorf(tx), iy = (int)floorf(ty), iz = (int)floorf(tz);
-    const unsigned c = ((unsigned)ix * (unsigned)g.res[1] + (unsigned)iy) * (unsigned)g.res[2] + (unsigned)iz;
-    return (g.bits[c >> 5] >> (c & 31u)) & 1u;
+    *c = ((unsigned)ix * (unsigned)g.res[1] + (unsigned)iy) * (unsigned)g.res[2] + (unsigned)iz;
+    return true;
+}
+
+__device__ __forceinline__ bool cell_bit(const GridArgs& g, unsigned c) { return (g.bits[c >> 5] >> (c & 31u)) & 1u; }
+
+__device__ __forceinline__ bool occupied(const GridArgs& g, const Pt& p) {
+    unsigned c;
+    if (!cell_of(g, p, &c)) return g.outside_skip == 0;
+    return cell_bit(g, c);
 }
 
 // lanes below this one whose bit is set in a wave ballot
@@ -485,15 +496,9 @@ __global__ __launch_bounds__(SPAN_THREADS) void occ_ray_span_kernel(GridArgs g, 
 // weights are those nerf_raw2outputs gives for raw = (0, 0, 0, sigma) without noise, bit for bit.  No colours, no ray integrals.
 // LDS: 2 S floats (alpha_i, 1 - alpha_i + 1e-10); each lane touches only its own segment: no synchronisation.
 __device__ __forceinline__ float proposal_sigma(const GridArgs& g, const float* __restrict__ density, float outside_sigma, const Pt& p) {
-    const float tx = (p.x - g.lo[0]) * g.scale[0];
-    const float ty = (p.y - g.lo[1]) * g.scale[1];
-    const float tz = (p.z - g.lo[2]) * g.scale[2];
-    // (a NaN fails every comparison: outside)
-    const bool inside = tx >= 0.0f && tx < (float)g.res[0] && ty >= 0.0f && ty < (float)g.res[1] && tz >= 0.0f && tz < (float)g.res[2];
-    if (!inside) return g.outside_skip ? 0.0f : outside_sigma;
-    const int ix = (int)floorf(tx), iy = (int)floorf(ty), iz = (int)floorf(tz);
-    const unsigned c = ((unsigned)ix * (unsigned)g.res[1] + (unsigned)iy) * (unsigned)g.res[2] + (unsigned)iz;
-    return ((g.bits[c >> 5] >> (c & 31u)) & 1u) ? density[c] : 0.0f;
+    unsigned c;
+    if (!cell_of(g, p, &c)) return g.outside_skip ? 0.0f : outside_sigma;
+    return cell_bit(g, c) ? density[c] : 0.0f;
 }
 
 __global__ __launch_bounds__(64) void occ_proposal_weights_kernel(GridArgs g, const float* __restrict__ density, float outside_sigma,
@@ -575,207 +580,129 @@ __global__ __launch_bounds__(STOP_THREADS) void occ_stop_depth_kernel(const floa
     if (walker) z_stop[my_ray] = (crossed >= 0 && crossed + 1 < S) ? z_vals[(size_t)my_ray * S + crossed + 1] : INFINITY;
 }
 
-// ---- nerf_occ_march (OccupancyGrid.march_reference is the definition)
-// One wavefront per ray, MARCH_RAYS rays per block.  A round takes 64 candidates: lane l builds z_k of k = k0 + l and classifies it
-// with sample_point / occupied -- the compaction's own functions, so the compaction sees the bits this kernel saw.  The keep mask is
-// a ballot; the closing candidates are (keep << 1 | carry) & ~keep, carry being lane 63's keep bit of the round before; a lane's rank
-// is the emitted lanes below it plus the running base.  Ranks below S - 1 store their depth, rank S - 1 is the stop depth (one
-// shuffle hands it to every lane), and the wave leaves once the base has passed S - 1: a ray that fills its slots in the first rounds
-// never looks at the rest of its M candidates.  Then the lanes pad the row with the stop depth.  Everything the wave branches on is
-// wave-uniform.
+// ---- nerf_occ_march, nerf_occ_march_stop, nerf_occ_march_step: one walk
+// (OccupancyGrid.march_reference / march_step_reference and DensityGrid.march_stop_reference / march_step_stop_reference are the definitions)
+// One wavefront per ray, MARCH_RAYS rays per block.  A round takes 64 candidates: lane l builds z_k of k = k0 + l, asks whether it is
+// `valid`, and classifies it with sample_point / occupied -- the compaction's own functions, so the compaction sees the bits this kernel
+// saw.  The keep mask is a ballot; the closing candidates are (keep << 1 | carry) & ~keep & valid, carry being lane 63's keep bit of the
+// round before; a lane's rank is the emitted lanes below it plus the running base.  Ranks below S - 1 store their depth, rank S - 1 is
+// the stop depth (one shuffle hands it to every lane), and the wave leaves the walk once the base has passed S - 1: a ray that fills its
+// slots in the first rounds never looks at the rest of its M candidates.  The valid candidates are a prefix of 0 .. M - 1, so a round
+// whose lane 63 is not valid is the ray's last.  Then the lanes pad the row with the stop depth.
+//
+// STOP: the ray also stops emitting at the first valid candidate in front of which the grid's own optical depth A_k = sum_{j < k} c_j
+// has reached tau = -ln(eps).  Per round the lane builds c of its candidate -- proposal_sigma at the point it classified (0 where the
+// candidate is not kept, where sigma <= 0 and where sigma is a NaN) times the interval up to the NEXT candidate (built from k + 1 by
+// the same expression; far where that one is not valid) times |d|, occ_proposal_weights_kernel's order of operations --, the wave scans
+// c (nerf::wave_incl_scan_add: the order of the additions is the definition's), A = depth + the inclusive sum of the lane below, and
+// one ballot of A >= tau finds the cut lane.  The emit mask keeps the lanes below the cut; a truncation hit inside what is left wins
+// (the slot limit bites first), otherwise the stop depth is the cut lane's z.  A NaN in A fails the comparison and poisons every later
+// A: such a ray never stops.
+//
+// Steps: how candidate k becomes a depth, when it counts, and whether the walk has levels.
+//   EqualSteps  M equal steps over [near, far]: t = (k + u) / M, z = near * (1 - t) + far * t; valid while k < M; one level.
+//   WorldSteps  steps of one length ds along the ray: dz = (ds / |d|) * 2^level, z = near + (k + u) * dz -- one addition, one
+//               multiplication, one addition --; valid while k < M and z < far.  The fit: a ray whose emitted candidates overflow its
+//               slots at a level below `fit` starts again with the doubled step; the plain stores of the later level overwrite its row
+//               (ranks 0 .. S - 2 that the later level does not reach are covered by the padding loop, which starts at
+//               min(base, S - 1) of the LAST level).  A ray leaves the kernel at the first level that fits.
+// Everything the wave branches on is wave-uniform (ballots, the level, the round); no atomics, no LDS.
 constexpr int MARCH_THREADS = 256;
 constexpr int MARCH_RAYS = MARCH_THREADS / 64;
 
-__global__ __launch_bounds__(MARCH_THREADS) void occ_march_kernel(GridArgs g, const float* __restrict__ rays, int ray_stride,
-                                                                  const float* __restrict__ u, int n_rays, int M, int S,
-                                                                  float* __restrict__ z_vals, float* __restrict__ z_stop,
-                                                                  int* __restrict__ truncated) {
-    const int ray = blockIdx.x * MARCH_RAYS + (threadIdx.x >> 6);
-    if (ray >= n_rays) return;          // (whole waves leave: the ballots below see full waves)
-    const int lane = threadIdx.x & 63;
-    const float* r = rays + (size_t)ray * ray_stride;
-    float* zrow = z_vals + (size_t)ray * S;
-    const float near = r[6], far = r[7];
-    bool ok = near < far;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) ok = ok && fabsf(r[c]) < INFINITY;      // (a NaN fails the comparison)
-    if (!ok) {
-        for (int j = lane; j < S; j += 64) zrow[j] = far;
-        if (lane == 0) {
-            z_stop[ray] = -INFINITY;
-            truncated[ray] = 0;
-        }
-        return;
-    }
-    const float uu = u ? u[ray] : 0.5f;
-    const float Mf = (float)M;
-    const int last = S - 1;
-    int base = 0, trunc = 0;
-    unsigned long long carry = 0ull;
-    float stop = far;
-    for (int k0 = 0; k0 < M && base <= last; k0 += 64) {
-        const int k = k0 + lane;
-        const float t = ((float)k + uu) / Mf;               // (IEEE division: hipcc's default for fp32)
-        const float z = near * (1.0f - t) + far * t;        // run_nerf.py:360 (no contraction)
-        const bool keep = k < M && occupied(g, sample_point(r, z));
-        const unsigned long long km = __ballot(keep);
-        const unsigned long long em = km | (((km << 1) | carry) & ~km & __ballot(k < M));
-        carry = km >> 63;
-        const int rank = base + lanes_below(em);
-        const bool emit = (em >> lane) & 1ull;
-        if (emit && rank < last) zrow[rank] = z;
-        const unsigned long long hit = __ballot(emit && rank == last);
-        if (hit) {
-            stop = __shfl(z, __ffsll((long long)hit) - 1);
-            trunc = 1;
-        }
-        base += __popcll(em);
-    }
-    for (int j = min(base, last) + lane; j < S; j += 64) zrow[j] = stop;
-    if (lane == 0) {
-        z_stop[ray] = stop;
-        truncated[ray] = trunc;
-    }
-}
+struct MarchArgs {
+    const float* density;       // STOP: one sigma per cell, and what counts outside the box
+    float outside_sigma;
+    const float* rays;
+    int ray_stride;
+    const float* u;             // one offset per ray, or null: 0.5
+    int n_rays;
+    float ds;                   // WorldSteps: the step's length along the ray
+    int M, S;
+    int fit;                    // WorldSteps: the highest level
+    float tau;                  // STOP
+    float* z_vals;
+    float* z_stop;
+    int* truncated;
+    int* level;                 // WorldSteps
+    int* stopped;               // STOP
+};
 
-// ---- nerf_occ_march_stop (DensityGrid.march_stop_reference is the definition)
-// occ_march_kernel with one more rule: the ray stops emitting at the first candidate in front of which the grid's own optical depth
-// A_k = sum_{j < k} c_j has reached tau = -ln(eps).  Per round the lane builds c of its candidate -- proposal_sigma at the point it
-// classified (0 where the candidate is not kept, where sigma <= 0 and where sigma is a NaN) times the interval up to the NEXT candidate
-// (built from k + 1 by the same expression; far behind the last one) times |d|, occ_proposal_weights_kernel's order of operations --,
-// the wave scans c (nerf::wave_incl_scan_add: the order of the additions is the definition's), A = base + the inclusive sum of the lane
-// below, and one ballot of A >= tau (k < M) finds the cut lane.  The emit mask keeps the lanes below the cut; a truncation hit inside
-// what is left wins (the slot limit bit first), otherwise the stop depth is the cut lane's z.  The wave leaves once the slots are full
-// or the cut has been seen.  A NaN in A fails the comparison and poisons every later A: such a ray never stops.  Everything the wave
-// branches on is wave-uniform; no LDS, no atomics.
-__global__ __launch_bounds__(MARCH_THREADS) void occ_march_stop_kernel(GridArgs g, const float* __restrict__ density, float outside_sigma,
-                                                                       const float* __restrict__ rays, int ray_stride,
-                                                                       const float* __restrict__ u, int n_rays, int M, int S, float tau,
-                                                                       float* __restrict__ z_vals, float* __restrict__ z_stop,
-                                                                       int* __restrict__ truncated, int* __restrict__ stopped) {
-    const int ray = blockIdx.x * MARCH_RAYS + (threadIdx.x >> 6);
-    if (ray >= n_rays) return;          // (whole waves leave: the ballots and shuffles below see full waves)
-    const int lane = threadIdx.x & 63;
-    const float* r = rays + (size_t)ray * ray_stride;
-    float* zrow = z_vals + (size_t)ray * S;
-    const float near = r[6], far = r[7];
-    bool ok = near < far;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) ok = ok && fabsf(r[c]) < INFINITY;      // (a NaN fails the comparison)
-    if (!ok) {
-        for (int j = lane; j < S; j += 64) zrow[j] = far;
-        if (lane == 0) {
-            z_stop[ray] = -INFINITY;
-            truncated[ray] = 0;
-            stopped[ray] = 0;
-        }
-        return;
+struct EqualSteps {
+    static constexpr bool LEVELS = false;
+    float near, far, Mf;
+    int M;
+    __device__ __forceinline__ bool start(const MarchArgs& a, float near_, float far_, float) {
+        near = near_; far = far_; M = a.M; Mf = (float)a.M;
+        return true;
     }
-    const float uu = u ? u[ray] : 0.5f;
-    const float Mf = (float)M;
-    const float dn = sqrtf(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
-    const int last = S - 1;
-    int base = 0, trunc = 0, stp = 0;
-    unsigned long long carry = 0ull;
-    float stop = far, depth = 0.0f;     // depth: A in front of the round's first candidate
-    for (int k0 = 0; k0 < M && base <= last && !stp; k0 += 64) {
-        const int k = k0 + lane;
+    __device__ __forceinline__ void set_level(int) {}
+    __device__ __forceinline__ float depth(int k, float uu) const {
         const float t = ((float)k + uu) / Mf;               // (IEEE division: hipcc's default for fp32)
-        const float z = near * (1.0f - t) + far * t;        // run_nerf.py:360 (no contraction)
-        const Pt p = sample_point(r, z);
-        const bool keep = k < M && occupied(g, p);
-        float c = 0.0f;
-        if (keep) {
-            const float t1 = ((float)(k + 1) + uu) / Mf;
-            const float z1 = k + 1 < M ? near * (1.0f - t1) + far * t1 : far;
-            const float sg = proposal_sigma(g, density, outside_sigma, p);
-            const float dist = (z1 - z) * dn;
-            c = (sg > 0.0f ? sg : 0.0f) * dist;             // (a NaN sigma fails the comparison: 0)
-        }
-        const float incl = nerf::wave_incl_scan_add(c, lane);
-        float below = __shfl_up(incl, 1);
-        if (lane == 0) below = 0.0f;
-        const unsigned long long cut = __ballot(k < M && depth + below >= tau);
-        const unsigned long long km = __ballot(keep);
-        unsigned long long em = km | (((km << 1) | carry) & ~km & __ballot(k < M));
-        carry = km >> 63;
-        const int cut_lane = cut ? __ffsll((long long)cut) - 1 : 64;
-        if (cut) em &= (1ull << cut_lane) - 1ull;
-        const int rank = base + lanes_below(em);
-        const bool emit = (em >> lane) & 1ull;
-        if (emit && rank < last) zrow[rank] = z;
-        const unsigned long long hit = __ballot(emit && rank == last);
-        if (hit) {
-            stop = __shfl(z, __ffsll((long long)hit) - 1);
-            trunc = 1;
-        } else if (cut) {
-            stop = __shfl(z, cut_lane);
-            stp = 1;
-        }
-        base += __popcll(em);
-        depth = depth + __shfl(incl, 63);
+        return near * (1.0f - t) + far * t;                 // run_nerf.py:360 (no contraction)
     }
-    for (int j = min(base, last) + lane; j < S; j += 64) zrow[j] = stop;
-    if (lane == 0) {
-        z_stop[ray] = stop;
-        truncated[ray] = trunc;
-        stopped[ray] = stp;
-    }
-}
+    __device__ __forceinline__ bool valid(int k, float) const { return k < M; }
+};
 
-// ---- nerf_occ_march_step (OccupancyGrid.march_step_reference / DensityGrid.march_step_stop_reference are the definition)
-// The march in world-space steps with a per-ray fit to the slots.  The walk of a level is occ_march_kernel's (STOP: occ_march_stop_kernel's)
-// with two differences: the candidates are z_k = near + (k + u) * dz, dz = (ds / |d|) * 2^level -- one addition, one multiplication, one
-// addition --, and a candidate counts only while z_k < far (`valid`, a ballot: z_k is nondecreasing in k, so the valid candidates are a
-// prefix and a round whose lane 63 is not valid is the ray's last).  The fit: a ray whose emitted candidates overflow its slots at a level
-// below `fit` starts again with the doubled step; the plain stores of the later level overwrite its row (ranks 0 .. S - 2 that the later
-// level does not reach are covered by the padding loop, which starts at min(base, S - 1) of the LAST level).  A ray leaves a level as
-// soon as its slots are full, its candidates run out or it stops; it leaves the kernel at the first level that fits.  Everything the
-// wave branches on is wave-uniform (ballots, the level, the round); no atomics, no LDS of its own.
-template <bool STOP>
-__global__ __launch_bounds__(MARCH_THREADS) void occ_march_step_kernel(GridArgs g, const float* __restrict__ density, float outside_sigma,
-                                                                       const float* __restrict__ rays, int ray_stride,
-                                                                       const float* __restrict__ u, int n_rays, float ds, int M, int S,
-                                                                       int fit, float tau, float* __restrict__ z_vals,
-                                                                       float* __restrict__ z_stop, int* __restrict__ truncated,
-                                                                       int* __restrict__ level, int* __restrict__ stopped) {
+struct WorldSteps {
+    static constexpr bool LEVELS = true;
+    float near, far, dz0, dz;
+    int M;
+    __device__ __forceinline__ bool start(const MarchArgs& a, float near_, float far_, float dn) {
+        near = near_; far = far_; M = a.M;
+        dz0 = a.ds / dn;                                    // (IEEE division: hipcc's default for fp32)
+        return dz0 > 0.0f && dz0 < INFINITY;                // (d = 0, an overflowing |d|, a NaN: no step)
+    }
+    __device__ __forceinline__ void set_level(int lvl) { dz = dz0 * (float)(1 << lvl); }     // (exact, or +inf: then no candidate is valid)
+    __device__ __forceinline__ float depth(int k, float uu) const { return near + ((float)k + uu) * dz; }   // (no contraction)
+    __device__ __forceinline__ bool valid(int k, float z) const { return k < M && z < far; }                // (a NaN fails the comparison)
+};
+
+template <class Steps, bool STOP>
+__global__ __launch_bounds__(MARCH_THREADS) void occ_march_walk_kernel(GridArgs g, MarchArgs a) {
     const int ray = blockIdx.x * MARCH_RAYS + (threadIdx.x >> 6);
-    if (ray >= n_rays) return;          // (whole waves leave: the ballots and shuffles below see full waves)
+    if (ray >= a.n_rays) return;        // (whole waves leave: the ballots and shuffles below see full waves)
     const int lane = threadIdx.x & 63;
-    const float* r = rays + (size_t)ray * ray_stride;
-    float* zrow = z_vals + (size_t)ray * S;
-    const float near = r[6], far = r[7];
+    const int S = a.S;
+    const float* ray_in = a.rays + (size_t)ray * a.ray_stride;
+    float* zrow = a.z_vals + (size_t)ray * S;
+    const float near = ray_in[6], far = ray_in[7];
     bool ok = near < far;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) ok = ok && fabsf(r[c]) < INFINITY;      // (a NaN fails the comparison)
-    const float dn = sqrtf(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
-    const float dz0 = ds / dn;                                          // (IEEE division: hipcc's default for fp32)
-    ok = ok && dz0 > 0.0f && dz0 < INFINITY;                            // (d = 0, an overflowing |d|, a NaN: no step)
+    for (int c = 0; c < 8; ++c) ok = ok && fabsf(ray_in[c]) < INFINITY;     // (a NaN fails the comparison)
+    // o and d, read once (the pointers inside a struct promise no __restrict__: behind a store to zrow the compiler would load them again
+    // in every round) and held in scalar registers: the wave has one ray
+    float r[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) r[c] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ray_in[c])));
+    const float dn = (STOP || Steps::LEVELS) ? sqrtf(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]) : 0.0f;
+    Steps steps;
+    ok = steps.start(a, near, far, dn) && ok;
     if (!ok) {
         for (int j = lane; j < S; j += 64) zrow[j] = far;
         if (lane == 0) {
-            z_stop[ray] = -INFINITY;
-            truncated[ray] = 0;
-            level[ray] = 0;
-            if (STOP) stopped[ray] = 0;
+            a.z_stop[ray] = -INFINITY;
+            a.truncated[ray] = 0;
+            if (Steps::LEVELS) a.level[ray] = 0;
+            if (STOP) a.stopped[ray] = 0;
         }
         return;
     }
-    const float uu = u ? u[ray] : 0.5f;
+    const float uu = a.u ? a.u[ray] : 0.5f;
     const int last = S - 1;
     int lvl = 0, base, trunc, stp;
     float stop;
     for (;; ++lvl) {
-        const float dz = dz0 * (float)(1 << lvl);           // (exact, or +inf: then no candidate is valid)
+        steps.set_level(lvl);
         base = 0; trunc = 0; stp = 0;
         stop = far;
         unsigned long long carry = 0ull;
         float depth = 0.0f;             // STOP: A in front of the round's first candidate
         bool more = true;
-        for (int k0 = 0; k0 < M && base <= last && !stp && more; k0 += 64) {
+        for (int k0 = 0; k0 < a.M && base <= last && !stp && more; k0 += 64) {
             const int k = k0 + lane;
-            const float z = near + ((float)k + uu) * dz;    // (no contraction)
-            const bool valid = k < M && z < far;            // (a NaN fails the comparison)
+            const float z = steps.depth(k, uu);
+            const bool valid = steps.valid(k, z);
             const unsigned long long vm = __ballot(valid);
             more = (vm >> 63) & 1ull;
             const Pt p = sample_point(r, z);
@@ -788,16 +715,16 @@ __global__ __launch_bounds__(MARCH_THREADS) void occ_march_step_kernel(GridArgs 
             if (STOP) {
                 float c = 0.0f;
                 if (keep) {
-                    const float z1 = near + ((float)(k + 1) + uu) * dz;
-                    const float zn = (k + 1 < M && z1 < far) ? z1 : far;
-                    const float sg = proposal_sigma(g, density, outside_sigma, p);
+                    const float z1 = steps.depth(k + 1, uu);
+                    const float zn = steps.valid(k + 1, z1) ? z1 : far;
+                    const float sg = proposal_sigma(g, a.density, a.outside_sigma, p);
                     const float dist = (zn - z) * dn;
                     c = (sg > 0.0f ? sg : 0.0f) * dist;     // (a NaN sigma fails the comparison: 0)
                 }
                 const float incl = nerf::wave_incl_scan_add(c, lane);
                 float below = __shfl_up(incl, 1);
                 if (lane == 0) below = 0.0f;
-                cut = __ballot(valid && depth + below >= tau);
+                cut = __ballot(valid && depth + below >= a.tau);
                 if (cut) {
                     cut_lane = __ffsll((long long)cut) - 1;
                     em &= (1ull << cut_lane) - 1ull;
@@ -817,17 +744,17 @@ __global__ __launch_bounds__(MARCH_THREADS) void occ_march_step_kernel(GridArgs 
             }
             base += __popcll(em);
         }
-        if (!trunc || lvl >= fit) break;
+        if (!Steps::LEVELS || !trunc || lvl >= a.fit) break;
         // the next level's stores land on this level's, from other lanes of the same wave: a wave's vector stores are performed in
         // issue order, which is what wavefront scope asks for (no instruction, the compiler keeps the order)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     }
     for (int j = min(base, last) + lane; j < S; j += 64) zrow[j] = stop;
     if (lane == 0) {
-        z_stop[ray] = stop;
-        truncated[ray] = trunc;
-        level[ray] = lvl;
-        if (STOP) stopped[ray] = stp;
+        a.z_stop[ray] = stop;
+        a.truncated[ray] = trunc;
+        if (Steps::LEVELS) a.level[ray] = lvl;
+        if (STOP) a.stopped[ray] = stp;
     }
 }
 
@@ -846,6 +773,48 @@ int check_grid(const char* fn, const NerfOccGrid* grid, GridArgs* g) {
 
 inline long occ_blocks(long n_points) { return (n_points + OCC_TILE - 1) / OCC_TILE; }
 
+// nerf_occ_compact (STOP false, z_stop unused) and nerf_occ_compact_stop
+template <bool STOP>
+int compact(const char* fn, const NerfOccGrid* grid, const float* rays, int ray_stride, const float* z_vals, const float* z_stop, int n_rays,
+            int n_samples, int* slot, float* records, int* count, int* scratch, void* stream) {
+    GridArgs g;
+    if (int rc = check_grid(fn, grid, &g)) return rc;
+    if (!(rays && z_vals && (z_stop || !STOP) && slot && records && count && scratch)) return fail_arg(fn, "null pointer");
+    if (!(ray_stride >= 11 && n_rays >= 0 && n_samples >= 1)) return fail_arg(fn, "bad size (ray records need 11 columns)");
+    const long P = (long)n_rays * n_samples;
+    if (!(P < (1L << 31) - OCC_TILE)) return fail_arg(fn, "too many points for one call");
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 0) return done(fn, hipMemsetAsync(count, 0, sizeof(int), st));
+    const int nb = (int)occ_blocks(P);
+    occ_count_kernel<STOP><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, z_stop, (unsigned)P, (unsigned)n_samples, scratch);
+    occ_scan_kernel<<<1, SCAN_THREADS, 0, st>>>(scratch, nb, count);
+    occ_write_kernel<STOP><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, z_stop, (unsigned)P, (unsigned)n_samples, scratch, slot,
+                                                       records);
+    return done(fn, hipGetLastError());
+}
+
+// the sizes the three march entry points take alike
+int check_march_sizes(const char* fn, int ray_stride, int n_rays, int n_steps, int n_slots) {
+    if (!(ray_stride >= 8 && n_rays >= 0 && n_steps >= 1 && n_steps <= 16384 && n_slots >= 1 && n_slots <= 4096))
+        return fail_arg(fn, "bad size (ray records need 8 columns, 1..16384 steps, 1..4096 slots)");
+    return 0;
+}
+
+// the march of checked arguments: a.density chooses the stop form, `world` the steps
+int launch_march(const char* fn, const GridArgs& g, const MarchArgs& a, bool world, void* stream) {
+    if (a.n_rays == 0) return 0;
+    const unsigned blocks = (unsigned)((a.n_rays + MARCH_RAYS - 1) / MARCH_RAYS);
+    hipStream_t st = (hipStream_t)stream;
+    if (world) {
+        if (a.density) occ_march_walk_kernel<WorldSteps, true><<<blocks, MARCH_THREADS, 0, st>>>(g, a);
+        else occ_march_walk_kernel<WorldSteps, false><<<blocks, MARCH_THREADS, 0, st>>>(g, a);
+    } else {
+        if (a.density) occ_march_walk_kernel<EqualSteps, true><<<blocks, MARCH_THREADS, 0, st>>>(g, a);
+        else occ_march_walk_kernel<EqualSteps, false><<<blocks, MARCH_THREADS, 0, st>>>(g, a);
+    }
+    return done(fn, hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -854,38 +823,12 @@ size_t nerf_occ_scratch_words(long n_points) { return n_points > 0 ? (size_t)occ
 
 int nerf_occ_compact(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* z_vals, int n_rays, int n_samples,
                      int* slot, float* records, int* count, int* scratch, void* stream) {
-    GridArgs g;
-    if (int rc = check_grid(__func__, grid, &g)) return rc;
-    REQUIRE(rays && z_vals && slot && records && count && scratch, "null pointer");
-    REQUIRE(ray_stride >= 11 && n_rays >= 0 && n_samples >= 1, "bad size (ray records need 11 columns)");
-    const long P = (long)n_rays * n_samples;
-    REQUIRE(P < (1L << 31) - OCC_TILE, "too many points for one call");
-    hipStream_t st = (hipStream_t)stream;
-    if (P == 0) return done(__func__, hipMemsetAsync(count, 0, sizeof(int), st));
-    const int nb = (int)occ_blocks(P);
-    occ_count_kernel<false><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, nullptr, (unsigned)P, (unsigned)n_samples, scratch);
-    occ_scan_kernel<<<1, SCAN_THREADS, 0, st>>>(scratch, nb, count);
-    occ_write_kernel<false><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, nullptr, (unsigned)P, (unsigned)n_samples, scratch, slot,
-                                                        records);
-    return done(__func__, hipGetLastError());
+    return compact<false>(__func__, grid, rays, ray_stride, z_vals, nullptr, n_rays, n_samples, slot, records, count, scratch, stream);
 }
 
 int nerf_occ_compact_stop(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* z_vals, const float* z_stop, int n_rays,
                           int n_samples, int* slot, float* records, int* count, int* scratch, void* stream) {
-    GridArgs g;
-    if (int rc = check_grid(__func__, grid, &g)) return rc;
-    REQUIRE(rays && z_vals && z_stop && slot && records && count && scratch, "null pointer");
-    REQUIRE(ray_stride >= 11 && n_rays >= 0 && n_samples >= 1, "bad size (ray records need 11 columns)");
-    const long P = (long)n_rays * n_samples;
-    REQUIRE(P < (1L << 31) - OCC_TILE, "too many points for one call");
-    hipStream_t st = (hipStream_t)stream;
-    if (P == 0) return done(__func__, hipMemsetAsync(count, 0, sizeof(int), st));
-    const int nb = (int)occ_blocks(P);
-    occ_count_kernel<true><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, z_stop, (unsigned)P, (unsigned)n_samples, scratch);
-    occ_scan_kernel<<<1, SCAN_THREADS, 0, st>>>(scratch, nb, count);
-    occ_write_kernel<true><<<nb, OCC_THREADS, 0, st>>>(g, rays, ray_stride, z_vals, z_stop, (unsigned)P, (unsigned)n_samples, scratch, slot,
-                                                       records);
-    return done(__func__, hipGetLastError());
+    return compact<true>(__func__, grid, rays, ray_stride, z_vals, z_stop, n_rays, n_samples, slot, records, count, scratch, stream);
 }
 
 int nerf_occ_stop_depth(const float* z_vals, const float* weights, int n_rays, int n_samples, float threshold, float* z_stop, void* stream) {
@@ -902,12 +845,9 @@ int nerf_occ_march(const NerfOccGrid* grid, const float* rays, int ray_stride, c
     GridArgs g;
     if (int rc = check_grid(__func__, grid, &g)) return rc;
     REQUIRE(rays && z_vals && z_stop && truncated, "null pointer");
-    REQUIRE(ray_stride >= 8 && n_rays >= 0 && n_steps >= 1 && n_steps <= 16384 && n_slots >= 1 && n_slots <= 4096,
-            "bad size (ray records need 8 columns, 1..16384 steps, 1..4096 slots)");
-    if (n_rays == 0) return 0;
-    occ_march_kernel<<<(unsigned)((n_rays + MARCH_RAYS - 1) / MARCH_RAYS), MARCH_THREADS, 0, (hipStream_t)stream>>>(
-        g, rays, ray_stride, u, n_rays, n_steps, n_slots, z_vals, z_stop, truncated);
-    return done(__func__, hipGetLastError());
+    if (int rc = check_march_sizes(__func__, ray_stride, n_rays, n_steps, n_slots)) return rc;
+    const MarchArgs a = {nullptr, 0.0f, rays, ray_stride, u, n_rays, 0.0f, n_steps, n_slots, 0, 0.0f, z_vals, z_stop, truncated, nullptr, nullptr};
+    return launch_march(__func__, g, a, false, stream);
 }
 
 int nerf_occ_march_stop(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride, const float* u,
@@ -916,13 +856,11 @@ int nerf_occ_march_stop(const NerfOccGrid* grid, const float* density, float out
     GridArgs g;
     if (int rc = check_grid(__func__, grid, &g)) return rc;
     REQUIRE(density && rays && z_vals && z_stop && truncated && stopped, "null pointer");
-    REQUIRE(ray_stride >= 8 && n_rays >= 0 && n_steps >= 1 && n_steps <= 16384 && n_slots >= 1 && n_slots <= 4096,
-            "bad size (ray records need 8 columns, 1..16384 steps, 1..4096 slots)");
+    if (int rc = check_march_sizes(__func__, ray_stride, n_rays, n_steps, n_slots)) return rc;
     REQUIRE(tau > 0.0f, "bad threshold (tau = -ln(eps) must be > 0)");        // (a NaN fails the comparison)
-    if (n_rays == 0) return 0;
-    occ_march_stop_kernel<<<(unsigned)((n_rays + MARCH_RAYS - 1) / MARCH_RAYS), MARCH_THREADS, 0, (hipStream_t)stream>>>(
-        g, density, outside_sigma, rays, ray_stride, u, n_rays, n_steps, n_slots, tau, z_vals, z_stop, truncated, stopped);
-    return done(__func__, hipGetLastError());
+    const MarchArgs a = {density, outside_sigma, rays, ray_stride, u, n_rays, 0.0f, n_steps, n_slots, 0, tau, z_vals, z_stop, truncated, nullptr,
+                         stopped};
+    return launch_march(__func__, g, a, false, stream);
 }
 
 int nerf_occ_march_step(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride, const float* u,
@@ -932,20 +870,13 @@ int nerf_occ_march_step(const NerfOccGrid* grid, const float* density, float out
     if (int rc = check_grid(__func__, grid, &g)) return rc;
     REQUIRE(rays && z_vals && z_stop && truncated && level, "null pointer");
     REQUIRE((density != nullptr) == (stopped != nullptr), "null pointer (density and stopped come together: the stop form, or neither)");
-    REQUIRE(ray_stride >= 8 && n_rays >= 0 && n_steps >= 1 && n_steps <= 16384 && n_slots >= 1 && n_slots <= 4096,
-            "bad size (ray records need 8 columns, 1..16384 steps, 1..4096 slots)");
+    if (int rc = check_march_sizes(__func__, ray_stride, n_rays, n_steps, n_slots)) return rc;
     REQUIRE(fit >= 0 && fit <= 8, "bad fit (0..8 doublings of the step)");
     REQUIRE(step_size > 0.0f && step_size < INFINITY, "bad step_size (finite and > 0)");        // (a NaN fails the comparison)
     if (density) REQUIRE(tau > 0.0f, "bad threshold (tau = -ln(eps) must be > 0)");
-    if (n_rays == 0) return 0;
-    const unsigned blocks = (unsigned)((n_rays + MARCH_RAYS - 1) / MARCH_RAYS);
-    if (density)
-        occ_march_step_kernel<true><<<blocks, MARCH_THREADS, 0, (hipStream_t)stream>>>(
-            g, density, outside_sigma, rays, ray_stride, u, n_rays, step_size, n_steps, n_slots, fit, tau, z_vals, z_stop, truncated, level, stopped);
-    else
-        occ_march_step_kernel<false><<<blocks, MARCH_THREADS, 0, (hipStream_t)stream>>>(
-            g, nullptr, 0.0f, rays, ray_stride, u, n_rays, step_size, n_steps, n_slots, fit, 0.0f, z_vals, z_stop, truncated, level, nullptr);
-    return done(__func__, hipGetLastError());
+    const MarchArgs a = {density, outside_sigma, rays, ray_stride, u, n_rays, step_size, n_steps, n_slots, fit, tau, z_vals, z_stop, truncated,
+                         level, stopped};
+    return launch_march(__func__, g, a, true, stream);
 }
 
 int nerf_occ_expand(const int* slot, const float* raw_c, long n_points, float* raw, void* stream) {

@@ -72,6 +72,14 @@ def _check_march_step(step_size, fit, who):
     return float(step_size), int(fit)
 
 
+def _march_inputs(who, rays, n_steps, n_slots, u):
+    """(rays, u, M, S) as the march kernels take them: detached contiguous fp32 tensors (u may be None), 1 <= M <= 16384, 1 <= S <= 4096"""
+    M, S = int(n_steps), int(n_slots)
+    if not (1 <= M <= 16384) or not (1 <= S <= 4096):
+        raise ValueError(f"{who}: 1 <= n_steps <= 16384 and 1 <= n_slots <= 4096, got {n_steps!r}, {n_slots!r}")
+    return rays.detach().to(torch.float32).contiguous(), None if u is None else u.detach().to(torch.float32).contiguous(), M, S
+
+
 def stop_depth_reference(z_vals, weights, eps):
     """The definition of the stop depth of render_rays(early_stop_eps=eps), in numpy (tensors of any device; fp32 [N] on z_vals' device).
 
@@ -308,12 +316,9 @@ class OccupancyGrid:
         """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N]) for rays [N, >= 8] on the GPU (nerf_occ_march):
         ``march_reference`` bit for bit.  Constants of the graph (computed without gradients from detached values, as the reference
         detaches z_samples)."""
-        M, S = int(n_steps), int(n_slots)
-        if not (1 <= M <= 16384) or not (1 <= S <= 4096):
-            raise ValueError(f"OccupancyGrid.march: 1 <= n_steps <= 16384 and 1 <= n_slots <= 4096, got {n_steps!r}, {n_slots!r}")
+        rays, u, M, S = _march_inputs("OccupancyGrid.march", rays, n_steps, n_slots, u)
         with torch.no_grad():
-            z_vals, z_stop, truncated = hb.occ_march(self._desc(), rays.detach().to(torch.float32).contiguous(),
-                                                     None if u is None else u.detach().to(torch.float32).contiguous(), M, S)
+            z_vals, z_stop, truncated = hb.occ_march(self._desc(), rays, u, M, S)
         return z_vals, z_stop, truncated.bool()
 
     # ------------------------------------------------------------------ ray marching in world-space steps, fitted to the slots
@@ -422,14 +427,10 @@ class OccupancyGrid:
         """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N], level int32 [N]) for rays [N, >= 8] on the GPU
         (nerf_occ_march_step): ``march_step_reference`` bit for bit.  Constants of the graph (computed without gradients from detached
         values, like ``march``)."""
-        M, S = int(n_steps), int(n_slots)
-        if not (1 <= M <= 16384) or not (1 <= S <= 4096):
-            raise ValueError(f"OccupancyGrid.march_step: 1 <= n_steps <= 16384 and 1 <= n_slots <= 4096, got {n_steps!r}, {n_slots!r}")
+        rays, u, M, S = _march_inputs("OccupancyGrid.march_step", rays, n_steps, n_slots, u)
         step_size, fit = _check_march_step(step_size, fit, "OccupancyGrid.march_step")
         with torch.no_grad():
-            z_vals, z_stop, truncated, level, _ = hb.occ_march_step(self._desc(), None, 0.0, rays.detach().to(torch.float32).contiguous(),
-                                                                    None if u is None else u.detach().to(torch.float32).contiguous(),
-                                                                    step_size, M, S, fit)
+            z_vals, z_stop, truncated, level, _ = hb.occ_march_step(self._desc(), None, 0.0, rays, u, step_size, M, S, fit)
         return z_vals, z_stop, truncated.bool(), level
 
     # ------------------------------------------------------------------ checkpoints
@@ -712,14 +713,11 @@ class DensityGrid(OccupancyGrid):
         """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N], stopped bool [N]) for rays [N, >= 8] on the GPU
         (nerf_occ_march_stop): ``march_stop_reference`` bit for bit.  Constants of the graph (computed without gradients from detached
         values, like ``march``)."""
-        M, S = int(n_steps), int(n_slots)
-        if not (1 <= M <= 16384) or not (1 <= S <= 4096):
-            raise ValueError(f"DensityGrid.march_stop: 1 <= n_steps <= 16384 and 1 <= n_slots <= 4096, got {n_steps!r}, {n_slots!r}")
+        rays, u, M, S = _march_inputs("DensityGrid.march_stop", rays, n_steps, n_slots, u)
         eps = _check_march_eps(eps, "DensityGrid.march_stop")
         with torch.no_grad():
             z_vals, z_stop, truncated, stopped = hb.occ_march_stop(
-                self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0,
-                rays.detach().to(torch.float32).contiguous(), None if u is None else u.detach().to(torch.float32).contiguous(), M, S, eps)
+                self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0, rays, u, M, S, eps)
         return z_vals, z_stop, truncated.bool(), stopped.bool()
 
     # ------------------------------------------------------------------ the world-space march with the stop
@@ -739,16 +737,12 @@ class DensityGrid(OccupancyGrid):
     def march_step_stop(self, rays, step_size, n_steps, n_slots, eps, fit=0, u=None):
         """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N], level int32 [N], stopped bool [N]) for rays [N, >= 8] on the
         GPU (nerf_occ_march_step with the densities): ``march_step_stop_reference`` bit for bit.  Constants of the graph."""
-        M, S = int(n_steps), int(n_slots)
-        if not (1 <= M <= 16384) or not (1 <= S <= 4096):
-            raise ValueError(f"DensityGrid.march_step_stop: 1 <= n_steps <= 16384 and 1 <= n_slots <= 4096, got {n_steps!r}, {n_slots!r}")
+        rays, u, M, S = _march_inputs("DensityGrid.march_step_stop", rays, n_steps, n_slots, u)
         step_size, fit = _check_march_step(step_size, fit, "DensityGrid.march_step_stop")
         eps = _check_march_eps(eps, "DensityGrid.march_step_stop")
         with torch.no_grad():
             z_vals, z_stop, truncated, level, stopped = hb.occ_march_step(
-                self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0,
-                rays.detach().to(torch.float32).contiguous(), None if u is None else u.detach().to(torch.float32).contiguous(),
-                step_size, M, S, fit, eps)
+                self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0, rays, u, step_size, M, S, fit, eps)
         return z_vals, z_stop, truncated.bool(), level, stopped.bool()
 
     # ------------------------------------------------------------------ checkpoints

@@ -13,7 +13,8 @@ from test_gpu_occupancy import BOX_HI, BOX_LO, ball_grid, bits_equal
 from test_gpu_occupancy_train import U, _small_scene, datapath_fp16x3, flat_of, fresh_nets, grads_of, zero_grads  # noqa: F401
 from test_gpu_parity import datapath, dev, maxdiff, nets, npa  # noqa: F401  (fixtures)
 from test_gpu_ray_grad import rel_l2
-from test_march_stop_cpu import ball_density_grid
+from test_march_cpu import hand_grid, hand_rays
+from test_march_stop_cpu import ball_density_grid, hand_dgrid
 
 pytestmark = pytest.mark.gpu
 
@@ -116,6 +117,81 @@ def test_kernel_equals_the_definitions_bit_for_bit(npa, dev, outside, ds, M, S, 
         assert seen["truncated"] > 0
     if S >= 32 and ds < 0.1:        # (with one or four slots nothing is emitted in front of a cut, or the slot limit bites first)
         assert seen["stopped"] > 0
+
+
+# ------------------------------------------------------------------------------------------------ 1b. the two kinds of steps agree
+# Rays 0 .. 6 of tests/test_march_cpu.hand_rays (pattern row, full row, miss, NaN component, near == far, near > far, infinite
+# direction) have |d| = 1, near = 0 and far = 8; with ds * M = 8, all powers of two, (k + u) * ds and (k + u) / M * far are the same
+# exact scalings and no candidate is cut by z < far before k = M: march_step_reference's docstring promises level 0 equal to
+# march_reference, and the same holds for the two stop definitions.
+AGREE_STEPS = [(16, 0.5), (128, 1.0 / 16), (1024, 1.0 / 128)]
+AGREE_EPS = 1e-2
+
+
+def agree_references(outside, density, M, ds, S, u):
+    """(equal steps, world steps at fit = 0) of the definitions on the CPU, each (z_vals, z_stop, truncated, level, stopped); density
+    None: the plain forms (stopped all False), else the stop forms on that hand-made density"""
+    rays = hand_rays()[:7]
+    if density is None:
+        grid = hand_grid(outside)
+        a = grid.march_reference(rays, u, M, S)
+        a = a + (torch.zeros(7, dtype=torch.int32), torch.zeros_like(a[2]))
+        b = grid.march_step_reference(rays, u, ds, M, S, 0)
+        return a, b + (torch.zeros_like(b[2]),)
+    grid = hand_dgrid(outside, density)
+    a = grid.march_stop_reference(rays, u, M, S, AGREE_EPS)
+    return a[:3] + (torch.zeros(7, dtype=torch.int32), a[3]), grid.march_step_stop_reference(rays, u, ds, M, S, AGREE_EPS, 0)
+
+
+def assert_case_mix(want, density, M, S):
+    """the rays of an agreement run do what the run is there for: some emit, some are truncated, some stop"""
+    z, z_stop, tr, _, st = want
+    if S >= 5:
+        assert int((z[:, 0] < z_stop).sum()) >= 2, (density, M, S)      # (a padded slot holds z_stop; an invalid ray's z_stop is -inf)
+    if (M, S) == (16, 64) and density not in (None, "zero"):
+        assert int(st.sum()) >= 1, (density, M, S)
+    if (M, S) == (128, 5):
+        assert int(tr.sum()) >= 2, (density, M, S)
+
+
+@pytest.mark.parametrize("outside", ["evaluate", "skip"])
+def test_world_steps_at_fit_0_equal_equal_steps_on_a_power_of_two_geometry(npa, dev, outside):
+    """hb.occ_march_step(fit=0) equals hb.occ_march, and its stop form hb.occ_march_stop at eps = 1e-2 on the "late", "odd", "run" and
+    "zero" densities, as raw bits in z_vals and z_stop, with equal flags and level 0 everywhere -- and both equal both definitions."""
+    hb = npa.hip_backend
+    rays = hand_rays()[:7].contiguous().to(dev)
+    g = torch.Generator().manual_seed(19)
+    for density, slots in [(None, (64, 20, 5, 1))] + [(d, (64, 20, 5)) for d in ("late", "odd", "run", "zero")]:
+        grid = (hand_grid(outside) if density is None else hand_dgrid(outside, density)).to(dev)
+        dens = None if density is None else grid.density
+        out_sigma = grid.sigma_threshold if density is not None and outside == "evaluate" else 0.0
+        for M, ds in AGREE_STEPS:
+            for S in slots:
+                for u in (None, torch.rand(7, generator=g)):
+                    want, want_step = agree_references(outside, density, M, ds, S, u)
+                    assert_same(want_step, want, ("the definitions", density, M, S))
+                    assert_case_mix(want, density, M, S)
+                    ud = None if u is None else u.to(dev)
+                    if density is None:
+                        z, z_stop, tr = hb.occ_march(grid._desc(), rays, ud, M, S)
+                        st = None
+                    else:
+                        z, z_stop, tr, st = hb.occ_march_stop(grid._desc(), dens, out_sigma, rays, ud, M, S, AGREE_EPS)
+                    zs, zs_stop, trs, lv, sts = hb.occ_march_step(grid._desc(), dens, out_sigma, rays, ud, ds, M, S, 0,
+                                                                  None if density is None else AGREE_EPS)
+                    torch.cuda.synchronize()
+                    what = (density, M, S, u is None)
+                    assert bits_equal(zs, z) and bits_equal(zs_stop, z_stop) and torch.equal(trs, tr), what
+                    assert not bool(lv.any()) and (sts is None) == (density is None), what
+                    if density is not None:
+                        assert torch.equal(sts, st), what
+                    got = (z.cpu(), z_stop.cpu(), tr.cpu().bool(), lv.cpu(), want[4] if st is None else st.cpu().bool())
+                    assert_same(got, want, ("the kernels against the definitions",) + what)
+
+
+def assert_same(got, want, what):
+    assert bits_equal(got[0], want[0]) and bits_equal(got[1], want[1]), (what, got[0], want[0], got[1], want[1])
+    assert torch.equal(got[2], want[2]) and torch.equal(got[3], want[3]) and torch.equal(got[4], want[4]), (what, got[2:], want[2:])
 
 
 # ------------------------------------------------------------------------------------------------ 2. the render against the chain
