@@ -815,6 +815,33 @@ int launch_march(const char* fn, const GridArgs& g, const MarchArgs& a, bool wor
     return done(fn, hipGetLastError());
 }
 
+// the one body of the three march entry points (fn: the public function's name).  MARCH_PLAIN and MARCH_STOP take equal steps, without
+// and with the densities; MARCH_STEP takes world-space steps, and whether density and stopped are there chooses its stop form.
+enum MarchForm { MARCH_PLAIN, MARCH_STOP, MARCH_STEP };
+int march_entry(const char* fn, MarchForm form, const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays,
+                int ray_stride, const float* u, int n_rays, float step_size, int n_steps, int n_slots, int fit, float tau, float* z_vals,
+                float* z_stop, int* truncated, int* level, int* stopped, void* stream) {
+    const bool world = form == MARCH_STEP;
+    GridArgs g;
+    if (int rc = check_grid(fn, grid, &g)) return rc;
+    bool have = rays && z_vals && z_stop && truncated;                  // what every form needs
+    if (form == MARCH_STOP) have = have && density && stopped;
+    if (form == MARCH_STEP) have = have && level;
+    if (!have) return fail_arg(fn, "null pointer");
+    if (world && (density != nullptr) != (stopped != nullptr))
+        return fail_arg(fn, "null pointer (density and stopped come together: the stop form, or neither)");
+    if (int rc = check_march_sizes(fn, ray_stride, n_rays, n_steps, n_slots)) return rc;
+    if (world && !(fit >= 0 && fit <= 8)) return fail_arg(fn, "bad fit (0..8 doublings of the step)");
+    if (world && !(step_size > 0.0f && step_size < INFINITY)) return fail_arg(fn, "bad step_size (finite and > 0)");     // (a NaN fails the comparison)
+    if (density && !(tau > 0.0f)) return fail_arg(fn, "bad threshold (tau = -ln(eps) must be > 0)");                    // (a NaN fails the comparison)
+    MarchArgs a;
+    a.rays = rays; a.ray_stride = ray_stride; a.u = u; a.n_rays = n_rays; a.M = n_steps; a.S = n_slots;
+    a.z_vals = z_vals; a.z_stop = z_stop; a.truncated = truncated;
+    a.ds = step_size; a.fit = fit; a.level = level;                                         // WorldSteps
+    a.density = density; a.outside_sigma = outside_sigma; a.tau = tau; a.stopped = stopped;    // STOP
+    return launch_march(fn, g, a, world, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -842,41 +869,22 @@ int nerf_occ_stop_depth(const float* z_vals, const float* weights, int n_rays, i
 
 int nerf_occ_march(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* u, int n_rays, int n_steps, int n_slots,
                    float* z_vals, float* z_stop, int* truncated, void* stream) {
-    GridArgs g;
-    if (int rc = check_grid(__func__, grid, &g)) return rc;
-    REQUIRE(rays && z_vals && z_stop && truncated, "null pointer");
-    if (int rc = check_march_sizes(__func__, ray_stride, n_rays, n_steps, n_slots)) return rc;
-    const MarchArgs a = {nullptr, 0.0f, rays, ray_stride, u, n_rays, 0.0f, n_steps, n_slots, 0, 0.0f, z_vals, z_stop, truncated, nullptr, nullptr};
-    return launch_march(__func__, g, a, false, stream);
+    return march_entry(__func__, MARCH_PLAIN, grid, nullptr, 0.0f, rays, ray_stride, u, n_rays, 0.0f, n_steps, n_slots, 0, 0.0f, z_vals, z_stop,
+                       truncated, nullptr, nullptr, stream);
 }
 
 int nerf_occ_march_stop(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride, const float* u,
                         int n_rays, int n_steps, int n_slots, float tau, float* z_vals, float* z_stop, int* truncated, int* stopped,
                         void* stream) {
-    GridArgs g;
-    if (int rc = check_grid(__func__, grid, &g)) return rc;
-    REQUIRE(density && rays && z_vals && z_stop && truncated && stopped, "null pointer");
-    if (int rc = check_march_sizes(__func__, ray_stride, n_rays, n_steps, n_slots)) return rc;
-    REQUIRE(tau > 0.0f, "bad threshold (tau = -ln(eps) must be > 0)");        // (a NaN fails the comparison)
-    const MarchArgs a = {density, outside_sigma, rays, ray_stride, u, n_rays, 0.0f, n_steps, n_slots, 0, tau, z_vals, z_stop, truncated, nullptr,
-                         stopped};
-    return launch_march(__func__, g, a, false, stream);
+    return march_entry(__func__, MARCH_STOP, grid, density, outside_sigma, rays, ray_stride, u, n_rays, 0.0f, n_steps, n_slots, 0, tau, z_vals,
+                       z_stop, truncated, nullptr, stopped, stream);
 }
 
 int nerf_occ_march_step(const NerfOccGrid* grid, const float* density, float outside_sigma, const float* rays, int ray_stride, const float* u,
                         int n_rays, float step_size, int n_steps, int n_slots, int fit, float tau, float* z_vals, float* z_stop,
                         int* truncated, int* level, int* stopped, void* stream) {
-    GridArgs g;
-    if (int rc = check_grid(__func__, grid, &g)) return rc;
-    REQUIRE(rays && z_vals && z_stop && truncated && level, "null pointer");
-    REQUIRE((density != nullptr) == (stopped != nullptr), "null pointer (density and stopped come together: the stop form, or neither)");
-    if (int rc = check_march_sizes(__func__, ray_stride, n_rays, n_steps, n_slots)) return rc;
-    REQUIRE(fit >= 0 && fit <= 8, "bad fit (0..8 doublings of the step)");
-    REQUIRE(step_size > 0.0f && step_size < INFINITY, "bad step_size (finite and > 0)");        // (a NaN fails the comparison)
-    if (density) REQUIRE(tau > 0.0f, "bad threshold (tau = -ln(eps) must be > 0)");
-    const MarchArgs a = {density, outside_sigma, rays, ray_stride, u, n_rays, step_size, n_steps, n_slots, fit, tau, z_vals, z_stop, truncated,
-                         level, stopped};
-    return launch_march(__func__, g, a, true, stream);
+    return march_entry(__func__, MARCH_STEP, grid, density, outside_sigma, rays, ray_stride, u, n_rays, step_size, n_steps, n_slots, fit, tau,
+                       z_vals, z_stop, truncated, level, stopped, stream);
 }
 
 int nerf_occ_expand(const int* slot, const float* raw_c, long n_points, float* raw, void* stream) {

@@ -1254,7 +1254,8 @@ def occ_stop_depth(z_vals, weights, eps):
 
 
 def _march_io(who, desc, rays, u, n_slots, flags, density=None, unpaired=False):
-    """the checks and the outputs the three marches share: (n, stride, z_vals fp32 [n, n_slots], z_stop fp32 [n], `flags` int32 [n] each)"""
+    """the checks, the timing block (<who>_kernel, entered around the launch) and the outputs the three marches share:
+    (n, stride, timed, z_vals fp32 [n, n_slots], z_stop fp32 [n], `flags` int32 [n] each)"""
     if rays.dim() != 2 or rays.shape[1] < 8:
         raise NerfHipError(f"{who}: rays [n, >= 8] (o, d, near, far, ...)")
     n, stride = rays.shape
@@ -1264,8 +1265,8 @@ def _march_io(who, desc, rays, u, n_slots, flags, density=None, unpaired=False):
         raise NerfHipError(f"{who}: density and eps come together (the stop form) or not at all")
     if density is not None and density.numel() != desc.res[0] * desc.res[1] * desc.res[2]:
         raise NerfHipError(f"{who}: one density per cell of the grid")
-    out = [n, stride, torch.empty((n, int(n_slots)), dtype=torch.float32, device=rays.device),
-           torch.empty(n, dtype=torch.float32, device=rays.device)]
+    out = [n, stride, _timed(who + "_kernel", 0.0, (4.0 * int(n_slots) + 40.0 + 4.0 * flags) * n),
+           torch.empty((n, int(n_slots)), dtype=torch.float32, device=rays.device), torch.empty(n, dtype=torch.float32, device=rays.device)]
     for _ in range(flags):
         out.append(torch.empty(n, dtype=torch.int32, device=rays.device))
     return out
@@ -1275,9 +1276,9 @@ def occ_march(desc, rays, u, n_steps, n_slots):
     """nerf_occ_march: (z_vals fp32 [n, n_slots], z_stop fp32 [n], truncated int32 [n]) of rays [n, >= 8] -- per ray the n_steps equal
     steps over [near, far] that fall in occupied cells (plus one closing step behind every occupied run), padded with the stop depth
     that nerf_occ_compact_stop drops; u: fp32 [n] in [0, 1), the offset of the ray's steps, or None (0.5)"""
-    n, stride, z_vals, z_stop, truncated = _march_io("occ_march", desc, rays, u, n_slots, 1)
+    n, stride, timed, z_vals, z_stop, truncated = _march_io("occ_march", desc, rays, u, n_slots, 1)
     M, S = int(n_steps), int(n_slots)
-    with _timed("occ_march_kernel", 0.0, (4.0 * S + 44.0) * n):
+    with timed:
         _check(lib().nerf_occ_march(ctypes.byref(desc), _ptr(rays, "rays"), stride, _ptr(u, "u", True), n, M, S, _ptr(z_vals), _ptr(z_stop),
                                     truncated.data_ptr(), _stream()), "nerf_occ_march")
     return z_vals, z_stop, truncated
@@ -1295,9 +1296,9 @@ def occ_march_stop(desc, density, outside_sigma, rays, u, n_steps, n_slots, eps)
     occ_march over a DensityGrid's densities (fp32 [cells]; outside the box outside_sigma, as occ_proposal_weights takes them) that stops
     emitting where the grid's own transmittance has fallen to eps (0 < eps < 1); a stopped ray's stop depth is the first candidate not
     emitted"""
-    n, stride, z_vals, z_stop, truncated, stopped = _march_io("occ_march_stop", desc, rays, u, n_slots, 2, density)
+    n, stride, timed, z_vals, z_stop, truncated, stopped = _march_io("occ_march_stop", desc, rays, u, n_slots, 2, density)
     M, S = int(n_steps), int(n_slots)
-    with _timed("occ_march_stop_kernel", 0.0, (4.0 * S + 48.0) * n):
+    with timed:
         _check(lib().nerf_occ_march_stop(ctypes.byref(desc), _ptr(density, "density"), float(outside_sigma), _ptr(rays, "rays"), stride,
                                          _ptr(u, "u", True), n, M, S, march_stop_threshold(eps), _ptr(z_vals), _ptr(z_stop),
                                          truncated.data_ptr(), stopped.data_ptr(), _stream()), "nerf_occ_march_stop")
@@ -1309,11 +1310,11 @@ def occ_march_step(desc, density, outside_sigma, rays, u, step_size, n_steps, n_
     rays [n, >= 8] -- the march in steps of step_size along the ray (a length in the scene: the depth step is step_size / |d|), at most
     n_steps candidates in front of far, and per ray the step doubled up to `fit` times until the emitted steps fit the slots (level: how
     often).  density None (eps None): occ_march's rule per level, stopped is None; density fp32 [cells] with eps: occ_march_stop's"""
-    n, stride, z_vals, z_stop, truncated, level, *stopped = _march_io("occ_march_step", desc, rays, u, n_slots, 2 if density is None else 3,
-                                                                      density, unpaired=(density is None) != (eps is None))
+    n, stride, timed, z_vals, z_stop, truncated, level, *stopped = _march_io(
+        "occ_march_step", desc, rays, u, n_slots, 2 if density is None else 3, density, unpaired=(density is None) != (eps is None))
     stopped = stopped[0] if stopped else None
     M, S = int(n_steps), int(n_slots)
-    with _timed("occ_march_step_kernel", 0.0, (4.0 * S + (52.0 if stopped is not None else 48.0)) * n):
+    with timed:
         _check(lib().nerf_occ_march_step(ctypes.byref(desc), _ptr(density, "density", True), float(outside_sigma), _ptr(rays, "rays"), stride,
                                          _ptr(u, "u", True), n, float(step_size), M, S, int(fit),
                                          0.0 if eps is None else march_stop_threshold(eps), _ptr(z_vals), _ptr(z_stop),

@@ -285,32 +285,8 @@ class OccupancyGrid:
         evaluated sample's interval z[i + 1] - z[i] reaches exactly to the next candidate and never across a gap.  Padding and
         truncation ride on z_stop: nerf_occ_compact_stop's not (z >= z_stop) drops every slot at or behind it, the last one -- the
         reference's 1e10 interval -- included.  Rows are nondecreasing: nothing is sorted."""
-        M, S = int(n_steps), int(n_slots)
-        if M < 1 or S < 1:
-            raise ValueError("march_reference: n_steps >= 1 and n_slots >= 1")
-        if rays.dim() != 2 or rays.shape[1] < 8:
-            raise ValueError("march_reference: rays [N, >= 8] (o, d, near, far, ...)")
-        dev = rays.device
-        r = rays.detach()[:, :8].to(torch.float32)
-        N = r.shape[0]
-        ok = torch.isfinite(r).all(-1) & (r[:, 6] < r[:, 7])
-        near, far = r[:, 6:7], r[:, 7:8]
-        uu = torch.full((N, 1), 0.5, dtype=torch.float32, device=dev) if u is None else u.detach().to(device=dev, dtype=torch.float32).reshape(N, 1)
-        k = torch.arange(M, dtype=torch.float32, device=dev)[None, :]
-        t = (k + uu) / torch.tensor(float(M), dtype=torch.float32, device=dev)
-        z = near * (1.0 - t) + far * t
-        keep = self.occupied(r[:, None, 0:3] + r[:, None, 3:6] * z[:, :, None]) & ok[:, None]
-        before = torch.cat([torch.zeros_like(keep[:, :1]), keep[:, :-1]], -1)
-        emit = keep | (before & ~keep)
-        rank = torch.cumsum(emit.to(torch.int64), -1) - 1
-        truncated = emit.sum(-1) > S - 1
-        first_out = emit & (rank == S - 1)          # (at most one per row)
-        z_stop = torch.where(truncated, z.gather(1, first_out.to(torch.uint8).argmax(-1, keepdim=True))[:, 0], r[:, 7])
-        z_stop = torch.where(ok, z_stop, torch.full_like(z_stop, float("-inf")))
-        z_vals = torch.where(ok, z_stop, r[:, 7])[:, None].repeat(1, S)
-        rows, cols = (emit & (rank < S - 1)).nonzero(as_tuple=True)
-        z_vals[rows, rank[rows, cols]] = z[rows, cols]
-        return z_vals, z_stop, truncated
+        r, ok, uu, _, M, S = self._march_rays("march_reference", rays, u, n_steps, n_slots)
+        return self._march_walk(r, ok, *self._equal_steps(r, ok, uu, M), S)[:3]
 
     def march(self, rays, n_steps, n_slots, u=None):
         """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N]) for rays [N, >= 8] on the GPU (nerf_occ_march):
@@ -321,20 +297,52 @@ class OccupancyGrid:
             z_vals, z_stop, truncated = hb.occ_march(self._desc(), rays, u, M, S)
         return z_vals, z_stop, truncated.bool()
 
-    # ------------------------------------------------------------------ ray marching in world-space steps, fitted to the slots
-    def _march_step_level(self, r, ok, uu, dz, dn, M, S, tau):
-        """one level of the world-space march for the valid rays' step dz [N, 1] (plain torch): (z_vals, z_stop, truncated, stopped).
-        tau None: the plain rule; else a DensityGrid's stop rule on top.  Candidates behind the last one that is valid on ANY ray are
-        not built: they emit nothing, add nothing to an optical depth and cut nothing."""
-        dev = r.device
+    # ------------------------------------------------------------------ the march references: one walk, two ways to step
+    @staticmethod
+    def _march_rays(who, rays, u, n_steps, n_slots):
+        """what every march reference starts from: (r fp32 [N, 8], ok bool [N] -- all finite and near < far --, u fp32 [N, 1],
+        |d| fp32 [N, 1], M, S)"""
+        M, S = int(n_steps), int(n_slots)
+        if M < 1 or S < 1:
+            raise ValueError(f"{who}: n_steps >= 1 and n_slots >= 1")
+        if rays.dim() != 2 or rays.shape[1] < 8:
+            raise ValueError(f"{who}: rays [N, >= 8] (o, d, near, far, ...)")
+        dev = rays.device
+        r = rays.detach()[:, :8].to(torch.float32)
         N = r.shape[0]
-        near, far = r[:, 6:7], r[:, 7:8]
-        kf = torch.arange(M, dtype=torch.float32, device=dev)[None, :]
-        z = near + (kf + uu) * dz
-        valid = (z < far) & ok[:, None]
+        ok = torch.isfinite(r).all(-1) & (r[:, 6] < r[:, 7])
+        uu = torch.full((N, 1), 0.5, dtype=torch.float32, device=dev) if u is None else u.detach().to(device=dev, dtype=torch.float32).reshape(N, 1)
+        d = r[:, 3:6]
+        # the correctly rounded fp32 square root, taken through float64 (53 >= 2 * 24 + 2 bits: rounding twice is rounding once): a torch
+        # build's own fp32 sqrt may be a vector-library routine that is an ulp off on some CPUs; the world-space step puts that ulp
+        # into every depth, and an optical depth next to tau can turn a stop on it
+        dn = torch.sqrt((d[:, 0:1] * d[:, 0:1] + d[:, 1:2] * d[:, 1:2] + d[:, 2:3] * d[:, 2:3]).to(torch.float64)).to(torch.float32)
+        return r, ok, uu, dn, M, S
+
+    @staticmethod
+    def _equal_steps(r, ok, uu, M):
+        """(z fp32 [N, M], valid bool [N, M]) of the M equal steps over [near, far]: every candidate of a valid ray counts"""
+        k = torch.arange(M, dtype=torch.float32, device=r.device)[None, :]
+        t = (k + uu) / torch.tensor(float(M), dtype=torch.float32, device=r.device)
+        return r[:, 6:7] * (1.0 - t) + r[:, 7:8] * t, ok[:, None].expand(-1, M)
+
+    @staticmethod
+    def _world_steps(r, ok, uu, dz, M):
+        """(z fp32 [N, K], valid bool [N, K]) of the steps dz [N, 1]: a candidate counts while it lies in front of far.  Candidates
+        behind the last one that is valid on ANY ray are not built: they emit nothing, add nothing to an optical depth and cut nothing."""
+        z = r[:, 6:7] + (torch.arange(M, dtype=torch.float32, device=r.device)[None, :] + uu) * dz
+        valid = (z < r[:, 7:8]) & ok[:, None]
         cols = valid.any(0).nonzero()
         K = min(M, (int(cols.max()) + 2) if cols.numel() else 1)       # (one column more: the candidate behind the last valid one)
-        z, valid = z[:, :K], valid[:, :K]
+        return z[:, :K], valid[:, :K]
+
+    def _march_walk(self, r, ok, z, valid, S, dn=None, tau=None):
+        """the rule of the four march references, once (plain torch): (z_vals, z_stop, truncated, stopped) of the rays r [N, 8] -- ok
+        [N] says which are valid -- for the candidate depths z [N, K], of which those under valid [N, K] count (a prefix of every row).
+        tau None: the plain rule; else a DensityGrid's stop rule on top, with |d| = dn [N, 1]."""
+        dev = r.device
+        N, K = z.shape
+        far = r[:, 7:8]
         pts = r[:, None, 0:3] + r[:, None, 3:6] * z[:, :, None]
         keep = self.occupied(pts) & valid
         before = torch.cat([torch.zeros_like(keep[:, :1]), keep[:, :-1]], -1)
@@ -372,31 +380,22 @@ class OccupancyGrid:
         return z_vals, z_stop, truncated, stopped
 
     def _march_step_levels(self, who, rays, u, step_size, n_steps, n_slots, fit, tau):
-        M, S = int(n_steps), int(n_slots)
-        if M < 1 or S < 1:
-            raise ValueError(f"{who}: n_steps >= 1 and n_slots >= 1")
-        if rays.dim() != 2 or rays.shape[1] < 8:
-            raise ValueError(f"{who}: rays [N, >= 8] (o, d, near, far, ...)")
+        """the levels of the world-space march over the shared walk: (z_vals, z_stop, truncated, level, stopped)"""
+        r, ok, uu, dn, M, S = self._march_rays(who, rays, u, n_steps, n_slots)
         step_size, fit = _check_march_step(step_size, fit, who)
         dev = rays.device
-        r = rays.detach()[:, :8].to(torch.float32)
-        N = r.shape[0]
-        d = r[:, 3:6]
-        # the correctly rounded fp32 square root, taken through float64 (53 >= 2 * 24 + 2 bits: rounding twice is rounding once): a torch
-        # build's own fp32 sqrt may be a vector-library routine that is an ulp off on some CPUs, and the step, unlike an optical depth,
-        # puts that ulp into every depth
-        dn = torch.sqrt((d[:, 0:1] * d[:, 0:1] + d[:, 1:2] * d[:, 1:2] + d[:, 2:3] * d[:, 2:3]).to(torch.float64)).to(torch.float32)
         dz0 = torch.tensor(step_size, dtype=torch.float32, device=dev) / dn
-        ok = torch.isfinite(r).all(-1) & (r[:, 6] < r[:, 7]) & (dz0[:, 0] > 0) & torch.isfinite(dz0[:, 0])
-        uu = torch.full((N, 1), 0.5, dtype=torch.float32, device=dev) if u is None else u.detach().to(device=dev, dtype=torch.float32).reshape(N, 1)
-        out = list(self._march_step_level(r, ok, uu, dz0, dn, M, S, tau))
-        level = torch.zeros(N, dtype=torch.int32, device=dev)
+        ok = ok & (dz0[:, 0] > 0) & torch.isfinite(dz0[:, 0])
+
+        def walk(rows, dz):
+            return self._march_walk(r[rows], ok[rows], *self._world_steps(r[rows], ok[rows], uu[rows], dz, M), S, dn[rows], tau)
+        out = list(walk(slice(None), dz0))
+        level = torch.zeros(r.shape[0], dtype=torch.int32, device=dev)
         for j in range(1, fit + 1):
             again = out[2].nonzero()[:, 0]          # the rays still truncated walk again with the step doubled
             if again.numel() == 0:
                 break
-            dz = dz0[again] * torch.tensor(float(1 << j), dtype=torch.float32, device=dev)
-            nxt = self._march_step_level(r[again], ok[again], uu[again], dz, dn[again], M, S, tau)
+            nxt = walk(again, dz0[again] * torch.tensor(float(1 << j), dtype=torch.float32, device=dev))
             for a, b in zip(out, nxt):
                 a[again] = b
             level[again] = j
@@ -612,6 +611,11 @@ class DensityGrid(OccupancyGrid):
         return True
 
     # ------------------------------------------------------------------ importance samples from the grid
+    def outside_sigma(self):
+        """the density of a point outside the box: sigma_threshold -- the least density the grid calls occupied -- with
+        outside="evaluate", 0 with outside="skip" (``proposal_sigma``; the kernels take it as their outside_sigma argument)"""
+        return self.sigma_threshold if self.outside == "evaluate" else 0.0
+
     def proposal_sigma(self, pts):
         """fp32 [...] for pts [..., 3] (any device): the density render_rays(proposal="grid") composites at a sample point, the
         definition nerf_occ_proposal_weights reproduces bit for bit (as ``occupied()`` is the classifier's).  The point is classified
@@ -621,7 +625,7 @@ class DensityGrid(OccupancyGrid):
         inside, c, bit = self._classify(pts)
         density = self.density if self.density.device == pts.device else self.density.to(pts.device)
         zero = torch.zeros((), dtype=torch.float32, device=pts.device)
-        out = torch.tensor(self.sigma_threshold if self.outside == "evaluate" else 0.0, dtype=torch.float32, device=pts.device)
+        out = torch.tensor(self.outside_sigma(), dtype=torch.float32, device=pts.device)
         return torch.where(inside, torch.where(bit, density[c], zero), out)
 
     def proposal_weights(self, rays, z_vals, want_sigma=False):
@@ -630,9 +634,8 @@ class DensityGrid(OccupancyGrid):
         noise.  A grid that was never updated has density 0 everywhere: every sample inside the box has a weight of exactly 0, which
         sample_pdf's 1e-5 floor turns into a uniform pdf.  Constants of the graph (computed without gradients from detached values).  want_sigma: (weights, sigma)."""
         with torch.no_grad():
-            w, sigma = hb.occ_proposal_weights(self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0,
-                                               rays.detach().to(torch.float32).contiguous(), z_vals.detach().to(torch.float32).contiguous(),
-                                               want_sigma)
+            w, sigma = hb.occ_proposal_weights(self._desc(), self.density, self.outside_sigma(), rays.detach().to(torch.float32).contiguous(),
+                                               z_vals.detach().to(torch.float32).contiguous(), want_sigma)
         return (w, sigma) if want_sigma else w
 
     # ------------------------------------------------------------------ the march that stops on the grid's own transmittance
@@ -659,55 +662,9 @@ class DensityGrid(OccupancyGrid):
         A only grows at kept candidates, so k_stop - 1 is always a kept candidate, and its interval ends exactly at z_stop, as every
         marched sample's does.  A grid that was never updated (density == 0) never stops: z_vals, z_stop and truncated then equal
         march_reference's bit for bit."""
-        M, S = int(n_steps), int(n_slots)
-        if M < 1 or S < 1:
-            raise ValueError("march_stop_reference: n_steps >= 1 and n_slots >= 1")
-        if rays.dim() != 2 or rays.shape[1] < 8:
-            raise ValueError("march_stop_reference: rays [N, >= 8] (o, d, near, far, ...)")
+        r, ok, uu, dn, M, S = self._march_rays("march_stop_reference", rays, u, n_steps, n_slots)
         tau = torch.tensor(hb.march_stop_threshold(_check_march_eps(eps, "march_stop_reference")), dtype=torch.float32, device=rays.device)
-        dev = rays.device
-        r = rays.detach()[:, :8].to(torch.float32)
-        N = r.shape[0]
-        ok = torch.isfinite(r).all(-1) & (r[:, 6] < r[:, 7])
-        near, far = r[:, 6:7], r[:, 7:8]
-        uu = torch.full((N, 1), 0.5, dtype=torch.float32, device=dev) if u is None else u.detach().to(device=dev, dtype=torch.float32).reshape(N, 1)
-        k = torch.arange(M, dtype=torch.float32, device=dev)[None, :]
-        t = (k + uu) / torch.tensor(float(M), dtype=torch.float32, device=dev)
-        z = near * (1.0 - t) + far * t
-        z_next = torch.cat([z[:, 1:], far], -1)
-        pts = r[:, None, 0:3] + r[:, None, 3:6] * z[:, :, None]
-        keep = self.occupied(pts) & ok[:, None]
-        # the optical depth of every candidate
-        sigma = self.proposal_sigma(pts)
-        sigma = torch.where(sigma > 0, sigma, torch.zeros_like(sigma))
-        d = r[:, 3:6]
-        dn = torch.sqrt(d[:, 0:1] * d[:, 0:1] + d[:, 1:2] * d[:, 1:2] + d[:, 2:3] * d[:, 2:3])
-        c = torch.where(keep, sigma * ((z_next - z) * dn), torch.zeros_like(z))
-        # its exclusive prefix sum, in the order of the kernel's wave scan
-        rounds = (M + 63) // 64
-        incl = torch.cat([c, torch.zeros((N, rounds * 64 - M), dtype=torch.float32, device=dev)], -1).view(N, rounds, 64)
-        for s in (1, 2, 4, 8, 16, 32):
-            incl = torch.cat([incl[..., :s], incl[..., s:] + incl[..., :-s]], -1)
-        base = torch.zeros((N, rounds), dtype=torch.float32, device=dev)
-        for j in range(1, rounds):
-            base[:, j] = base[:, j - 1] + incl[:, j - 1, 63]
-        A = (base[:, :, None] + torch.cat([torch.zeros_like(incl[..., :1]), incl[..., :-1]], -1)).view(N, rounds * 64)[:, :M]
-        cut = A >= tau                                  # (a NaN never is)
-        has_cut = cut.any(-1)
-        k_stop = torch.where(has_cut, cut.to(torch.uint8).argmax(-1), torch.full((N,), M, dtype=torch.int64, device=dev))
-        before = torch.cat([torch.zeros_like(keep[:, :1]), keep[:, :-1]], -1)
-        emit = (keep | (before & ~keep)) & (torch.arange(M, device=dev)[None, :] < k_stop[:, None])
-        rank = torch.cumsum(emit.to(torch.int64), -1) - 1
-        truncated = emit.sum(-1) > S - 1
-        stopped = has_cut & ~truncated
-        first_out = emit & (rank == S - 1)          # (at most one per row)
-        z_stop = torch.where(truncated, z.gather(1, first_out.to(torch.uint8).argmax(-1, keepdim=True))[:, 0], r[:, 7])
-        z_stop = torch.where(stopped, z.gather(1, k_stop.clamp(max=M - 1)[:, None])[:, 0], z_stop)
-        z_stop = torch.where(ok, z_stop, torch.full_like(z_stop, float("-inf")))
-        z_vals = torch.where(ok, z_stop, r[:, 7])[:, None].repeat(1, S)
-        rows, cols = (emit & (rank < S - 1)).nonzero(as_tuple=True)
-        z_vals[rows, rank[rows, cols]] = z[rows, cols]
-        return z_vals, z_stop, truncated, stopped
+        return self._march_walk(r, ok, *self._equal_steps(r, ok, uu, M), S, dn, tau)
 
     def march_stop(self, rays, n_steps, n_slots, eps, u=None):
         """(z_vals fp32 [N, n_slots], z_stop fp32 [N], truncated bool [N], stopped bool [N]) for rays [N, >= 8] on the GPU
@@ -716,8 +673,7 @@ class DensityGrid(OccupancyGrid):
         rays, u, M, S = _march_inputs("DensityGrid.march_stop", rays, n_steps, n_slots, u)
         eps = _check_march_eps(eps, "DensityGrid.march_stop")
         with torch.no_grad():
-            z_vals, z_stop, truncated, stopped = hb.occ_march_stop(
-                self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0, rays, u, M, S, eps)
+            z_vals, z_stop, truncated, stopped = hb.occ_march_stop(self._desc(), self.density, self.outside_sigma(), rays, u, M, S, eps)
         return z_vals, z_stop, truncated.bool(), stopped.bool()
 
     # ------------------------------------------------------------------ the world-space march with the stop
@@ -742,7 +698,7 @@ class DensityGrid(OccupancyGrid):
         eps = _check_march_eps(eps, "DensityGrid.march_step_stop")
         with torch.no_grad():
             z_vals, z_stop, truncated, level, stopped = hb.occ_march_step(
-                self._desc(), self.density, self.sigma_threshold if self.outside == "evaluate" else 0.0, rays, u, step_size, M, S, fit, eps)
+                self._desc(), self.density, self.outside_sigma(), rays, u, step_size, M, S, fit, eps)
         return z_vals, z_stop, truncated.bool(), level, stopped.bool()
 
     # ------------------------------------------------------------------ checkpoints

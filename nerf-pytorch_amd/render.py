@@ -670,15 +670,15 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
         if cfg["march_step_size"] is not None:      # world-space steps, march_steps is the cap: one kernel for both forms
             dens = cfg["march_stop_eps"] is not None
             z_m, z_stop, truncated, level, stopped = hb.occ_march_step(
-                desc, grid.density if dens else None, grid.sigma_threshold if dens and grid.outside == "evaluate" else 0.0, rays,
-                rnd.get("u_march"), cfg["march_step_size"], cfg["march_steps"], n_c, cfg["march_fit"], cfg["march_stop_eps"])
+                desc, grid.density if dens else None, grid.outside_sigma() if dens else 0.0, rays, rnd.get("u_march"),
+                cfg["march_step_size"], cfg["march_steps"], n_c, cfg["march_fit"], cfg["march_stop_eps"])
             if dens:
                 n_stopped = stopped.sum()
             if cfg["march_fit"] > 0:
                 n_refit = (level > 0).sum()
         elif cfg["march_stop_eps"] is not None:
-            z_m, z_stop, truncated, stopped = hb.occ_march_stop(desc, grid.density, grid.sigma_threshold if grid.outside == "evaluate" else 0.0,
-                                                                rays, rnd.get("u_march"), cfg["march_steps"], n_c, cfg["march_stop_eps"])
+            z_m, z_stop, truncated, stopped = hb.occ_march_stop(desc, grid.density, grid.outside_sigma(), rays, rnd.get("u_march"),
+                                                                cfg["march_steps"], n_c, cfg["march_stop_eps"])
             n_stopped = stopped.sum()
         else:
             z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), cfg["march_steps"], n_c)
