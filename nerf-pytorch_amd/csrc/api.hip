@@ -387,7 +387,11 @@ size_t nerf_live_tiles_words(int n_rays, int n_samples) {
     if (n_rays <= 0 || n_samples <= 0) return 0;
     const size_t P = (size_t)n_rays * n_samples;
     if (P > ((size_t)1 << 36)) return 0;
+#if NERF_LIVE_GROUPS     // (experiment builds, csrc/launchers.h: the group words behind the tile list)
+    return nerf::live_groups((unsigned)((P + 31) / 32)).total;
+#else
     return nerf::live_tiles((unsigned)((P + 31) / 32)).total;
+#endif
 }
 
 int nerf_bwd_skip_dead(void) { return skip_dead_enabled() ? 1 : 0; }

@@ -195,6 +195,9 @@ struct WgradArgs {
     // wgrad1_kernel: the live-tile list of this pass (launchers.h, LiveTiles) or null = every tile.  A workgroup streams the live
     // tiles of its chunk only: a dead tile's deltas are exact zeros (and were never written), its products add +-0 to sums that start at +0
     const unsigned* live;
+    // NERF_LIVE_GROUPS builds, 16 / 8: the list also carries group masks (launchers.h, LiveGroups), and the DMA pieces of a live tile's
+    // dead groups are zeros that were not fetched from the tile; anything else: whole tiles only
+    int group;
 };
 
 __device__ inline f32x4 load_row4(const float* base, int ld, long row, bool row_ok, int col, int ncols, int vec) {
@@ -460,6 +463,20 @@ __device__ inline void dma_1k_s(const void* sbase, unsigned voff, unsigned lds_d
         : "v"(voff), "s"(sbase), "s"(lds_dst_uniform)
         : "memory");
 }
+// the same piece from a full per-lane address (the group path: a lane's source is either its piece of the tile or the zero line, which
+// lies in another buffer -- no 32-bit offset from one scalar base reaches both)
+__device__ inline void dma_1k_v(const void* vaddr, unsigned lds_dst_uniform) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off nt\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(vaddr), "s"(lds_dst_uniform)
+        : "memory");
+}
 // SP: element type of the stored operands (split_types.h: bf16, or fp16 = the hi words of the fp16 split -- then every delta
 // carries the launch's power-of-two scale, which wgrad_reduce_kernel removes)
 // TERMS = 1: the operands are the stored hi words (11 / 8 significant bits).  TERMS = 3 (round 6, "fp16x3w"): TWO-WORD operands --
@@ -468,8 +485,13 @@ __device__ inline void dma_1k_s(const void* sbase, unsigned voff, unsigned lds_d
 // in the same 128 KiB of LDS, every word fetched from HBM once; a k-step reads 12 fragments and issues 24 MFMAs.  (First form, measured:
 // three 32-KiB stages per tile -- hi.hi, hi.lo, lo.hi -- re-fetching the hi tiles: 3.05x the one-word kernel's time, i.e. bound by its
 // 3x DMA traffic, which L2 does not absorb; this form moves 2x the bytes.)
+// NERF_LIVE_GROUPS (launchers.h; 0 in the default build, where none of the group path below is compiled): 1 = a dead group's pieces of a
+// stage come from the list's zero line, by DMA from a per-lane address; 2 = no memory request -- the DMA runs with the dead lanes
+// switched off and those lanes write their 16 zero bytes to LDS themselves.  Measured (profiles/r16_dead_groups_measurements.md): both
+// LOSE 3-11 % per launch against whole tiles on the same list -- the kernel's time does not follow bytes below the 64-byte row.
 template <typename SP, int TERMS = 1>
 __global__ __launch_bounds__(512) void wgrad1_kernel(WgradArgs a) {
+    constexpr bool GRP = NERF_LIVE_GROUPS != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char sm1[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_n = wave >> 2, wave_k = wave & 3;
@@ -503,6 +525,31 @@ __global__ __launch_bounds__(512) void wgrad1_kernel(WgradArgs a) {
         }
     }
     const bool sparse = lv != nullptr;
+    // group path: some group of a live tile is dead.  The masks are scalar loads like the tile numbers; a list in which every group of
+    // every live tile is live (or a launch made for whole tiles) never looks at them.
+    const_words gm = nullptr;
+    const char* zline = nullptr;
+    unsigned gm_last = 0u;
+    if (GRP && a.live && (a.group == 16 || a.group == 8)) {
+        const_words lw = as_const_words(a.live);
+        const LiveGroups lg = live_groups(lw[1]);
+        // (a list written for another group size has no such words: whole tiles)
+        if (lw[lg.ext + 2] == (unsigned)a.group && lw[lg.ext + (a.group == 16 ? 1 : 0)] != 0u) {
+            gm = lw + lg.gmask;
+            gm_last = lw[1] - 1u;
+            zline = reinterpret_cast<const char*>(a.live + lg.zero) + 16 * (lane & 7);
+        }
+    }
+    const bool grp = GRP && gm != nullptr;
+    const bool g16 = a.group == 16;
+    // the 8-point group (2 * t + hf of `fragment` below) a lane's DMA pieces belong to: the same for its four instructions
+    const unsigned dgrp = (unsigned)((lane & 3) ^ ((lane >> 4) & 3));
+    auto group_mask = [&](int t) {          // live groups of tile t of the chunk (4 bits; a 16-point group lives with either half)
+        const unsigned tt = min((unsigned)(tile0 + t), gm_last);        // (the look-ahead past the slice's end may be any word)
+        unsigned m = (gm[tt >> 3] >> (4u * (tt & 7u))) & 15u;
+        if (g16) m = ((m & 3u) ? 3u : 0u) | ((m & 12u) ? 12u : 0u);
+        return m;
+    };
     constexpr int STAGE_BYTES = TERMS == 3 ? 2 * WG1_STAGE_BYTES : WG1_STAGE_BYTES;      // 64 KiB: [d_hi | X_hi | d_lo | X_lo]
     constexpr int STAGES = TERMS == 3 ? WG1_LDS_BYTES / STAGE_BYTES : WG1_STAGES;        // 2 (one in flight) / 4 (three in flight)
 
@@ -543,11 +590,49 @@ __global__ __launch_bounds__(512) void wgrad1_kernel(WgradArgs a) {
     // NEXT stage's tile is fetched one call ahead, so that the list's indirection does not sit in front of the DMA issue.  (The word
     // behind the chunk's slice, read by the last call and never used, is another word of the list buffer.)
     int t_next = sparse ? (int)(lv[0] - (unsigned)tile0) : 0;
+    unsigned m_next = grp ? group_mask(t_next) : 15u;
     auto issue = [&](int st) {
         int t = st;
         if (sparse) { t = t_next; t_next = (int)(lv[st + 1] - (unsigned)tile0); }
         const char* src = ray_tiles > 0 ? rbase + (size_t)((tile0 + t) / ray_tiles) * (size_t)(16 * sld) : cbase + (size_t)t * tile_bytes;
         const unsigned dst = lds0 + (unsigned)(st % STAGES) * STAGE_BYTES;
+        if (GRP && grp) {
+            // as many DMA instructions as below (the vmcnt arithmetic of enter() stands: a live tile has a live group, and every
+            // instruction has 16 lanes of each group, so none is ever skipped).  The per-ray records of the direction encoding are not
+            // worth redirecting: they never leave L2.
+            const unsigned m = m_next;
+            m_next = group_mask(sparse ? t_next : st + 1);
+            const bool dead = ray_tiles == 0 && ((m >> dgrp) & 1u) == 0u;
+#if NERF_LIVE_GROUPS != 2
+#pragma unroll
+            for (int u = 0; u < 4; ++u) dma_1k_v(dead ? zline : src + (doff[u] + (unsigned)t * dstep[u]), dst + 1024u * u);
+            if constexpr (TERMS == 3) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    dma_1k_v(dead ? zline : src + lo_bytes + (doff[u] + (unsigned)t * dstep[u]), dst + WG1_STAGE_BYTES + 1024u * u);
+            }
+#else
+            if (!dead) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) dma_1k_s(src, doff[u] + (unsigned)t * dstep[u], dst + 1024u * u);
+                if constexpr (TERMS == 3) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) dma_1k_s(src + lo_bytes, doff[u] + (unsigned)t * dstep[u], dst + WG1_STAGE_BYTES + 1024u * u);
+                }
+            } else {
+                // (visible to the consumers like the DMA's bytes: this wave passes enter()'s barrier, which waits for its LDS
+                // writes, before any wave reads the stage)
+                unsigned char* zp = sm1 + (st % STAGES) * STAGE_BYTES + sop * WG1_OP_BYTES + (wave & 3) * 4096 + 16 * lane;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) *reinterpret_cast<u32x4*>(zp + 1024 * u) = u32x4{0u, 0u, 0u, 0u};
+                if constexpr (TERMS == 3) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) *reinterpret_cast<u32x4*>(zp + WG1_STAGE_BYTES + 1024 * u) = u32x4{0u, 0u, 0u, 0u};
+                }
+            }
+#endif
+            return;
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) dma_1k_s(src, doff[u] + (unsigned)t * dstep[u], dst + 1024u * u);
         if constexpr (TERMS == 3) {             // the lo words of the same pieces, behind the hi blocks of the stage
@@ -1024,6 +1109,7 @@ hipError_t launch_field_wgrad(const float* act, const float* delta, const float*
     big.a_lo_bytes = lo_a;
     big.b_lo_bytes = lo_b;
     big.live = live;
+    big.group = live ? live_group() : 32;
     small.total_tiles = small_tiles;
     static bool attr_set = false;
     if (!attr_set) {

@@ -49,12 +49,15 @@ __device__ inline void apply_mask3r(float (&d)[NV], const f32x16* acc, u32x4 m) 
 // LIVE: the same pass over d_raw also says which 32-point tiles carry anything.  A lane holds one point (four words), 32 consecutive
 // lanes one tile, a workgroup iteration 1024 points = 32 tiles = ONE word of the liveness bitmap (bit b = tile 32 * word + b has a
 // word with (bits & 0x7fffffff) != 0: NaN, Inf and subnormals are live, +-0 is not).  No atomics: every bitmap word has one writer.
+// gmask (NERF_LIVE_GROUPS builds only, else null; launchers.h, LiveGroups): the same ballot at 8-point granularity -- eight lanes one group, a wave's two tiles one
+// byte, an iteration FOUR words of group masks, each with one writer.
 template <bool LIVE>
 __global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restrict__ d_raw, long n4, unsigned* __restrict__ slot,
-                                                          unsigned* __restrict__ bitmap) {
+                                                          unsigned* __restrict__ bitmap, unsigned* __restrict__ gmask) {
     float m = 0.0f;
     __shared__ float wm[16];
     __shared__ unsigned wb[2][16];
+    __shared__ unsigned wg[2][16];
     if constexpr (LIVE) {
         const long n_it = (n4 + 1023) / 1024;           // = bitmap words
         int par = 0;
@@ -68,13 +71,25 @@ __global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restric
             }
             const unsigned long long b = __ballot(any != 0u);
             const unsigned two = ((b & 0xffffffffull) ? 1u : 0u) | ((b >> 32) ? 2u : 0u);       // this wave's two tiles
-            if ((threadIdx.x & 63) == 0) wb[par][threadIdx.x >> 6] = two << (2 * (threadIdx.x >> 6));
-            __syncthreads();        // (wb is double-buffered by iteration parity: one barrier per iteration is enough)
+            if ((threadIdx.x & 63) == 0) {
+                wb[par][threadIdx.x >> 6] = two << (2 * (threadIdx.x >> 6));
+                if (NERF_LIVE_GROUPS && gmask) {
+                    unsigned byte = 0u;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) byte |= (((b >> (8 * k)) & 0xffull) ? 1u : 0u) << k;
+                    wg[par][threadIdx.x >> 6] = byte;
+                }
+            }
+            __syncthreads();        // (wb, wg are double-buffered by iteration parity: one barrier per iteration is enough)
             if (threadIdx.x == 0) {
                 unsigned w = 0u;
 #pragma unroll
                 for (int k = 0; k < 16; ++k) w |= wb[par][k];
                 bitmap[it] = w;
+            }
+            if (NERF_LIVE_GROUPS && gmask && threadIdx.x >= 64 && threadIdx.x < 68) {       // (a wave other than the bitmap's writer)
+                const int j = threadIdx.x - 64;
+                gmask[it * 4 + j] = wg[par][4 * j] | (wg[par][4 * j + 1] << 8) | (wg[par][4 * j + 2] << 16) | (wg[par][4 * j + 3] << 24);
             }
         }
         if (!slot) return;
@@ -98,8 +113,12 @@ __global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restric
 
 // bitmap -> the ascending list of live tile numbers, its count, and per bitmap word the number of live tiles before it (the
 // weight-gradient GEMM finds its chunk's slice of the list from those without a search).  One workgroup, a scan: the order is fixed.
-__global__ __launch_bounds__(1024) void live_scan_kernel(unsigned* __restrict__ live, unsigned n_tiles) {
+// group = 16 / 8 (NERF_LIVE_GROUPS builds only, else 0): also the header of the group words -- how many groups of either size are dead inside live tiles (zero =
+// the GEMM has nothing to leave out beyond the tile list) -- and the zero line.
+__global__ __launch_bounds__(1024) void live_scan_kernel(unsigned* __restrict__ live, unsigned n_tiles, unsigned group) {
     const LiveTiles lt = live_tiles(n_tiles);
+    const LiveGroups lg = live_groups(n_tiles);
+    unsigned dead8 = 0u, dead16 = 0u;
     const unsigned* bitmap = live + lt.bitmap;
     unsigned* prefix = live + lt.prefix;
     unsigned* list = live + LIVE_HEADER;
@@ -112,6 +131,17 @@ __global__ __launch_bounds__(1024) void live_scan_kernel(unsigned* __restrict__ 
         const unsigned w = w0 + threadIdx.x;
         unsigned bits = w < lt.n_words ? bitmap[w] : 0u;
         const unsigned c = __popc(bits);
+        if (NERF_LIVE_GROUPS && group && bits) {
+            for (int j = 0; j < 4; ++j) {
+                const unsigned gw = live[lg.gmask + 4 * (size_t)w + j];
+                for (int t = 0; t < 8; ++t)
+                    if ((bits >> (8 * j + t)) & 1u) {
+                        const unsigned nib = (gw >> (4 * t)) & 15u;
+                        dead8 += 4u - __popc(nib);
+                        dead16 += ((nib & 3u) ? 0u : 1u) + ((nib & 12u) ? 0u : 1u);
+                    }
+            }
+        }
         unsigned inc = c;           // inclusive scan inside the wave
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -142,6 +172,22 @@ __global__ __launch_bounds__(1024) void live_scan_kernel(unsigned* __restrict__ 
         live[1] = n_tiles;
         live[2] = 0u;
         live[3] = 0u;
+    }
+    if (NERF_LIVE_GROUPS && group) {
+        __shared__ unsigned wd[2][16];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { dead8 += __shfl_xor(dead8, o); dead16 += __shfl_xor(dead16, o); }
+        if (lane == 0) { wd[0][wave] = dead8; wd[1][wave] = dead16; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned s8 = 0u, s16 = 0u;
+            for (int k = 0; k < 16; ++k) { s8 += wd[0][k]; s16 += wd[1][k]; }
+            live[lg.ext] = s8;
+            live[lg.ext + 1] = s16;
+            live[lg.ext + 2] = group;
+            live[lg.ext + 3] = 0u;
+        }
+        if (threadIdx.x < LIVE_ZERO_WORDS) live[lg.zero + threadIdx.x] = 0u;
     }
 }
 
@@ -310,8 +356,11 @@ static hipError_t launch_dgrad_one(const FieldBwdRingArgs& ba, unsigned blocks, 
 
 // split: 0 bf16, 1 fp16 parts (of the products and of the stored deltas); 5 = fp16 with two-word deltas (and a two-word save buffer)
 // live (nullable, live_tiles(P).total words): the launch writes the live-tile list there and skips the dead tiles
+// (NERF_LIVE_GROUPS builds with live_group() = 16 / 8: `live` has live_groups(P).total words and also receives the group masks, read by
+// the weight-gradient GEMM; the delta chain itself works on whole tiles)
 hipError_t launch_field_dgrad3r(const float* packed3, const float* act, const float* d_raw, int n_rays, int S,
                                 float* delta, int split, hipStream_t stream, unsigned* live) {
+    const int group = live_group();
     const long P = (long)n_rays * S;
     if (P <= 0) return hipSuccess;
     FieldBwdRingArgs ba{packed3, act, d_raw, delta, n_rays, S, live};
@@ -326,14 +375,16 @@ hipError_t launch_field_dgrad3r(const float* packed3, const float* act, const fl
     if (live) {
         // one bitmap word per 1024 points and workgroup iteration: a grid of up to 1024 workgroups strides over them
         const LiveTiles lt = live_tiles((unsigned)((P + 31) / 32));
+        const bool groups = group == 16 || group == 8;
+        unsigned* gmask = groups ? live + live_groups(lt.n_tiles).gmask : nullptr;
         const unsigned sb = (unsigned)min((long)1024, (P + 1023) / 1024);
-        hipLaunchKernelGGL(delta_amax_kernel<true>, dim3(sb), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot, live + lt.bitmap);
-        hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, stream, live, lt.n_tiles);
+        hipLaunchKernelGGL(delta_amax_kernel<true>, dim3(sb), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot, live + lt.bitmap, gmask);
+        hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, stream, live, lt.n_tiles, groups ? (unsigned)group : 0u);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     } else if (split) {
         const unsigned sb = (unsigned)min((long)1024, (P + 1023) / 1024);      // one 16-byte load per thread: the launch is latency, not bytes
-        hipLaunchKernelGGL(delta_amax_kernel<false>, dim3(sb), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot, (unsigned*)nullptr);
+        hipLaunchKernelGGL(delta_amax_kernel<false>, dim3(sb), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot, (unsigned*)nullptr, (unsigned*)nullptr);
     }
     if (split) return split == 5 ? launch_dgrad_one<SplitF16, true>(ba, blocks, stream) : launch_dgrad_one<SplitF16>(ba, blocks, stream);
     return launch_dgrad_one<SplitBF16>(ba, blocks, stream);

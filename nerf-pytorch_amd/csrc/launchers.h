@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace nerf {
 
@@ -137,6 +138,41 @@ __host__ __device__ inline LiveTiles live_tiles(unsigned n_tiles) {
     l.prefix = l.bitmap + l.n_words;
     l.total = (l.prefix + l.n_words + 1 + 3) & ~(size_t)3;
     return l;
+}
+// ---- EXPERIMENT, not in the default build (NERF_LIVE_GROUPS = 0): dead point groups inside live tiles.  Measured slower than whole
+// tiles (profiles/r16_dead_groups_measurements.md); the source stays so that those rows can be reproduced:
+//   tools/build_variant.sh groups -DNERF_LIVE_GROUPS=1    (2: the dead pieces are zero-filled in LDS instead of fetched from the zero line)
+// and NERF_BWD_LIVE_GROUP = 16 or 8 in the environment of a process that loads that library (NERF_HIP_LIB); 32 or unset = whole tiles.
+// In such a build the list buffer (nerf_live_tiles_words) has live_groups(n_tiles).total words and the *_live entry points use them.
+// Group liveness, appended BEHIND the words above.  A group is G consecutive points of a tile, dead when all 4 G words of its d_raw
+// are +-0.  The masks are kept at 8-point granularity whatever G is; a 16-point group is live when either of its halves is.
+//   [ext + 0]       dead 8-point groups inside LIVE tiles     [ext + 1]  dead 16-point groups inside live tiles
+//   [ext + 2]       the G this list was written for           [ext + 3]  zero
+//   [gmask + w]     nibble j (bits 4 j .. 4 j + 3) = tile 8 w + j: bit k = points 8 k .. 8 k + 7 of the tile carry something
+//                   (4 * n_words words: every tile the bitmap has a bit for; tiles past the launch read 0)
+//   [zero + i]      LIVE_ZERO_WORDS zero words (16-byte aligned): the source of a dead group's DMA pieces
+#ifndef NERF_LIVE_GROUPS
+#define NERF_LIVE_GROUPS 0
+#endif
+constexpr unsigned LIVE_ZERO_WORDS = 64;
+struct LiveGroups { size_t ext, gmask, zero, total; };
+__host__ __device__ inline LiveGroups live_groups(unsigned n_tiles) {
+    const LiveTiles t = live_tiles(n_tiles);
+    LiveGroups g;
+    g.ext = t.total;
+    g.gmask = g.ext + 4;
+    g.zero = g.gmask + 4 * (size_t)t.n_words;
+    g.total = g.zero + LIVE_ZERO_WORDS;
+    return g;
+}
+// the group size of this process: 32 (whole tiles) in the default build whatever the environment says
+inline int live_group() {
+#if NERF_LIVE_GROUPS
+    static const int g = [] { const char* e = getenv("NERF_BWD_LIVE_GROUP"); const int v = e ? atoi(e) : 32; return (v == 8 || v == 16) ? v : 32; }();
+    return g;
+#else
+    return 32;
+#endif
 }
 
 }  // namespace nerf

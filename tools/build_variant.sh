@@ -7,7 +7,7 @@ PKG=$(cd "$(dirname "$0")/../nerf-pytorch_amd" && pwd)
 OBJ=$PKG/build/variant_$NAME; mkdir -p $OBJ $PKG/build/variants
 HIPCC=${HIPCC:-$(command -v hipcc || echo /opt/rocm/bin/hipcc)}
 pids=()
-for src in api render_abi pack ray_ops field_fwd field_bwd field_fwd_ring field_bwd_ring render_fused dense; do
+for src in $(cd $PKG/csrc && ls *.hip | sed 's/\.hip$//'); do
   $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC "$@" -I $PKG/csrc -I $PKG/../include -c $PKG/csrc/$src.hip -o $OBJ/$src.o &
   pids+=($!)
 done

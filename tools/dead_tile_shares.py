@@ -7,6 +7,10 @@ copy of the two header words of the live-tile list (count, tiles); they are read
 synchronises inside a step.  Prints one JSON line: per pass (64 = coarse, 192 = fine) the mean / min / max dead share and the share
 of every launch in order (the networks train towards random targets: the shares move from step to step), and the max / mean live
 share over the weight-gradient GEMM's 21 point chunks (what unequal chunks cost it).
+
+The result also says what share of all points a backward working on tiles, on groups of 16 and on groups of 8 consecutive points
+inside a tile would touch ("touched_share_*"; a group is dead when all words of its d_raw are +-0): counted from the same d_raw with
+torch on the device, next to the launch, and read back with the rest.
 """
 import argparse
 import json
@@ -47,13 +51,23 @@ def main():
     targets = [torch.rand(args.rays, 3, generator=gen).to(dev) for _ in range(pool)]
     kwargs = dict(network_query_fn=None, perturb=1.0, N_importance=128, network_fine=nf, N_samples=64, network_fn=nc, use_viewdirs=True,
                   white_bkgd=cfg["white_bkgd"], raw_noise_std=cfg["raw_noise_std"], ndc=cfg["ndc"], lindisp=False, near=cfg["near"], far=cfg["far"])
-    seen = []           # (S, P, device copy of the list up to the end of the tile numbers) per sparse field backward
+    seen = []           # (S, P, device copy of the list up to the end of the tile numbers, live groups of 16 / of 8) per sparse field backward
     inner = hb._field_bwd
+
+    def live_groups(d_raw, T):
+        """device tensor [live 16-point groups, live 8-point groups] of d_raw (points past the launch count as zeros)"""
+        bits = d_raw.reshape(-1, 4).view(torch.int32) & 0x7fffffff
+        pad = torch.zeros(T * 32, 4, dtype=torch.int32, device=d_raw.device)
+        pad[:bits.shape[0]] = bits
+        g8 = (pad.view(T, 4, 32) != 0).any(2)
+        g16 = g8[:, 0::2] | g8[:, 1::2]
+        return torch.stack([g16.sum(), g8.sum()])
 
     def spy(L, packed, act, d_raw, grad, accumulate, precision, delta, partial, n, S, params, input_grad=None):
         out = inner(L, packed, act, d_raw, grad, accumulate, precision, delta, partial, n, S, params, input_grad)
         if hb.LAST_LIVE is not None:
-            seen.append((S, n * S, hb.LAST_LIVE[:4 + (n * S + 31) // 32].clone()))
+            T = (n * S + 31) // 32
+            seen.append((S, n * S, hb.LAST_LIVE[:4 + T].clone(), live_groups(d_raw, T)))
         return out
 
     hb._field_bwd = spy
@@ -69,21 +83,28 @@ def main():
     finally:
         hb._field_bwd = inner
     res = {"config": args.config, "rays": args.rays, "steps": args.steps, "precision": npa.get_precision(), "passes": {}}
-    for S in sorted({s for s, _, _ in seen}):
-        shares, imbalance = [], []
-        for s, P, words in seen:
+    for S in sorted({s for s, _, _, _ in seen}):
+        shares, imbalance, touched16, touched8 = [], [], [], []
+        for s, P, words, groups in seen:
             if s != S:
                 continue
             w = words.cpu()
             count, T = int(w[0]), int(w[1])
             shares.append(1.0 - count / T)
+            live16, live8 = (int(x) for x in groups.cpu())
+            touched16.append(live16 / (2 * T))
+            touched8.append(live8 / (4 * T))
             n = max(1, min(21, (P + 255) // 256))
             ct = ((P + n - 1) // n + 31) // 32 * 32 // 32
             per_chunk = torch.bincount(w[4:4 + count].long() // ct, minlength=(T + ct - 1) // ct).double()
             imbalance.append(float(per_chunk.max() / per_chunk.mean()) if count else 1.0)
         res["passes"][str(S)] = {"launches": len(shares), "dead_share_mean": sum(shares) / len(shares), "dead_share_min": min(shares),
                                  "dead_share_max": max(shares), "chunk_max_over_mean_live": sum(imbalance) / len(imbalance),
-                                 "dead_share_by_launch": [round(x, 4) for x in shares]}
+                                 "touched_share_tiles": 1.0 - sum(shares) / len(shares),
+                                 "touched_share_groups16": sum(touched16) / len(touched16), "touched_share_groups8": sum(touched8) / len(touched8),
+                                 "dead_share_by_launch": [round(x, 4) for x in shares],
+                                 "touched_share_groups16_by_launch": [round(x, 4) for x in touched16],
+                                 "touched_share_groups8_by_launch": [round(x, 4) for x in touched8]}
     line = json.dumps(res)
     print(line)
     if args.out:

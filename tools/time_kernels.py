@@ -8,7 +8,11 @@ prints one JSON line: {kernel: {"coarse_ms": .., "fine_ms": ..}}.  tools/ab.sh a
     --live          the sparse forms of the delta chain and the weight-gradient GEMM (nerf_field_dgrad_split_live /
                     nerf_field_wgrad_phase_live; "dgrad" includes the liveness launches).  With the default d_raw = randn no tile is
                     dead: what a dense batch pays for the list.
-    --dead SHARE    zero that share of d_raw's 32-point tiles, in runs of 13 tiles (with or without --live)"""
+    --dead SHARE    zero that share of d_raw's 32-point tiles, in runs of 13 tiles (with or without --live)
+                    (the dead-group experiment: a library built with tools/build_variant.sh NAME -DNERF_LIVE_GROUPS=1 or 2 in
+                    NERF_HIP_LIB, and NERF_BWD_LIVE_GROUP=16 or 8 in the environment; csrc/launchers.h)
+    --dead-points SHARE   zero that share of the POINTS, ray by ray: one live run of (1 - SHARE) * S samples at a random place of every
+                    ray, everything else zero -- the shape of a compositing gradient; dead tiles and dead groups follow from it"""
 import argparse
 import json
 import os
@@ -30,6 +34,7 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--live", action="store_true")
     ap.add_argument("--dead", type=float, default=0.0)
+    ap.add_argument("--dead-points", default="", help="one share, or coarse,fine")
     args = ap.parse_args()
     hb = npa.hip_backend
     L = hb.lib()
@@ -65,6 +70,14 @@ def main():
             T = n * S // 32
             runs = torch.rand((T + 12) // 13, device=dev) < args.dead
             d_raw.view(T, 32, 4)[runs.repeat_interleave(13)[:T]] = 0.0
+        if args.dead_points:
+            shares = [float(x) for x in args.dead_points.split(",")]
+            share = shares[0] if tag == "coarse" or len(shares) == 1 else shares[1]
+            run = max(1, round((1.0 - share) * S))
+            g = torch.Generator().manual_seed(S)
+            start = torch.randint(0, S - run + 1, (n, 1), generator=g)
+            idx = torch.arange(S).view(1, S)
+            d_raw[((idx < start) | (idx >= start + run)).to(dev)] = 0.0
         raw = torch.empty(n, S, 4, device=dev)
         act = torch.empty(max(hb.act_floats(n, S), hb.act_floats(n, S, prec)), device=dev)
         delta = torch.empty(max(L.nerf_delta_floats(n, S), hb.delta_floats(n, S, prec)), device=dev)
@@ -93,7 +106,8 @@ def main():
             if args.only and name not in args.only.split(","):
                 continue
             out.setdefault(name, {})[tag + "_ms"] = timed(fn)
-    print(json.dumps({"lib": os.environ.get("NERF_HIP_LIB", "in-tree"), "precision": prec, "live": bool(args.live), "dead": args.dead, "kernels": out}))
+    print(json.dumps({"lib": os.environ.get("NERF_HIP_LIB", "in-tree"), "precision": prec, "live": bool(args.live), "group": os.environ.get("NERF_BWD_LIVE_GROUP", "32"), "dead": args.dead,
+                      "dead_points": args.dead_points, "kernels": out}))
 
 
 if __name__ == "__main__":
