@@ -575,6 +575,30 @@ int nerf_occ_march_stop(const NerfOccGrid* grid, const float* density, float out
 int nerf_occ_march_step(const NerfOccGrid* grid, const float* density /* nullable */, float outside_sigma, const float* rays, int ray_stride,
                         const float* u /* nullable: 0.5 */, int n_rays, float step_size, int n_steps, int n_slots, int fit, float tau,
                         float* z_vals, float* z_stop, int* truncated, int* level, int* stopped /* non-NULL iff density */, void* stream);
+/* ---- grids from cameras and silhouettes (additive in ABI v10): project the cells of a grid into n_views training cameras.  World
+ * space only (a grid for ndc rays lives in NDC space and is not supported).  OccupancyGrid.view_counts_reference / carved_reference are
+ * the definition.  grid gives lo and res (scale and bits are not read); width[a] = fp32((hi[a] - lo[a]) / res[a]) computed by the host
+ * in double.  cams[v] = 16 floats: c2w[3][4] row-major (columns right, up, back, position: the reference's get_rays convention), fx,
+ * fy, cx, cy.  Corner o in {0,1}^3 of cell (ix, iy, iz): p[a] = lo[a] + fp32(i[a] + o[a]) * width[a] (one multiplication, one addition).
+ * In camera v, with d = p - position:  x = d . right,  y = d . up,  s = -(d . back)  -- three products added left to right, not
+ * contracted; s is the depth render() samples.  Six inside-tests per corner:
+ *   s >= near_m,  s <= far_m,  fx x >= (-m - cx) s,  fx x <= ((W - 1 + m) - cx) s,  -(fy y) >= (-m - cy) s,  -(fy y) <= ((H - 1 + m) - cy) s
+ * (m = margin_px; near_m = fp32(near (1 - 2^-10)), far_m = fp32(far (1 + 2^-10)) from the host).  The cell is UNSEEN by v iff all eight
+ * corners fail one and the same test (the conservative box-against-frustum test: each test is a half-space); a NaN fails every test.
+ *   seen[c] (int32, n_cells) = the number of cameras that see cell c   (accumulate != 0: added to what seen holds)
+ * With sat (int32 [n_views][H + 1][W + 1], the summed-area tables of the foreground masks: sat[v][j][i] = foreground pixels with row < j
+ * and column < i) camera v CARVES the cell iff all eight corners have s >= near_m, every i = fx x / s + cx and j = cy - fy y / s (IEEE
+ * division) is finite, the rectangle i0 = floor(min i - m) .. i1 = ceil(max i + m), j0 .. j1 likewise, lies inside [0, W - 1] x
+ * [0, H - 1] (else the camera abstains) and sat[j1+1][i1+1] - sat[j0][i1+1] - sat[j1+1][i0] + sat[j0][i0] == 0: no foreground pixel in
+ * it.  The rectangle covers the projection of the whole cell, so no foreground pixel's ray of v crosses a cell that v carves.
+ *   carved_words ((n_cells + 31) / 32 words, the grid's bit layout) = the OR over the cameras   (accumulate != 0: ORed into the words)
+ * sat and carved_words are both given or both NULL.  One thread per cell, a wave-uniform loop over the views, the four table words
+ * loaded only where the camera does not abstain; seen by plain stores, carved_words whole words from a wave ballot (the unused bits of
+ * the last word are 0); no atomics: the same inputs give the same bits.  Reads 64 B per view (shared by all cells) and up to 16 B of sat
+ * per cell and view; writes 4 B + 1 bit per cell.  n_views >= 1; 1 <= H, W <= 16384; margin_px finite and >= 0. */
+int nerf_occ_view_carve(const NerfOccGrid* grid, const float width[3], const float* cams /* [n_views][16] */, int n_views, int H, int W,
+                        float near_m, float far_m, float margin_px, const int* sat /* nullable */, int accumulate, int* seen,
+                        unsigned* carved_words /* non-NULL iff sat */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,9 @@
 //                      render_rays(proposal="march", march_step_size=ds, march_fit=J).
 //                      The three are one kernel, occ_march_walk_kernel<Steps, STOP>: Steps (EqualSteps, WorldSteps) says how a candidate
 //                      becomes a depth, when it counts and whether there are levels; STOP adds the stop on the optical depth.
+//   nerf_occ_view_carve : the cells of a grid projected into a set of training cameras -- per cell the number of cameras whose frustum
+//                      it touches and, with silhouette masks, whether some camera sees only background behind it (the visual hull):
+//                      OccupancyGrid.from_views, DensityGrid.restrict_to_views.  Needs no network.
 // The compaction is deterministic: a count per block of OCC_TILE points, an exclusive scan of the block counts, then the
 // write -- inside a block the position of a point is a wave ballot + popcount and a prefix over the block's wave counts, so the
 // list is in stable ray-major, sample-minor order and no atomic decides anything.
@@ -758,6 +761,101 @@ __global__ __launch_bounds__(MARCH_THREADS) void occ_march_walk_kernel(GridArgs 
     }
 }
 
+// ---- nerf_occ_view_carve (OccupancyGrid.view_counts_reference / carved_reference are the definitions)
+// One thread per cell.  The cell's corner coordinates -- two per axis, lo + float(i + o) * width -- are built once and stay in
+// registers; the loop over the views is wave-uniform, so the 16 floats of a camera record (c2w row-major, fx, fy, cx, cy) are the same
+// address for every lane.  Per view the eight corners go through the camera once: d = p - t, x / y / s as three products added left to
+// right, the six inside-tests as running ANDs of "this corner fails test k" (a NaN fails every test: a NaN camera sees nothing), and,
+// with masks, the projected pixel (i, j) by one IEEE division each with running minima and maxima.  A camera carves only where all
+// eight corners have s >= near_m, every i and j is finite and the rectangle [floor(min - m), ceil(max + m)] lies inside the image: only
+// then are the four words of its summed-area table loaded.  No atomics: a cell's count is its own thread's, and a word of the carved
+// bits is stored whole by one lane from the wave's ballot (accumulate: that lane ORs into the word it owns).
+constexpr int CARVE_THREADS = 256;
+
+struct CarveArgs {
+    float lo[3], width[3];
+    int res[3];
+    const float* cams;          // [n_views][16]
+    int n_views, H, W;
+    float near_m, far_m, m;
+    const int* sat;             // [n_views][H + 1][W + 1], or null: no carving
+    int accumulate;
+    int* seen;
+    unsigned* carved;
+};
+
+__global__ __launch_bounds__(CARVE_THREADS) void occ_view_carve_kernel(CarveArgs a) {
+    const long n_cells = (long)a.res[0] * a.res[1] * a.res[2];
+    const long cell = (long)blockIdx.x * CARVE_THREADS + threadIdx.x;
+    const bool live = cell < n_cells;       // (no early return: the ballot below wants whole waves)
+    int count = 0;
+    bool carved = false;
+    if (live) {
+        const int iz = (int)(cell % a.res[2]), iy = (int)((cell / a.res[2]) % a.res[1]), ix = (int)(cell / ((long)a.res[2] * a.res[1]));
+        float px[2], py[2], pz[2];
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            px[o] = a.lo[0] + (float)(ix + o) * a.width[0];
+            py[o] = a.lo[1] + (float)(iy + o) * a.width[1];
+            pz[o] = a.lo[2] + (float)(iz + o) * a.width[2];
+        }
+        const float m = a.m;
+        const float w_hi = (float)(a.W - 1) + m, h_hi = (float)(a.H - 1) + m;
+        const size_t sat_row = (size_t)a.W + 1, sat_view = ((size_t)a.H + 1) * sat_row;
+        for (int v = 0; v < a.n_views; ++v) {
+            const float* __restrict__ c = a.cams + (size_t)v * 16;
+            const float fx = c[12], fy = c[13], cx = c[14], cy = c[15];
+            const float i_lo = -m - cx, i_hi = w_hi - cx, j_lo = -m - cy, j_hi = h_hi - cy;
+            bool f_near = true, f_far = true, f_l = true, f_r = true, f_t = true, f_b = true;       // "every corner so far fails this test"
+            bool all_near = true, finite = true;
+            float i_min = INFINITY, i_max = -INFINITY, j_min = INFINITY, j_max = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float dx = px[(k >> 2) & 1] - c[3], dy = py[(k >> 1) & 1] - c[7], dz = pz[k & 1] - c[11];
+                const float x = dx * c[0] + dy * c[4] + dz * c[8];
+                const float y = dx * c[1] + dy * c[5] + dz * c[9];
+                const float s = -(dx * c[2] + dy * c[6] + dz * c[10]);
+                const float fxx = fx * x, fyy = fy * y;
+                const bool near_ok = s >= a.near_m;
+                f_near = f_near && !near_ok;
+                f_far = f_far && !(s <= a.far_m);
+                f_l = f_l && !(fxx >= i_lo * s);
+                f_r = f_r && !(fxx <= i_hi * s);
+                f_t = f_t && !(-fyy >= j_lo * s);
+                f_b = f_b && !(-fyy <= j_hi * s);
+                if (a.sat) {
+                    const float pi = fxx / s + cx, pj = cy - fyy / s;       // (IEEE division: hipcc's default for fp32)
+                    all_near = all_near && near_ok;
+                    finite = finite && fabsf(pi) < INFINITY && fabsf(pj) < INFINITY;       // (a NaN fails the comparison)
+                    i_min = fminf(i_min, pi); i_max = fmaxf(i_max, pi);
+                    j_min = fminf(j_min, pj); j_max = fmaxf(j_max, pj);
+                }
+            }
+            if (!(f_near || f_far || f_l || f_r || f_t || f_b)) ++count;
+            if (a.sat && all_near && finite) {
+                const float i0 = floorf(i_min - m), i1 = ceilf(i_max + m), j0 = floorf(j_min - m), j1 = ceilf(j_max + m);
+                if (i0 >= 0.0f && i1 <= (float)(a.W - 1) && j0 >= 0.0f && j1 <= (float)(a.H - 1)) {     // else the camera abstains
+                    const int* __restrict__ t = a.sat + (size_t)v * sat_view;
+                    const size_t r0 = (size_t)(int)j0 * sat_row, r1 = ((size_t)(int)j1 + 1) * sat_row;
+                    const size_t c0 = (size_t)(int)i0, c1 = (size_t)(int)i1 + 1;
+                    const int n = t[r1 + c1] - t[r0 + c1] - t[r1 + c0] + t[r0 + c0];
+                    carved = carved || n == 0;
+                }
+            }
+        }
+        a.seen[cell] = a.accumulate ? a.seen[cell] + count : count;
+    }
+    if (a.carved) {
+        const unsigned long long mask = __ballot(carved);
+        const int lane = threadIdx.x & 63;
+        if ((lane & 31) == 0 && cell < ((n_cells + 31) & ~31L)) {
+            const unsigned w = lane ? (unsigned)(mask >> 32) : (unsigned)mask;
+            unsigned* out = a.carved + (cell >> 5);
+            *out = a.accumulate ? (*out | w) : w;
+        }
+    }
+}
+
 int check_grid(const char* fn, const NerfOccGrid* grid, GridArgs* g) {
     if (!grid || !grid->bits) return fail_arg(fn, "null pointer");
     for (int a = 0; a < 3; ++a) {
@@ -951,6 +1049,27 @@ int nerf_occ_ray_span(const NerfOccGrid* grid, const float* rays, int ray_stride
     if (n_rays == 0) return 0;
     const unsigned lanes = 2u * (unsigned)n_rays;
     occ_ray_span_kernel<<<(lanes + SPAN_THREADS - 1) / SPAN_THREADS, SPAN_THREADS, 0, (hipStream_t)stream>>>(g, rays, ray_stride, n_rays, span, hit);
+    return done(__func__, hipGetLastError());
+}
+
+int nerf_occ_view_carve(const NerfOccGrid* grid, const float width[3], const float* cams, int n_views, int H, int W, float near_m,
+                        float far_m, float margin_px, const int* sat, int accumulate, int* seen, unsigned* carved_words, void* stream) {
+    REQUIRE(grid && width && cams && seen, "null pointer");        // (grid->bits is not read: the cells are projected, not looked up)
+    REQUIRE((sat != nullptr) == (carved_words != nullptr), "null pointer (sat and carved_words come together: with masks, or neither)");
+    REQUIRE(n_views >= 1 && H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "bad size (at least one view, images of 1..16384 pixels a side)");
+    REQUIRE(margin_px >= 0.0f && margin_px < INFINITY, "bad margin_px (finite and >= 0)");      // (a NaN fails the comparison)
+    CarveArgs a;
+    for (int k = 0; k < 3; ++k) {
+        REQUIRE(grid->res[k] >= 1 && grid->res[k] <= 512, "grid resolution must be 1..512 per axis");
+        a.lo[k] = grid->lo[k];
+        a.width[k] = width[k];
+        a.res[k] = grid->res[k];
+    }
+    a.cams = cams; a.n_views = n_views; a.H = H; a.W = W;
+    a.near_m = near_m; a.far_m = far_m; a.m = margin_px;
+    a.sat = sat; a.accumulate = accumulate != 0; a.seen = seen; a.carved = carved_words;
+    const long n_cells = (long)a.res[0] * a.res[1] * a.res[2];
+    occ_view_carve_kernel<<<(unsigned)((n_cells + CARVE_THREADS - 1) / CARVE_THREADS), CARVE_THREADS, 0, (hipStream_t)stream>>>(a);
     return done(__func__, hipGetLastError());
 }
 

@@ -98,6 +98,7 @@ def _declare(lib):
         "nerf_occ_march": (i, [p, p, i, p, i, i, i, p, p, p, p]),
         "nerf_occ_march_stop": (i, [p, p, f, p, i, p, i, i, i, f, p, p, p, p, p]),
         "nerf_occ_march_step": (i, [p, p, f, p, i, p, i, f, i, i, i, f, p, p, p, p, p, p]),
+        "nerf_occ_view_carve": (i, [p, p, p, i, i, i, f, f, f, p, i, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -125,6 +126,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_occ_scratch_words", "nerf_occ_compact", "nerf_occ_expand", "nerf_occ_mark", "nerf_occ_dilate",
            "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span", "nerf_occ_proposal_weights",
            "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march", "nerf_occ_march_stop", "nerf_occ_march_step",
+           "nerf_occ_view_carve",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
 
 
@@ -1321,6 +1323,36 @@ def occ_march_step(desc, density, outside_sigma, rays, u, step_size, n_steps, n_
                                          truncated.data_ptr(), level.data_ptr(), None if stopped is None else stopped.data_ptr(), _stream()),
                "nerf_occ_march_step")
     return z_vals, z_stop, truncated, level, stopped
+
+
+def view_planes(near, far):
+    """(near_m, far_m) = (fp32(near (1 - 2^-10)), fp32(far (1 + 2^-10))), computed in double: the depth range nerf_occ_view_carve tests
+    the corners of a cell against (include/nerf_hip.h)"""
+    import numpy as np
+    return float(np.float32(float(near) * (1.0 - 2.0 ** -10))), float(np.float32(float(far) * (1.0 + 2.0 ** -10)))
+
+
+def occ_view_carve(desc, width, cams, H, W, near_m, far_m, margin_px, sat, seen, carved_words, accumulate=False):
+    """nerf_occ_view_carve: seen (int32 [cells], preallocated) (+)= per cell the number of the cameras cams (fp32 [V, 16]: c2w row-major,
+    fx, fy, cx, cy) that see it; with sat (int32 [V, H + 1, W + 1], the summed-area tables of the masks) carved_words (int32 [words],
+    preallocated) (|)= the cells some camera carves.  sat and carved_words are both tensors or both None.  Returns (seen, carved_words)."""
+    n_cells = desc.res[0] * desc.res[1] * desc.res[2]
+    V = cams.shape[0] if cams.dim() == 2 else -1
+    if cams.dim() != 2 or cams.shape[1] != 16 or V < 1:
+        raise NerfHipError("occ_view_carve: cams [V >= 1, 16] (c2w row-major, fx, fy, cx, cy)")
+    if seen.numel() != n_cells or (carved_words is not None and carved_words.numel() != (n_cells + 31) // 32):
+        raise NerfHipError("occ_view_carve: seen holds one count per cell, carved_words one word per 32 cells")
+    if (sat is None) != (carved_words is None):
+        raise NerfHipError("occ_view_carve: sat and carved_words come together (with masks) or not at all")
+    if sat is not None and tuple(sat.shape) != (V, int(H) + 1, int(W) + 1):
+        raise NerfHipError("occ_view_carve: sat [V, H + 1, W + 1]")
+    w3 = (ctypes.c_float * 3)(*[float(v) for v in width])
+    with _timed("occ_view_carve_kernel", 0.0, 4.0 * n_cells + 64.0 * V):
+        _check(lib().nerf_occ_view_carve(ctypes.byref(desc), w3, _ptr(cams, "cams"), V, int(H), int(W), float(near_m), float(far_m),
+                                         float(margin_px), None if sat is None else _words(sat, "sat"), int(bool(accumulate)),
+                                         _words(seen, "seen"), None if carved_words is None else _words(carved_words, "carved_words"),
+                                         _stream()), "nerf_occ_view_carve")
+    return seen, carved_words
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

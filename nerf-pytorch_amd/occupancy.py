@@ -113,6 +113,45 @@ def stop_depth(z_vals, weights, eps):
         return hb.occ_stop_depth(z_vals.detach().to(torch.float32).contiguous(), weights.detach().to(torch.float32).contiguous(), eps)
 
 
+_SAT_BYTES = 64 << 20       # most summed-area tables held at once by view_counts / carved (the views are fed in chunks)
+
+
+def _view_inputs(who, c2w, H, W, K, near, far, margin_px, masks=None):
+    """what the view tests start from: (cams fp32 [V, 16] on the CPU -- c2w row-major, fx, fy, cx, cy --, H, W, near_m, far_m, m, masks
+    bool [V, H, W] or None)"""
+    c2w = torch.as_tensor(c2w).detach().to(device="cpu", dtype=torch.float32)
+    if c2w.dim() == 2:
+        c2w = c2w[None]
+    if c2w.dim() != 3 or c2w.shape[0] < 1 or c2w.shape[1] < 3 or c2w.shape[2] != 4:
+        raise ValueError(f"{who}: c2w [V >= 1, 3, 4] (columns right, up, back, position)")
+    V = c2w.shape[0]
+    K = torch.as_tensor(K).detach().to(device="cpu", dtype=torch.float32)
+    if tuple(K.shape) == (3, 3):
+        K = K[None].expand(V, 3, 3)
+    if tuple(K.shape) != (V, 3, 3):
+        raise ValueError(f"{who}: K [3, 3] or [V, 3, 3]")
+    H, W, m = int(H), int(W), float(margin_px)
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"{who}: 1 <= H, W <= 16384, got {H}, {W}")
+    if not (0.0 <= m < float("inf")):       # (also refuses NaN)
+        raise ValueError(f"{who}: margin_px must be finite and >= 0, got {margin_px!r}")
+    near_m, far_m = hb.view_planes(near, far)
+    cams = torch.cat([c2w[:, :3, :].reshape(V, 12), K[:, 0, 0:1], K[:, 1, 1:2], K[:, 0, 2:3], K[:, 1, 2:3]], -1).contiguous()
+    if masks is not None:
+        masks = torch.as_tensor(masks)
+        if masks.dtype != torch.bool or tuple(masks.shape) != (V, H, W):
+            raise ValueError(f"{who}: masks must be bool [V, H, W] = {(V, H, W)}, True meaning foreground")
+    return cams, H, W, near_m, far_m, m, masks
+
+
+def _mask_sat(masks):
+    """int32 [V, H + 1, W + 1]: sat[v, j, i] = the foreground pixels of masks[v] with row < j and column < i"""
+    V, H, W = masks.shape
+    sat = torch.zeros((V, H + 1, W + 1), dtype=torch.int32, device=masks.device)
+    sat[:, 1:, 1:] = masks.to(torch.int32).cumsum(1, dtype=torch.int32).cumsum(2, dtype=torch.int32)
+    return sat
+
+
 class OccupancyGrid:
     """One bit per cell of the axis-aligned box [lo, hi] at resolution (Rx, Ry, Rz) (an int means cubic; 1..512 per axis), in the
     space of the points ``o + d z`` the network sees -- for ``ndc=True`` rays that is NDC space.
@@ -132,7 +171,9 @@ class OccupancyGrid:
     (``march_reference`` is the definition) -- render_rays(proposal="march"), whose last_stats carry {"rays_truncated"} (and, with
     march_stop_eps over a DensityGrid, {"rays_stopped"}).  ``march_step`` is the march in steps of one length in the scene, with the
     step doubled per ray until its emitted steps fit the slots (``march_step_reference`` is the definition) --
-    render_rays(proposal="march", march_step_size=ds, march_fit=J), whose last_stats carry {"rays_refit"} when J > 0."""
+    render_rays(proposal="march", march_step_size=ds, march_fit=J), whose last_stats carry {"rays_refit"} when J > 0.
+    ``from_views`` builds a grid without a network, from the training cameras (and silhouettes) alone: the cells some camera sees, minus
+    the cells some camera carves (``view_counts_reference`` / ``carved_reference`` are the definitions); ``restrict`` ANDs such a grid in."""
 
     def __init__(self, lo, hi, resolution, outside="evaluate", device=None):
         if outside not in _OUTSIDE:
@@ -152,6 +193,7 @@ class OccupancyGrid:
             raise ValueError("OccupancyGrid: hi must exceed lo on every axis")
         r = np.asarray(self.resolution, dtype=np.float64)
         self.scale = (r / (self.hi.astype(np.float64) - self.lo.astype(np.float64))).astype(np.float32)
+        self.width = ((self.hi.astype(np.float64) - self.lo.astype(np.float64)) / r).astype(np.float32)     # (a cell's edges: the view tests)
 
     # ------------------------------------------------------------------ plain properties
     @property
@@ -432,6 +474,176 @@ class OccupancyGrid:
             z_vals, z_stop, truncated, level, _ = hb.occ_march_step(self._desc(), None, 0.0, rays, u, step_size, M, S, fit)
         return z_vals, z_stop, truncated.bool(), level
 
+    # ------------------------------------------------------------------ grids from cameras and silhouettes
+    _CORNERS = tuple(((k >> 2) & 1, (k >> 1) & 1, k & 1) for k in range(8))
+
+    def _views_reference(self, who, c2w, H, W, K, near, far, margin_px, masks):
+        """the rule of view_counts_reference / carved_reference, once (plain torch on c2w's device, the CPU for anything that is no
+        tensor): (count int32 [n_cells], carved bool [n_cells] -- all False without masks)"""
+        dev = c2w.device if isinstance(c2w, torch.Tensor) else torch.device("cpu")
+        cams, H, W, near_m, far_m, m, masks = _view_inputs(who, c2w, H, W, K, near, far, margin_px, masks)
+        f = lambda a: torch.tensor(a, dtype=torch.float32, device=dev)
+        cams, lo, width = cams.to(dev), f(self.lo), f(self.width)
+        sat = None if masks is None else _mask_sat(masks.to(dev))
+        near_m, far_m, m = f(near_m), f(far_m), f(m)
+        w_hi, h_hi = f(float(W - 1)) + m, f(float(H - 1)) + m
+        rx, ry, rz = self.resolution
+        offs = torch.tensor(self._CORNERS, dtype=torch.int64, device=dev)
+        count = torch.zeros(self.n_cells, dtype=torch.int32, device=dev)
+        carved = torch.zeros(self.n_cells, dtype=torch.bool, device=dev)
+        for first in range(0, self.n_cells, 1 << 18):
+            run = slice(first, min(first + (1 << 18), self.n_cells))
+            c = torch.arange(run.start, run.stop, dtype=torch.int64, device=dev)
+            idx = torch.stack([c // (ry * rz), (c // rz) % ry, c % rz], -1)
+            p = lo + (idx[:, None, :] + offs[None, :, :]).to(torch.float32) * width         # [cells, 8, 3]: one multiplication, one addition
+            for v in range(cams.shape[0]):
+                cam = cams[v]
+                d0, d1, d2 = p[..., 0] - cam[3], p[..., 1] - cam[7], p[..., 2] - cam[11]
+                x = d0 * cam[0] + d1 * cam[4] + d2 * cam[8]                 # (added left to right)
+                y = d0 * cam[1] + d1 * cam[5] + d2 * cam[9]
+                s = -(d0 * cam[2] + d1 * cam[6] + d2 * cam[10])
+                fx, fy, cx, cy = cam[12], cam[13], cam[14], cam[15]
+                fxx, fyy = fx * x, fy * y
+                tests = (s >= near_m, s <= far_m, fxx >= (-m - cx) * s, fxx <= (w_hi - cx) * s, -fyy >= (-m - cy) * s, -fyy <= (h_hi - cy) * s)
+                unseen = torch.stack([(~t).all(-1) for t in tests], -1).any(-1)      # all eight corners fail one and the same test
+                count[run] += (~unseen).to(torch.int32)
+                if sat is None:
+                    continue
+                pi, pj = fxx / s + cx, cy - fyy / s
+                ok = (s >= near_m).all(-1) & torch.isfinite(pi).all(-1) & torch.isfinite(pj).all(-1)
+                i0, i1 = torch.floor(pi.amin(-1) - m), torch.ceil(pi.amax(-1) + m)
+                j0, j1 = torch.floor(pj.amin(-1) - m), torch.ceil(pj.amax(-1) + m)
+                ok = ok & (i0 >= 0) & (i1 <= float(W - 1)) & (j0 >= 0) & (j1 <= float(H - 1))       # else the camera abstains
+                i0, i1, j0, j1 = (torch.where(ok, t, torch.zeros_like(t)).to(torch.int64) for t in (i0, i1, j0, j1))
+                t = sat[v]
+                n = t[j1 + 1, i1 + 1] - t[j0, i1 + 1] - t[j1 + 1, i0] + t[j0, i0]
+                carved[run] |= ok & (n == 0)
+        return count, carved
+
+    def view_counts_reference(self, c2w, H, W, K, near, far, margin_px=0.5):
+        """The definition of "seen by a camera", in plain torch (on c2w's device): int32 [Rx, Ry, Rz], the number of the cameras c2w
+        [V, 3, 4] -- columns right, up, back, position, the convention of get_rays: pixel (i, j) looks along ((i - cx) / fx,
+        -(j - cy) / fy, -1) rotated by c2w[:3, :3] -- with intrinsics K ([3, 3] or [V, 3, 3]) and H x W pixels that see each cell
+        between the depths near and far.  WORLD SPACE ONLY: a grid used with ndc=True rays lives in NDC space, where a camera's frustum
+        is not this one; such a grid is not supported here.
+
+        Corner o in {0, 1}^3 of cell (ix, iy, iz) is lo + fp32(i + o) * width in fp32, one multiplication and one addition per axis,
+        width = fp32((hi - lo) / R) computed once in float64 (as scale is).  In camera v, with d = p - c2w[:, 3]: x = d . c2w[:, 0],
+        y = d . c2w[:, 1], s = -(d . c2w[:, 2]), each three products added left to right in fp32; s is the depth z that render() samples.
+        Six inside-tests per corner, m = margin_px:
+            s >= near_m        s <= far_m
+            fx x >= (-m - cx) s        fx x <= ((W - 1 + m) - cx) s
+            -(fy y) >= (-m - cy) s     -(fy y) <= ((H - 1 + m) - cy) s
+        near_m = fp32(near (1 - 2^-10)), far_m = fp32(far (1 + 2^-10)) (computed in float64): a slack far above the rounding of a sample
+        point o + d z and far below a cell.  The cell is UNSEEN by v only if all eight corners fail one and the same test.  Every test
+        is a half-space and a cell is convex, so a cell whose corners all lie outside one of them has no point inside the frustum:
+        the test errs only towards "seen".  They are written as inside-tests so that a NaN pose or corner fails all six: a NaN camera
+        sees nothing."""
+        count, _ = self._views_reference("OccupancyGrid.view_counts_reference", c2w, H, W, K, near, far, margin_px, None)
+        return count.view(self.resolution)
+
+    def carved_reference(self, c2w, H, W, K, near, far, masks, margin_px=0.5):
+        """The definition of the visual hull's complement, in plain torch (on c2w's device): bool [Rx, Ry, Rz], the cells that some camera
+        carves.  masks: bool [V, H, W], True meaning foreground (a silhouette: alpha > 0); the rest as ``view_counts_reference``.
+
+        Camera v carves a cell iff all eight corners have s >= near_m, every i = fx x / s + cx and j = cy - fy y / s (IEEE division) is
+        finite, the pixel rectangle i0 = floor(min i - m) .. i1 = ceil(max i + m), j0 .. j1 likewise, lies inside [0, W - 1] x
+        [0, H - 1] -- otherwise the camera abstains: what it cannot see whole it does not judge -- and the rectangle holds no foreground
+        pixel.  That count is read from a summed-area table, sat int32 [V, H + 1, W + 1] built with cumsum:
+        sat[j1 + 1, i1 + 1] - sat[j0, i1 + 1] - sat[j1 + 1, i0] + sat[j0, i0].
+        With all s > 0 the projection of the cell is the hull of its projected corners, which the rectangle contains with m pixels to
+        spare: no foreground pixel's ray of camera v crosses a cell that v carves, whatever the object is."""
+        if masks is None:
+            raise ValueError("OccupancyGrid.carved_reference: masks bool [V, H, W] are required")
+        _, carved = self._views_reference("OccupancyGrid.carved_reference", c2w, H, W, K, near, far, margin_px, masks)
+        return carved.view(self.resolution)
+
+    @staticmethod
+    def _check_min_views(min_views, who):
+        if isinstance(min_views, bool) or not isinstance(min_views, (int, np.integer)) or int(min_views) < 1:
+            raise ValueError(f"{who}: min_views must be an int >= 1, got {min_views!r}")
+        return int(min_views)
+
+    def views_keep_reference(self, c2w, H, W, K, near, far, masks=None, min_views=1, margin_px=0.5):
+        """bool [Rx, Ry, Rz]: keep = (view count >= min_views) & ~carved -- with masks None the visibility alone.  What ``from_views`` and
+        ``DensityGrid.restrict_to_views`` put into a grid, by the two definitions above."""
+        min_views = self._check_min_views(min_views, "OccupancyGrid.views_keep_reference")
+        count, carved = self._views_reference("OccupancyGrid.views_keep_reference", c2w, H, W, K, near, far, margin_px, masks)
+        return ((count >= min_views) & ~carved).view(self.resolution)
+
+    def _views_kernel(self, who, c2w, H, W, K, near, far, margin_px, masks):
+        """(seen int32 [n_cells], carved words int32 or None) on the grid's device (nerf_occ_view_carve), the views fed in chunks whose
+        summed-area tables stay under _SAT_BYTES"""
+        desc = self._desc()
+        dev = self.device
+        cams, H, W, near_m, far_m, m, masks = _view_inputs(who, c2w, H, W, K, near, far, margin_px, masks)
+        V = cams.shape[0]
+        chunk = V if masks is None else max(1, _SAT_BYTES // (4 * (H + 1) * (W + 1)))
+        seen = torch.empty(self.n_cells, dtype=torch.int32, device=dev)
+        carved = None if masks is None else torch.empty_like(self.bits)
+        with torch.no_grad():
+            cams = cams.to(dev)
+            for v0 in range(0, V, chunk):
+                sat = None if masks is None else _mask_sat(masks[v0:v0 + chunk].to(dev)).contiguous()
+                hb.occ_view_carve(desc, self.width, cams[v0:v0 + chunk].contiguous(), H, W, near_m, far_m, m, sat, seen, carved, accumulate=v0 > 0)
+        return seen, carved
+
+    def view_counts(self, c2w, H, W, K, near, far, margin_px=0.5):
+        """int32 [Rx, Ry, Rz] on the GPU (nerf_occ_view_carve): ``view_counts_reference`` bit for bit"""
+        return self._views_kernel("OccupancyGrid.view_counts", c2w, H, W, K, near, far, margin_px, None)[0].view(self.resolution)
+
+    def carved(self, c2w, H, W, K, near, far, masks, margin_px=0.5):
+        """bool [Rx, Ry, Rz] on the GPU (nerf_occ_view_carve): ``carved_reference`` bit for bit"""
+        if masks is None:
+            raise ValueError("OccupancyGrid.carved: masks bool [V, H, W] are required")
+        words = self._views_kernel("OccupancyGrid.carved", c2w, H, W, K, near, far, margin_px, masks)[1]
+        return _unpack_bits(words, self.n_cells).view(self.resolution)
+
+    def _views_keep_words(self, who, c2w, H, W, K, near, far, masks, min_views, margin_px, dilate):
+        """the bit words of ``views_keep_reference`` on the GPU, then `dilate` rounds of the 3x3x3 OR"""
+        min_views = self._check_min_views(min_views, who)
+        if isinstance(dilate, bool) or int(dilate) < 0:
+            raise ValueError(f"{who}: dilate >= 0")
+        seen, carved = self._views_kernel(who, c2w, H, W, K, near, far, margin_px, masks)
+        with torch.no_grad():
+            words = hb.occ_mark(seen.to(torch.float32), 1, min_views - 0.5, torch.empty_like(self.bits))       # count > min_views - 1/2
+            if carved is not None:
+                words = words & ~carved
+            for _ in range(int(dilate)):
+                words = hb.occ_dilate(words, self.resolution)
+        return words
+
+    @classmethod
+    def from_views(cls, c2w, H, W, K, near, far, lo, hi, resolution, masks=None, min_views=1, margin_px=0.5, dilate=0, outside="evaluate",
+                   device=None):
+        """Grid of a set of training cameras, before any network exists: cell c is occupied iff at least min_views cameras see it
+        (``view_counts_reference``) and, with silhouette masks, no camera carves it (``carved_reference``: the visual hull); then `dilate`
+        rounds of the 3x3x3 OR.  A cell no training camera sees is never supervised, and a cell outside the hull is empty whatever the
+        network says.  The grid lives on the GPU (the cells are projected by nerf_occ_view_carve); world space only.  (A DensityGrid
+        recomputes its bits on every update: there the same cells are a restriction, DensityGrid.restrict_to_views.)"""
+        g = cls(lo, hi, resolution, outside, device)
+        g.bits = g._views_keep_words("OccupancyGrid.from_views", c2w, H, W, K, near, far, masks, min_views, margin_px, dilate)
+        return g
+
+    def _keep_words(self, keep, who):
+        """the bit words, on this grid's device, of a restriction given as a grid of the same box and resolution or as bool [Rx, Ry, Rz]"""
+        if isinstance(keep, OccupancyGrid):
+            if keep.resolution != self.resolution or not (np.array_equal(keep.lo, self.lo) and np.array_equal(keep.hi, self.hi)):
+                raise ValueError(f"{who}: the restricting grid must have this grid's box and resolution")
+            return keep.bits.to(self.device).clone()
+        keep = torch.as_tensor(keep)
+        if keep.dtype != torch.bool or tuple(keep.shape) != self.resolution:
+            raise ValueError(f"{who}: keep must be an OccupancyGrid or bool [Rx, Ry, Rz] = {self.resolution}, got {keep.dtype} {tuple(keep.shape)}")
+        return _pack_bits(keep.to(self.device).reshape(-1))
+
+    def restrict(self, keep):
+        """bits &= keep, once: keep is an OccupancyGrid of the same box and resolution (``from_views``' for instance) or bool
+        [Rx, Ry, Rz].  Returns self.  (A DensityGrid remembers the restriction: DensityGrid.restrict.)"""
+        if keep is None:
+            raise ValueError("OccupancyGrid.restrict: a plain grid keeps no restriction that could be removed")
+        self.bits = self.bits & self._keep_words(keep, "OccupancyGrid.restrict")
+        return self
+
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):
         return {"lo": torch.tensor(self.lo), "hi": torch.tensor(self.hi), "resolution": torch.tensor(self.resolution, dtype=torch.int64),
@@ -520,7 +732,12 @@ class DensityGrid(OccupancyGrid):
     compositing weights of ``proposal_sigma`` at the coarse depths (``proposal_weights``) and evaluates one network only.
     And a third: ``march_stop`` is ``march`` that adds the densities up as it walks and stops emitting where the grid's own
     transmittance has fallen to eps (``march_stop_reference`` is the definition) -- render_rays(proposal="march", march_stop_eps=eps);
-    ``march_step_stop`` is the same rule on the world-space march (``march_step_stop_reference``)."""
+    ``march_step_stop`` is the same rule on the world-space march (``march_step_stop_reference``).
+
+    ``restrict(keep)`` / ``restrict_to_views(cameras, silhouettes)`` cap the grid from outside: ``keep`` (bit words, None at first) is
+    ANDed into the bits now and after every update, so a cell no training camera sees, or one outside the visual hull, is never
+    occupied whatever density the network reports there -- and during the warm-up the grid is the hull instead of all-occupied.  A grid
+    without a restriction runs exactly the launches it ran before there was one."""
 
     def __init__(self, lo, hi, resolution, outside="evaluate", device=None, decay=0.95, sigma_threshold=0.01, dilate=0, update_every=16,
                  warmup_steps=256):
@@ -532,10 +749,13 @@ class DensityGrid(OccupancyGrid):
         self.density = torch.zeros(self.n_cells, dtype=torch.float32, device=self.bits.device)
         self.cursor = 0             # first cell of the next update's run (a multiple of 32: runs are whole words)
         self.n_updates = 0
+        self.keep = None            # the restriction: int32 bit words ANDed into `bits`, or None
 
     def to(self, device):
         super().to(device)
         self.density = self.density.to(device)
+        if self.keep is not None:
+            self.keep = self.keep.to(device)
         return self
 
     # ------------------------------------------------------------------ the definition (plain torch, any device)
@@ -547,12 +767,17 @@ class DensityGrid(OccupancyGrid):
         d = self.density[first:last] * torch.tensor(self.decay, dtype=torch.float32, device=self.density.device)
         self.density[first:last] = torch.where(m > d, m, d)
 
-    def _bits_reference(self):
-        """bits of the whole grid from ``density``: dilate^dilate(density > sigma_threshold)"""
+    def _density_bits_reference(self):
+        """bits of the whole grid from ``density`` alone: dilate^dilate(density > sigma_threshold)"""
         mask = (self.density > torch.tensor(self.sigma_threshold, dtype=torch.float32, device=self.density.device)).view(self.resolution)
         for _ in range(self.dilate):
             mask = torch.nn.functional.max_pool3d(mask[None, None].float(), 3, 1, 1)[0, 0] > 0
         return _pack_bits(mask.reshape(-1))
+
+    def _bits_reference(self):
+        """bits of the whole grid after an update: those of ``density``, ANDed with ``keep`` where one is set"""
+        bits = self._density_bits_reference()
+        return bits if self.keep is None else bits & self.keep.to(bits.device)
 
     def _next_runs(self, fraction):
         """the cells one update visits, as [(first, last)] (two runs when the visit wraps), and the cursor moved past them: `fraction`
@@ -596,11 +821,50 @@ class DensityGrid(OccupancyGrid):
                     vd = torch.tensor([0.0, 0.0, 1.0], device=dev).expand(pts.shape[0], 3)
                     sigma = query_points(model, pts, vd)[:, 3].contiguous()
                     hb.occ_density_update(sigma, K, self.decay, self.density[first:last])
+            bits = self._density_bits()
+            if self.keep is not None:       # after thresholding and dilation: the restriction survives every update
+                bits = bits & self.keep
+        self.bits = bits
+        return self
+
+    def _density_bits(self):
+        """``_density_bits_reference`` on the GPU: nerf_occ_mark, then `dilate` rounds of nerf_occ_dilate"""
+        with torch.no_grad():
             bits = hb.occ_mark(self.density, 1, self.sigma_threshold, torch.empty_like(self.bits))
             for _ in range(self.dilate):
                 bits = hb.occ_dilate(bits, self.resolution)
-        self.bits = bits
+        return bits
+
+    # ------------------------------------------------------------------ the restriction
+    def _unrestricted_bits(self):
+        """the bits this grid would hold without a restriction: all ones before its first update, afterwards those of ``density``"""
+        if self.n_updates == 0:
+            return _pack_bits(torch.ones(self.n_cells, dtype=torch.bool, device=self.device))
+        return self._density_bits() if self.bits.is_cuda else self._density_bits_reference()
+
+    def restrict(self, keep):
+        """Cap the grid: ``keep`` -- an OccupancyGrid of the same box and resolution, or bool [Rx, Ry, Rz] -- is stored as ``self.keep``
+        (int32 bit words on the grid's device) and ANDed into ``bits`` now; ``update()`` ANDs it in after thresholding and dilation
+        (``_bits_reference()`` does the same), so the restriction survives every update and holds during the warm-up.  A second
+        restriction replaces the first.  ``restrict(None)`` removes it: the bits are again what the grid's own state gives -- all ones
+        before the first update, those of ``density`` afterwards.  Returns self."""
+        return self._set_keep(None if keep is None else self._keep_words(keep, "DensityGrid.restrict"))
+
+    def _set_keep(self, words):
+        had, self.keep = self.keep is not None, words
+        if had:                     # the bits without the restriction they carry
+            self.bits = self._unrestricted_bits()
+        if words is not None:
+            self.bits = self.bits & words
         return self
+
+    def restrict_to_views(self, c2w, H, W, K, near, far, masks=None, min_views=1, margin_px=0.5, dilate=0):
+        """``restrict`` to what the training cameras see and, with silhouette masks, to their visual hull -- OccupancyGrid.from_views'
+        cells for this grid's box and resolution, computed on the GPU (nerf_occ_view_carve).  Called once, before step 0: the grid path
+        then skips empty space from the first step instead of after the warm-up, and ``update()`` can never turn on a cell that no
+        camera supervises.  World space only.  Returns self."""
+        return self._set_keep(self._views_keep_words("DensityGrid.restrict_to_views", c2w, H, W, K, near, far, masks, min_views, margin_px,
+                                                     dilate))
 
     def maybe_update(self, model, global_step, **kw):
         """the training loop's call, once per step: False (nothing done) while global_step < warmup_steps or when global_step is no
@@ -708,6 +972,8 @@ class DensityGrid(OccupancyGrid):
         state = super().state_dict()
         state.update(density=self.density.detach().cpu().clone(), cursor=self.cursor, n_updates=self.n_updates,
                      **{k: getattr(self, k) for k in self._SCALARS})
+        if self.keep is not None:       # (a grid without a restriction keeps exactly the keys it had)
+            state["keep"] = self.keep.detach().cpu().clone()
         return state
 
     def load_state_dict(self, state):
@@ -720,7 +986,13 @@ class DensityGrid(OccupancyGrid):
             raise ValueError("DensityGrid.load_state_dict: `density` does not match `resolution`")
         if int(state["cursor"]) % 32 or not (0 <= int(state["cursor"]) < max(density.numel(), 1)):
             raise ValueError("DensityGrid.load_state_dict: `cursor` must be a multiple of 32 inside the grid")
+        keep = state.get("keep")
+        if keep is not None:
+            keep = torch.as_tensor(keep).to(torch.int32).reshape(-1)
+            if keep.numel() != (density.numel() + 31) // 32:
+                raise ValueError("DensityGrid.load_state_dict: `keep` does not match `resolution`")
         super().load_state_dict(state)
+        self.keep = None if keep is None else keep.to(self.device).contiguous().clone()
         self.density = density.to(self.device).contiguous().clone()
         self.cursor, self.n_updates = int(state["cursor"]), int(state["n_updates"])
         self.decay, self.sigma_threshold = float(state["decay"]), float(state["sigma_threshold"])
