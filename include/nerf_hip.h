@@ -600,6 +600,30 @@ int nerf_occ_view_carve(const NerfOccGrid* grid, const float width[3], const flo
                         float near_m, float far_m, float margin_px, const int* sat /* nullable */, int accumulate, int* seen,
                         unsigned* carved_words /* non-NULL iff sat */, void* stream);
 
+/* ---- isosurface (additive in ABI v10): the triangle mesh of a volume at `level`, marching tetrahedra on the Kuhn subdivision of the
+ * lattice.  mesh.extract_mesh_reference is the definition, nerf-pytorch_amd/csrc/iso_tables.h holds the tables.  volume is fp32
+ * [nx][ny][nz], one value per lattice node; node = (i ny + j) nz + k sits at lo[a] + fp32(index[a]) * step[a].  A node is inside iff
+ * value >= level (a NaN is outside).  Every cube (i, j, k), i < nx - 1 ..., is cut into six tetrahedra, one per permutation of the
+ * axes.  keep_words (nullable: every cube) holds one bit per cube in the layout of an occupancy grid of resolution (nx - 1, ny - 1,
+ * nz - 1); a cube whose bit is 0 emits nothing.
+ *   vertices  one per lattice edge with exactly one endpoint inside that belongs to a kept cube, in ascending edge id = 7 node(lower
+ *             endpoint) + class (the seven directions 100 010 001 110 101 011 111).  With a, b the values at the lower and upper
+ *             endpoint made finite (NaN -> -FLT_MAX, +-inf -> +-FLT_MAX): t = (level - a) / (b - a) (IEEE division; a NaN t is 1/2) and
+ *             p = p_a + t (p_b - p_a) per component, nothing contracted.
+ *   faces     int32 vertex indices, one triangle per tetrahedron with 1 or 3 inside corners, two with 2, ordered by cube, tetrahedron,
+ *             triangle; (p1 - p0) x (p2 - p0) points from inside to outside.
+ * The count call fills counts (device int[2]) = (V, F) and the block offsets inside scratch; the emit call, given the same volume,
+ * sizes, level, keep_words and scratch afterwards, writes vertices [V][3] and faces [F][3] (and needs V > 0).  Six launches in all: a
+ * count per block, a scan and a write for the edges and again for the cubes; plain loads and stores, no atomics: the same inputs give
+ * the same bytes.  scratch: as many ints as the size call says (7 per node for the rank of every edge, one per block of 1024 edges and
+ * of 256 cubes).  2 <= nx, ny, nz; 7 nodes < 2^31 and 12 cubes < 2^31 (vertex and triangle counts are 32-bit; the size call gives 0
+ * otherwise); level finite. */
+size_t nerf_iso_scratch_words(int nx, int ny, int nz);
+int nerf_iso_count(const float* volume, int nx, int ny, int nz, float level, const unsigned* keep_words /* nullable */, int* scratch,
+                   int* counts /* device int[2]: V, F */, void* stream);
+int nerf_iso_emit(const float* volume, int nx, int ny, int nz, float level, const float lo[3], const float step[3],
+                  const unsigned* keep_words /* nullable */, int* scratch, float* vertices, int* faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,9 @@ from .sampling import RayBatcher, sample_ray_batch  # noqa: F401
 from .pose import PoseRefinement  # noqa: F401
 from .occupancy import DensityGrid, OccupancyGrid  # noqa: F401
 from . import occupancy  # noqa: F401
+from .mesh import density_volume, extract_mesh, extract_mesh_reference, mesh_from_network, write_ply  # noqa: F401
+from . import mesh  # noqa: F401
 
-__all__ = ["Embedder", "NeRF", "get_embedder", "batchify", "batchify_rays", "get_rays", "get_rays_np", "img2mse",
+__all__ = ["density_volume", "extract_mesh", "extract_mesh_reference", "mesh_from_network", "write_ply", "mesh","Embedder", "NeRF", "get_embedder", "batchify", "batchify_rays", "get_rays", "get_rays_np", "img2mse",
            "mse2psnr", "ndc_rays", "query_points", "raw2outputs", "render", "render_path", "render_rays",
            "run_network", "sample_pdf", "to8b", "config_parser", "create_nerf", "hip_backend", "parallel", "set_precision", "get_precision", "FlatAdam", "sample_ray_batch", "RayBatcher", "PoseRefinement", "DEFAULT_PRECISION", "check_range", "OccupancyGrid", "DensityGrid", "occupancy"]

@@ -36,6 +36,7 @@
 #include <stdint.h>
 #include "api_util.h"
 #include "ray_device.h"
+#include "scan_device.h"       // occ_scan_kernel: the scan between the count and the write
 
 using namespace nerf_api;
 
@@ -45,7 +46,6 @@ constexpr int OCC_THREADS = 256;                // 4 waves
 constexpr int OCC_ITERS = 4;
 constexpr int OCC_TILE = OCC_THREADS * OCC_ITERS;   // points per block
 constexpr int OCC_WAVES = OCC_THREADS / 64;
-constexpr int SCAN_THREADS = 1024;
 
 struct GridArgs {
     float lo[3], scale[3];
@@ -130,34 +130,6 @@ __global__ __launch_bounds__(OCC_THREADS) void occ_count_kernel(GridArgs g, cons
         for (int w = 0; w < OCC_WAVES; ++w) s += wave_n[w];
         block_count[blockIdx.x] = s;
     }
-}
-
-// exclusive scan of the block counts in place (one workgroup walks them in SCAN_THREADS-sized pieces with a carry); count[0] = total
-__global__ __launch_bounds__(SCAN_THREADS) void occ_scan_kernel(int* __restrict__ block_count, int n_blocks, int* __restrict__ count) {
-    __shared__ int part[SCAN_THREADS / 64];
-    __shared__ int carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int base = 0; base < n_blocks; base += SCAN_THREADS) {
-        const int i = base + tid;
-        const int v = i < n_blocks ? block_count[i] : 0;
-        int incl = v;       // inclusive scan inside the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) part[wave] = incl;
-        __syncthreads();
-        int before = carry_s;
-        for (int w = 0; w < wave; ++w) before += part[w];
-        if (i < n_blocks) block_count[i] = before + incl - v;
-        __syncthreads();
-        if (tid == SCAN_THREADS - 1) carry_s = before + incl;
-        __syncthreads();
-    }
-    if (tid == 0) count[0] = carry_s;
 }
 
 template <bool STOP>

@@ -99,6 +99,9 @@ def _declare(lib):
         "nerf_occ_march_stop": (i, [p, p, f, p, i, p, i, i, i, f, p, p, p, p, p]),
         "nerf_occ_march_step": (i, [p, p, f, p, i, p, i, f, i, i, i, f, p, p, p, p, p, p]),
         "nerf_occ_view_carve": (i, [p, p, p, i, i, i, f, f, f, p, i, p, p, p]),
+        "nerf_iso_scratch_words": (sz, [i, i, i]),
+        "nerf_iso_count": (i, [p, i, i, i, f, p, p, p, p]),
+        "nerf_iso_emit": (i, [p, i, i, i, f, p, p, p, p, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -127,6 +130,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span", "nerf_occ_proposal_weights",
            "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march", "nerf_occ_march_stop", "nerf_occ_march_step",
            "nerf_occ_view_carve",
+           "nerf_iso_scratch_words", "nerf_iso_count", "nerf_iso_emit",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
 
 
@@ -1353,6 +1357,53 @@ def occ_view_carve(desc, width, cams, H, W, near_m, far_m, margin_px, sat, seen,
                                          _words(seen, "seen"), None if carved_words is None else _words(carved_words, "carved_words"),
                                          _stream()), "nerf_occ_view_carve")
     return seen, carved_words
+
+
+# ---- isosurface (csrc/isosurface.hip; the user-facing functions are in mesh.py)
+def _iso_volume(who, volume, keep_words):
+    """(nx, ny, nz, nodes, cubes) of a lattice volume fp32 [nx, ny, nz] and its optional keep words (int32, one bit per cube)"""
+    _ptr(volume, "volume")
+    if volume.dim() != 3:
+        raise NerfHipError(f"{who}: volume [nx, ny, nz]")
+    nx, ny, nz = (int(v) for v in volume.shape)
+    cubes = (nx - 1) * (ny - 1) * (nz - 1)
+    if keep_words is not None and keep_words.numel() != (cubes + 31) // 32:
+        raise NerfHipError(f"{who}: keep_words holds one bit per cube, {(cubes + 31) // 32} words")
+    return nx, ny, nz, nx * ny * nz, cubes
+
+
+def iso_count(volume, level, keep_words=None):
+    """nerf_iso_count: (counts int32 [2] on the device = (V, F), scratch int32) of the mesh of volume (fp32 [nx, ny, nz], values at the
+    lattice nodes) at `level`; keep_words (int32, one bit per cube, or None) restricts it to the kept cubes.  scratch carries the block
+    offsets to iso_emit."""
+    nx, ny, nz, nodes, cubes = _iso_volume("iso_count", volume, keep_words)
+    words = lib().nerf_iso_scratch_words(nx, ny, nz)
+    scratch = torch.empty(max(words, 1), dtype=torch.int32, device=volume.device)
+    counts = torch.empty(2, dtype=torch.int32, device=volume.device)
+    # both count passes read the volume once (the neighbours come from the caches) and the keep bits; the scans walk the block counts
+    with _timed("iso_count (edges + scan + cubes + scan)", 0.0, 8.0 * nodes + cubes / 4.0 + 8.0 * (words - 7 * nodes)):
+        _check(lib().nerf_iso_count(_ptr(volume, "volume"), nx, ny, nz, float(level), None if keep_words is None else _words(keep_words, "keep_words"),
+                                    scratch.data_ptr(), counts.data_ptr(), _stream()), "nerf_iso_count")
+    return counts, scratch
+
+
+def iso_emit(volume, level, lo, step, keep_words, scratch, n_vertices, n_faces):
+    """nerf_iso_emit: (vertices fp32 [V, 3], faces int32 [F, 3]) after iso_count on the same volume, level and keep_words, whose scratch
+    and read-back counts (V > 0) this takes; lo / step: the position of node 0 and the lattice step per axis"""
+    nx, ny, nz, nodes, cubes = _iso_volume("iso_emit", volume, keep_words)
+    V, F = int(n_vertices), int(n_faces)
+    if V < 1 or F < 1 or scratch.numel() < lib().nerf_iso_scratch_words(nx, ny, nz):
+        raise NerfHipError("iso_emit: the counts (V, F >= 1) and the scratch of iso_count on this volume")
+    vertices = torch.empty((V, 3), dtype=torch.float32, device=volume.device)
+    faces = torch.empty((F, 3), dtype=torch.int32, device=volume.device)
+    lo3 = (ctypes.c_float * 3)(*[float(v) for v in lo])
+    step3 = (ctypes.c_float * 3)(*[float(v) for v in step])
+    # vertices: the volume, 28 B per node of edge ranks, the positions; faces: the volume, three ranks read and three indices written per triangle
+    with _timed("iso_emit (vertices + faces)", 0.0, 8.0 * nodes + 28.0 * nodes + 12.0 * V + cubes / 8.0 + 24.0 * F):
+        _check(lib().nerf_iso_emit(_ptr(volume, "volume"), nx, ny, nz, float(level), lo3, step3,
+                                   None if keep_words is None else _words(keep_words, "keep_words"), _words(scratch, "scratch"),
+                                   _ptr(vertices), faces.data_ptr(), _stream()), "nerf_iso_emit")
+    return vertices, faces
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

@@ -725,7 +725,8 @@ class DensityGrid(OccupancyGrid):
     all-occupied: it must not hide geometry the network has not learnt yet), afterwards an update every `update_every` steps.
 
     The defaults (decay 0.95, sigma_threshold 0.01, update_every 16, warmup_steps 256) are Instant-NGP's habits, not measurements made
-    with these networks: the threshold in particular is in the units of the scene's density and wants a look at ``fraction_occupied()``.
+    with these networks: the threshold in particular is in the units of the scene's density and wants a look at ``fraction_occupied()``
+    -- or at ``extract_mesh()``, the surface density = sigma_threshold of the grid's own densities (mesh.py).
     ``_update_reference`` / ``_bits_reference`` are the definition of the step in plain torch, as ``occupied()`` is the classifier's.
 
     The densities have a second reader: render_rays(..., occupancy=grid, proposal="grid") draws its importance samples from the
@@ -873,6 +874,18 @@ class DensityGrid(OccupancyGrid):
             return False
         self.update(model, **kw)
         return True
+
+    # ------------------------------------------------------------------ the grid's own surface
+    def extract_mesh(self, level=None):
+        """(vertices fp32 [V, 3], faces int32 [F, 3]): the surface density = level (default: sigma_threshold) of the grid's own ``density``,
+        taken as values at the cell centres -- mesh.extract_mesh on the lattice of `resolution` nodes from lo + width / 2 to
+        hi - width / 2 (fp32).  At sigma_threshold that is the boundary of what the grid path evaluates, before dilation and
+        restriction.  A preview that costs no network evaluation; the grid is not changed.  Needs the grid on the GPU and at least 2
+        cells per axis."""
+        from .mesh import extract_mesh
+        half = np.float32(0.5) * self.width
+        return extract_mesh(self.density.view(self.resolution), self.sigma_threshold if level is None else level, self.lo + half,
+                            self.hi - half)
 
     # ------------------------------------------------------------------ importance samples from the grid
     def outside_sigma(self):
