@@ -145,6 +145,25 @@ int nerf_raw2outputs_bwd(const float* raw, const float* z_vals, const float* ray
                          const float* d_rgb, const float* d_acc, const float* d_disp, const float* d_weights,
                          const float* d_depth, float* d_raw, void* stream);
 
+/* ---- distortion loss of the compositing weights (mip-NeRF 360's regulariser; additive in ABI v10; not in the reference).  Per ray
+ * with depths z_0 <= ... <= z_{S-1} (the CALLER's contract, not checked), weights w_i and the ray's own near / far:
+ *   s_i = (z_i - near) / (far - near), or 0 for every i when far - near is not > 0 (such a ray has loss 0 and gradient 0);
+ *   sample i < S-1 owns [s_i, s_{i+1}]: m_i = (s_i + s_{i+1}) / 2, dl_i = s_{i+1} - s_i; the last sample owns a zero-length
+ *   interval, m_{S-1} = s_{S-1}, dl_{S-1} = 0 (its compositing distance of 1e10 is a sentinel, not a length);
+ *   loss[r] = sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 dl_i
+ *   dloss/dw_k = 2 sum_j w_j |m_k - m_j| + 2/3 w_k dl_k
+ * evaluated in O(n_samples) from exclusive prefix and (directly summed) suffix sums of w and w m, one wavefront per ray, lane
+ * segments and wave scans as in nerf_raw2outputs; no atomics: the same inputs give the same bits.  near_far[0], near_far[1] are ray
+ * 0's near and far, ray r's lie r * nf_stride floats further on (rays + 6 with stride 11 for ray records; stride 0: one pair for
+ * all rays).  No gradient to z_vals, near or far: depths are constants of the graph.  1 <= n_samples <= 4096; n_rays = 0 launches
+ * nothing.  Reads 8 B per point, writes 4 B per ray. */
+int nerf_distortion_fwd(const float* weights, const float* z_vals, const float* near_far, int nf_stride, int n_rays,
+                        int n_samples, float* loss, void* stream);
+/* its adjoint, recomputed from the inputs (nothing saved): d_weights[r][k] = d_loss[r] * dloss/dw_k, written (accumulate = 0) or
+ * added to what d_weights holds (accumulate = 1).  Reads 8 B per point (12 B with accumulate), writes 4 B per point. */
+int nerf_distortion_bwd(const float* weights, const float* z_vals, const float* near_far, int nf_stride, int n_rays,
+                        int n_samples, const float* d_loss, float* d_weights, int accumulate, void* stream);
+
 /* ---- hierarchical sampling (run_nerf.py:392-396,412 + sample_pdf, run_nerf_helpers.py:196-239):
  * z_mid, sample_pdf(z_mid, weights[1:-1], n_fine, det = (u == NULL)), sort(cat(z_vals, z_samples)), z_std.
  * u [n_rays][n_fine] uniform draws or NULL; u_lin = torch.linspace(0,1,n_fine) (read when u == NULL).

@@ -292,6 +292,22 @@ int nerf_raw2outputs_bwd(const float* raw, const float* z_vals, const float* ray
     return done(__func__, nerf::launch_composite(a, true, (hipStream_t)stream));
 }
 
+int nerf_distortion_fwd(const float* weights, const float* z_vals, const float* near_far, int nf_stride, int n_rays,
+                        int n_samples, float* loss, void* stream) {
+    REQUIRE(weights && z_vals && near_far && loss, "null pointer");
+    REQUIRE(nf_stride >= 0 && n_rays >= 0 && n_samples >= 1 && n_samples <= 4096, "bad size");
+    nerf::DistortionArgs a{weights, z_vals, near_far, nf_stride, n_rays, n_samples, loss, nullptr, nullptr, 0};
+    return done(__func__, nerf::launch_distortion(a, false, (hipStream_t)stream));
+}
+
+int nerf_distortion_bwd(const float* weights, const float* z_vals, const float* near_far, int nf_stride, int n_rays,
+                        int n_samples, const float* d_loss, float* d_weights, int accumulate, void* stream) {
+    REQUIRE(weights && z_vals && near_far && d_loss && d_weights, "null pointer");
+    REQUIRE(nf_stride >= 0 && n_rays >= 0 && n_samples >= 1 && n_samples <= 4096, "bad size");
+    nerf::DistortionArgs a{weights, z_vals, near_far, nf_stride, n_rays, n_samples, nullptr, d_loss, d_weights, accumulate ? 1 : 0};
+    return done(__func__, nerf::launch_distortion(a, true, (hipStream_t)stream));
+}
+
 int nerf_sample_fine(const float* z_vals, const float* weights, int n_rays, int n_coarse, int n_fine,
                      const float* u, const float* u_lin, float* z_all, float* z_samples, float* z_std, void* stream) {
     REQUIRE(z_vals && weights && z_all && z_std, "null pointer");

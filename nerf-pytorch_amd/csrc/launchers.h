@@ -28,6 +28,18 @@ struct CompositeArgs {
     float* d_z;             // [N][S] nullable: dL/d z_vals through dists and the depth integral (written)
 };
 
+// distortion loss of the compositing weights (ray_device.h: distortion_ray)
+struct DistortionArgs {
+    const float* w;         // [N][S] compositing weights
+    const float* z;         // [N][S] depths, non-decreasing per ray
+    const float* near_far;  // near_far[r*nf_stride + 0..1] = the ray's near, far
+    int nf_stride, n_rays, S;
+    float* loss;            // [N]                                       (forward)
+    const float* d_loss;    // [N] upstream gradient                     (adjoint)
+    float* d_w;             // [N][S] written, or added to with accumulate (adjoint)
+    int accumulate;
+};
+
 struct FineArgs {
     // direct == 0: in0 = coarse depths z[N][Sc], in1 = coarse weights[N][Sc]
     //              bins = mid-points, pdf from weights[1:-1]               (run_nerf.py:392-393)
@@ -88,6 +100,7 @@ hipError_t launch_sample_ray_views(int H, int W, const float* K9, const int* vie
 hipError_t launch_ray_pose_grad(int W, const float* K9, const float* d_rays, int n_rays, const int* pixels, const int* views, int n_views,
                                 float* d_pose, int accumulate, hipStream_t stream);
 hipError_t launch_composite(const CompositeArgs& a, bool bwd, hipStream_t stream);
+hipError_t launch_distortion(const DistortionArgs& a, bool bwd, hipStream_t stream);
 hipError_t launch_sample_fine(const FineArgs& a, hipStream_t stream);
 hipError_t launch_field_fwd(const float* packed, const float* rays, int ray_stride, const float* z_vals,
                             int n_rays, int S, float* raw, float* act, hipStream_t stream);

@@ -2,6 +2,7 @@
 // render_fused.hip for the one-launch inference kernel that calls the same functions):
 //   coarse_depth        run_nerf.py:357-379   (z_vals: linspace / lindisp / stratified jitter)
 //   composite_ray       run_nerf.py:262-305   (raw2outputs) and its adjoint
+//   distortion_ray      the distortion loss of a ray's compositing weights and its adjoint (not in the reference)
 //   sample_fine_ray     run_nerf.py:392-396,412 + run_nerf_helpers.py:196-239 (sample_pdf, sort, z_std)
 // Sync: how the lanes of the ray's wavefront order their LDS traffic -- BlockSync when the wavefront is the whole workgroup
 // (__syncthreads), WaveSync when other wavefronts of the workgroup work on other rays (LDS operations of one wavefront
@@ -214,6 +215,85 @@ __device__ __forceinline__ void composite_ray(const CompositeArgs& a, int ray, i
             prev = s_e[i];
         }
     }
+}
+
+// ------------------------------------------------------------------ distortion loss on the compositing weights
+// mip-NeRF 360's regulariser, per ray, with s_i = (z_i - near) / (far - near) (0 when far - near is not > 0), sample i < S-1 owning
+// [s_i, s_i+1] (m_i the mid-point, dl_i the length) and the last sample a zero-length interval at s_S-1:
+//   L = sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 dl_i,      dL/dw_k = 2 sum_j w_j |m_k - m_j| + 2/3 w_k dl_k
+// The depths are non-decreasing, so are the m: sum_j w_j |m_k - m_j| = (m_k W_<k - WM_<k) + (WM_>k - m_k W_>k) with exclusive prefixes
+// and exclusive suffixes of w and w m -- O(S).  Both are built like composite_ray's scans: sequentially inside the lane's segment,
+// across lanes by wave_incl_scan_add / wave_incl_scan_add_rev (the suffix is summed directly, never total minus prefix).
+// BWD = false: loss[ray].  BWD = true: d_w[ray][k] (+)= d_loss[ray] dL/dw_k, recomputed from w and z.
+// LDS per ray: 2*S floats (fwd) / 4*S floats (bwd); each lane touches only its own segment: no synchronisation
+template <bool BWD>
+__device__ __forceinline__ void distortion_ray(const DistortionArgs& a, int ray, int lane, float* sm) {
+    const int S = a.S;
+    const int C = (S + 63) >> 6;
+    const int lo = min(lane * C, S), hi = min(lo + C, S);
+    const float* w = a.w + (size_t)ray * S;
+    const float* z = a.z + (size_t)ray * S;
+    const float near = a.near_far[(size_t)ray * a.nf_stride], far = a.near_far[(size_t)ray * a.nf_stride + 1];
+    const float span = far - near;
+    const bool ok = span > 0.0f;            // (a NaN span fails the comparison too: s = 0, loss 0)
+    float* s_w = sm;                // w_i
+    float* s_m = sm + S;            // m_i
+    float* s_d = sm + 2 * S;        // dl_i                            (bwd)
+    float* s_a = sm + 3 * S;        // m_i W_<i - WM_<i                (bwd)
+
+    // pass 1: interval mid-points and lengths, segment sums of w and w m
+    float segw = 0.0f, segwm = 0.0f, own = 0.0f;
+    float s_cur = (lo < hi && ok) ? (z[lo] - near) / span : 0.0f;
+    for (int i = lo; i < hi; ++i) {
+        float m = s_cur, dl = 0.0f;
+        if (i + 1 < S) {
+            const float s_next = ok ? (z[i + 1] - near) / span : 0.0f;
+            m = 0.5f * (s_cur + s_next);
+            dl = s_next - s_cur;
+            s_cur = s_next;
+        }
+        const float wi = w[i];
+        s_w[i] = wi;
+        s_m[i] = m;
+        if (BWD) s_d[i] = dl; else own += (wi * wi) * dl;
+        segw += wi;
+        segwm = fmaf(wi, m, segwm);
+    }
+    const float pw = wave_incl_scan_add(segw, lane), pwm = wave_incl_scan_add(segwm, lane);
+    float Wp = __shfl_up(pw, 1), WMp = __shfl_up(pwm, 1);             // sums over the lanes before this one
+    if (lane == 0) { Wp = 0.0f; WMp = 0.0f; }
+    const float sw = wave_incl_scan_add_rev(segw, lane), swm = wave_incl_scan_add_rev(segwm, lane);
+    float Ws = __shfl_down(sw, 1), WMs = __shfl_down(swm, 1);         // sums over the lanes behind this one
+    if (lane == 63) { Ws = 0.0f; WMs = 0.0f; }
+
+    // pass 2, ascending: the part of sum_j w_j |m_k - m_j| that lies before k
+    float part = 0.0f;
+    for (int i = lo; i < hi; ++i) {
+        const float wi = s_w[i], m = s_m[i];
+        const float before = fmaf(m, Wp, -WMp);         // (one rounding: the two products nearly cancel on a compact ray)
+        if (BWD) s_a[i] = before; else part += wi * before;
+        Wp += wi;
+        WMp = fmaf(wi, m, WMp);
+    }
+    // pass 3, descending: the part behind k
+    const float g = BWD ? a.d_loss[ray] : 0.0f;
+    float* dw = BWD ? a.d_w + (size_t)ray * S : nullptr;
+    for (int i = hi - 1; i >= lo; --i) {
+        const float wi = s_w[i], m = s_m[i];
+        const float behind = fmaf(-m, Ws, WMs);
+        if (BWD) {
+            const float d = g * (2.0f * (s_a[i] + behind) + (2.0f / 3.0f) * (wi * s_d[i]));
+            dw[i] = a.accumulate ? dw[i] + d : d;
+        } else {
+            part += wi * behind;
+        }
+        Ws += wi;
+        WMs = fmaf(wi, m, WMs);
+    }
+    if (BWD) return;
+    part = wave_sum(part);
+    own = wave_sum(own);
+    if (lane == 0) a.loss[ray] = part + own / 3.0f;
 }
 
 // ------------------------------------------------------------------ hierarchical sampling

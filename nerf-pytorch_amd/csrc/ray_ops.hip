@@ -5,6 +5,7 @@
 //   sample_coarse_kernel   run_nerf.py:357-379   (z_vals: linspace / lindisp / stratified jitter)
 //   composite_fwd_kernel   run_nerf.py:262-305   (raw2outputs)
 //   composite_bwd_kernel   autograd of run_nerf.py:275-303
+//   distortion_kernel      the distortion loss of the compositing weights and its adjoint (not in the reference)
 //   sample_fine_kernel     run_nerf.py:392-396,412 + run_nerf_helpers.py:196-239 (sample_pdf, sort, z_std)
 //   embed_kernel           run_nerf_helpers.py:15-45 (Embedder.embed, standalone form)
 //
@@ -32,6 +33,12 @@ template <bool BWD>
 __global__ __launch_bounds__(64) void composite_kernel(CompositeArgs a) {
     extern __shared__ float sm[];
     composite_ray<BWD>(a, blockIdx.x, threadIdx.x, sm);
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(64) void distortion_kernel(DistortionArgs a) {
+    extern __shared__ float sm[];
+    distortion_ray<BWD>(a, blockIdx.x, threadIdx.x, sm);
 }
 
 __global__ __launch_bounds__(64) void sample_fine_kernel(FineArgs a) {
@@ -433,6 +440,13 @@ hipError_t launch_composite(const CompositeArgs& a, bool bwd, hipStream_t stream
     if (a.n_rays <= 0) return hipSuccess;
     if (bwd) hipLaunchKernelGGL(composite_kernel<true>, dim3(a.n_rays), dim3(64), 4 * a.S * sizeof(float), stream, a);
     else hipLaunchKernelGGL(composite_kernel<false>, dim3(a.n_rays), dim3(64), 2 * a.S * sizeof(float), stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_distortion(const DistortionArgs& a, bool bwd, hipStream_t stream) {
+    if (a.n_rays <= 0) return hipSuccess;
+    if (bwd) hipLaunchKernelGGL(distortion_kernel<true>, dim3(a.n_rays), dim3(64), 4 * a.S * sizeof(float), stream, a);
+    else hipLaunchKernelGGL(distortion_kernel<false>, dim3(a.n_rays), dim3(64), 2 * a.S * sizeof(float), stream, a);
     return hipGetLastError();
 }
 

@@ -227,7 +227,10 @@ def render_rays_dense(cfg, rays, rnd, model_c, model_f):
         u = rnd.get("u")
         z, z_std, _ = hb.sample_fine(z, weights.detach().contiguous(), n_f, u, None if u is not None else _linspace01(n_f, dev))
         raw = (model_c if model_f is None else model_f).query(rays, z)
-        rgb, disp, acc, _, _ = _Composite.apply(raw[..., :4].contiguous(), z, rays_d, rnd.get("noise_f"), std, wb)
+        rgb, disp, acc, weights, _ = _Composite.apply(raw[..., :4].contiguous(), z, rays_d, rnd.get("noise_f"), std, wb)
         ret["z_std"] = z_std
     ret.update(rgb_map=rgb, disp_map=disp, acc_map=acc, raw=raw)
+    if cfg.get("distortion", False):        # of the last pass's weights (differentiable through _Composite); the key comes last
+        from .render import distortion_loss
+        ret["distortion"] = distortion_loss(weights, z, rays[:, 6], rays[:, 7])
     return ret

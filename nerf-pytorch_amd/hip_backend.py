@@ -49,6 +49,8 @@ def _declare(lib):
         "nerf_raw2outputs": (i, [p, p, p, i, i, i, p, f, i, p, p, p, p, p, p]),
         "nerf_raw2outputs_bwd": (i, [p, p, p, i, i, i, p, f, i, p, p, p, p, p, p, p]),
         "nerf_sample_fine": (i, [p, p, i, i, i, p, p, p, p, p, p]),
+        "nerf_distortion_fwd": (i, [p, p, p, i, i, i, p, p]),
+        "nerf_distortion_bwd": (i, [p, p, p, i, i, i, p, p, i, p]),
         "nerf_sample_pdf": (i, [p, p, i, i, i, p, p, p, p]),
         "nerf_delta_floats": (sz, [i, i]),
         "nerf_wgrad_partial_floats": (sz, [i, i]),
@@ -131,7 +133,8 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march", "nerf_occ_march_stop", "nerf_occ_march_step",
            "nerf_occ_view_carve",
            "nerf_iso_scratch_words", "nerf_iso_count", "nerf_iso_emit",
-           "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live"]
+           "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live",
+           "nerf_distortion_fwd", "nerf_distortion_bwd"]
 
 
 def lib():
@@ -937,6 +940,49 @@ def raw2outputs_bwd(raw, z_vals, rays_d, dir_stride, noise, raw_noise_std, white
                                       _ptr(d_weights, "d_weights", True), _ptr(d_depth, "d_depth", True),
                                       _ptr(d_raw), _stream()), "nerf_raw2outputs_bwd")
     return d_raw
+
+
+def _near_far_ptr(near_far, nf_stride, nf_offset, n):
+    """pointer to ray 0's near and the float stride between rays: near_far is a tensor whose element [nf_offset] is ray 0's near, with
+    ray r's near / far nf_stride floats further on (default: the row length of a 2-D tensor; 0 = one pair for all rays)"""
+    if nf_stride is None:
+        nf_stride = near_far.shape[-1] if (isinstance(near_far, torch.Tensor) and near_far.dim() == 2) else 0
+    nf_stride, nf_offset = int(nf_stride), int(nf_offset)
+    base = _ptr(near_far, "near_far")
+    if nf_stride < 0 or nf_offset < 0 or (n > 0 and nf_offset + (n - 1) * nf_stride + 2 > near_far.numel()):
+        raise NerfHipError(f"near_far holds {near_far.numel()} floats: too few for {n} rays at stride {nf_stride}, offset {nf_offset}")
+    return base + 4 * nf_offset, nf_stride
+
+
+def distortion(weights, z_vals, near_far, nf_stride=None, nf_offset=0):
+    """loss [n] of nerf_distortion_fwd: the distortion loss of the compositing weights [n, S] on the depths z_vals [n, S] (non-decreasing
+    per ray: the caller's contract).  near_far: see _near_far_ptr (ray records: nf_stride=11, nf_offset=6)."""
+    n, S = z_vals.shape
+    if tuple(weights.shape) != (n, S):
+        raise NerfHipError(f"weights {tuple(weights.shape)} and z_vals {tuple(z_vals.shape)} differ in shape")
+    nfp, stride = _near_far_ptr(near_far, nf_stride, nf_offset, n)
+    loss = torch.empty((n,), dtype=torch.float32, device=z_vals.device)
+    _check(lib().nerf_distortion_fwd(_ptr(weights, "weights"), _ptr(z_vals, "z_vals"), nfp, stride, n, S, _ptr(loss), _stream()),
+           "nerf_distortion_fwd")
+    return loss
+
+
+def distortion_bwd(weights, z_vals, near_far, d_loss, out=None, accumulate=False, nf_stride=None, nf_offset=0):
+    """d_weights [n, S] = d_loss [n] * d loss / d weights (nerf_distortion_bwd), recomputed from the inputs; written into `out` (a new
+    tensor without one), or added to what `out` holds with accumulate=True"""
+    n, S = z_vals.shape
+    if tuple(weights.shape) != (n, S) or tuple(d_loss.shape) != (n,):
+        raise NerfHipError(f"weights {tuple(weights.shape)}, z_vals {tuple(z_vals.shape)} and d_loss {tuple(d_loss.shape)} do not belong together")
+    if out is None:
+        if accumulate:
+            raise NerfHipError("accumulate=True needs the tensor to add to (out=)")
+        out = torch.empty((n, S), dtype=torch.float32, device=z_vals.device)
+    elif tuple(out.shape) != (n, S):
+        raise NerfHipError(f"out {tuple(out.shape)} is not [{n}, {S}]")
+    nfp, stride = _near_far_ptr(near_far, nf_stride, nf_offset, n)
+    _check(lib().nerf_distortion_bwd(_ptr(weights, "weights"), _ptr(z_vals, "z_vals"), nfp, stride, n, S, _ptr(d_loss, "d_loss"),
+                                     _ptr(out, "out"), int(bool(accumulate)), _stream()), "nerf_distortion_bwd")
+    return out
 
 
 def sample_fine(z_vals, weights, n_fine, u, u_lin, want_samples=False):

@@ -177,17 +177,22 @@ def _field_pass(cfg, rays, rnd, model_c, model_f, save):
         nxt = (guard(mf), raw_f)
     r["raw_c"], r["act_c"] = hb.field_fwd(r["packed_c"], rays, r["z_c"], save_act=save, precision=prec_c,
                                           guard_packed=guard(model_c) if prec_c == "fp16_fp8c" else None, next_guard=nxt)
+    dist = cfg.get("distortion", False)     # the last pass also hands out its weights (one more store, every other output keeps its bits)
     r["rgb_c"], r["disp_c"], r["acc_c"], w_c, _ = hb.raw2outputs(r["raw_c"], r["z_c"], rays, rays.shape[1], rnd.get("noise_c"), std, wb,
-                                                              want_weights=n_f > 0, want_depth=False, rays_d_offset=3)
+                                                              want_weights=n_f > 0 or dist, want_depth=False, rays_d_offset=3)
     if n_f <= 0:
+        if dist:
+            r["w"], r["distortion"] = w_c, hb.distortion(w_c, r["z_c"], rays, nf_stride=rays.shape[1], nf_offset=6)
         return r
     u = rnd.get("u")
     r["z_f"], r["z_std"], _ = hb.sample_fine(r["z_c"], w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
     r["packed_f"] = packed_f if packed_f is not None else mf.packed_params(prec)
     r["raw_f"], r["act_f"] = hb.field_fwd(r["packed_f"], rays, r["z_f"], save_act=save, precision=prec,
                                           guard_packed="done" if raw_f is not None else guard(mf), raw=raw_f)
-    r["rgb_f"], r["disp_f"], r["acc_f"], _, _ = hb.raw2outputs(r["raw_f"], r["z_f"], rays, rays.shape[1], rnd.get("noise_f"), std, wb,
-                                                             want_weights=False, want_depth=False, rays_d_offset=3)
+    r["rgb_f"], r["disp_f"], r["acc_f"], w_f, _ = hb.raw2outputs(r["raw_f"], r["z_f"], rays, rays.shape[1], rnd.get("noise_f"), std, wb,
+                                                               want_weights=dist, want_depth=False, rays_d_offset=3)
+    if dist:
+        r["w"], r["distortion"] = w_f, hb.distortion(w_f, r["z_f"], rays, nf_stride=rays.shape[1], nf_offset=6)
     return r
 
 
@@ -214,7 +219,11 @@ class _RenderRays(torch.autograd.Function):
     ~90 GB on fp32) every sub-chunk keeps its own lease and the backward walks them: no
     recomputation, deltas and partial sums re-use one sub-chunk-sized scratch.  Beyond that the forward runs WITHOUT
     saving and the backward re-runs it, with saving, one sub-chunk at a time (the kernels are deterministic, so the
-    recomputed pass is bit-identical to the first): bounded memory for +1 inference-speed forward."""
+    recomputed pass is bit-identical to the first): bounded memory for +1 inference-speed forward.
+
+    cfg["distortion"]: one trailing differentiable output, the distortion loss [N] of the last pass's weights (_field_pass), which stay
+    among the saved tensors; its upstream gradient enters the last pass's compositing backward as d_weights (nerf_distortion_bwd), in
+    all three plans."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, *params):
@@ -242,7 +251,8 @@ class _RenderRays(torch.autograd.Function):
         LAST_BACKWARD_PLAN = ("recompute" if ctx.checkpoint else "resident sub-chunks" if ctx.tiles is not None else "one launch", n, sub)
         ctx.sub_rays = sub
         prec = cfg.get("precision", "fp32")
-        if not need and hb.INFER_ONE_LAUNCH and hb.render_infer_supported(cfg["N_samples"], n_f, prec):
+        dist = cfg.get("distortion", False)
+        if not need and not dist and hb.INFER_ONE_LAUNCH and hb.render_infer_supported(cfg["N_samples"], n_f, prec):
             # no gradients: coarse depths -> network -> compositing -> hierarchical depths -> network -> compositing in ONE launch
             mf = None if (model_f is None or model_f is model_c or n_f <= 0) else model_f
             r = hb.render_rays_infer(model_c.packed_params(prec), None if mf is None else mf.packed_params(prec), rays, cfg["N_samples"],
@@ -269,7 +279,7 @@ class _RenderRays(torch.autograd.Function):
                 r = _field_pass(cfg, rays, rnd, model_c, model_f, save=False)
             else:
                 out_keys = ("rgb_c", "disp_c", "acc_c", "raw_c") if n_f <= 0 else ("rgb_f", "disp_f", "acc_f", "raw_f", "rgb_c", "disp_c", "acc_c", "z_std")
-                r = {k_: torch.cat([p_[k_] for p_ in parts], 0) for k_ in out_keys}
+                r = {k_: torch.cat([p_[k_] for p_ in parts], 0) for k_ in out_keys + (("distortion",) if dist else ())}
         if need and not ctx.checkpoint and prec in ("fp16x3", "fp16x3w"):
             # the fp16 split's range guard rail: every RANGE_MONITOR.every-th training render scans what the forward saved
             # (hb.RangeMonitor; replaces run_nerf.py:414-416's DEBUG-gated NaN / Inf check)
@@ -293,10 +303,11 @@ class _RenderRays(torch.autograd.Function):
         # `raw` of the last pass, goes through save_for_backward, which autograd knows how to hold without a cycle.
         ctx.saved = None
         if ctx.tiles is not None:
-            keep = ("packed_c", "z_c", "act_c", "raw_c", "packed_f", "z_f", "act_f", "raw_f")
+            keep = ("packed_c", "z_c", "act_c", "raw_c", "packed_f", "z_f", "act_f", "raw_f", "w")
             ctx.saved = [{k_: p_[k_] for k_ in keep if k_ in p_} for p_ in parts]     # per-sub-chunk tensors, none is an output
         elif need and not ctx.checkpoint:
-            keep = ("packed_c", "z_c", "act_c", "packed_f", "z_f", "act_f") + (("raw_c",) if n_f > 0 else ())
+            # ("w": the last pass's weights under cfg["distortion"], N S 4 bytes, not an output)
+            keep = ("packed_c", "z_c", "act_c", "packed_f", "z_f", "act_f", "w") + (("raw_c",) if n_f > 0 else ())
             ctx.saved = {k: r[k] for k in keep if k in r}
             ctx.save_for_backward(r["raw_f"] if n_f > 0 else r["raw_c"])
         elif not need:
@@ -305,10 +316,11 @@ class _RenderRays(torch.autograd.Function):
         # fragments packed at forward time: remember which parameter state this forward saw
         ctx.param_state = tuple(_param_state(m) for m in (model_c, model_f) if m is not None)
         ctx.consumed = False
+        tail = (r["distortion"],) if dist else ()      # one trailing differentiable output
         if n_f <= 0:
-            return r["rgb_c"], r["disp_c"], r["acc_c"], r["raw_c"]
+            return (r["rgb_c"], r["disp_c"], r["acc_c"], r["raw_c"]) + tail
         ctx.mark_non_differentiable(r["z_std"])     # the reference detaches z_samples (run_nerf.py:394)
-        return r["rgb_f"], r["disp_f"], r["acc_f"], r["raw_f"], r["rgb_c"], r["disp_c"], r["acc_c"], r["z_std"]
+        return (r["rgb_f"], r["disp_f"], r["acc_f"], r["raw_f"], r["rgb_c"], r["disp_c"], r["acc_c"], r["z_std"]) + tail
 
     @staticmethod
     def backward(ctx, *gouts):
@@ -329,9 +341,10 @@ class _RenderRays(torch.autograd.Function):
         n_all = rays_all.shape[0]
         n_f = cfg["N_importance"]
         fine = n_f > 0
-        # upstream gradients of (rgb, disp, acc, raw) of the fine (or only) pass and of the coarse pass
-        up_f = (gouts[0], gouts[1], gouts[2], gouts[3])
-        up_c = (gouts[4], gouts[5], gouts[6], None) if fine else None
+        # upstream gradients of (rgb, disp, acc, raw, distortion) of the fine (or only) pass and of the coarse pass; the distortion loss
+        # is the trailing output and belongs to the last pass
+        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-1] if cfg.get("distortion", False) else None)
+        up_c = (gouts[4], gouts[5], gouts[6], None, None) if fine else None
         if not fine:
             up_c, up_f = up_f, None
         has = lambda up: up is not None and any(g is not None for g in up)
@@ -348,10 +361,10 @@ class _RenderRays(torch.autograd.Function):
         # dL/d(ray records), summed over both passes (near / far: zero -- render() builds them from Python floats)
         d_rays_all = torch.zeros((n_all, 11), dtype=torch.float32, device=dev) if ctx.rays_grad else None
 
-        def field_grad(rays, model, packed, act, raw, z, noise, up, lo, hi, grad, key):
-            d_rgb, d_disp, d_acc, d_raw_up = (None if g is None else g[lo:hi] for g in up)
+        def field_grad(rays, model, packed, act, raw, z, noise, up, lo, hi, grad, key, w=None):
+            d_rgb, d_disp, d_acc, d_raw_up, d_dist = (None if g is None else g[lo:hi] for g in up)
             m = hi - lo
-            if d_rgb is None and (d_disp is not None or d_acc is not None):
+            if d_rgb is None and (d_disp is not None or d_acc is not None or d_dist is not None):
                 d_rgb = torch.zeros((m, 3), dtype=torch.float32, device=dev)
             c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
             d_rays = None if d_rays_all is None else d_rays_all[lo:hi]
@@ -361,8 +374,10 @@ class _RenderRays(torch.autograd.Function):
             else:
                 if d_rays is not None:
                     d_dn = torch.empty((m, 3), dtype=torch.float32, device=dev)
+                # the distortion loss reaches raw (and |d|) through the weights' adjoint: d_weights of the compositing backward
+                extra = {} if d_dist is None else {"d_weights": hb.distortion_bwd(w, z, rays, c(d_dist), nf_stride=rays.shape[1], nf_offset=6)}
                 d_raw = hb.raw2outputs_bwd(raw, z, rays, rays.shape[1], noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
-                                           rays_d_offset=3, d_rays_d=d_dn)
+                                           rays_d_offset=3, d_rays_d=d_dn, **extra)
                 if d_raw_up is not None:
                     d_raw += d_raw_up
             if grad is None and d_rays is None:
@@ -378,18 +393,21 @@ class _RenderRays(torch.autograd.Function):
 
         def backprop(r, rays, rnd, lo, hi, last=True):
             if has(up_c):
-                field_grad(rays, ctx.model_c, r["packed_c"], r["act_c"], r["raw_c"], r["z_c"], rnd.get("noise_c"), up_c, lo, hi, grad_c, "c")
+                field_grad(rays, ctx.model_c, r["packed_c"], r["act_c"], r["raw_c"], r["z_c"], rnd.get("noise_c"), up_c, lo, hi, grad_c, "c",
+                           None if fine else r.get("w"))
                 if last and not shared and grad_c is not None:     # final: its all-reduce may start under the fine network's backward
                     _grad_ready(ctx.model_c, grad_c)
             hb.WORKSPACE.give(r["act_c"])
             r["act_c"] = None
             if fine and has(up_f):
                 if ctx.same_net:
-                    field_grad(rays, ctx.model_c, r["packed_f"], r["act_f"], r["raw_f"], r["z_f"], rnd.get("noise_f"), up_f, lo, hi, grad_c, "c")
+                    field_grad(rays, ctx.model_c, r["packed_f"], r["act_f"], r["raw_f"], r["z_f"], rnd.get("noise_f"), up_f, lo, hi, grad_c, "c",
+                               r.get("w"))
                     if last and grad_c is not None:
                         _grad_ready(ctx.model_c, grad_c)
                 else:
-                    field_grad(rays, ctx.model_f, r["packed_f"], r["act_f"], r["raw_f"], r["z_f"], rnd.get("noise_f"), up_f, lo, hi, grad_f, "f")
+                    field_grad(rays, ctx.model_f, r["packed_f"], r["act_f"], r["raw_f"], r["z_f"], rnd.get("noise_f"), up_f, lo, hi, grad_f, "f",
+                               r.get("w"))
                     if last and grad_f is not None:
                         _grad_ready(ctx.model_f, grad_f)
             _release(r)
@@ -448,6 +466,73 @@ class _Composite(torch.autograd.Function):
         d_raw = hb.raw2outputs_bwd(raw, z_vals, rays_d, 3, noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
                                    d_weights=c(d_w), d_depth=c(d_depth), d_rays_d=d_dn, d_z_vals=d_z)
         return d_raw, d_z, d_dn, None, None, None
+
+
+class _Distortion(torch.autograd.Function):
+    """distortion_loss over nerf_distortion_fwd / _bwd: gradient to the weights only, recomputed from the inputs"""
+
+    @staticmethod
+    def forward(ctx, weights, z_vals, near_far, nf_stride):
+        weights = weights.detach()
+        ctx.args = (weights, z_vals, near_far, nf_stride)
+        ctx.set_materialize_grads(False)
+        return hb.distortion(weights, z_vals, near_far, nf_stride=nf_stride)
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        if d_loss is None:      # nothing upstream: no launch
+            return None, None, None, None
+        weights, z_vals, near_far, nf_stride = ctx.args
+        return hb.distortion_bwd(weights, z_vals, near_far, d_loss.to(torch.float32).contiguous(), nf_stride=nf_stride), None, None, None
+
+
+def _near_far_pair(near, far, lead, dtype, device):
+    """near / far ([...] tensors or Python numbers) as two detached tensors of shape `lead`"""
+    as_t = lambda v: (v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(float(v))).to(dtype=dtype, device=device)
+    return as_t(near).expand(lead), as_t(far).expand(lead)
+
+
+def distortion_loss(weights, z_vals, near, far):
+    """The distortion loss of mip-NeRF 360 on compositing weights, per ray: [..., S] weights and depths -> [...] (two HIP launches, forward
+    and adjoint; distortion_loss_reference is the definition).  With s = (z - near) / (far - near) -- 0 where far - near is not > 0: such a
+    ray has loss 0 and gradient 0 --, sample i < S-1 owning [s_i, s_i+1] (mid-point m_i, length dl_i) and the last sample a zero-length
+    interval at s_S-1 (its compositing distance of 1e10 is a sentinel, not a length):
+
+        L = sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 dl_i
+
+    ``near`` / ``far``: [...] tensors (one value per ray) or Python numbers.  Gradient to ``weights`` only: depths, near and far are
+    constants of the graph, like the reference's z_samples.  THE CALLER'S CONTRACT: z_vals is non-decreasing along the last axis (what
+    every path of render_rays produces); it is not checked, a check would be a host synchronisation.  1 <= S <= 4096.  Composes with
+    raw2outputs, whose weights (output 3) are differentiable: distortion_loss(raw2outputs(raw, z, d)[3], z, near, far)."""
+    lead, S = tuple(weights.shape[:-1]), weights.shape[-1]
+    if tuple(z_vals.shape) != tuple(weights.shape):
+        raise ValueError(f"distortion_loss: weights {tuple(weights.shape)} and z_vals {tuple(z_vals.shape)} differ in shape")
+    w = weights.to(torch.float32).reshape(-1, S).contiguous()
+    z = z_vals.detach().to(torch.float32).reshape(-1, S).contiguous()
+    if isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor):
+        near, far = _near_far_pair(near, far, lead, torch.float32, w.device)
+        near_far, stride = torch.stack([near.reshape(-1), far.reshape(-1)], -1).contiguous(), 2
+    else:       # one pair for all rays
+        near_far, stride = torch.tensor([float(near), float(far)], dtype=torch.float32, device=w.device), 0
+    return _Distortion.apply(w, z, near_far, stride).reshape(lead)
+
+
+def distortion_loss_reference(weights, z_vals, near, far):
+    """THE DEFINITION distortion_loss and the render paths' "distortion" key are held to: the formulas of distortion_loss as the pairwise
+    sum in plain torch, on any device, in the dtype of ``weights`` (the tests call it in float64); an [..., S, S] tensor per call.
+    Differentiable w.r.t. ``weights`` by torch's autograd: dL/dw_k = 2 sum_j w_j |m_k - m_j| + 2/3 w_k dl_k.  z_vals, near and far are
+    constants."""
+    w = weights
+    lead = tuple(w.shape[:-1])
+    z = z_vals.detach().to(dtype=w.dtype, device=w.device)
+    near, far = _near_far_pair(near, far, lead, w.dtype, w.device)
+    span = (far - near)[..., None]
+    ok = span > 0
+    s = torch.where(ok, (z - near[..., None]) / torch.where(ok, span, torch.ones_like(span)), torch.zeros_like(z))
+    m = torch.cat([0.5 * (s[..., :-1] + s[..., 1:]), s[..., -1:]], -1)
+    dl = torch.cat([s[..., 1:] - s[..., :-1], torch.zeros_like(s[..., -1:])], -1)
+    pair = (w[..., :, None] * w[..., None, :] * (m[..., :, None] - m[..., None, :]).abs()).sum((-1, -2))
+    return pair + (w * w * dl).sum(-1) / 3
 
 
 # --------------------------------------------------------------------------- reference call surface
@@ -557,7 +642,8 @@ def _is_builtin_query(network_query_fn):
     return network_query_fn is None or getattr(network_query_fn, "_nerf_amd_builtin", False)
 
 
-def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f, network_fine, lindisp, white_bkgd, std, retraw):
+def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f, network_fine, lindisp, white_bkgd, std, retraw,
+                        distortion=False):
     """render_rays with a USER-SUPPLIED network_query_fn (run_nerf.py:385, :401 call it for every pass): the hook sees the reference's
     arguments -- pts [N, S, 3], viewdirs [N, 3], the network module -- and whatever it returns is composited, exactly as in the
     reference (a density regulariser, a clamp, a different network call all work).  Stage by stage through the C ABI: coarse depths
@@ -571,18 +657,20 @@ def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f,
         raw = network_query_fn(pts, viewdirs, net)
         return raw, _Composite.apply(raw.to(torch.float32).contiguous(), z_vals, rays_d, noise, std, bool(white_bkgd))
 
-    z_c = hb.sample_coarse(rays, _linspace01(N_samples, dev), lindisp, rnd.get("t_rand"))
+    z = z_c = hb.sample_coarse(rays, _linspace01(N_samples, dev), lindisp, rnd.get("t_rand"))
     raw, (rgb, disp, acc, weights, _) = one_pass(z_c, network_fn, rnd.get("noise_c"))
     ret = {}
     if n_f > 0:
         ret.update(rgb0=rgb, disp0=disp, acc0=acc)
         u = rnd.get("u")
-        z_f, z_std, _ = hb.sample_fine(z_c, weights.detach().contiguous(), n_f, u, None if u is not None else _linspace01(n_f, dev))
-        raw, (rgb, disp, acc, _, _) = one_pass(z_f, network_fn if network_fine is None else network_fine, rnd.get("noise_f"))
+        z, z_std, _ = hb.sample_fine(z_c, weights.detach().contiguous(), n_f, u, None if u is not None else _linspace01(n_f, dev))
+        raw, (rgb, disp, acc, weights, _) = one_pass(z, network_fn if network_fine is None else network_fine, rnd.get("noise_f"))
         ret["z_std"] = z_std
     ret.update(rgb_map=rgb, disp_map=disp, acc_map=acc)
     if retraw:
         ret["raw"] = raw
+    if distortion:      # of the last pass's weights (differentiable through _Composite)
+        ret["distortion"] = distortion_loss(weights, z, rays[:, 6], rays[:, 7])
     return ret
 
 
@@ -594,7 +682,7 @@ def _grid_pass_lease(m, P, prec):
     return hb.act_floats(q * max(1, -(-m // q)), 1, prec)
 
 
-def _grid_pass(cfg, desc, rays, z_vals, model, noise, want_weights, z_stop=None, *, stats, passes=None, budget=None):
+def _grid_pass(cfg, desc, rays, z_vals, model, noise, want_weights, z_stop=None, *, stats, passes=None, budget=None, keep_weights=False):
     """THE compacted pass of both grid paths: depths -> nerf_occ_compact[_stop] (classify o + d z, drop what lies at or behind z_stop,
     compact the rest into n_samples = 1 ray records) -> ONE read-back of the count M -> the field on the M records, as query_points
     evaluates points (no launch when M == 0) -> nerf_occ_expand (raw, zeros for skipped samples) -> nerf_raw2outputs.  Returns
@@ -606,7 +694,8 @@ def _grid_pass(cfg, desc, rays, z_vals, model, noise, want_weights, z_stop=None,
     gradient), m, packed, raw -- is appended to `passes` BEFORE anything can fail, so that the node hands its leases back with the
     others' on an error.  budget = {"rays_grad": bool, "resident": bytes the call keeps so far, "rays": rays of the whole call} goes with
     it: beyond hb.SAVE_TOTAL_BYTES in total the pass raises.
-    The compacted raw and the M zero depths live inside the pass and are plain torch allocations on both paths."""
+    The compacted raw and the M zero depths live inside the pass and are plain torch allocations on both paths.
+    keep_weights (cfg["distortion"], the last pass): the record also keeps the pass's compositing weights as "w" for the backward."""
     n, S = z_vals.shape
     P = n * S
     dev, prec = rays.device, cfg["precision"]
@@ -642,8 +731,11 @@ def _grid_pass(cfg, desc, rays, z_vals, model, noise, want_weights, z_stop=None,
     p["raw"] = raw
     stats["evaluated"] += m
     stats["total"] += P
-    return raw, hb.raw2outputs(raw, z_vals, rays, rays.shape[1], noise, cfg["raw_noise_std"], cfg["white_bkgd"], want_weights=want_weights,
-                               want_depth=False, rays_d_offset=3)
+    outs = hb.raw2outputs(raw, z_vals, rays, rays.shape[1], noise, cfg["raw_noise_std"], cfg["white_bkgd"], want_weights=want_weights,
+                          want_depth=False, rays_d_offset=3)
+    if keep_weights:
+        p["w"] = outs[3]
+    return raw, outs
 
 
 def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
@@ -659,12 +751,17 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
         model_c, which is the whole chunk when N_importance = 0;
       cfg["early_stop_eps"]: the coarse weights give one stop depth per ray (nerf_occ_stop_depth), with which the refining pass compacts;
       nerf_sample_fine, and the refining pass on model_f (model_c without one).
-    One host synchronisation per pass and none of its own.  Returns the output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std])
+    One host synchronisation per pass and none of its own.  Returns the output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std][, distortion])
     and the device counters (stopped rays, truncated rays, refit rays; None without the option), which the caller reads back after its
     passes.  cfg["march_step_size"] (with cfg["march_fit"]): the march's depths are nerf_occ_march_step's -- steps of one length in the
     scene, march_steps the cap on candidates, the step doubled per ray until it fits the slots -- and nothing else of the chunk changes."""
     n_c, n_f = cfg["N_samples"], cfg["N_importance"]
     dev = rays.device
+    # cfg["distortion"]: the LAST pass hands out and keeps its weights, and the chain's tuple ends with their distortion loss on the depths
+    # the pass was given and the near / far of `rays` (the clipped ones under clip_to_occupancy)
+    dist = cfg.get("distortion", False)
+    last_kw = {"keep_weights": True} if dist else {}
+    loss_of = lambda w, z: (hb.distortion(w, z, rays, nf_stride=rays.shape[1], nf_offset=6),) if dist else ()
     if cfg["march_steps"] is not None:
         n_stopped = n_refit = None
         if cfg["march_step_size"] is not None:      # world-space steps, march_steps is the cap: one kernel for both forms
@@ -683,16 +780,17 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
         else:
             z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), cfg["march_steps"], n_c)
         n_truncated = truncated.sum()
-        raw, (rgb, disp, acc, _, _) = run_pass(rays, z_m, model_c, rnd.get("noise_c"), False, z_stop)
-        return (rgb, disp, acc, raw), n_stopped, n_truncated, n_refit
+        raw, (rgb, disp, acc, w_m, _) = run_pass(rays, z_m, model_c, rnd.get("noise_c"), dist, z_stop, **last_kw)
+        return (rgb, disp, acc, raw) + loss_of(w_m, z_m), n_stopped, n_truncated, n_refit
     z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
     coarse = ()
     if cfg["proposal"] is not None:
         w_c = grid.proposal_weights(rays, z_c)
     else:
-        raw_c, (rgb_c, disp_c, acc_c, w_c, _) = run_pass(rays, z_c, model_c, rnd.get("noise_c"), n_f > 0, None)
+        raw_c, (rgb_c, disp_c, acc_c, w_c, _) = run_pass(rays, z_c, model_c, rnd.get("noise_c"), n_f > 0 or dist, None,
+                                                         **({} if n_f > 0 else last_kw))
         if n_f <= 0:
-            return (rgb_c, disp_c, acc_c, raw_c), None, None, None
+            return (rgb_c, disp_c, acc_c, raw_c) + loss_of(w_c, z_c), None, None, None
         coarse = (rgb_c, disp_c, acc_c)
     z_stop = n_stopped = None
     if cfg["early_stop_eps"] is not None:
@@ -700,8 +798,9 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
         n_stopped = torch.isfinite(z_stop).sum()
     u = rnd.get("u")
     z_f, z_std, _ = hb.sample_fine(z_c, w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
-    raw_f, (rgb_f, disp_f, acc_f, _, _) = run_pass(rays, z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), False, z_stop)
-    return (rgb_f, disp_f, acc_f, raw_f) + coarse + (z_std,), n_stopped, None, None
+    raw_f, (rgb_f, disp_f, acc_f, w_f, _) = run_pass(rays, z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), dist, z_stop,
+                                                     **last_kw)
+    return (rgb_f, disp_f, acc_f, raw_f) + coarse + (z_std,) + loss_of(w_f, z_f), n_stopped, None, None
 
 
 def _grid_stats(grid, stats, n_stopped, n_truncated, n_refit=None):
@@ -750,7 +849,8 @@ class _RenderRaysGrid(torch.autograd.Function):
     -- so nothing beyond slot is kept for it and the backward is unchanged.  cfg["march_steps"]: depths and stop depth are constants of
     the graph, computed per sub-chunk; with N_importance = 0 the backward is the coarse-only one; outputs (rgb, disp, acc, raw) --
     cfg["march_stop_eps"], cfg["march_step_size"] and cfg["march_fit"] change which kernel computes those constants and nothing of the
-    backward."""
+    backward.  cfg["distortion"]: the tuple ends with the distortion loss [N] of the last pass's weights, which that pass's record keeps
+    as "w"; its upstream gradient enters the pass's compositing backward as d_weights, in front of nerf_occ_gather."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
@@ -811,8 +911,8 @@ class _RenderRaysGrid(torch.autograd.Function):
         ctx.param_state = tuple(_param_state(m_) for m_ in (model_c, model_f) if m_ is not None)
         ctx.consumed = False
         ctx.set_materialize_grads(False)
-        if n_f > 0:
-            ctx.mark_non_differentiable(out[-1])    # z_std: the reference detaches z_samples (run_nerf.py:394)
+        if n_f > 0:     # z_std (in front of the distortion loss if there is one): the reference detaches z_samples (run_nerf.py:394)
+            ctx.mark_non_differentiable(out[-2 if cfg.get("distortion", False) else -1])
         return tuple(out)
 
     @staticmethod
@@ -830,11 +930,12 @@ class _RenderRaysGrid(torch.autograd.Function):
         dev = rays_all.device
         n_all = rays_all.shape[0]
         fine = cfg["N_importance"] > 0
-        up_f = (gouts[0], gouts[1], gouts[2], gouts[3])
+        # (the distortion loss is the trailing output and belongs to the last pass)
+        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-1] if cfg.get("distortion", False) else None)
         if ctx.proposal:        # one pass, the refining one: there is no coarse image
             up_c = None
         else:
-            up_c = (gouts[4], gouts[5], gouts[6], None) if fine else None
+            up_c = (gouts[4], gouts[5], gouts[6], None, None) if fine else None
         if not fine:
             up_c, up_f = up_f, None
         has = lambda up: up is not None and any(g is not None for g in up)
@@ -857,9 +958,9 @@ class _RenderRaysGrid(torch.autograd.Function):
         d_rays_all = torch.zeros((n_all, 11), dtype=torch.float32, device=dev) if ctx.rays_grad else None
 
         def field_grad(rays, model, p, raw, noise, up, lo, hi, grad, key):
-            d_rgb, d_disp, d_acc, d_raw_up = (None if g is None else g[lo:hi] for g in up)
+            d_rgb, d_disp, d_acc, d_raw_up, d_dist = (None if g is None else g[lo:hi] for g in up)
             nt, z, m = hi - lo, p["z"], p["m"]
-            if d_rgb is None and (d_disp is not None or d_acc is not None):
+            if d_rgb is None and (d_disp is not None or d_acc is not None or d_dist is not None):
                 d_rgb = torch.zeros((nt, 3), dtype=torch.float32, device=dev)
             c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
             d_rays = None if d_rays_all is None else d_rays_all[lo:hi]
@@ -869,11 +970,13 @@ class _RenderRaysGrid(torch.autograd.Function):
             else:
                 if d_rays is not None:
                     d_dn = torch.empty((nt, 3), dtype=torch.float32, device=dev)
+                # the distortion loss enters as d_weights of the compositing backward, in front of nerf_occ_gather
+                extra = {} if d_dist is None else {"d_weights": hb.distortion_bwd(p["w"], z, rays, c(d_dist), nf_stride=rays.shape[1], nf_offset=6)}
                 d_raw = hb.raw2outputs_bwd(raw, z, rays, rays.shape[1], noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
-                                           rays_d_offset=3, d_rays_d=d_dn)
+                                           rays_d_offset=3, d_rays_d=d_dn, **extra)
                 if d_raw_up is not None:
                     d_raw += d_raw_up
-            if m == 0:          # no point of this pass was evaluated: no field launch, zero gradient from it
+            if m == 0:         # no point of this pass was evaluated: no field launch, zero gradient from it
                 if grad is not None and not wrote[key]:
                     grad.zero_()
                     wrote[key] = True
@@ -1038,15 +1141,18 @@ def _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, random
     return rnd, std
 
 
-def _result_dict(outs, retraw, coarse_first):
-    """the returned dict of an output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std]).  coarse_first: the key order of
-    _render_rays_hooked, which the grid paths share (the coarse image and z_std in front); else the fused dense path's, which the empty
-    batch has always had"""
+def _result_dict(outs, retraw, coarse_first, distortion=False):
+    """the returned dict of an output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std][, distortion]).  coarse_first: the key
+    order of _render_rays_hooked, which the grid paths share (the coarse image and z_std in front); else the fused dense path's, which
+    the empty batch has always had.  distortion: the tuple ends with the distortion loss, whose key comes last"""
+    last = {}
+    if distortion:
+        outs, last = outs[:-1], {"distortion": outs[-1]}
     fine = dict(rgb_map=outs[0], disp_map=outs[1], acc_map=outs[2], **({"raw": outs[3]} if retraw else {}))
     coarse = dict(zip(("rgb0", "disp0", "acc0"), outs[4:7])) if len(outs) == 8 else {}
     if len(outs) > 4:
         coarse["z_std"] = outs[-1]
-    return {**coarse, **fine} if coarse_first else {**fine, **coarse}
+    return {**coarse, **fine, **last} if coarse_first else {**fine, **coarse, **last}
 
 
 def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal, march_stop_eps=None, march_fit=0):
@@ -1061,7 +1167,7 @@ def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal, march_stop_e
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
                 *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None, march_steps=None,
-                march_stop_eps=None, march_step_size=None, march_fit=0):
+                march_stop_eps=None, march_step_size=None, march_fit=0, distortion=False):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -1158,7 +1264,26 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     of the graph), the draws (u_march, then noise_f), the output keys, clip_to_occupancy before the march.  last_stats additionally
     carries "rays_refit" (rays whose step was doubled at least once) when march_fit > 0.  Refused: either option without
     proposal="march", a step that is not a finite real number > 0 or a fit that is not an int in 0..8 (bools included), march_fit > 0
-    without march_step_size; lindisp stays NotImplementedError.  None / 0: nothing changes -- same launches, same bits, same draws."""
+    without march_step_size; lindisp stays NotImplementedError.  None / 0: nothing changes -- same launches, same bits, same draws.
+
+    ``distortion`` (keyword-only, not in the reference; a bool): True adds one key, "distortion" [N] fp32, last in the dict: the
+    distortion loss (distortion_loss; distortion_loss_reference is the definition) of the compositing weights of the pass whose image
+    is rgb_map -- the refining pass, or the only one with N_importance = 0, under a proposal or under the march -- computed from
+    exactly the weights the compositing used (noise included), that pass's depths and the near / far of the ray records the pass
+    saw.  Under clip_to_occupancy those are the clipped ones: the identity render_rays(occupancy.clip_rays(rays)[0], ...) holds for
+    this key too, and THE LOSS'S SCALE THEN FOLLOWS THE CLIPPED SPAN (depths are normalised by far' - near' per ray).  A skipped,
+    stopped or padded sample of the grid paths has raw = 0, weight 0, and contributes nothing.  There is no loss on the coarse or the
+    proposal weights and no gradient to depths, near or far; gradients reach parameters and ray records through the weights, by the
+    compositing's and the field's existing adjoints (nerf_distortion_bwd -> d_weights of nerf_raw2outputs_bwd), on every path and in
+    all backward plans.  render() delivers it as extras["distortion"] with the rays' leading shape:
+    loss = img_loss + lam * extras["distortion"].mean().  Cost: the last pass's compositing also stores its weights (the same kernel,
+    every other output keeps its bits), one launch for the loss, and one for its adjoint when the key carries a gradient; the fused
+    node keeps the weights (N * S * 4 bytes) for its backward.  A call WITHOUT a needed gradient takes the staged passes with the
+    option, not the one-launch inference kernel, which has no weights to give.  False: nothing changes -- same launches, same bits,
+    same draws."""
+    if not isinstance(distortion, (bool, np.bool_)):
+        raise ValueError(f"render_rays: distortion must be a bool, got {distortion!r}")
+    distortion = bool(distortion)
     march, early_stop_eps, march_steps, march_stop_eps, march_step_size, march_fit = _check_grid_options(
         N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal, early_stop_eps, march_steps, march_stop_eps, march_step_size,
         march_fit)
@@ -1186,14 +1311,18 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         outs = (e(3), e(), e(), e(N_samples + max(n_f, 0) if march else N_samples + n_f, 4))
         if n_f > 0 and not march:
             outs += ((e(3), e(), e()) if proposal is None else ()) + (e(),)
+        if distortion:
+            outs += (e(),)
         if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
             occupancy._desc()
             occupancy.last_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal,
                                                                                              march_stop_eps, march_fit), 0)
-        return _result_dict(outs, retraw, coarse_first=False)
+        return _result_dict(outs, retraw, coarse_first=False, distortion=distortion)
     rnd, std = _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march)
     cfg = dict(N_samples=int(N_samples), N_importance=n_f, lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
                raw_noise_std=std, precision=_PRECISION)
+    if distortion:      # (the key exists only with the option: the passes read cfg.get("distortion", False))
+        cfg["distortion"] = True
     if occupancy is not None:
         if not _is_builtin_query(network_query_fn):
             raise NotImplementedError("render_rays: occupancy= together with a user network_query_fn is not implemented (mask inside the "
@@ -1235,13 +1364,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             outs = _RenderRaysGrid.apply(cfg, rays, rnd, model_c, model_f, occupancy, *params)
         else:
             outs = _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, occupancy)
-        ret = _result_dict(outs, retraw, coarse_first=True)
+        ret = _result_dict(outs, retraw, coarse_first=True, distortion=distortion)
         if n_hit is not None:
             occupancy.last_stats = dict(occupancy.last_stats, rays_hit=int(n_hit.item()), rays=n)
         return ret
     if not _is_builtin_query(network_query_fn):
         return _render_rays_hooked(rays, rnd, network_fn, network_query_fn, int(N_samples), n_f, network_fine if n_f > 0 else None,
-                                   bool(lindisp), white_bkgd, std, retraw)
+                                   bool(lindisp), white_bkgd, std, retraw, distortion)
     if dense:
         from .dense import render_rays_dense
         ret = render_rays_dense(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None)
@@ -1257,11 +1386,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     if cfg["precision"] == "fp16_fp8c" and cfg["need_grad"]:
         cfg["precision"] = "fp16x3"         # the reduced class is an inference form; gradients: the fp16x3 datapath, unchanged
     outs = _RenderRays.apply(cfg, rays, rnd, network_fn, None if (same or n_f <= 0) else network_fine, *params)
+    last = {}
+    if distortion:      # the node's trailing output; its key comes last
+        outs, last = outs[:-1], {'distortion': outs[-1]}
     if n_f <= 0:
         rgb_map, disp_map, acc_map, raw = outs
         ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map}
         if retraw:
             ret['raw'] = raw
+        ret.update(last)
         return ret
     rgb_map, disp_map, acc_map, raw, rgb0, disp0, acc0, z_std = outs
     ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map}
@@ -1271,6 +1404,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     ret['disp0'] = disp0
     ret['acc0'] = acc0
     ret['z_std'] = z_std
+    ret.update(last)
     return ret
 
 
