@@ -164,6 +164,28 @@ int nerf_distortion_fwd(const float* weights, const float* z_vals, const float* 
 int nerf_distortion_bwd(const float* weights, const float* z_vals, const float* near_far, int nf_stride, int n_rays,
                         int n_samples, const float* d_loss, float* d_weights, int accumulate, void* stream);
 
+/* ---- interlevel loss of proposal weights against a target histogram (mip-NeRF 360's proposal loss; additive in ABI v10; not in the
+ * reference).  Per ray: proposal depths zp_0 <= ... <= zp_{P-1} with weights wp_i, target depths z_0 <= ... <= z_{S-1} with weights w_j
+ * (sorted depths are the CALLER's contract, not checked).  Sample k of either side owns the half-open interval from its depth to the
+ * next one, the last sample [depth_last, +inf).  Intervals j and i overlap when max(z_j, zp_i) < min(z_{j+1}, zp_{i+1}), +inf behind
+ * each last depth: a zero-length interval overlaps nothing, the two last intervals always overlap.
+ *   bound_j = sum of wp_i over the proposal intervals overlapping target interval j, added in ascending i in fp32 (a direct sum)
+ *   loss[r] = sum_j max(0, w_j - bound_j)^2 / (w_j + 1e-7)
+ *   dloss/dwp_i = sum over the j overlapping i, in ascending j, of -2 max(0, w_j - bound_j) / (w_j + 1e-7)
+ * One wavefront per ray, the proposal row staged in LDS; every lane finds the contiguous run of candidates of its interval by binary
+ * search, applies the predicate to each and sums in order; no atomics: the same inputs give the same bits.  At most P + S - 1 pairs
+ * overlap: linear work per ray.  The target side is a constant of the graph: no gradient to w, to either set of depths.
+ * 1 <= n_proposal, n_samples <= 4096; n_rays = 0 launches nothing.  Reads 8 B per proposal point and 8 B per target point, writes 4 B
+ * per ray. */
+int nerf_interlevel_fwd(const float* proposal_weights, const float* proposal_z, int n_proposal, const float* weights,
+                        const float* z_vals, int n_samples, int n_rays, float* loss, void* stream);
+/* its adjoint, bound_j recomputed from the inputs (nothing saved): d_proposal_weights[r][i] = d_loss[r] * dloss/dwp_i, gathered per
+ * proposal interval, written (accumulate = 0) or added to what d_proposal_weights holds (accumulate = 1).  Reads 8 B per proposal
+ * point (12 B with accumulate) and 8 B per target point, writes 4 B per proposal point. */
+int nerf_interlevel_bwd(const float* proposal_weights, const float* proposal_z, int n_proposal, const float* weights,
+                        const float* z_vals, int n_samples, int n_rays, const float* d_loss, float* d_proposal_weights,
+                        int accumulate, void* stream);
+
 /* ---- hierarchical sampling (run_nerf.py:392-396,412 + sample_pdf, run_nerf_helpers.py:196-239):
  * z_mid, sample_pdf(z_mid, weights[1:-1], n_fine, det = (u == NULL)), sort(cat(z_vals, z_samples)), z_std.
  * u [n_rays][n_fine] uniform draws or NULL; u_lin = torch.linspace(0,1,n_fine) (read when u == NULL).

@@ -308,6 +308,24 @@ int nerf_distortion_bwd(const float* weights, const float* z_vals, const float* 
     return done(__func__, nerf::launch_distortion(a, true, (hipStream_t)stream));
 }
 
+int nerf_interlevel_fwd(const float* proposal_weights, const float* proposal_z, int n_proposal, const float* weights,
+                        const float* z_vals, int n_samples, int n_rays, float* loss, void* stream) {
+    REQUIRE(proposal_weights && proposal_z && weights && z_vals && loss, "null pointer");
+    REQUIRE(n_rays >= 0 && n_proposal >= 1 && n_proposal <= 4096 && n_samples >= 1 && n_samples <= 4096, "bad size");
+    nerf::InterlevelArgs a{proposal_weights, proposal_z, weights, z_vals, n_rays, n_proposal, n_samples, loss, nullptr, nullptr, 0};
+    return done(__func__, nerf::launch_interlevel(a, false, (hipStream_t)stream));
+}
+
+int nerf_interlevel_bwd(const float* proposal_weights, const float* proposal_z, int n_proposal, const float* weights,
+                        const float* z_vals, int n_samples, int n_rays, const float* d_loss, float* d_proposal_weights,
+                        int accumulate, void* stream) {
+    REQUIRE(proposal_weights && proposal_z && weights && z_vals && d_loss && d_proposal_weights, "null pointer");
+    REQUIRE(n_rays >= 0 && n_proposal >= 1 && n_proposal <= 4096 && n_samples >= 1 && n_samples <= 4096, "bad size");
+    nerf::InterlevelArgs a{proposal_weights, proposal_z, weights, z_vals, n_rays, n_proposal, n_samples, nullptr, d_loss,
+                           d_proposal_weights, accumulate ? 1 : 0};
+    return done(__func__, nerf::launch_interlevel(a, true, (hipStream_t)stream));
+}
+
 int nerf_sample_fine(const float* z_vals, const float* weights, int n_rays, int n_coarse, int n_fine,
                      const float* u, const float* u_lin, float* z_all, float* z_samples, float* z_std, void* stream) {
     REQUIRE(z_vals && weights && z_all && z_std, "null pointer");

@@ -40,6 +40,19 @@ struct DistortionArgs {
     int accumulate;
 };
 
+// interlevel loss of proposal weights against a target histogram (ray_device.h: interlevel_ray)
+struct InterlevelArgs {
+    const float* wp;        // [N][P] proposal weights
+    const float* zp;        // [N][P] proposal depths, non-decreasing per ray
+    const float* w;         // [N][S] target weights (a constant of the graph)
+    const float* z;         // [N][S] target depths, non-decreasing per ray
+    int n_rays, P, S;
+    float* loss;            // [N]                                       (forward)
+    const float* d_loss;    // [N] upstream gradient                     (adjoint)
+    float* d_wp;            // [N][P] written, or added to with accumulate (adjoint)
+    int accumulate;
+};
+
 struct FineArgs {
     // direct == 0: in0 = coarse depths z[N][Sc], in1 = coarse weights[N][Sc]
     //              bins = mid-points, pdf from weights[1:-1]               (run_nerf.py:392-393)
@@ -101,6 +114,7 @@ hipError_t launch_ray_pose_grad(int W, const float* K9, const float* d_rays, int
                                 float* d_pose, int accumulate, hipStream_t stream);
 hipError_t launch_composite(const CompositeArgs& a, bool bwd, hipStream_t stream);
 hipError_t launch_distortion(const DistortionArgs& a, bool bwd, hipStream_t stream);
+hipError_t launch_interlevel(const InterlevelArgs& a, bool bwd, hipStream_t stream);
 hipError_t launch_sample_fine(const FineArgs& a, hipStream_t stream);
 hipError_t launch_field_fwd(const float* packed, const float* rays, int ray_stride, const float* z_vals,
                             int n_rays, int S, float* raw, float* act, hipStream_t stream);

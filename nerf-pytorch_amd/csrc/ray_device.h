@@ -3,6 +3,7 @@
 //   coarse_depth        run_nerf.py:357-379   (z_vals: linspace / lindisp / stratified jitter)
 //   composite_ray       run_nerf.py:262-305   (raw2outputs) and its adjoint
 //   distortion_ray      the distortion loss of a ray's compositing weights and its adjoint (not in the reference)
+//   interlevel_ray      the interlevel loss of a ray's proposal weights against a target histogram and its adjoint (not in the reference)
 //   sample_fine_ray     run_nerf.py:392-396,412 + run_nerf_helpers.py:196-239 (sample_pdf, sort, z_std)
 // Sync: how the lanes of the ray's wavefront order their LDS traffic -- BlockSync when the wavefront is the whole workgroup
 // (__syncthreads), WaveSync when other wavefronts of the workgroup work on other rays (LDS operations of one wavefront
@@ -294,6 +295,91 @@ __device__ __forceinline__ void distortion_ray(const DistortionArgs& a, int ray,
     part = wave_sum(part);
     own = wave_sum(own);
     if (lane == 0) a.loss[ray] = part + own / 3.0f;
+}
+
+// ------------------------------------------------------------------ interlevel loss of proposal weights against a target histogram
+// mip-NeRF 360's proposal loss, per ray.  Sample k of either side owns [depth_k, depth_k+1), the last one [depth_last, +inf); target
+// interval j and proposal interval i overlap when max(z_j, zp_i) < min(z_j+1, zp_i+1) (a zero-length interval overlaps nothing):
+//   bound_j = sum of wp_i over the i overlapping j, ascending i;   L = sum_j max(0, w_j - bound_j)^2 / (w_j + 1e-7)
+//   dL/dwp_i = sum over the j overlapping i, ascending j, of -2 max(0, w_j - bound_j) / (w_j + 1e-7)
+// Both sides are sorted (the caller's contract), so what overlaps one interval is a contiguous run of the other side -- the intervals that
+// end behind its start and begin before its end -- with zero-length intervals inside the run: two binary searches give the run, THE
+// PREDICATE ITSELF decides every candidate, and the sum is direct (never a difference of prefix sums).  Sorted partitions overlap in at
+// most P + S - 1 pairs: linear work per ray.  The searches return indices in [0, n] whatever the depths hold (NaN, unsorted): every
+// candidate index lies inside its row.
+
+// number of entries of v[0..n) that are <= x (UPPER = true) or < x (UPPER = false); v non-decreasing
+template <bool UPPER>
+__device__ __forceinline__ int interlevel_count(const float* v, int n, float x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const float t = v[mid];
+        if (UPPER ? (t <= x) : (t < x)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// sum, in ascending order, of val[k] over the intervals k of the row `edge` [n] that overlap [lo_x, hi_x).  COMP = false: the plain fp32
+// sum (bound_j: terms >= 0, so the rounded sum is never below its largest term and an envelope proposal gives exactly 0).  COMP = true:
+// the same order with Kahan's carry (the adjoint: a proposal interval gathers up to S terms of size <= 2, and the plain sum's error
+// would grow with their count)
+template <bool COMP>
+__device__ __forceinline__ float interlevel_gather(const float* edge, const float* val, int n, float lo_x, float hi_x) {
+    int first = interlevel_count<true>(edge, n, lo_x) - 1;       // the last interval that begins at or before lo_x ends behind it
+    if (first < 0) first = 0;
+    const int last = interlevel_count<false>(edge, n, hi_x) - 1; // the last interval that begins before hi_x
+    float sum = 0.0f, carry = 0.0f;
+    for (int k = first; k <= last; ++k) {
+        const float e1 = k + 1 < n ? edge[k + 1] : __builtin_inff();
+        if (fmaxf(lo_x, edge[k]) < fminf(hi_x, e1)) {
+            if (COMP) {
+                const float y = val[k] - carry, t = sum + y;
+                carry = (t - sum) - y;
+                sum = t;
+            } else {
+                sum += val[k];
+            }
+        }
+    }
+    return sum;
+}
+
+// BWD = false: loss[ray].  BWD = true: d_wp[ray][i] (+)= d_loss[ray] dL/dwp_i, bound_j recomputed from the inputs.
+// LDS per ray: zp | wp (2 P floats), and in the adjoint z | g (2 S floats more, g_j = -2 max(0, w_j - bound_j) / (w_j + 1e-7)).
+// Lanes stride over target intervals (forward, and the adjoint's first phase) and over proposal intervals (its second phase).
+template <bool BWD, typename Sync>
+__device__ __forceinline__ void interlevel_ray(const InterlevelArgs& a, int ray, int lane, float* sm) {
+    const int P = a.P, S = a.S;
+    const float* wp = a.wp + (size_t)ray * P;
+    const float* zp = a.zp + (size_t)ray * P;
+    const float* w = a.w + (size_t)ray * S;
+    const float* z = a.z + (size_t)ray * S;
+    float* s_zp = sm;
+    float* s_wp = sm + P;
+    float* s_z = sm + 2 * P;            // (bwd)
+    float* s_g = sm + 2 * P + S;        // (bwd)
+    for (int i = lane; i < P; i += 64) { s_zp[i] = zp[i]; s_wp[i] = wp[i]; }
+    Sync::sync();
+    float part = 0.0f;
+    for (int j = lane; j < S; j += 64) {
+        const float z0 = z[j], z1 = j + 1 < S ? z[j + 1] : __builtin_inff();
+        const float wj = w[j];
+        const float over = fmaxf(0.0f, wj - interlevel_gather<false>(s_zp, s_wp, P, z0, z1));
+        if (BWD) { s_z[j] = z0; s_g[j] = -2.0f * over / (wj + 1e-7f); } else part += (over * over) / (wj + 1e-7f);
+    }
+    if (!BWD) {
+        part = wave_sum(part);
+        if (lane == 0) a.loss[ray] = part;
+        return;
+    }
+    Sync::sync();
+    const float g = a.d_loss[ray];
+    float* d_wp = a.d_wp + (size_t)ray * P;
+    for (int i = lane; i < P; i += 64) {
+        const float d = g * interlevel_gather<true>(s_z, s_g, S, s_zp[i], i + 1 < P ? s_zp[i + 1] : __builtin_inff());
+        d_wp[i] = a.accumulate ? d_wp[i] + d : d;
+    }
 }
 
 // ------------------------------------------------------------------ hierarchical sampling

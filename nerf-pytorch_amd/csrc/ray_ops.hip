@@ -6,6 +6,7 @@
 //   composite_fwd_kernel   run_nerf.py:262-305   (raw2outputs)
 //   composite_bwd_kernel   autograd of run_nerf.py:275-303
 //   distortion_kernel      the distortion loss of the compositing weights and its adjoint (not in the reference)
+//   interlevel_kernel      the interlevel loss of proposal weights against a target histogram and its adjoint (not in the reference)
 //   sample_fine_kernel     run_nerf.py:392-396,412 + run_nerf_helpers.py:196-239 (sample_pdf, sort, z_std)
 //   embed_kernel           run_nerf_helpers.py:15-45 (Embedder.embed, standalone form)
 //
@@ -39,6 +40,12 @@ template <bool BWD>
 __global__ __launch_bounds__(64) void distortion_kernel(DistortionArgs a) {
     extern __shared__ float sm[];
     distortion_ray<BWD>(a, blockIdx.x, threadIdx.x, sm);
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(64) void interlevel_kernel(InterlevelArgs a) {
+    extern __shared__ float sm[];
+    interlevel_ray<BWD, BlockSync>(a, blockIdx.x, threadIdx.x, sm);
 }
 
 __global__ __launch_bounds__(64) void sample_fine_kernel(FineArgs a) {
@@ -447,6 +454,13 @@ hipError_t launch_distortion(const DistortionArgs& a, bool bwd, hipStream_t stre
     if (a.n_rays <= 0) return hipSuccess;
     if (bwd) hipLaunchKernelGGL(distortion_kernel<true>, dim3(a.n_rays), dim3(64), 4 * a.S * sizeof(float), stream, a);
     else hipLaunchKernelGGL(distortion_kernel<false>, dim3(a.n_rays), dim3(64), 2 * a.S * sizeof(float), stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_interlevel(const InterlevelArgs& a, bool bwd, hipStream_t stream) {
+    if (a.n_rays <= 0) return hipSuccess;
+    if (bwd) hipLaunchKernelGGL(interlevel_kernel<true>, dim3(a.n_rays), dim3(64), 2 * (a.P + a.S) * sizeof(float), stream, a);
+    else hipLaunchKernelGGL(interlevel_kernel<false>, dim3(a.n_rays), dim3(64), 2 * a.P * sizeof(float), stream, a);
     return hipGetLastError();
 }
 

@@ -221,6 +221,7 @@ def render_rays_dense(cfg, rays, rnd, model_c, model_f):
     z = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
     raw = model_c.query(rays, z)
     rgb, disp, acc, weights, _ = _Composite.apply(raw[..., :4].contiguous(), z, rays_d, rnd.get("noise_c"), std, wb)
+    w_c, z_c = weights, z
     ret = {}
     if n_f > 0:
         ret.update(rgb0=rgb, disp0=disp, acc0=acc)
@@ -233,4 +234,7 @@ def render_rays_dense(cfg, rays, rnd, model_c, model_f):
     if cfg.get("distortion", False):        # of the last pass's weights (differentiable through _Composite); the key comes last
         from .render import distortion_loss
         ret["distortion"] = distortion_loss(weights, z, rays[:, 6], rays[:, 7])
+    if cfg.get("interlevel", False):        # the coarse pass's weights against the refining pass's; behind "distortion"
+        from .render import interlevel_loss
+        ret["interlevel"] = interlevel_loss(w_c, z_c, weights, z)
     return ret

@@ -51,6 +51,8 @@ def _declare(lib):
         "nerf_sample_fine": (i, [p, p, i, i, i, p, p, p, p, p, p]),
         "nerf_distortion_fwd": (i, [p, p, p, i, i, i, p, p]),
         "nerf_distortion_bwd": (i, [p, p, p, i, i, i, p, p, i, p]),
+        "nerf_interlevel_fwd": (i, [p, p, i, p, p, i, i, p, p]),
+        "nerf_interlevel_bwd": (i, [p, p, i, p, p, i, i, p, p, i, p]),
         "nerf_sample_pdf": (i, [p, p, i, i, i, p, p, p, p]),
         "nerf_delta_floats": (sz, [i, i]),
         "nerf_wgrad_partial_floats": (sz, [i, i]),
@@ -134,7 +136,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_occ_view_carve",
            "nerf_iso_scratch_words", "nerf_iso_count", "nerf_iso_emit",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live",
-           "nerf_distortion_fwd", "nerf_distortion_bwd"]
+           "nerf_distortion_fwd", "nerf_distortion_bwd", "nerf_interlevel_fwd", "nerf_interlevel_bwd"]
 
 
 def lib():
@@ -982,6 +984,43 @@ def distortion_bwd(weights, z_vals, near_far, d_loss, out=None, accumulate=False
     nfp, stride = _near_far_ptr(near_far, nf_stride, nf_offset, n)
     _check(lib().nerf_distortion_bwd(_ptr(weights, "weights"), _ptr(z_vals, "z_vals"), nfp, stride, n, S, _ptr(d_loss, "d_loss"),
                                      _ptr(out, "out"), int(bool(accumulate)), _stream()), "nerf_distortion_bwd")
+    return out
+
+
+def _interlevel_shapes(proposal_weights, proposal_z, weights, z_vals):
+    n, P = proposal_z.shape
+    S = z_vals.shape[1]
+    if tuple(proposal_weights.shape) != (n, P) or tuple(weights.shape) != (n, S) or z_vals.shape[0] != n:
+        raise NerfHipError(f"proposal_weights {tuple(proposal_weights.shape)}, proposal_z {tuple(proposal_z.shape)}, weights "
+                           f"{tuple(weights.shape)} and z_vals {tuple(z_vals.shape)} do not belong together")
+    return n, P, S
+
+
+def interlevel(proposal_weights, proposal_z, weights, z_vals):
+    """loss [n] of nerf_interlevel_fwd: the interlevel loss of the proposal weights [n, P] on the depths proposal_z [n, P] against the
+    target weights [n, S] on z_vals [n, S] (both sets of depths non-decreasing per ray: the caller's contract)"""
+    n, P, S = _interlevel_shapes(proposal_weights, proposal_z, weights, z_vals)
+    loss = torch.empty((n,), dtype=torch.float32, device=z_vals.device)
+    _check(lib().nerf_interlevel_fwd(_ptr(proposal_weights, "proposal_weights"), _ptr(proposal_z, "proposal_z"), P, _ptr(weights, "weights"),
+                                     _ptr(z_vals, "z_vals"), S, n, _ptr(loss), _stream()), "nerf_interlevel_fwd")
+    return loss
+
+
+def interlevel_bwd(proposal_weights, proposal_z, weights, z_vals, d_loss, out=None, accumulate=False):
+    """d_proposal_weights [n, P] = d_loss [n] * d loss / d proposal_weights (nerf_interlevel_bwd), recomputed from the inputs; written into
+    `out` (a new tensor without one), or added to what `out` holds with accumulate=True"""
+    n, P, S = _interlevel_shapes(proposal_weights, proposal_z, weights, z_vals)
+    if tuple(d_loss.shape) != (n,):
+        raise NerfHipError(f"d_loss {tuple(d_loss.shape)} is not [{n}]")
+    if out is None:
+        if accumulate:
+            raise NerfHipError("accumulate=True needs the tensor to add to (out=)")
+        out = torch.empty((n, P), dtype=torch.float32, device=z_vals.device)
+    elif tuple(out.shape) != (n, P):
+        raise NerfHipError(f"out {tuple(out.shape)} is not [{n}, {P}]")
+    _check(lib().nerf_interlevel_bwd(_ptr(proposal_weights, "proposal_weights"), _ptr(proposal_z, "proposal_z"), P, _ptr(weights, "weights"),
+                                     _ptr(z_vals, "z_vals"), S, n, _ptr(d_loss, "d_loss"), _ptr(out, "out"), int(bool(accumulate)),
+                                     _stream()), "nerf_interlevel_bwd")
     return out
 
 

@@ -178,6 +178,7 @@ def _field_pass(cfg, rays, rnd, model_c, model_f, save):
     r["raw_c"], r["act_c"] = hb.field_fwd(r["packed_c"], rays, r["z_c"], save_act=save, precision=prec_c,
                                           guard_packed=guard(model_c) if prec_c == "fp16_fp8c" else None, next_guard=nxt)
     dist = cfg.get("distortion", False)     # the last pass also hands out its weights (one more store, every other output keeps its bits)
+    inter = cfg.get("interlevel", False)    # likewise, and the coarse weights are kept too (render_rays refuses it without a refining pass)
     r["rgb_c"], r["disp_c"], r["acc_c"], w_c, _ = hb.raw2outputs(r["raw_c"], r["z_c"], rays, rays.shape[1], rnd.get("noise_c"), std, wb,
                                                               want_weights=n_f > 0 or dist, want_depth=False, rays_d_offset=3)
     if n_f <= 0:
@@ -190,9 +191,11 @@ def _field_pass(cfg, rays, rnd, model_c, model_f, save):
     r["raw_f"], r["act_f"] = hb.field_fwd(r["packed_f"], rays, r["z_f"], save_act=save, precision=prec,
                                           guard_packed="done" if raw_f is not None else guard(mf), raw=raw_f)
     r["rgb_f"], r["disp_f"], r["acc_f"], w_f, _ = hb.raw2outputs(r["raw_f"], r["z_f"], rays, rays.shape[1], rnd.get("noise_f"), std, wb,
-                                                               want_weights=dist, want_depth=False, rays_d_offset=3)
+                                                               want_weights=dist or inter, want_depth=False, rays_d_offset=3)
     if dist:
         r["w"], r["distortion"] = w_f, hb.distortion(w_f, r["z_f"], rays, nf_stride=rays.shape[1], nf_offset=6)
+    if inter:       # the coarse histogram as the proposal, the refining pass's as the target
+        r["w"], r["w_c"], r["interlevel"] = w_f, w_c, hb.interlevel(w_c, r["z_c"], w_f, r["z_f"])
     return r
 
 
@@ -223,7 +226,10 @@ class _RenderRays(torch.autograd.Function):
 
     cfg["distortion"]: one trailing differentiable output, the distortion loss [N] of the last pass's weights (_field_pass), which stay
     among the saved tensors; its upstream gradient enters the last pass's compositing backward as d_weights (nerf_distortion_bwd), in
-    all three plans."""
+    all three plans.  cfg["interlevel"]: one trailing differentiable output (behind the distortion loss), the interlevel loss [N] of the
+    coarse pass's weights against the refining pass's; both passes' weights stay among the saved tensors (the recompute plan recomputes
+    them) and its upstream gradient enters the COARSE pass's compositing backward as d_weights (nerf_interlevel_bwd): it reaches model_c
+    through the coarse pass only, and alone it runs no backward of the refining pass."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, *params):
@@ -251,8 +257,8 @@ class _RenderRays(torch.autograd.Function):
         LAST_BACKWARD_PLAN = ("recompute" if ctx.checkpoint else "resident sub-chunks" if ctx.tiles is not None else "one launch", n, sub)
         ctx.sub_rays = sub
         prec = cfg.get("precision", "fp32")
-        dist = cfg.get("distortion", False)
-        if not need and not dist and hb.INFER_ONE_LAUNCH and hb.render_infer_supported(cfg["N_samples"], n_f, prec):
+        dist, inter = cfg.get("distortion", False), cfg.get("interlevel", False)
+        if not need and not dist and not inter and hb.INFER_ONE_LAUNCH and hb.render_infer_supported(cfg["N_samples"], n_f, prec):
             # no gradients: coarse depths -> network -> compositing -> hierarchical depths -> network -> compositing in ONE launch
             mf = None if (model_f is None or model_f is model_c or n_f <= 0) else model_f
             r = hb.render_rays_infer(model_c.packed_params(prec), None if mf is None else mf.packed_params(prec), rays, cfg["N_samples"],
@@ -279,7 +285,7 @@ class _RenderRays(torch.autograd.Function):
                 r = _field_pass(cfg, rays, rnd, model_c, model_f, save=False)
             else:
                 out_keys = ("rgb_c", "disp_c", "acc_c", "raw_c") if n_f <= 0 else ("rgb_f", "disp_f", "acc_f", "raw_f", "rgb_c", "disp_c", "acc_c", "z_std")
-                r = {k_: torch.cat([p_[k_] for p_ in parts], 0) for k_ in out_keys + (("distortion",) if dist else ())}
+                r = {k_: torch.cat([p_[k_] for p_ in parts], 0) for k_ in out_keys + (("distortion",) if dist else ()) + (("interlevel",) if inter else ())}
         if need and not ctx.checkpoint and prec in ("fp16x3", "fp16x3w"):
             # the fp16 split's range guard rail: every RANGE_MONITOR.every-th training render scans what the forward saved
             # (hb.RangeMonitor; replaces run_nerf.py:414-416's DEBUG-gated NaN / Inf check)
@@ -303,11 +309,12 @@ class _RenderRays(torch.autograd.Function):
         # `raw` of the last pass, goes through save_for_backward, which autograd knows how to hold without a cycle.
         ctx.saved = None
         if ctx.tiles is not None:
-            keep = ("packed_c", "z_c", "act_c", "raw_c", "packed_f", "z_f", "act_f", "raw_f", "w")
+            keep = ("packed_c", "z_c", "act_c", "raw_c", "packed_f", "z_f", "act_f", "raw_f", "w", "w_c")
             ctx.saved = [{k_: p_[k_] for k_ in keep if k_ in p_} for p_ in parts]     # per-sub-chunk tensors, none is an output
         elif need and not ctx.checkpoint:
-            # ("w": the last pass's weights under cfg["distortion"], N S 4 bytes, not an output)
-            keep = ("packed_c", "z_c", "act_c", "packed_f", "z_f", "act_f", "w") + (("raw_c",) if n_f > 0 else ())
+            # ("w": the last pass's weights under cfg["distortion"] or cfg["interlevel"], N S 4 bytes, "w_c": the coarse pass's under
+            # cfg["interlevel"], N N_samples 4 bytes; neither is an output)
+            keep = ("packed_c", "z_c", "act_c", "packed_f", "z_f", "act_f", "w", "w_c") + (("raw_c",) if n_f > 0 else ())
             ctx.saved = {k: r[k] for k in keep if k in r}
             ctx.save_for_backward(r["raw_f"] if n_f > 0 else r["raw_c"])
         elif not need:
@@ -316,7 +323,7 @@ class _RenderRays(torch.autograd.Function):
         # fragments packed at forward time: remember which parameter state this forward saw
         ctx.param_state = tuple(_param_state(m) for m in (model_c, model_f) if m is not None)
         ctx.consumed = False
-        tail = (r["distortion"],) if dist else ()      # one trailing differentiable output
+        tail = ((r["distortion"],) if dist else ()) + ((r["interlevel"],) if inter else ())      # trailing differentiable outputs
         if n_f <= 0:
             return (r["rgb_c"], r["disp_c"], r["acc_c"], r["raw_c"]) + tail
         ctx.mark_non_differentiable(r["z_std"])     # the reference detaches z_samples (run_nerf.py:394)
@@ -341,10 +348,11 @@ class _RenderRays(torch.autograd.Function):
         n_all = rays_all.shape[0]
         n_f = cfg["N_importance"]
         fine = n_f > 0
-        # upstream gradients of (rgb, disp, acc, raw, distortion) of the fine (or only) pass and of the coarse pass; the distortion loss
-        # is the trailing output and belongs to the last pass
-        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-1] if cfg.get("distortion", False) else None)
-        up_c = (gouts[4], gouts[5], gouts[6], None, None) if fine else None
+        # upstream gradients of (rgb, disp, acc, raw, distortion, interlevel) of the fine (or only) pass and of the coarse pass; the two
+        # losses are the trailing outputs: the distortion loss belongs to the last pass, the interlevel loss to the coarse one
+        inter = cfg.get("interlevel", False)
+        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-2 if inter else -1] if cfg.get("distortion", False) else None, None)
+        up_c = (gouts[4], gouts[5], gouts[6], None, None, gouts[-1] if inter else None) if fine else None
         if not fine:
             up_c, up_f = up_f, None
         has = lambda up: up is not None and any(g is not None for g in up)
@@ -361,10 +369,10 @@ class _RenderRays(torch.autograd.Function):
         # dL/d(ray records), summed over both passes (near / far: zero -- render() builds them from Python floats)
         d_rays_all = torch.zeros((n_all, 11), dtype=torch.float32, device=dev) if ctx.rays_grad else None
 
-        def field_grad(rays, model, packed, act, raw, z, noise, up, lo, hi, grad, key, w=None):
-            d_rgb, d_disp, d_acc, d_raw_up, d_dist = (None if g is None else g[lo:hi] for g in up)
+        def field_grad(rays, model, packed, act, raw, z, noise, up, lo, hi, grad, key, w=None, target=None):
+            d_rgb, d_disp, d_acc, d_raw_up, d_dist, d_inter = (None if g is None else g[lo:hi] for g in up)
             m = hi - lo
-            if d_rgb is None and (d_disp is not None or d_acc is not None or d_dist is not None):
+            if d_rgb is None and (d_disp is not None or d_acc is not None or d_dist is not None or d_inter is not None):
                 d_rgb = torch.zeros((m, 3), dtype=torch.float32, device=dev)
             c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
             d_rays = None if d_rays_all is None else d_rays_all[lo:hi]
@@ -376,6 +384,8 @@ class _RenderRays(torch.autograd.Function):
                     d_dn = torch.empty((m, 3), dtype=torch.float32, device=dev)
                 # the distortion loss reaches raw (and |d|) through the weights' adjoint: d_weights of the compositing backward
                 extra = {} if d_dist is None else {"d_weights": hb.distortion_bwd(w, z, rays, c(d_dist), nf_stride=rays.shape[1], nf_offset=6)}
+                if d_inter is not None:     # the interlevel loss, likewise: w, z are the proposal, target = the refining pass's (weights, depths)
+                    extra = {"d_weights": hb.interlevel_bwd(w, z, target[0], target[1], c(d_inter))}
                 d_raw = hb.raw2outputs_bwd(raw, z, rays, rays.shape[1], noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
                                            rays_d_offset=3, d_rays_d=d_dn, **extra)
                 if d_raw_up is not None:
@@ -394,7 +404,7 @@ class _RenderRays(torch.autograd.Function):
         def backprop(r, rays, rnd, lo, hi, last=True):
             if has(up_c):
                 field_grad(rays, ctx.model_c, r["packed_c"], r["act_c"], r["raw_c"], r["z_c"], rnd.get("noise_c"), up_c, lo, hi, grad_c, "c",
-                           None if fine else r.get("w"))
+                           r.get("w_c") if fine else r.get("w"), (r.get("w"), r.get("z_f")))
                 if last and not shared and grad_c is not None:     # final: its all-reduce may start under the fine network's backward
                     _grad_ready(ctx.model_c, grad_c)
             hb.WORKSPACE.give(r["act_c"])
@@ -535,6 +545,63 @@ def distortion_loss_reference(weights, z_vals, near, far):
     return pair + (w * w * dl).sum(-1) / 3
 
 
+class _Interlevel(torch.autograd.Function):
+    """interlevel_loss over nerf_interlevel_fwd / _bwd: gradient to the proposal weights only, recomputed from the inputs"""
+
+    @staticmethod
+    def forward(ctx, proposal_weights, proposal_z, weights, z_vals):
+        ctx.args = (proposal_weights.detach(), proposal_z, weights, z_vals)
+        ctx.set_materialize_grads(False)
+        return hb.interlevel(*ctx.args)
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        if d_loss is None:      # nothing upstream: no launch
+            return None, None, None, None
+        return hb.interlevel_bwd(*ctx.args, d_loss.to(torch.float32).contiguous()), None, None, None
+
+
+def interlevel_loss(proposal_weights, proposal_z, weights, z_vals):
+    """The interlevel (proposal) loss of mip-NeRF 360, per ray: [..., P] proposal weights and depths, [..., S] target weights and depths
+    -> [...] (two HIP launches, forward and adjoint; interlevel_loss_reference is the definition).  Sample k of either side owns the
+    half-open interval from its depth to the next one, the last sample [depth_last, +inf) -- the interval whose length the compositing
+    used for that sample's alpha.  Intervals overlap when their intersection has positive length, max(z_j, zp_i) < min(z_j+1, zp_i+1):
+    a zero-length interval overlaps nothing, the two last intervals always overlap.  With bound_j the sum of wp_i over the proposal
+    intervals overlapping target interval j:
+
+        L = sum_j max(0, w_j - bound_j)^2 / (w_j + 1e-7)
+
+    the penalty for every target weight the proposal histogram does not cover.  Gradient to ``proposal_weights`` ONLY: the target
+    weights and both sets of depths are constants of the graph (the stop-gradient of the original).  THE CALLER'S CONTRACT: both sets of
+    depths are non-decreasing along the last axis (what every path of render_rays produces); it is not checked, a check would be a
+    host synchronisation.  1 <= P, S <= 4096.  Composes with raw2outputs, whose weights (output 3) are differentiable:
+    interlevel_loss(raw2outputs(raw_c, z_c, d)[3], z_c, raw2outputs(raw_f, z_f, d)[3], z_f)."""
+    lead, P, S = tuple(proposal_weights.shape[:-1]), proposal_weights.shape[-1], weights.shape[-1]
+    if tuple(proposal_z.shape) != tuple(proposal_weights.shape) or tuple(z_vals.shape) != tuple(weights.shape) or tuple(weights.shape[:-1]) != lead:
+        raise ValueError(f"interlevel_loss: proposal_weights {tuple(proposal_weights.shape)}, proposal_z {tuple(proposal_z.shape)}, weights "
+                         f"{tuple(weights.shape)} and z_vals {tuple(z_vals.shape)} do not belong together")
+    f = lambda t, k: t.to(torch.float32).reshape(-1, k).contiguous()
+    return _Interlevel.apply(f(proposal_weights, P), f(proposal_z.detach(), P), f(weights.detach(), S), f(z_vals.detach(), S)).reshape(lead)
+
+
+def interlevel_loss_reference(proposal_weights, proposal_z, weights, z_vals):
+    """THE DEFINITION interlevel_loss and the render paths' "interlevel" key are held to, in plain torch, on any device, in the dtype of
+    ``proposal_weights`` for the sums (the tests call it in float64): the [..., S, P] overlap mask from the comparisons of the depths as
+    they are given -- no searchsorted, no prefix differences --, bound = (mask * wp).sum(-1).  Differentiable w.r.t.
+    ``proposal_weights`` by torch's autograd; the target weights are detached and the depths are constants."""
+    wp = proposal_weights
+    w = weights.detach().to(dtype=wp.dtype, device=wp.device)
+    zp, z = proposal_z.detach().to(wp.device), z_vals.detach().to(wp.device)
+    if zp.dtype != z.dtype:     # (comparisons of fp32 depths are exact in any wider type)
+        zp, z = zp.to(torch.promote_types(zp.dtype, z.dtype)), z.to(torch.promote_types(zp.dtype, z.dtype))
+    inf = lambda t: torch.full_like(t[..., :1], float("inf"))
+    z0, z1 = z[..., :, None], torch.cat([z[..., 1:], inf(z)], -1)[..., :, None]             # [..., S, 1]
+    p0, p1 = zp[..., None, :], torch.cat([zp[..., 1:], inf(zp)], -1)[..., None, :]          # [..., 1, P]
+    mask = torch.maximum(z0, p0) < torch.minimum(z1, p1)                                    # [..., S, P]
+    bound = (mask.to(wp.dtype) * wp[..., None, :]).sum(-1)
+    return ((w - bound).clamp_min(0) ** 2 / (w + 1e-7)).sum(-1)
+
+
 # --------------------------------------------------------------------------- reference call surface
 def query_points(model, pts, viewdirs_per_point):
     """Evaluate the field at explicit points: every point is its own ray record
@@ -643,7 +710,7 @@ def _is_builtin_query(network_query_fn):
 
 
 def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f, network_fine, lindisp, white_bkgd, std, retraw,
-                        distortion=False):
+                        distortion=False, interlevel=False):
     """render_rays with a USER-SUPPLIED network_query_fn (run_nerf.py:385, :401 call it for every pass): the hook sees the reference's
     arguments -- pts [N, S, 3], viewdirs [N, 3], the network module -- and whatever it returns is composited, exactly as in the
     reference (a density regulariser, a clamp, a different network call all work).  Stage by stage through the C ABI: coarse depths
@@ -659,6 +726,7 @@ def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f,
 
     z = z_c = hb.sample_coarse(rays, _linspace01(N_samples, dev), lindisp, rnd.get("t_rand"))
     raw, (rgb, disp, acc, weights, _) = one_pass(z_c, network_fn, rnd.get("noise_c"))
+    w_c = weights
     ret = {}
     if n_f > 0:
         ret.update(rgb0=rgb, disp0=disp, acc0=acc)
@@ -671,6 +739,8 @@ def _render_rays_hooked(rays, rnd, network_fn, network_query_fn, N_samples, n_f,
         ret["raw"] = raw
     if distortion:      # of the last pass's weights (differentiable through _Composite)
         ret["distortion"] = distortion_loss(weights, z, rays[:, 6], rays[:, 7])
+    if interlevel:      # the coarse pass's weights against the refining pass's (differentiable through the coarse _Composite only)
+        ret["interlevel"] = interlevel_loss(w_c, z_c, weights, z)
     return ret
 
 
@@ -695,7 +765,7 @@ def _grid_pass(cfg, desc, rays, z_vals, model, noise, want_weights, z_stop=None,
     others' on an error.  budget = {"rays_grad": bool, "resident": bytes the call keeps so far, "rays": rays of the whole call} goes with
     it: beyond hb.SAVE_TOTAL_BYTES in total the pass raises.
     The compacted raw and the M zero depths live inside the pass and are plain torch allocations on both paths.
-    keep_weights (cfg["distortion"], the last pass): the record also keeps the pass's compositing weights as "w" for the backward."""
+    keep_weights (cfg["distortion"], the last pass; cfg["interlevel"], both passes): the record also keeps the pass's compositing weights as "w" for the backward."""
     n, S = z_vals.shape
     P = n * S
     dev, prec = rays.device, cfg["precision"]
@@ -751,7 +821,7 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
         model_c, which is the whole chunk when N_importance = 0;
       cfg["early_stop_eps"]: the coarse weights give one stop depth per ray (nerf_occ_stop_depth), with which the refining pass compacts;
       nerf_sample_fine, and the refining pass on model_f (model_c without one).
-    One host synchronisation per pass and none of its own.  Returns the output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std][, distortion])
+    One host synchronisation per pass and none of its own.  Returns the output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std][, distortion][, interlevel])
     and the device counters (stopped rays, truncated rays, refit rays; None without the option), which the caller reads back after its
     passes.  cfg["march_step_size"] (with cfg["march_fit"]): the march's depths are nerf_occ_march_step's -- steps of one length in the
     scene, march_steps the cap on candidates, the step doubled per ray until it fits the slots -- and nothing else of the chunk changes."""
@@ -759,8 +829,10 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
     dev = rays.device
     # cfg["distortion"]: the LAST pass hands out and keeps its weights, and the chain's tuple ends with their distortion loss on the depths
     # the pass was given and the near / far of `rays` (the clipped ones under clip_to_occupancy)
-    dist = cfg.get("distortion", False)
-    last_kw = {"keep_weights": True} if dist else {}
+    # cfg["interlevel"] (two passes, no proposal: render_rays refuses the rest): BOTH passes hand out and keep their weights, and the tuple
+    # ends with the interlevel loss of the coarse pass's weights against the refining pass's (skipped and stopped samples: weight 0)
+    dist, inter = cfg.get("distortion", False), cfg.get("interlevel", False)
+    last_kw = {"keep_weights": True} if dist or inter else {}
     loss_of = lambda w, z: (hb.distortion(w, z, rays, nf_stride=rays.shape[1], nf_offset=6),) if dist else ()
     if cfg["march_steps"] is not None:
         n_stopped = n_refit = None
@@ -788,7 +860,7 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
         w_c = grid.proposal_weights(rays, z_c)
     else:
         raw_c, (rgb_c, disp_c, acc_c, w_c, _) = run_pass(rays, z_c, model_c, rnd.get("noise_c"), n_f > 0 or dist, None,
-                                                         **({} if n_f > 0 else last_kw))
+                                                         **(({"keep_weights": True} if inter else {}) if n_f > 0 else last_kw))
         if n_f <= 0:
             return (rgb_c, disp_c, acc_c, raw_c) + loss_of(w_c, z_c), None, None, None
         coarse = (rgb_c, disp_c, acc_c)
@@ -798,9 +870,10 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
         n_stopped = torch.isfinite(z_stop).sum()
     u = rnd.get("u")
     z_f, z_std, _ = hb.sample_fine(z_c, w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
-    raw_f, (rgb_f, disp_f, acc_f, w_f, _) = run_pass(rays, z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), dist, z_stop,
-                                                     **last_kw)
-    return (rgb_f, disp_f, acc_f, raw_f) + coarse + (z_std,) + loss_of(w_f, z_f), n_stopped, None, None
+    raw_f, (rgb_f, disp_f, acc_f, w_f, _) = run_pass(rays, z_f, model_c if model_f is None else model_f, rnd.get("noise_f"), dist or inter,
+                                                     z_stop, **last_kw)
+    return ((rgb_f, disp_f, acc_f, raw_f) + coarse + (z_std,) + loss_of(w_f, z_f) + ((hb.interlevel(w_c, z_c, w_f, z_f),) if inter else ()),
+            n_stopped, None, None)
 
 
 def _grid_stats(grid, stats, n_stopped, n_truncated, n_refit=None):
@@ -850,7 +923,10 @@ class _RenderRaysGrid(torch.autograd.Function):
     the graph, computed per sub-chunk; with N_importance = 0 the backward is the coarse-only one; outputs (rgb, disp, acc, raw) --
     cfg["march_stop_eps"], cfg["march_step_size"] and cfg["march_fit"] change which kernel computes those constants and nothing of the
     backward.  cfg["distortion"]: the tuple ends with the distortion loss [N] of the last pass's weights, which that pass's record keeps
-    as "w"; its upstream gradient enters the pass's compositing backward as d_weights, in front of nerf_occ_gather."""
+    as "w"; its upstream gradient enters the pass's compositing backward as d_weights, in front of nerf_occ_gather.  cfg["interlevel"] (the
+    two-pass form only): the tuple ends with the interlevel loss [N] of the coarse pass's weights against the refining pass's, both
+    records keep their "w", and its upstream gradient enters the COARSE pass's compositing backward as d_weights (nerf_interlevel_bwd):
+    alone it runs no backward of the refining pass."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
@@ -911,8 +987,8 @@ class _RenderRaysGrid(torch.autograd.Function):
         ctx.param_state = tuple(_param_state(m_) for m_ in (model_c, model_f) if m_ is not None)
         ctx.consumed = False
         ctx.set_materialize_grads(False)
-        if n_f > 0:     # z_std (in front of the distortion loss if there is one): the reference detaches z_samples (run_nerf.py:394)
-            ctx.mark_non_differentiable(out[-2 if cfg.get("distortion", False) else -1])
+        if n_f > 0:     # z_std (in front of the trailing losses if there are any): the reference detaches z_samples (run_nerf.py:394)
+            ctx.mark_non_differentiable(out[-1 - int(cfg.get("distortion", False)) - int(cfg.get("interlevel", False))])
         return tuple(out)
 
     @staticmethod
@@ -930,12 +1006,13 @@ class _RenderRaysGrid(torch.autograd.Function):
         dev = rays_all.device
         n_all = rays_all.shape[0]
         fine = cfg["N_importance"] > 0
-        # (the distortion loss is the trailing output and belongs to the last pass)
-        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-1] if cfg.get("distortion", False) else None)
+        # (the losses are the trailing outputs: the distortion loss belongs to the last pass, the interlevel loss behind it to the coarse one)
+        inter = cfg.get("interlevel", False)
+        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-2 if inter else -1] if cfg.get("distortion", False) else None, None)
         if ctx.proposal:        # one pass, the refining one: there is no coarse image
             up_c = None
         else:
-            up_c = (gouts[4], gouts[5], gouts[6], None, None) if fine else None
+            up_c = (gouts[4], gouts[5], gouts[6], None, None, gouts[-1] if inter else None) if fine else None
         if not fine:
             up_c, up_f = up_f, None
         has = lambda up: up is not None and any(g is not None for g in up)
@@ -957,10 +1034,10 @@ class _RenderRaysGrid(torch.autograd.Function):
         wrote = {"c": False, "f": False}
         d_rays_all = torch.zeros((n_all, 11), dtype=torch.float32, device=dev) if ctx.rays_grad else None
 
-        def field_grad(rays, model, p, raw, noise, up, lo, hi, grad, key):
-            d_rgb, d_disp, d_acc, d_raw_up, d_dist = (None if g is None else g[lo:hi] for g in up)
+        def field_grad(rays, model, p, raw, noise, up, lo, hi, grad, key, target=None):
+            d_rgb, d_disp, d_acc, d_raw_up, d_dist, d_inter = (None if g is None else g[lo:hi] for g in up)
             nt, z, m = hi - lo, p["z"], p["m"]
-            if d_rgb is None and (d_disp is not None or d_acc is not None or d_dist is not None):
+            if d_rgb is None and (d_disp is not None or d_acc is not None or d_dist is not None or d_inter is not None):
                 d_rgb = torch.zeros((nt, 3), dtype=torch.float32, device=dev)
             c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
             d_rays = None if d_rays_all is None else d_rays_all[lo:hi]
@@ -972,6 +1049,8 @@ class _RenderRaysGrid(torch.autograd.Function):
                     d_dn = torch.empty((nt, 3), dtype=torch.float32, device=dev)
                 # the distortion loss enters as d_weights of the compositing backward, in front of nerf_occ_gather
                 extra = {} if d_dist is None else {"d_weights": hb.distortion_bwd(p["w"], z, rays, c(d_dist), nf_stride=rays.shape[1], nf_offset=6)}
+                if d_inter is not None:     # the interlevel loss, likewise: this pass is the proposal, target = the refining pass's record
+                    extra = {"d_weights": hb.interlevel_bwd(p["w"], z, target["w"], target["z"], c(d_inter))}
                 d_raw = hb.raw2outputs_bwd(raw, z, rays, rays.shape[1], noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
                                            rays_d_offset=3, d_rays_d=d_dn, **extra)
                 if d_raw_up is not None:
@@ -1003,7 +1082,7 @@ class _RenderRaysGrid(torch.autograd.Function):
             rnd = rnd_all if len(ctx.tiles) == 1 else {k: v[lo:hi] for k, v in rnd_all.items()}
             raw_of = lambda p: p["raw"] if "raw" in p else raw_last
             if has(up_c):
-                field_grad(rays, ctx.model_c, passes[0], raw_of(passes[0]), rnd.get("noise_c"), up_c, lo, hi, grad_c, "c")
+                field_grad(rays, ctx.model_c, passes[0], raw_of(passes[0]), rnd.get("noise_c"), up_c, lo, hi, grad_c, "c", passes[-1])
                 if last and not shared and grad_c is not None:     # final: its all-reduce may start under the fine network's backward
                     _grad_ready(ctx.model_c, grad_c)
             if fine and has(up_f):
@@ -1141,13 +1220,15 @@ def _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, random
     return rnd, std
 
 
-def _result_dict(outs, retraw, coarse_first, distortion=False):
-    """the returned dict of an output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std][, distortion]).  coarse_first: the key
+def _result_dict(outs, retraw, coarse_first, distortion=False, interlevel=False):
+    """the returned dict of an output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std][, distortion][, interlevel]).  coarse_first: the key
     order of _render_rays_hooked, which the grid paths share (the coarse image and z_std in front); else the fused dense path's, which
-    the empty batch has always had.  distortion: the tuple ends with the distortion loss, whose key comes last"""
+    the empty batch has always had.  distortion: the tuple ends with the distortion loss, whose key comes last; interlevel: with the interlevel loss, behind it"""
     last = {}
+    if interlevel:
+        outs, last = outs[:-1], {"interlevel": outs[-1]}
     if distortion:
-        outs, last = outs[:-1], {"distortion": outs[-1]}
+        outs, last = outs[:-1], {"distortion": outs[-1], **last}
     fine = dict(rgb_map=outs[0], disp_map=outs[1], acc_map=outs[2], **({"raw": outs[3]} if retraw else {}))
     coarse = dict(zip(("rgb0", "disp0", "acc0"), outs[4:7])) if len(outs) == 8 else {}
     if len(outs) > 4:
@@ -1167,7 +1248,7 @@ def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal, march_stop_e
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
                 *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None, march_steps=None,
-                march_stop_eps=None, march_step_size=None, march_fit=0, distortion=False):
+                march_stop_eps=None, march_step_size=None, march_fit=0, distortion=False, interlevel=False):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -1280,10 +1361,37 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     every other output keeps its bits), one launch for the loss, and one for its adjoint when the key carries a gradient; the fused
     node keeps the weights (N * S * 4 bytes) for its backward.  A call WITHOUT a needed gradient takes the staged passes with the
     option, not the one-launch inference kernel, which has no weights to give.  False: nothing changes -- same launches, same bits,
-    same draws."""
+    same draws.
+
+    ``interlevel`` (keyword-only, not in the reference; a bool; needs N_importance > 0 and a coarse pass): True adds one key,
+    "interlevel" [N] fp32, last in the dict (behind "distortion" when both are on): the interlevel loss of mip-NeRF 360
+    (interlevel_loss; interlevel_loss_reference is the definition) with the COARSE pass's compositing weights on the coarse depths as
+    the proposal histogram and the refining pass's weights on its depths as the target -- both exactly the weights the compositing
+    used, noise included.  It penalises every refining weight that exceeds what the coarse histogram holds over the same span, and so
+    trains network_fn for what its weights are used for: telling nerf_sample_fine where to draw.  The target is a constant of the
+    graph: the upstream gradient enters the coarse pass's compositing backward as d_weights (nerf_interlevel_bwd -> nerf_raw2outputs_bwd)
+    and reaches network_fn, and the ray records when they require grad, by the existing adjoints; network_fine gets nothing from it
+    (a loss of this key alone leaves its .grad None and runs no backward of the refining pass), and a network that serves both passes
+    gets it through the coarse pass only.  There is no gradient to depths.  Supported on the fused node in all backward plans (it keeps
+    both passes' weights, N * (2 N_samples + N_importance) * 4 bytes; the recompute plan recomputes them), through a DensityGrid in
+    its two-pass form, also with clip_to_occupancy and early_stop_eps (skipped and stopped samples have weight 0 and contribute
+    nothing), with a user network_query_fn and with general (DenseNeRF) networks (interlevel_loss on _Composite's weights).  A call
+    WITHOUT a needed gradient takes the staged passes, as with ``distortion``.  render() delivers it as extras["interlevel"] with the
+    rays' leading shape.  Refused with ValueError: N_importance = 0, proposal="grid" (a grid is not trained by gradients),
+    proposal="march" (there is no coarse pass), a value that is not a bool.  False: nothing changes -- same launches, same bits, same
+    draws."""
     if not isinstance(distortion, (bool, np.bool_)):
         raise ValueError(f"render_rays: distortion must be a bool, got {distortion!r}")
     distortion = bool(distortion)
+    if not isinstance(interlevel, (bool, np.bool_)):
+        raise ValueError(f"render_rays: interlevel must be a bool, got {interlevel!r}")
+    interlevel = bool(interlevel)
+    if interlevel:
+        if proposal is not None:
+            raise ValueError(f"render_rays: interlevel=True fits the coarse network's weights to the refining pass's; proposal={proposal!r} "
+                             "has no coarse network pass")
+        if int(N_importance) <= 0:
+            raise ValueError("render_rays: interlevel=True needs a refining pass to fit the coarse weights to: N_importance must be > 0")
     march, early_stop_eps, march_steps, march_stop_eps, march_step_size, march_fit = _check_grid_options(
         N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal, early_stop_eps, march_steps, march_stop_eps, march_step_size,
         march_fit)
@@ -1311,18 +1419,19 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         outs = (e(3), e(), e(), e(N_samples + max(n_f, 0) if march else N_samples + n_f, 4))
         if n_f > 0 and not march:
             outs += ((e(3), e(), e()) if proposal is None else ()) + (e(),)
-        if distortion:
-            outs += (e(),)
+        outs += (e(),) * (int(distortion) + int(interlevel))
         if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
             occupancy._desc()
             occupancy.last_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal,
                                                                                              march_stop_eps, march_fit), 0)
-        return _result_dict(outs, retraw, coarse_first=False, distortion=distortion)
+        return _result_dict(outs, retraw, coarse_first=False, distortion=distortion, interlevel=interlevel)
     rnd, std = _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march)
     cfg = dict(N_samples=int(N_samples), N_importance=n_f, lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
                raw_noise_std=std, precision=_PRECISION)
     if distortion:      # (the key exists only with the option: the passes read cfg.get("distortion", False))
         cfg["distortion"] = True
+    if interlevel:
+        cfg["interlevel"] = True
     if occupancy is not None:
         if not _is_builtin_query(network_query_fn):
             raise NotImplementedError("render_rays: occupancy= together with a user network_query_fn is not implemented (mask inside the "
@@ -1364,13 +1473,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             outs = _RenderRaysGrid.apply(cfg, rays, rnd, model_c, model_f, occupancy, *params)
         else:
             outs = _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, occupancy)
-        ret = _result_dict(outs, retraw, coarse_first=True, distortion=distortion)
+        ret = _result_dict(outs, retraw, coarse_first=True, distortion=distortion, interlevel=interlevel)
         if n_hit is not None:
             occupancy.last_stats = dict(occupancy.last_stats, rays_hit=int(n_hit.item()), rays=n)
         return ret
     if not _is_builtin_query(network_query_fn):
         return _render_rays_hooked(rays, rnd, network_fn, network_query_fn, int(N_samples), n_f, network_fine if n_f > 0 else None,
-                                   bool(lindisp), white_bkgd, std, retraw, distortion)
+                                   bool(lindisp), white_bkgd, std, retraw, distortion, interlevel)
     if dense:
         from .dense import render_rays_dense
         ret = render_rays_dense(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None)
@@ -1387,8 +1496,10 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         cfg["precision"] = "fp16x3"         # the reduced class is an inference form; gradients: the fp16x3 datapath, unchanged
     outs = _RenderRays.apply(cfg, rays, rnd, network_fn, None if (same or n_f <= 0) else network_fine, *params)
     last = {}
-    if distortion:      # the node's trailing output; its key comes last
-        outs, last = outs[:-1], {'distortion': outs[-1]}
+    if interlevel:      # the node's trailing outputs; their keys come last
+        outs, last = outs[:-1], {'interlevel': outs[-1]}
+    if distortion:
+        outs, last = outs[:-1], {'distortion': outs[-1], **last}
     if n_f <= 0:
         rgb_map, disp_map, acc_map, raw = outs
         ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map}
