@@ -665,6 +665,37 @@ int nerf_iso_count(const float* volume, int nx, int ny, int nz, float level, con
 int nerf_iso_emit(const float* volume, int nx, int ny, int nz, float level, const float lo[3], const float step[3],
                   const unsigned* keep_words /* nullable */, int* scratch, float* vertices, int* faces, void* stream);
 
+/* ---- baked field (additive in ABI v10): render rays from values stored on the lattice nodes of an occupancy grid, without a network.
+ * BakedField.render_rays_reference (nerf-pytorch_amd/baked.py) is the definition.  The grid of resolution (Rx, Ry, Rz) has
+ * (Rx + 1)(Ry + 1)(Rz + 1) nodes, node = (i (Ry + 1) + j) (Rz + 1) + k; node_index[node] is the node's row in table, or 0; table is fp16
+ * [n_rows][W], row 0 all zeros (it serves every node that is not stored), W = 4 / 16 / 32 halves for sh_degree 0 / 1 / 2.  With
+ * B = (sh_degree + 1)^2 a row is sigma, R_0 .. R_{B-1}, G_0 .., B_0 .., zero-padded: the density after the ReLU and the coefficients of
+ * the colour LOGITS in the real spherical harmonics Y_0 .. Y_8 of PlenOctrees' order and signs (baked.sh_basis).  Every corner of an
+ * occupied cell must have a row; an index outside [0, n_rows) reads row 0.
+ * Per ray (11 columns: o, d, near, far, viewdir): the walk of nerf_occ_march_step at level 0 -- |d| added left to right, dz = step_size /
+ * |d|; invalid when one of the first eight components is not finite, when near >= far or when dz is not a finite number > 0;
+ * z_k = near + (fp32(k) + u) * dz for k = 0 .. max_steps - 1, valid_k = z_k < far, p = o + d * z_k, t = (p - lo) * scale -- and
+ *   keep_k = valid_k && 0 <= t < R on all axes && the bit of cell floor(t) is set        (grid->outside_skip is not read: a point
+ *                                                                                          outside the box is never sampled)
+ * At a kept candidate f = t - floor(t); the eight corner rows are blended in fp32 with the weights (wx wy) wz, w = f or 1 - f, in the
+ * order 000 001 .. 111 (x the slowest bit); sigma = max(blend, 0); logit_c = sum_b coefficient_{c,b} * Y_b(viewdir) added left to right
+ * (viewdir = columns 8:11, used as given); rgb = 1 / (1 + expf(-logit)); alpha = 1 - expf(-sigma * step_size); the transmittance in
+ * front of the candidate is the product of 1 - alpha_j + 1e-10 over the kept j < k (a wave scan inside a round of 64 candidates times
+ * the value carried from the rounds before); w = alpha T.
+ *   rgb_map [n][3] = sum w rgb (+ 1 - acc with white_bkgd),  acc_map [n] = sum w,  depth_map [n] = sum w z_k,
+ *   disp_map [n] = 1 / max(1e-10, depth / acc) with the NaN of 0 / 0 kept (nerf_raw2outputs' expression),
+ *   n_samples [n] = the number of kept candidates that were composited; bit 30 (0x40000000) is set on top when a round ended with the
+ *                   transmittance below stop_eps (never with stop_eps = 0).
+ * stop_eps > 0: behind the first round of 64 candidates at whose end T < stop_eps no further round is walked; what is dropped weighs
+ * at most T.  An invalid ray and a ray that keeps nothing give the background, acc = depth = 0 and n_samples = 0.
+ * One wavefront per ray; plain loads and stores, no atomics, no LDS: the same inputs give the same bits.  Per kept candidate 32 B of
+ * indices and 8 rows of 2 W bytes are read; per ray 28 B are written.  table must be 16-byte aligned.  ray_stride >= 11; sh_degree 0, 1
+ * or 2; step_size finite and > 0; 1 <= max_steps <= 2^24; 0 <= stop_eps < 1; n_rows >= 1; n_rays == 0 is a no-op. */
+int nerf_baked_render(const NerfOccGrid* grid, const int* node_index, const void* table /* fp16 rows */, int n_rows, int sh_degree,
+                      const float* rays, int ray_stride, const float* u /* nullable: 0.5 */, int n_rays, float step_size, int max_steps,
+                      float stop_eps, int white_bkgd, float* rgb_map, float* disp_map, float* acc_map, float* depth_map,
+                      int* n_samples, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

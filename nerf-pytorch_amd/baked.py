@@ -1,0 +1,381 @@
+"""Baked fields: a trained network written into a sparse grid of spherical-harmonic coefficients, and rendered without the network.
+
+``render()`` evaluates the 8x256 network at every sample point it keeps.  A ``BakedField`` evaluates it once per lattice node of an
+occupancy grid instead (PlenOctrees, Yu et al. 2021; SNeRG, Hedman et al. 2021): every node that touches an occupied cell stores the
+density and the coefficients of the colour logits in the real spherical harmonics of degree <= 2, and a ray is rendered by marching
+the grid in world-space steps, blending the eight nodes of each kept sample's cell and compositing on the spot (csrc/baked.hip,
+nerf_baked_render).  ``BakedField.render_rays_reference`` is the definition the kernel is tested against; ``render_rays(...,
+baked=field)`` and ``render_kwargs_test["baked"] = field`` are the ways in.  No gradients: a baked field is an inference artefact.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import hip_backend as hb
+from .occupancy import OccupancyGrid
+
+_SH_C0 = 0.28209479177387814
+_SH_C1 = 0.4886025119029199
+_SH_C2 = (1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
+_ROUND = 64                 # candidates per round of the kernel's walk: the unit of the stop rule
+_SLICE_NODES = 1 << 20      # lattice nodes whose positions from_network builds at a time
+
+
+def _check_degree(sh_degree, who):
+    if isinstance(sh_degree, (bool, np.bool_)) or not isinstance(sh_degree, (int, np.integer)) or int(sh_degree) not in (0, 1, 2):
+        raise ValueError(f"{who}: sh_degree must be 0, 1 or 2, got {sh_degree!r}")
+    return int(sh_degree)
+
+
+def _check_stop_eps(stop_eps, who):
+    real = not isinstance(stop_eps, (bool, np.bool_)) and isinstance(stop_eps, (int, float, np.integer, np.floating))
+    if not real or not (0.0 <= float(stop_eps) < 1.0) or not (float(np.float32(stop_eps)) < 1.0):      # (also refuses NaN)
+        raise ValueError(f"{who}: stop_eps must be a real number with 0 <= stop_eps < 1, got {stop_eps!r}")
+    return float(stop_eps)
+
+
+def _check_step(step_size, grid, who):
+    """step_size as a float; None: half the smallest cell edge of the grid"""
+    if step_size is None:
+        return 0.5 * float(np.min(grid.width))
+    real = not isinstance(step_size, (bool, np.bool_)) and isinstance(step_size, (int, float, np.integer, np.floating))
+    if real:
+        try:
+            with np.errstate(all="ignore"):
+                real = 0.0 < float(np.float32(step_size)) < float("inf")       # (the kernel's step is fp32(step_size); also refuses NaN)
+        except OverflowError:
+            real = False
+    if not real:
+        raise ValueError(f"{who}: step_size must be None or a finite real number > 0 (as an fp32 value), got {step_size!r}")
+    return float(step_size)
+
+
+def _check_max_steps(max_steps, who):
+    if isinstance(max_steps, (bool, np.bool_)) or not isinstance(max_steps, (int, np.integer)) or not (1 <= int(max_steps) <= 1 << 24):
+        raise ValueError(f"{who}: max_steps must be an int with 1 <= max_steps <= 2^24, got {max_steps!r}")
+    return int(max_steps)
+
+
+def sh_basis(dirs, degree):
+    """[..., B], B = (degree + 1)^2: the real spherical harmonics of degree <= `degree` (0, 1 or 2) at the unit vectors dirs [..., 3], in
+    the order and with the signs of PlenOctrees / svox, in dirs' dtype:
+    Y0 = c0;  Y1 = -c1 y, Y2 = c1 z, Y3 = -c1 x;  Y4 = c2 xy, Y5 = -c2 yz, Y6 = c3 (2 z^2 - x^2 - y^2), Y7 = -c2 xz, Y8 = c4 (x^2 - y^2)."""
+    degree = _check_degree(degree, "sh_basis")
+    if dirs.shape[-1] != 3 or not dirs.is_floating_point():
+        raise ValueError("sh_basis: dirs must be a floating-point tensor [..., 3]")
+    x, y, z = dirs[..., 0], dirs[..., 1], dirs[..., 2]
+    out = [torch.full_like(x, _SH_C0)]
+    if degree >= 1:
+        out += [-_SH_C1 * y, _SH_C1 * z, -_SH_C1 * x]
+    if degree >= 2:
+        xx, yy, zz = x * x, y * y, z * z
+        out += [_SH_C2[0] * (x * y), -_SH_C2[0] * (y * z), _SH_C2[1] * (2.0 * zz - xx - yy), -_SH_C2[0] * (x * z), _SH_C2[2] * (xx - yy)]
+    return torch.stack(out, -1)
+
+
+def fibonacci_sphere(n, dtype=torch.float64, device=None):
+    """[n, 3] unit vectors: z_i = 1 - (2 i + 1) / n, phi_i = i pi (3 - sqrt 5), computed in float64"""
+    n = int(n)
+    if n < 1:
+        raise ValueError("fibonacci_sphere: n >= 1")
+    i = torch.arange(n, dtype=torch.float64)
+    z = 1.0 - (2.0 * i + 1.0) / n
+    phi = i * (math.pi * (3.0 - math.sqrt(5.0)))
+    s = torch.sqrt(torch.clamp(1.0 - z * z, min=0.0))
+    return torch.stack([s * torch.cos(phi), s * torch.sin(phi), z], -1).to(dtype=dtype, device=device)
+
+
+class BakedField:
+    """Density and view-dependent colour on the lattice nodes of one OccupancyGrid (or DensityGrid) of resolution (Rx, Ry, Rz).
+
+    Storage.  The (Rx + 1)(Ry + 1)(Rz + 1) nodes are numbered as ``mesh.lattice_points`` numbers them, n = (i (Ry + 1) + j)(Rz + 1) + k.
+    ``index`` (int32, one entry per node) is the node's row in ``table``, or 0; ``table`` is fp16 [M + 1, W], row 0 all zeros, serving
+    every node that is not stored.  A node is stored iff one of its up to eight adjacent cells is occupied, so every corner of an
+    occupied cell has a row.  With B = (sh_degree + 1)^2 a row is [sigma, R_0 .. R_{B-1}, G_0 .., B_0 ..] zero-padded to W = 4 / 16 /
+    32 halves (8 / 32 / 64 bytes) for sh_degree 0 / 1 / 2: sigma is the density after the ReLU, the rest the coefficients of the
+    colour LOGITS raw[..., :3] in ``sh_basis``.  ``n_rows`` = M + 1.
+
+    ``step_size`` is the length of a march step in the scene (None: half the smallest cell edge); ``stop_eps`` > 0 ends a ray behind
+    the first round of 64 candidates at whose end its transmittance is below stop_eps (0: never).
+    ``last_stats`` = {"rays", "samples", "rays_stopped"} of the last ``render_rays`` call (through render_rays(baked=) /
+    batchify_rays / render: summed over the chunks).  The grid's bits decide which candidates are sampled: changing them after the
+    field was built leaves cells whose corners have no row, which then read zeros."""
+
+    def __init__(self, grid, index, table, sh_degree, step_size=None, stop_eps=0.0):
+        if not isinstance(grid, OccupancyGrid):
+            raise ValueError("BakedField: grid must be an occupancy.OccupancyGrid or DensityGrid")
+        self.grid = grid
+        self.sh_degree = _check_degree(sh_degree, "BakedField")
+        self.step_size = _check_step(step_size, grid, "BakedField")
+        self.stop_eps = _check_stop_eps(stop_eps, "BakedField")
+        self._set_storage(index, table)
+        self.last_stats = None
+
+    # ------------------------------------------------------------------ plain properties
+    @property
+    def n_basis(self):
+        return (self.sh_degree + 1) ** 2
+
+    @property
+    def n_rows(self):
+        return int(self.table.shape[0])
+
+    @property
+    def device(self):
+        return self.table.device
+
+    @property
+    def node_resolution(self):
+        return tuple(r + 1 for r in self.grid.resolution)
+
+    def to(self, device):
+        self.grid.to(device)
+        self.index = self.index.to(device)
+        self.table = self.table.to(device)
+        return self
+
+    def _set_storage(self, index, table):
+        nodes = int(np.prod(self.node_resolution))
+        index = torch.as_tensor(index)
+        table = torch.as_tensor(table)
+        W = hb.BAKED_ROW_HALVES[self.sh_degree]
+        if index.dtype != torch.int32 or index.numel() != nodes:
+            raise ValueError(f"BakedField: index must be int32 with one entry per lattice node ({nodes}), got {index.dtype} {tuple(index.shape)}")
+        if table.dtype != torch.float16 or table.dim() != 2 or table.shape[0] < 1 or table.shape[1] != W:
+            raise ValueError(f"BakedField: table must be fp16 [rows >= 1, {W}] for sh_degree {self.sh_degree}, got {table.dtype} {tuple(table.shape)}")
+        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= table.shape[0]):
+            raise ValueError("BakedField: index must hold rows of the table")
+        dev = self.grid.device
+        self.index = index.reshape(-1).to(dev).contiguous()
+        self.table = table.to(dev).contiguous()
+
+    # ------------------------------------------------------------------ building
+    @staticmethod
+    def stored_nodes(grid):
+        """bool [Rx + 1, Ry + 1, Rz + 1] on the grid's device: the nodes with at least one occupied adjacent cell (eight shifted ORs of
+        the grid's mask)"""
+        mask = grid.to_mask()
+        rx, ry, rz = grid.resolution
+        stored = torch.zeros((rx + 1, ry + 1, rz + 1), dtype=torch.bool, device=mask.device)
+        for dx in (0, 1):
+            for dy in (0, 1):
+                for dz in (0, 1):
+                    stored[dx:dx + rx, dy:dy + ry, dz:dz + rz] |= mask
+        return stored
+
+    @classmethod
+    def _pack(cls, grid, stored, rows, sh_degree, step_size, stop_eps):
+        """the field of `rows` fp32 [M, 1 + 3B], the values of the stored nodes in node order"""
+        W = hb.BAKED_ROW_HALVES[sh_degree]
+        flat = stored.reshape(-1)
+        rank = torch.cumsum(flat.to(torch.int64), 0)
+        index = torch.where(flat, rank, torch.zeros_like(rank)).to(torch.int32)
+        table = torch.zeros((rows.shape[0] + 1, W), dtype=torch.float16, device=rows.device)
+        table[1:, :rows.shape[1]] = rows.to(torch.float16)
+        return cls(grid, index, table, sh_degree, step_size, stop_eps)
+
+    @classmethod
+    def from_nodes(cls, grid, nodes, sh_degree, step_size=None, stop_eps=0.0):
+        """The field of explicit node values: nodes fp32 [Rx + 1, Ry + 1, Rz + 1, 1 + 3B] -- sigma, then the R, G and B coefficients --
+        of which the stored nodes' rows are packed and rounded to fp16 (plain torch on the grid's device); the others are dropped."""
+        sh_degree = _check_degree(sh_degree, "BakedField.from_nodes")
+        if not isinstance(grid, OccupancyGrid):
+            raise ValueError("BakedField.from_nodes: grid must be an occupancy.OccupancyGrid or DensityGrid")
+        V = 1 + 3 * (sh_degree + 1) ** 2
+        nodes = torch.as_tensor(nodes)
+        want = tuple(r + 1 for r in grid.resolution) + (V,)
+        if tuple(nodes.shape) != want or not nodes.is_floating_point():
+            raise ValueError(f"BakedField.from_nodes: nodes must be a floating-point tensor {want}, got {tuple(nodes.shape)}")
+        stored = cls.stored_nodes(grid)
+        rows = nodes.detach().to(device=stored.device, dtype=torch.float32)[stored]
+        return cls._pack(grid, stored, rows, sh_degree, step_size, stop_eps)
+
+    @staticmethod
+    def sh_fit_matrix(n_dirs, sh_degree):
+        """fp32 [B, n_dirs]: the pseudo-inverse of sh_basis(fibonacci_sphere(n_dirs), sh_degree), computed in float64 -- the least-squares
+        fit of B coefficients to values at those directions.  n_dirs >= B."""
+        sh_degree = _check_degree(sh_degree, "BakedField.sh_fit_matrix")
+        B = (sh_degree + 1) ** 2
+        if isinstance(n_dirs, (bool, np.bool_)) or not isinstance(n_dirs, (int, np.integer)) or int(n_dirs) < B:
+            raise ValueError(f"BakedField.sh_fit_matrix: n_dirs must be an int >= {B} (the basis functions of degree {sh_degree}), got {n_dirs!r}")
+        return torch.linalg.pinv(sh_basis(fibonacci_sphere(int(n_dirs)), sh_degree)).to(torch.float32)
+
+    @classmethod
+    def from_network(cls, model, grid, sh_degree=2, n_dirs=32, chunk=1 << 20, step_size=None, stop_eps=0.0):
+        """The field of a trained network on `grid` (on the network's device).  For the stored nodes only: the positions are
+        mesh.lattice_points'; the network is evaluated through query_points under no_grad at every node from the n_dirs directions of
+        fibonacci_sphere, at most `chunk` (node, direction) pairs at a time; sigma is the mean over the directions of
+        relu(raw[..., 3]) (the density does not depend on the direction: the mean keeps the definition symmetric) and the colour
+        coefficients are sh_fit_matrix(n_dirs, sh_degree) @ raw[..., :3].  Both sums run over the directions left to right in fp32,
+        one multiplication and one addition per term, so the table does not depend on `chunk`."""
+        from .mesh import lattice_points
+        from .render import query_points
+        sh_degree = _check_degree(sh_degree, "BakedField.from_network")
+        if not isinstance(grid, OccupancyGrid):
+            raise ValueError("BakedField.from_network: grid must be an occupancy.OccupancyGrid or DensityGrid")
+        step_size = _check_step(step_size, grid, "BakedField.from_network")
+        stop_eps = _check_stop_eps(stop_eps, "BakedField.from_network")
+        fit = cls.sh_fit_matrix(n_dirs, sh_degree)
+        n_dirs = int(n_dirs)
+        if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or int(chunk) < n_dirs:
+            raise ValueError(f"BakedField.from_network: chunk must be an int >= n_dirs ({n_dirs}), got {chunk!r}")
+        dev = grid.device
+        B = fit.shape[0]
+        fit = fit.to(dev)
+        dirs = fibonacci_sphere(n_dirs, torch.float32, dev)
+        stored = cls.stored_nodes(grid)
+        flat = stored.reshape(-1)
+        res = tuple(r + 1 for r in grid.resolution)
+        per = max(1, int(chunk) // n_dirs)
+        rows = []
+        with torch.no_grad():
+            pts = [lattice_points(grid.lo, grid.hi, res, first, min(first + _SLICE_NODES, flat.numel()), dev)[flat[first:first + _SLICE_NODES]]
+                   for first in range(0, flat.numel(), _SLICE_NODES)]
+            pts = torch.cat(pts, 0)
+            for first in range(0, pts.shape[0], per):
+                p = pts[first:first + per]
+                m = p.shape[0]
+                raw = query_points(model, p[:, None, :].expand(m, n_dirs, 3).reshape(-1, 3),
+                                   dirs[None, :, :].expand(m, n_dirs, 3).reshape(-1, 3)).view(m, n_dirs, 4)
+                sigma = torch.zeros(m, dtype=torch.float32, device=dev)
+                coef = torch.zeros((m, 3, B), dtype=torch.float32, device=dev)
+                for i in range(n_dirs):
+                    sigma = sigma + torch.relu(raw[:, i, 3])
+                    coef = coef + raw[:, i, :3, None] * fit[None, None, :, i]
+                rows.append(torch.cat([(sigma / n_dirs)[:, None], coef.reshape(m, 3 * B)], -1))
+        rows = torch.cat(rows, 0) if rows else torch.zeros((0, 1 + 3 * B), dtype=torch.float32, device=dev)
+        return cls._pack(grid, stored, rows, sh_degree, step_size, stop_eps)
+
+    # ------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        return {"grid": self.grid.state_dict(), "index": self.index.detach().cpu().clone(), "table": self.table.detach().cpu().clone(),
+                "sh_degree": self.sh_degree, "step_size": self.step_size, "stop_eps": self.stop_eps}
+
+    def load_state_dict(self, state):
+        """Takes the state of a field of the SAME sh_degree and grid resolution (the box, the bits and the values are the state's)"""
+        if int(state["sh_degree"]) != self.sh_degree:
+            raise ValueError(f"BakedField.load_state_dict: the state has sh_degree {int(state['sh_degree'])}, this field {self.sh_degree}")
+        res = tuple(int(v) for v in state["grid"]["resolution"])
+        if res != self.grid.resolution:
+            raise ValueError(f"BakedField.load_state_dict: the state's grid is {res}, this field's {self.grid.resolution}")
+        step_size = _check_step(state["step_size"], self.grid, "BakedField.load_state_dict")
+        stop_eps = _check_stop_eps(state["stop_eps"], "BakedField.load_state_dict")
+        self.grid.load_state_dict(state["grid"])
+        self._set_storage(torch.as_tensor(state["index"]).to(torch.int32), torch.as_tensor(state["table"]).to(torch.float16))
+        self.step_size, self.stop_eps = step_size, stop_eps
+        return self
+
+    # ------------------------------------------------------------------ the definition
+    def render_rays_reference(self, rays, u=None, white_bkgd=False, max_steps=1 << 14, dtype=torch.float64):
+        """The definition of the baked render, in plain torch on rays' device: rays [N, >= 11] (o, d, near, far, viewdir), u fp32 [N] in
+        [0, 1) or None (0.5) -> {"rgb_map" [N, 3], "disp_map", "acc_map", "depth_map" [N] in `dtype`, "n_samples" int32 [N],
+        "rays_stopped" int}.  Every discrete decision is the fp32 expression of the march references; the continuous arithmetic runs in
+        `dtype`.
+
+        Geometry, fp32 (OccupancyGrid._march_rays / _world_steps): dn = the correctly rounded root of dx dx + dy dy + dz dz added left
+        to right; dz = fp32(step_size) / dn; a ray is invalid when one of its first eight components is not finite, when near >= far
+        or when dz is not a finite number > 0.  Candidates k = 0 .. max_steps - 1 at z_k = near + (fp32(k) + u) * dz, valid_k = z_k <
+        far, p = o + d * z_k (one multiplication, one addition per axis).
+        Classification (OccupancyGrid._classify): t = (p - lo) * scale in fp32, inside iff 0 <= t < R on all axes, cell floor(t);
+        keep_k = valid_k and inside and the cell's bit.  A point outside the box is never sampled, whatever grid.outside says.
+        Sample value, in dtype from the fp32 t: f = t - floor(t) (exact); the eight corner rows blended with the weights (wx wy) wz,
+        w = f or 1 - f, corners in the order 000 001 .. 111 (x the slowest bit); sigma = max(blend, 0); logits = sum_b coefficient_b
+        Y_b(viewdir) added left to right, viewdir = columns 8:11 as given; rgb = sigmoid(logits).
+        Compositing over the kept samples in order of k: alpha_k = 1 - exp(-sigma_k fp32(step_size)); T_k = the exclusive product of
+        1 - alpha_j + 1e-10 over the kept j < k; w_k = alpha_k T_k; rgb_map = sum w rgb (+ 1 - acc with white_bkgd), acc_map = sum w,
+        depth_map = sum w z_k, disp_map = 1 / max(1e-10, depth / acc) with the NaN of 0 / 0 kept.  An invalid ray and a ray that keeps
+        nothing give the background, acc = depth = 0 and n_samples = 0.
+        The stop (stop_eps > 0), in units of the kernel's rounds: the candidates are taken 64 at a time; behind the first round at
+        whose end the running T -- the product over everything kept so far -- is below stop_eps no further round is walked.
+        "rays_stopped" counts the rays with such a round (never one with stop_eps = 0); n_samples counts what was composited."""
+        max_steps = _check_max_steps(max_steps, "BakedField.render_rays_reference")
+        grid = self.grid
+        r, ok, uu, dn, M, _ = OccupancyGrid._march_rays("BakedField.render_rays_reference", rays, u, max_steps, 1)
+        if rays.shape[1] < 11:
+            raise ValueError("BakedField.render_rays_reference: rays [N, >= 11] (o, d, near, far, viewdir)")
+        dev = rays.device
+        N = r.shape[0]
+        ds32 = torch.tensor(self.step_size, dtype=torch.float32, device=dev)
+        dz = ds32 / dn
+        ok = ok & (dz[:, 0] > 0) & torch.isfinite(dz[:, 0])
+        out_rgb = torch.zeros((N, 3), dtype=dtype, device=dev)
+        out_acc = torch.zeros(N, dtype=dtype, device=dev)
+        out_depth = torch.zeros(N, dtype=dtype, device=dev)
+        n_samples = torch.zeros(N, dtype=torch.int32, device=dev)
+        stopped = torch.zeros(N, dtype=torch.bool, device=dev)
+        if N > 0:
+            z, valid = OccupancyGrid._world_steps(r, ok, uu, dz, M)
+            K = z.shape[1]
+            pts = r[:, None, 0:3] + r[:, None, 3:6] * z[:, :, None]
+            f32 = lambda a: torch.tensor(np.asarray(a, dtype=np.float32), device=dev)
+            t = (pts - f32(grid.lo)) * f32(grid.scale)
+            inside, _, bit = grid._classify(pts)
+            keep = valid & inside & bit
+            Y = sh_basis(rays.detach()[:, 8:11].to(torch.float32).to(dtype), self.sh_degree)       # [N, B]
+            B = self.n_basis
+            index = self.index.to(dev).to(torch.int64)
+            table = self.table.to(dev)
+            ny, nz = grid.resolution[1] + 1, grid.resolution[2] + 1
+            rows, cols = keep.nonzero(as_tuple=True)
+            tk = t[rows, cols]
+            cell = torch.floor(tk)
+            f = (tk - cell).to(dtype)
+            ci = cell.to(torch.int64)
+            val = torch.zeros((rows.numel(), 1 + 3 * B), dtype=dtype, device=dev)
+            for c in range(8):
+                ox, oy, oz = (c >> 2) & 1, (c >> 1) & 1, c & 1
+                node = ((ci[:, 0] + ox) * ny + (ci[:, 1] + oy)) * nz + (ci[:, 2] + oz)
+                w = (f[:, 0] if ox else 1.0 - f[:, 0]) * (f[:, 1] if oy else 1.0 - f[:, 1]) * (f[:, 2] if oz else 1.0 - f[:, 2])
+                val = val + w[:, None] * table[index[node]][:, :1 + 3 * B].to(dtype)
+            sigma = torch.clamp(val[:, 0], min=0.0)
+            Yk = Y[rows]
+            logits = torch.zeros((rows.numel(), 3), dtype=dtype, device=dev)
+            for b in range(B):
+                logits = logits + val[:, 1 + b:1 + 3 * B:B] * Yk[:, b:b + 1]
+            rgb_k = torch.sigmoid(logits)
+            alpha_k = 1.0 - torch.exp(-sigma * ds32.to(dtype))
+            alpha = torch.zeros((N, K), dtype=dtype, device=dev)
+            alpha[rows, cols] = alpha_k
+            step_t = 1.0 - alpha + 1e-10
+            step_t = torch.where(keep, step_t, torch.ones_like(step_t))
+            incl = torch.cumprod(step_t, -1)
+            T = torch.cat([torch.ones((N, 1), dtype=dtype, device=dev), incl[:, :-1]], -1)
+            live = keep
+            if self.stop_eps > 0.0:         # the rounds: T at the end of round j is incl[:, 64 j + 63] (or the last column)
+                ends = torch.arange(_ROUND - 1, K + _ROUND - 1, _ROUND, device=dev).clamp(max=K - 1)
+                kept_in = torch.stack([keep[:, e0:e0 + _ROUND].any(-1) for e0 in range(0, K, _ROUND)], -1)
+                below = (incl[:, ends] < np.float32(self.stop_eps).item()) & kept_in        # (a round that keeps nothing changes nothing)
+                stopped = below.any(-1)
+                first = torch.where(stopped, below.to(torch.uint8).argmax(-1), torch.full((N,), ends.numel(), device=dev))
+                live = keep & (torch.arange(K, device=dev)[None, :] < ((first + 1) * _ROUND)[:, None])
+            w = torch.where(live, alpha * T, torch.zeros_like(T))
+            rgb_full = torch.zeros((N, K, 3), dtype=dtype, device=dev)
+            rgb_full[rows, cols] = rgb_k
+            out_rgb = (w[:, :, None] * rgb_full).sum(1)
+            out_acc = w.sum(-1)
+            out_depth = (w * torch.where(live, z, torch.zeros_like(z)).to(dtype)).sum(-1)       # (a candidate that is not kept may lie at inf)
+            n_samples = live.sum(-1).to(torch.int32)
+        if white_bkgd:
+            out_rgb = out_rgb + (1.0 - out_acc)[:, None]
+        ratio = out_depth / out_acc
+        disp = 1.0 / torch.max(torch.full_like(ratio, 1e-10), ratio)
+        return {"rgb_map": out_rgb, "disp_map": disp, "acc_map": out_acc, "depth_map": out_depth, "n_samples": n_samples,
+                "rays_stopped": int(stopped.sum())}
+
+    # ------------------------------------------------------------------ the kernel
+    def render_rays(self, rays, u=None, white_bkgd=False, max_steps=1 << 14):
+        """{"rgb_map" fp32 [N, 3], "disp_map", "acc_map", "depth_map" fp32 [N]} of rays [N, >= 11] on the GPU (nerf_baked_render):
+        ``render_rays_reference`` within fp32 rounding, its kept samples exactly.  Runs under no_grad; the results are detached.  Sets
+        ``last_stats`` = {"rays", "samples", "rays_stopped"}."""
+        max_steps = _check_max_steps(max_steps, "BakedField.render_rays")
+        if rays.dim() != 2 or rays.shape[1] < 11:
+            raise ValueError("BakedField.render_rays: rays [N, >= 11] (o, d, near, far, viewdir)")
+        with torch.no_grad():
+            rays = rays.detach().to(torch.float32).contiguous()
+            u = None if u is None else u.detach().to(device=rays.device, dtype=torch.float32).contiguous()
+            rgb, disp, acc, depth, n_samples, stopped = hb.baked_render(self.grid._desc(), self.index, self.table, self.sh_degree, rays, u,
+                                                                        self.step_size, max_steps, self.stop_eps, white_bkgd)
+            n = rays.shape[0]
+            self.last_stats = {"rays": n, "samples": int(n_samples.sum()) if n else 0, "rays_stopped": int(stopped.sum()) if n else 0}
+        return {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "depth_map": depth}

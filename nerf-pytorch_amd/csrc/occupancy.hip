@@ -35,10 +35,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "api_util.h"
+#include "grid_device.h"     // GridArgs, sample_point, the classification, dir_norm, check_grid: shared with baked.hip
 #include "ray_device.h"
 #include "scan_device.h"       // occ_scan_kernel: the scan between the count and the write
 
 using namespace nerf_api;
+using namespace nerf_grid;
 
 namespace {
 
@@ -46,45 +48,6 @@ constexpr int OCC_THREADS = 256;                // 4 waves
 constexpr int OCC_ITERS = 4;
 constexpr int OCC_TILE = OCC_THREADS * OCC_ITERS;   // points per block
 constexpr int OCC_WAVES = OCC_THREADS / 64;
-
-struct GridArgs {
-    float lo[3], scale[3];
-    int res[3];
-    int outside_skip;
-    const unsigned* bits;
-};
-
-struct Pt { float x, y, z; };
-
-__device__ __forceinline__ Pt sample_point(const float* __restrict__ ray, float z) {
-    // run_nerf.py:381: pts = rays_o + rays_d * z_vals -- one multiply, one add (no contraction)
-    Pt p;
-    p.x = ray[0] + ray[3] * z;
-    p.y = ray[1] + ray[4] * z;
-    p.z = ray[2] + ray[5] * z;
-    return p;
-}
-
-// The classification of a point, shared by occupied() and proposal_sigma(): false outside the box, else true and the point's cell in *c
-__device__ __forceinline__ bool cell_of(const GridArgs& g, const Pt& p, unsigned* c) {
-    const float tx = (p.x - g.lo[0]) * g.scale[0];
-    const float ty = (p.y - g.lo[1]) * g.scale[1];
-    const float tz = (p.z - g.lo[2]) * g.scale[2];
-    // (a NaN fails every comparison: outside)
-    const bool inside = tx >= 0.0f && tx < (float)g.res[0] && ty >= 0.0f && ty < (float)g.res[1] && tz >= 0.0f && tz < (float)g.res[2];
-    if (!inside) return false;
-    const int ix = (int)floorf(tx), iy = (int)floorf(ty), iz = (int)floorf(tz);
-    *c = ((unsigned)ix * (unsigned)g.res[1] + (unsigned)iy) * (unsigned)g.res[2] + (unsigned)iz;
-    return true;
-}
-
-__device__ __forceinline__ bool cell_bit(const GridArgs& g, unsigned c) { return (g.bits[c >> 5] >> (c & 31u)) & 1u; }
-
-__device__ __forceinline__ bool occupied(const GridArgs& g, const Pt& p) {
-    unsigned c;
-    if (!cell_of(g, p, &c)) return g.outside_skip == 0;
-    return cell_bit(g, c);
-}
 
 // lanes below this one whose bit is set in a wave ballot
 __device__ __forceinline__ int lanes_below(unsigned long long m) {
@@ -486,7 +449,7 @@ __global__ __launch_bounds__(64) void occ_proposal_weights_kernel(GridArgs g, co
     const int lo = lane * C, hi = min(lo + C, S);
     const float* r = rays + (size_t)ray * ray_stride;
     const float* z = z_vals + (size_t)ray * S;
-    const float dn = sqrtf(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+    const float dn = dir_norm(r);
     float* s_alpha = sm;            // alpha_i
     float* s_t = sm + S;            // 1 - alpha_i + 1e-10
     float seg = 1.0f;
@@ -650,7 +613,7 @@ __global__ __launch_bounds__(MARCH_THREADS) void occ_march_walk_kernel(GridArgs 
     float r[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) r[c] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ray_in[c])));
-    const float dn = (STOP || Steps::LEVELS) ? sqrtf(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]) : 0.0f;
+    const float dn = (STOP || Steps::LEVELS) ? dir_norm(r) : 0.0f;
     Steps steps;
     ok = steps.start(a, near, far, dn) && ok;
     if (!ok) {
@@ -826,19 +789,6 @@ __global__ __launch_bounds__(CARVE_THREADS) void occ_view_carve_kernel(CarveArgs
             *out = a.accumulate ? (*out | w) : w;
         }
     }
-}
-
-int check_grid(const char* fn, const NerfOccGrid* grid, GridArgs* g) {
-    if (!grid || !grid->bits) return fail_arg(fn, "null pointer");
-    for (int a = 0; a < 3; ++a) {
-        if (grid->res[a] < 1 || grid->res[a] > 512) return fail_arg(fn, "grid resolution must be 1..512 per axis");
-        g->lo[a] = grid->lo[a];
-        g->scale[a] = grid->scale[a];
-        g->res[a] = grid->res[a];
-    }
-    g->outside_skip = grid->outside_skip != 0;
-    g->bits = grid->bits;
-    return 0;
 }
 
 inline long occ_blocks(long n_points) { return (n_points + OCC_TILE - 1) / OCC_TILE; }

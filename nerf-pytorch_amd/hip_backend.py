@@ -106,6 +106,7 @@ def _declare(lib):
         "nerf_iso_scratch_words": (sz, [i, i, i]),
         "nerf_iso_count": (i, [p, i, i, i, f, p, p, p, p]),
         "nerf_iso_emit": (i, [p, i, i, i, f, p, p, p, p, p, p, p]),
+        "nerf_baked_render": (i, [p, p, p, i, i, p, i, p, i, f, i, f, i, p, p, p, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -134,7 +135,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_occ_gather", "nerf_occ_fold_rays", "nerf_occ_density_update", "nerf_occ_ray_span", "nerf_occ_proposal_weights",
            "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march", "nerf_occ_march_stop", "nerf_occ_march_step",
            "nerf_occ_view_carve",
-           "nerf_iso_scratch_words", "nerf_iso_count", "nerf_iso_emit",
+           "nerf_iso_scratch_words", "nerf_iso_count", "nerf_iso_emit", "nerf_baked_render",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live",
            "nerf_distortion_fwd", "nerf_distortion_bwd", "nerf_interlevel_fwd", "nerf_interlevel_bwd"]
 
@@ -1489,6 +1490,44 @@ def iso_emit(volume, level, lo, step, keep_words, scratch, n_vertices, n_faces):
                                    None if keep_words is None else _words(keep_words, "keep_words"), _words(scratch, "scratch"),
                                    _ptr(vertices), faces.data_ptr(), _stream()), "nerf_iso_emit")
     return vertices, faces
+
+
+# ---- baked field (csrc/baked.hip; the user-facing object is baked.BakedField)
+BAKED_ROW_HALVES = (4, 16, 32)      # fp16 values per table row for sh_degree 0, 1, 2
+BAKED_STOPPED = 1 << 30             # the flag nerf_baked_render sets in n_samples
+
+
+def baked_render(desc, node_index, table, sh_degree, rays, u, step_size, max_steps, stop_eps=0.0, white_bkgd=False):
+    """nerf_baked_render: (rgb_map fp32 [n, 3], disp_map, acc_map, depth_map fp32 [n], n_samples int32 [n], stopped bool [n]) of rays
+    [n, >= 11] rendered from a baked field: node_index int32 [one per lattice node of the grid], table fp16 [rows, W] with row 0 zero;
+    u: fp32 [n] in [0, 1) or None (0.5); stopped: the rays whose transmittance fell below stop_eps at the end of a round"""
+    deg = int(sh_degree)
+    if deg not in (0, 1, 2):
+        raise NerfHipError(f"baked_render: sh_degree must be 0, 1 or 2, got {sh_degree!r}")
+    if rays.dim() != 2 or rays.shape[1] < 11:
+        raise NerfHipError("baked_render: rays [n, >= 11] (o, d, near, far, viewdir)")
+    n, stride = rays.shape
+    if u is not None and tuple(u.shape) != (n,):
+        raise NerfHipError("baked_render: u must hold one offset per ray")
+    nodes = (desc.res[0] + 1) * (desc.res[1] + 1) * (desc.res[2] + 1)
+    if node_index.numel() != nodes:
+        raise NerfHipError(f"baked_render: node_index holds one entry per lattice node, {nodes}")
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float16 and table.is_contiguous() and table.dim() == 2
+            and table.shape[0] >= 1 and table.shape[1] == BAKED_ROW_HALVES[deg]):
+        raise NerfHipError(f"baked_render: table must be a contiguous fp16 tensor [rows >= 1, {BAKED_ROW_HALVES[deg]}] on the GPU")
+    dev = rays.device
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    disp, acc, depth = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+    n_samples = torch.empty(n, dtype=torch.int32, device=dev)
+    if n > 0:
+        # per ray 44 B in and 28 B out; what the kept candidates gather depends on the scene and is not counted
+        with _timed("baked_render_kernel", 0.0, 72.0 * n):
+            _check(lib().nerf_baked_render(ctypes.byref(desc), _words(node_index, "node_index"), table.data_ptr(), int(table.shape[0]), deg,
+                                           _ptr(rays, "rays"), stride, _ptr(u, "u", True), n, float(step_size), int(max_steps), float(stop_eps),
+                                           int(bool(white_bkgd)), _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(depth), n_samples.data_ptr(),
+                                           _stream()), "nerf_baked_render")
+    stopped = (n_samples & BAKED_STOPPED) != 0
+    return rgb, disp, acc, depth, n_samples & (BAKED_STOPPED - 1), stopped
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

@@ -1245,10 +1245,34 @@ def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal, march_stop_e
             + (("rays_refit",) if refit else ()))
 
 
+def _render_rays_baked(ray_batch, baked, network_query_fn, perturb, white_bkgd, pytest, refused):
+    """render_rays(baked=field): the guards (`refused`: option name -> whether the call set it), the one draw, the field's own launch"""
+    from .baked import BakedField
+    if not isinstance(baked, BakedField):
+        raise ValueError(f"render_rays: baked must be None or a baked.BakedField, got {type(baked).__name__}")
+    bad = [k for k, v in refused.items() if v]
+    if bad:
+        raise ValueError(f"render_rays: baked= renders from the baked field alone and cannot be combined with {', '.join(bad)}")
+    if not _is_builtin_query(network_query_fn):
+        raise ValueError("render_rays: baked= together with a user network_query_fn: there is no network to query")
+    if ray_batch.dim() != 2 or ray_batch.shape[-1] < 11:
+        raise ValueError("render_rays: baked= needs ray records of 11 columns (o, d, near, far, viewdir: render(use_viewdirs=True))")
+    if torch.is_grad_enabled() and ray_batch.requires_grad:
+        raise ValueError("render_rays: baked= has no backward: rays that require grad are refused (render under torch.no_grad() or detach them)")
+    n = ray_batch.shape[0]
+    u = None
+    if perturb > 0.:
+        u = torch.rand(n, device=ray_batch.device)
+        if pytest:
+            np.random.seed(0)
+            u = torch.Tensor(np.random.rand(n)).to(ray_batch.device)
+    return baked.render_rays(ray_batch, u=u, white_bkgd=bool(white_bkgd))
+
+
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
                 *, randoms=None, occupancy=None, clip_to_occupancy=False, proposal=None, early_stop_eps=None, march_steps=None,
-                march_stop_eps=None, march_step_size=None, march_fit=0, distortion=False, interlevel=False):
+                march_stop_eps=None, march_step_size=None, march_fit=0, distortion=False, interlevel=False, baked=None):
     """run_nerf.py:308-418.  Same arguments, same returned dict.
 
     ``network_query_fn``: None or the function create_nerf built (builtin_query_fn) -> the fused path; ANY other callable is called
@@ -1379,7 +1403,25 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     WITHOUT a needed gradient takes the staged passes, as with ``distortion``.  render() delivers it as extras["interlevel"] with the
     rays' leading shape.  Refused with ValueError: N_importance = 0, proposal="grid" (a grid is not trained by gradients),
     proposal="march" (there is no coarse pass), a value that is not a bool.  False: nothing changes -- same launches, same bits, same
-    draws."""
+    draws.
+
+    ``baked`` (keyword-only, not in the reference): a baked.BakedField -- the rays are rendered from the field's grid of densities and
+    spherical-harmonic colours by one launch (nerf_baked_render; BakedField.render_rays_reference is the definition) and NO network is
+    touched: network_fn and network_fine may be None, N_samples / N_importance / lindisp are not read (the field marches in its own
+    step_size).  perturb > 0 draws one offset per ray with one torch.rand(N) (all steps of a ray move together; 0.5 without);
+    white_bkgd is honoured.  The dict holds exactly rgb_map, disp_map, acc_map and depth_map; the field's last_stats = {"rays",
+    "samples", "rays_stopped"}.  Inference only: refused with ValueError, before anything reaches the library, together with
+    occupancy, clip_to_occupancy, proposal, early_stop_eps, the march options, distortion, interlevel, retraw, randoms,
+    raw_noise_std > 0, a user network_query_fn, and -- in grad mode -- rays that require grad (there is no backward).  Clipping stays
+    possible by hand: baked.grid.clip_rays(rays)[0].  None: nothing changes -- same launches, same bits, same draws."""
+    if baked is not None:
+        return _render_rays_baked(ray_batch, baked, network_query_fn, perturb, white_bkgd, pytest,
+                                  dict(retraw=bool(retraw), raw_noise_std=raw_noise_std > 0., randoms=randoms is not None,
+                                       occupancy=occupancy is not None, clip_to_occupancy=bool(clip_to_occupancy), proposal=proposal is not None,
+                                       early_stop_eps=early_stop_eps is not None, march_steps=march_steps is not None,
+                                       march_stop_eps=march_stop_eps is not None, march_step_size=march_step_size is not None,
+                                       march_fit=not (march_fit is None or (isinstance(march_fit, (int, np.integer)) and int(march_fit) == 0)),
+                                       distortion=distortion is not False, interlevel=interlevel is not False))
     if not isinstance(distortion, (bool, np.bool_)):
         raise ValueError(f"render_rays: distortion must be a bool, got {distortion!r}")
     distortion = bool(distortion)
@@ -1523,7 +1565,7 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """run_nerf.py:54-66.  Injected ``randoms`` (one row per ray) are sliced with the rays, so a chunked call consumes
     the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks (with ``clip_to_occupancy``
     its "rays_hit" / "rays" too, with ``early_stop_eps`` its "rays_stopped", with ``proposal="march"`` its "rays_truncated" and with
-    ``march_stop_eps`` its "rays_stopped", with ``march_fit`` > 0 its "rays_refit")."""
+    ``march_stop_eps`` its "rays_stopped", with ``march_fit`` > 0 its "rays_refit"); so are a ``baked`` field's."""
     all_ret = {}
     randoms = kwargs.pop("randoms", None)
     occ = kwargs.get("occupancy")
@@ -1534,16 +1576,22 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
         for k, v in randoms.items():
             if v.shape[0] != rays_flat.shape[0]:
                 raise ValueError(f"randoms[{k!r}] has {v.shape[0]} rows for {rays_flat.shape[0]} rays")
+    baked = kwargs.get("baked")
+    baked_stats = dict.fromkeys(("rays", "samples", "rays_stopped"), 0)
     for i in range(0, rays_flat.shape[0], chunk):
         if randoms is not None:
             kwargs["randoms"] = {k: v[i:i + chunk] for k, v in randoms.items()}
         ret = render_rays(rays_flat[i:i + chunk], **kwargs)
         if occ is not None and occ.last_stats is not None:
             occ_stats = {k: occ_stats[k] + occ.last_stats[k] for k in occ_stats}
+        if baked is not None:
+            baked_stats = {k: baked_stats[k] + baked.last_stats[k] for k in baked_stats}
         for k in ret:
             all_ret.setdefault(k, []).append(ret[k])
     if occ is not None:
         occ.last_stats = occ_stats
+    if baked is not None:
+        baked.last_stats = baked_stats
     return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in all_ret.items()}
 
 
@@ -1595,7 +1643,10 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
         c2w = None
     if c2w is not None:
         net = kwargs.get("network_fn")
-        dev = next(net.parameters()).device if net is not None else (c2w.device if isinstance(c2w, torch.Tensor) else None)
+        if net is None and kwargs.get("baked") is not None:     # no network: the rays are built where the baked field lives
+            dev = kwargs["baked"].device
+        else:
+            dev = next(net.parameters()).device if net is not None else (c2w.device if isinstance(c2w, torch.Tensor) else None)
         rays = hb.make_rays(H, W, K, c2w, c2w_staticcam, ndc, near, far, dev)
         sh = (H, W, 3)
     elif (not geo_grad and c2w_staticcam is None and isinstance(rays[0], torch.Tensor) and rays[0].is_cuda
