@@ -398,7 +398,11 @@ int nerf_render_rays_bwd(const NerfRenderCfg* cfg, const float* packed_c, const 
  *   nerf_dense_fwd    : y[P,N] (+)= x[P,K] w[N,K]^T (+ bias) (then ReLU)               = F.linear (+ F.relu), helpers:99-100
  *   nerf_dense_dgrad  : dx[P,K] (+)= dy[P,N] w[N,K]; then dx *= (act > 0) if act       (act = post-ReLU output of the layer below)
  *   nerf_dense_wgrad  : dw[N,K] (+)= dy^T x; dbias[N] (+)= column sums of dy (deterministic two-pass sum; scratch of
- *                       nerf_dense_wgrad_scratch_floats(P, N) floats) */
+ *                       nerf_dense_wgrad_scratch_floats(P, N) floats)
+ * The empty batch (P == 0, n_rays == 0) is a valid call and returns 0: the row operands (x, y, dy, dx, act, scratch; rays, z_vals)
+ * are not touched and may be NULL, as the data pointer of an empty tensor is; sizes and leading dimensions are still checked, and
+ * w / dw must be given.  nerf_dense_wgrad then writes what a sum over no rows is: with accumulate = 0 zeros into dw's N x K range
+ * (honouring lddw) and into dbias, on `stream`; with accumulate = 1 nothing. */
 int nerf_build_inputs(const float* rays, int ray_stride, const float* z_vals, int n_rays, int n_samples, int multires, int multires_views,
                       int use_viewdirs, float* x, int ldx, void* stream);
 int nerf_dense_fwd(const float* x, int ldx, int K, const float* w, int ldw, const float* bias, float* y, int ldy, int N, long P,

@@ -92,6 +92,14 @@ __global__ void colsum_final_kernel(const float* __restrict__ partial, int n_blo
     db[n] = accumulate ? db[n] + s : s;
 }
 
+// zeros into a [rows, cols] range of a row-major matrix with leading dimension ld (the weight gradient of an empty batch)
+__global__ void zero_fill_kernel(float* __restrict__ a, int ld, int cols, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long r = i / cols;
+    a[r * ld + (i - r * cols)] = 0.0f;
+}
+
 // ---- network input: row p = (ray r, sample j) of x = [enc(o + d z) | enc(viewdir)] (run_nerf.py:381, :41-47)
 __device__ inline void encode3(float* out, float v0, float v1, float v2, int L) {
     out[0] = v0; out[1] = v1; out[2] = v2;
@@ -145,9 +153,10 @@ extern "C" {
 
 int nerf_dense_fwd(const float* x, int ldx, int K, const float* w, int ldw, const float* bias, float* y, int ldy, int N, long P,
                    int accumulate, int relu, void* stream) {
-    if (!x || !w || !y) return fail_arg(__func__, "null pointer");
+    if (!w) return fail_arg(__func__, "null pointer");
     if (check_dims(__func__, P, K, N) || ldx < K || ldw < K || ldy < N) return fail_arg(__func__, "bad size / leading dimension");
-    if (P == 0) return 0;
+    if (P == 0) return 0;        // no rows: x and y are not read (an empty tensor's data pointer is null)
+    if (!x || !y) return fail_arg(__func__, "null pointer");
     const RocBlas& rb = rocblas();
     if (!rb.h) return fail_arg(__func__, rb.error);
     hipStream_t st = (hipStream_t)stream;
@@ -159,9 +168,10 @@ int nerf_dense_fwd(const float* x, int ldx, int K, const float* w, int ldw, cons
 
 int nerf_dense_dgrad(const float* dy, int lddy, int N, const float* w, int ldw, float* dx, int lddx, int K, long P, int accumulate,
                      const float* act, int ldact, void* stream) {
-    if (!dy || !w || !dx) return fail_arg(__func__, "null pointer");
+    if (!w) return fail_arg(__func__, "null pointer");
     if (check_dims(__func__, P, K, N) || lddy < N || ldw < K || lddx < K || (act && ldact < K)) return fail_arg(__func__, "bad size / leading dimension");
-    if (P == 0) return 0;
+    if (P == 0) return 0;        // no rows: dy, dx and act are not read
+    if (!dy || !dx) return fail_arg(__func__, "null pointer");
     const RocBlas& rb = rocblas();
     if (!rb.h) return fail_arg(__func__, rb.error);
     hipStream_t st = (hipStream_t)stream;
@@ -178,13 +188,19 @@ size_t nerf_dense_wgrad_scratch_floats(long P, int N) {
 
 int nerf_dense_wgrad(const float* dy, int lddy, int N, const float* x, int ldx, int K, long P, float* dw, int lddw, float* dbias,
                      float* scratch, int accumulate, void* stream) {
-    if (!dy || !x || !dw) return fail_arg(__func__, "null pointer");
+    if (!dw) return fail_arg(__func__, "null pointer");
     if (check_dims(__func__, P, K, N) || lddy < N || ldx < K || lddw < K) return fail_arg(__func__, "bad size / leading dimension");
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 0) {        // no rows: dy, x and scratch are not read; the sums over nothing are zeros (accumulate: dw / dbias stay)
+        if (accumulate) return 0;
+        hipLaunchKernelGGL(zero_fill_kernel, dim3(blocks_for((long)N * K)), dim3(256), 0, st, dw, lddw, K, (long)N * K);
+        if (dbias) hipLaunchKernelGGL(zero_fill_kernel, dim3(blocks_for(N)), dim3(256), 0, st, dbias, N, N, (long)N);
+        return done(__func__, hipGetLastError());
+    }
+    if (!dy || !x) return fail_arg(__func__, "null pointer");
     if (dbias && !scratch) return fail_arg(__func__, "the bias gradient needs nerf_dense_wgrad_scratch_floats(P, N) floats of scratch");
-    if (P == 0) return 0;
     const RocBlas& rb = rocblas();
     if (!rb.h) return fail_arg(__func__, rb.error);
-    hipStream_t st = (hipStream_t)stream;
     // row-major dw[N,K] = dy[P,N]^T x[P,K]  ==  column-major dw^T (K x N, ld lddw) = x^T (K x P, ld ldx) * (dy^T (N x P, ld lddy))^T
     if (gemm(rb, st, RB_OP_N, RB_OP_T, K, N, (int)P, x, ldx, dy, lddy, accumulate ? 1.0f : 0.0f, dw, lddw) != 0) return fail_arg(__func__, "rocblas_sgemm failed");
     if (dbias) {
@@ -197,12 +213,12 @@ int nerf_dense_wgrad(const float* dy, int lddy, int N, const float* x, int ldx, 
 
 int nerf_build_inputs(const float* rays, int ray_stride, const float* z_vals, int n_rays, int n_samples, int multires, int multires_views,
                       int use_viewdirs, float* x, int ldx, void* stream) {
-    if (!rays || !z_vals || !x) return fail_arg(__func__, "null pointer");
     const int cx = multires < 0 ? 3 : 3 + 6 * multires, cd = !use_viewdirs ? 0 : (multires_views < 0 ? 3 : 3 + 6 * multires_views);
     if (n_rays < 0 || n_samples <= 0 || multires > 24 || multires_views > 24 || ldx < cx + cd ||
         ray_stride < (use_viewdirs ? 11 : 8)) return fail_arg(__func__, "bad size (rays: o3 d3 near far [viewdir3])");
     const long P = (long)n_rays * n_samples;
-    if (P == 0) return 0;
+    if (P == 0) return 0;        // no rays: nothing is read or written
+    if (!rays || !z_vals || !x) return fail_arg(__func__, "null pointer");
     hipLaunchKernelGGL(build_inputs_kernel, dim3(blocks_for(P)), dim3(256), 0, (hipStream_t)stream, rays, ray_stride, z_vals, P, n_samples,
                        multires, multires_views, use_viewdirs, x, ldx);
     return done(__func__, hipGetLastError());

@@ -13,6 +13,8 @@ import torch.nn as nn
 
 from . import hip_backend as hb
 
+QUERY_SLICE_POINTS = 1 << 20        # sample points per slice of a DenseNeRF.query without gradients
+
 
 def _cols(t, lo, width):
     """(data pointer of column `lo`, leading dimension) of a row-major 2-D tensor"""
@@ -189,7 +191,7 @@ class DenseNeRF(nn.Module):
         n, S = z_vals.shape
         # without gradients nothing has to outlive a layer: bound the transient activations (D + 2 arrays of P x W floats) by
         # evaluating ~2^20 points at a time -- what the reference's netchunk does (run_nerf.py:27-34; results do not depend on it)
-        rays_per_slice = max(1, (1 << 20) // max(S, 1))
+        rays_per_slice = max(1, QUERY_SLICE_POINTS // max(S, 1))
         if n > rays_per_slice and not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             return torch.cat([self.query(rays[i:i + rays_per_slice].contiguous(), z_vals[i:i + rays_per_slice].contiguous())
                               for i in range(0, n, rays_per_slice)], 0)
@@ -209,6 +211,29 @@ def _freqs_of(ch):
     return (ch - 3) // 6
 
 
+def _render_no_rays(cfg, rays, model_c, model_f):
+    """render_rays_dense for an empty batch: the per-ray kernels have nothing to launch, but the networks still see their (empty)
+    inputs, so the outputs stay in the graph as the reference's do and a backward leaves exact zeros in every used parameter."""
+    n_c, n_f, dev = cfg["N_samples"], cfg["N_importance"], rays.device
+    empty = torch.zeros(0, dtype=torch.float32, device=dev)
+
+    def one_pass(model, S):
+        raw = model.query(rays, torch.zeros((0, S), dtype=torch.float32, device=dev))
+        return raw[..., :3].sum(1), raw[..., 3].sum(1), raw[..., 3].sum(1), raw
+    rgb, disp, acc, raw = one_pass(model_c, n_c)
+    ret = {}
+    if n_f > 0:
+        ret.update(rgb0=rgb, disp0=disp, acc0=acc)
+        rgb, disp, acc, raw = one_pass(model_c if model_f is None else model_f, n_c + n_f)
+        ret["z_std"] = empty
+    ret.update(rgb_map=rgb, disp_map=disp, acc_map=acc, raw=raw)
+    if cfg.get("distortion", False):
+        ret["distortion"] = empty
+    if cfg.get("interlevel", False):
+        ret["interlevel"] = empty
+    return ret
+
+
 def render_rays_dense(cfg, rays, rnd, model_c, model_f):
     """run_nerf.py:351-412 for DenseNeRF networks: the same per-ray kernels as the fused path around DenseNeRF.query; autograd
     through the compositing (render._Composite) and the layer stack (_DenseMLP).  Returns the reference's dict."""
@@ -217,6 +242,8 @@ def render_rays_dense(cfg, rays, rnd, model_c, model_f):
     std, wb, dev = cfg["raw_noise_std"], cfg["white_bkgd"], rays.device
     if model_c.use_viewdirs and rays.shape[1] < 11:
         raise ValueError("render_rays: a network with view directions needs ray records with 11 columns")
+    if rays.shape[0] == 0:
+        return _render_no_rays(cfg, rays, model_c, model_f)
     rays_d = rays[:, 3:6].contiguous()
     z = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
     raw = model_c.query(rays, z)

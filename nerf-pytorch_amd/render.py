@@ -1456,6 +1456,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     n = rays.shape[0]
     dev = rays.device
     n_f = int(N_importance)
+    if n == 0 and dense and occupancy is None and _is_builtin_query(network_query_fn):
+        # general networks: the dense path's own keys and order, outputs attached to the networks (dense._render_no_rays)
+        from .dense import render_rays_dense
+        ret = render_rays_dense(dict(N_samples=int(N_samples), N_importance=n_f, raw_noise_std=0., white_bkgd=bool(white_bkgd),
+                                     distortion=distortion, interlevel=interlevel), rays, {}, network_fn, network_fine if n_f > 0 else None)
+        if not retraw:
+            ret.pop("raw")
+        return ret
     if n == 0:      # empty batch: the reference returns empty tensors of the right trailing shapes
         e = lambda *tail: torch.zeros((0,) + tail, dtype=torch.float32, device=dev)
         outs = (e(3), e(), e(), e(N_samples + max(n_f, 0) if march else N_samples + n_f, 4))
