@@ -33,6 +33,29 @@ extern "C" {
 #define NERF_E_BADARG (-1)      /* null pointer / non-positive size / unsupported shape */
 #define NERF_E_UNSUPPORTED (-2) /* configuration outside the fixed architecture */
 
+/* ---- THE DATAPATH TABLE.  Everything below runs on one of four training datapaths, plus one inference form of the third.  Each
+ * family of entry points names them by an integer code of its own; this is every code there is ("-": the family has no such form).
+ *
+ *                          fp32          bf16x3        fp16x3        fp16x3w            fp16_fp8c (inference form of fp16x3)
+ *   products               exact fp32    3 x bf16      3 x fp16      3 x fp16           fp16 main + 2 x fp8 corrections
+ *   `split`   forward      - (a)         0             1             5 (b)              2, 3 = last sample left out; act NULL
+ *             dgrad        - (a)         0             1             5                  -
+ *             repack       - (a)         0             1             1                  2 (nerf_pack_params_split only)
+ *   `datapath` wgrad (c)   0             4             5             6                  -
+ *   `datapath` sizes (d)   0             1             1             2                  -
+ *   `family`   layout (d)  0             1             1             2                  -
+ *   NerfRenderCfg.precision 0            1             3             5                  -
+ *   act kind    (e)        0             4             5             6                  -
+ *   delta kind  (e)        0             2             3             4                  -
+ *
+ *   (a) the entry points without `split`: nerf_pack_params, nerf_field_fwd, nerf_field_bwd / _dgrad / _wgrad
+ *   (b) with act = NULL the launch is split 1's
+ *   (c) nerf_field_wgrad_phase[_live]; -1 = as recorded for the act / delta pair
+ *   (d) nerf_*_floats_dp, nerf_debug_layout: 0 fp32 rows, 1 tiles of 16-bit elements, 2 hi + lo tiles (two-word saves)
+ *   (e) what nerf_buffer_layout returns for a save buffer / a delta buffer that datapath's forward / dgrad wrote
+ * A dgrad reads the save buffer of a forward of its own column; bf16x3 and fp16x3 may read each other's (the same tiles), but the
+ * weight gradient then refuses the mixed pair.  Any other code is NERF_E_BADARG (the size functions return 0). */
+
 int nerf_abi_version(void);
 const char* nerf_last_error(void);
 
@@ -122,9 +145,9 @@ size_t nerf_act_floats(int n_rays, int n_samples);
  * owns this memory (persistent across steps; any datapath); 0 when training == 0 -- inference needs no scratch.
  * = nerf_act_floats(coarse) + nerf_act_floats(fine) + nerf_delta_floats(larger) + nerf_wgrad_partial_floats(larger). */
 size_t nerf_workspace_floats(int n_rays, int n_coarse, int n_fine, int training);
-/* The same three sizes for ONE datapath (ABI v9).  datapath: 0 = exact fp32 (fp32 rows, 10.6 KB / point each way), 1 = the split
- * datapaths (16-bit tiles of either type, 4.8 / 4.4 KB / point), 2 (ABI v10) = the fp16 split with TWO-WORD saves (hi and lo words:
- * twice datapath 1); the two-argument forms above return the larger of datapaths 0 and 1, i.e. a buffer either of those may write.  A caller that knows its datapath keeps ~2.2x more rays resident per GB of HBM with these:
+/* The same three sizes for ONE datapath (ABI v9; `datapath`: the sizes row of the datapath table -- 10.6 KB / point each way on
+ * fp32 rows, 4.8 / 4.4 KB on 16-bit tiles, twice that with two-word saves); the two-argument forms above return the larger of 0
+ * and 1, i.e. a buffer either of those may write.  A caller that knows its datapath keeps ~2.2x more rays resident per GB of HBM with these:
  * the 32,768-ray batch of BASELINE configs[3] holds ~40 GB of saved activations on the split datapaths instead of ~90 GB. */
 size_t nerf_act_floats_dp(int n_rays, int n_samples, int datapath);
 size_t nerf_delta_floats_dp(int n_rays, int n_samples, int datapath);
@@ -230,24 +253,21 @@ int nerf_field_wgrad(const float* act, const float* delta, const float* d_raw, i
  *   Kernels: 16 points per wavefront at 2 waves / SIMD, weights through a 17-slot LDS ring of 8 KiB fragment units (csrc/field_ring.h);
  * the delta chain 32 points per wavefront on the same ring.  The save buffers hold 16-bit elements in tiles (rows of the 256- /
  * 128-wide regions in 16-point tiles, row16h order; deltas and encodings in 32-point feature-major tiles; csrc/nerf_common.h), the
- * ReLU bitmask words are in these kernels' lane order: forward, dgrad and weight gradients of one evaluation must use the same
- * split (nerf_field_wgrad_phase(datapath = -1) picks the GEMM from the buffer records: 4 = bf16 operands, 5 = fp16 operands).
+ * ReLU bitmask words are in these kernels' lane order: forward, dgrad and weight gradients of one evaluation must use the same split.
  *   Range (split = 1): weights, encodings and activations must stay below 65520 in magnitude (a NeRF's are O(1..100)); an overflow
  * turns into inf / NaN in `raw` (the ReLU propagates NaN).  Deltas are tiny (upstream gradients ~1e-6): nerf_field_dgrad_split(split
  * = 1) first reduces max|d_raw| on the device and runs the chain on s * d_raw with s the power of two that puts that maximum in
  * [16, 32) (the chain is linear; the maximum lives in the delta buffer), every stored delta and partial weight gradient carries s, and
  * the reduction phase of nerf_field_wgrad_phase multiplies by 1/s -- exact.  A non-finite d_raw propagates to the gradient.
- *   split = 5 (ABI v10, "fp16x3w"; nerf_field_fwd_split with act, nerf_field_dgrad_split): the fp16 split with TWO-WORD saves -- the
- * forward and the delta chain store the lo words (T(v - hi)) next to the hi words (mirror regions at ActLayout3::lo /
- * DeltaLayout3::lo; buffers of nerf_act_floats_dp / nerf_delta_floats_dp(datapath = 2) floats), and the weight-gradient GEMM
- * (nerf_field_wgrad_phase datapath 6) contracts  d_hi^T X_hi + d_hi^T X_lo + d_lo^T X_hi : the products of the forward's class
- * (~2^-22) instead of 11-bit operands, at twice the saved bytes and three times the GEMM's MFMAs.  Same packed3 as split = 1.  Not
- * the default: it prices and bounds what the one-word operand storage costs the gradients.
+ *   split = 5 (ABI v10, "fp16x3w"): the fp16 split with TWO-WORD saves -- the forward and the delta chain store the lo words
+ * (T(v - hi)) next to the hi words (mirror regions at ActLayout3::lo / DeltaLayout3::lo), and the weight-gradient GEMM contracts
+ * d_hi^T X_hi + d_hi^T X_lo + d_lo^T X_hi : the products of the forward's class (~2^-22) instead of 11-bit operands, at twice the saved
+ * bytes and three times the GEMM's MFMAs.  Not the default: it prices and bounds what the one-word operand storage costs the gradients.
  * Replace run_nerf.py:37-51 + run_nerf_helpers.py:15-45, :96-119 and their autograd like nerf_field_fwd / nerf_field_bwd. */
 int nerf_packed3_floats(void);
 int nerf_pack_params_split(const float* params, float* packed3, int streams, int split, void* stream);
 /* the repack of TWO networks (a training step's coarse and fine network after the optimizer step) in the same two launches as one
- * (ABI v9; split 0 / 1; results identical to two nerf_pack_params_split calls) */
+ * (ABI v9; results identical to two nerf_pack_params_split calls) */
 int nerf_pack_params_split_pair(const float* params_a, float* packed3_a, const float* params_b, float* packed3_b, int streams,
                                 int split, void* stream);
 int nerf_field_fwd_split(const float* packed3, const float* rays, int ray_stride, const float* z_vals, int n_rays,
@@ -293,13 +313,12 @@ int nerf_field_fwd_last_sample(const float* packed3, const float* rays, int ray_
  *     ray / sample count, or an (act, delta) pair that no datapath contracts -- instead of computing garbage;
  *   - nerf_field_wgrad_phase(datapath = -1) takes the datapath from the record.
  * Buffers the library has not written (copies, foreign producers) are not checked.
- * nerf_buffer_layout: the recorded kind, or -1 for an unknown buffer.  act: 0 fp32 point-major rows (nerf_field_fwd), 4 / 5 = rows
- * in 16-point tiles of bf16 / fp16 (nerf_field_fwd_split(split = 0 / 1)), 6 = fp16 hi + lo rows (split = 5); delta (*is_delta = 1):
- * 0 fp32 rows, 2 / 3 = 32-point tiles of bf16 / fp16, 4 = fp16 hi + lo tiles (split = 5). */
+ * nerf_buffer_layout: the recorded kind (the act kind / delta kind rows of the datapath table; *is_delta says which), or -1 for an
+ * unknown buffer.  Save buffers hold point-major rows (fp32) or 16-point tiles, delta buffers rows or 32-point tiles. */
 int nerf_buffer_layout(const float* buf, int* is_delta, int* n_rays, int* n_samples);
 /* test hook (host only): where the regions of such a buffer start, in floats from its base, for n_rays x n_samples points.
- * family 0 = fp32 point-major rows, 1 = the split datapaths' tiles of 16-bit elements, 2 = the same with two-word saves (the offsets
- * of family 1 plus [15] = offset of the mirror that holds the lo words; [14] total = twice family 1's).  out_host[16]:
+ * family: the layout row of the datapath table (2 = the offsets of family 1 plus [15] = offset of the mirror that holds the lo
+ * words; [14] total = twice family 1's).  out_host[16]:
  *   save buffer  (is_delta = 0): [0..7] post-ReLU rows of trunk layers 0..7, [8] feature (fp32 rows only; the split datapaths fold
  *                that layer and use the slot as the dump tile of out-of-range waves), [9] view branch, [10] xyz encoding,
  *                [11] direction encoding per ray, [12] its per-point / per-ray-record expansion, [13] ReLU bitmasks, [14] total;
@@ -313,8 +332,7 @@ int nerf_debug_layout(int n_rays, int n_samples, int family, int is_delta, long 
  * Calling it with phases 1, 2, 4 in that order equals one call with 7. */
 int nerf_field_wgrad_phase(const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
                            float* partial, float* grad, int accumulate,
-                           int datapath /* -1 as recorded for act / delta (above); 0 fp32; 4 bf16 operands; 5 fp16 operands;
-                                           6 fp16 two-word operands (split = 5 buffers) */,
+                           int datapath /* the wgrad row of the datapath table; -1 as recorded for act / delta (above) */,
                            int phases, const float* params /* canonical parameters; may be NULL for datapath 0 */,
                            void* stream);
 /* ---- dead-tile skipping in the backward of the split datapaths (additive entry points; ABI version unchanged).
@@ -348,9 +366,8 @@ int nerf_field_wgrad_phase_live(const float* act, const float* delta, const floa
  * outputs, and ONE scratch buffer of nerf_render_workspace_floats() floats that lives from the forward to its backward
  * (depths, coarse raw, compositing weights; when training also the saved activations, deltas and partial gradients: ~9.2 KB
  * per sample point on the split datapaths, ~21 KB on fp32 -- split larger ray batches, the reference's `chunk` argument does exactly that).
- *   precision 0: exact fp32 datapath; 1: split-bf16; 3: split-fp16 (packed buffers from nerf_pack_params_split with the
- *   matching split; 16-bit operand storage of the weight-gradient GEMM either way); 5: split-fp16 with two-word saves and the
- *   three-term weight-gradient GEMM (packed buffers of split 1; workspace of nerf_render_workspace_floats for THIS cfg).
+ *   precision: the NerfRenderCfg row of the datapath table (packed buffers from that column's repack; workspace of
+ *   nerf_render_workspace_floats for THIS cfg).
  *   Backward with accumulate = 0: every gradient vector handed in is written -- a network whose pass received no upstream
  *   gradient gets zeros; d_disp / d_acc may be given without d_rgb.
  *   packed_f / params_f / grad_f NULL (or packed_f == packed_c): the fine pass uses the coarse network (network_fine None).
@@ -362,7 +379,7 @@ typedef struct NerfRenderCfg {
     int n_coarse, n_fine;          /* N_samples, N_importance */
     int lindisp, white_bkgd;
     float raw_noise_std;
-    int precision;                 /* 0 fp32, 1 split-bf16, 3 split-fp16, 5 split-fp16 with two-word saves */
+    int precision;                 /* the datapath table's NerfRenderCfg.precision row: 0, 1, 3, 5 */
     int reserved;                  /* (round 3: operand storage switch; ignored) */
 } NerfRenderCfg;
 size_t nerf_render_workspace_floats(const NerfRenderCfg* cfg, int n_rays, int training);

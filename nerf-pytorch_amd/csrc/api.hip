@@ -9,8 +9,6 @@
 #include "nerf_common.h"
 #include "api_util.h"
 
-#include "launchers.h"
-
 using nerf_api::done;
 using nerf_api::fail_arg;
 
@@ -21,7 +19,7 @@ static std::unordered_map<const void*, BufTag> g_tags;
 
 static unsigned long g_tag_seq = 0;
 
-void tag_record(const void* buf, int is_delta, int kind, int n_rays, int n_samples) {
+void tag_record(const void* buf, int is_delta, Datapath dp, int n_rays, int n_samples) {
     if (!buf) return;
     std::lock_guard<std::mutex> lock(g_tag_mutex);
     // a training loop re-uses a handful of buffers; the bound only limits leaks.  Eviction is by AGE (the 2048 most recently
@@ -30,7 +28,7 @@ void tag_record(const void* buf, int is_delta, int kind, int n_rays, int n_sampl
     if (g_tags.size() > 4096)
         for (auto it = g_tags.begin(); it != g_tags.end();)
             it = (g_tag_seq - it->second.seq > 2048) ? g_tags.erase(it) : std::next(it);
-    g_tags[buf] = BufTag{is_delta, kind, n_rays, n_samples, ++g_tag_seq};
+    g_tags[buf] = BufTag{is_delta, dp, n_rays, n_samples, ++g_tag_seq};
 }
 bool tag_lookup(const void* buf, BufTag* out) {
     std::lock_guard<std::mutex> lock(g_tag_mutex);
@@ -39,26 +37,32 @@ bool tag_lookup(const void* buf, BufTag* out) {
     *out = it->second;
     return true;
 }
-int datapath_of(int act_kind, int delta_kind) {
-    if (act_kind == ACT_ROWS_F32 && delta_kind == DELTA_ROWS_F32) return 0;
-    if (act_kind == ACT_TILE16_BF16 && delta_kind == DELTA_TILE32_BF16) return 4;
-    if (act_kind == ACT_TILE16_F16 && delta_kind == DELTA_TILE32_F16) return 5;
-    if (act_kind == ACT_TILE16_F16X2 && delta_kind == DELTA_TILE32_F16X2) return 6;
-    return -1;
+size_t act_floats(int n_rays, int n_samples, Datapath dp) {
+    if (n_rays <= 0 || n_samples <= 0) return 0;
+    const size_t P = (size_t)n_rays * n_samples;
+    const DatapathDesc& d = nerf::desc(dp);
+    return d.split ? nerf::act_layout3(P, (size_t)n_rays, d.two_word).total : nerf::act_layout(P, (size_t)n_rays).total;
+}
+size_t delta_floats(int n_rays, int n_samples, Datapath dp) {
+    if (n_rays <= 0 || n_samples <= 0) return 0;
+    const size_t P = (size_t)n_rays * n_samples;
+    const DatapathDesc& d = nerf::desc(dp);
+    return d.split ? nerf::delta_layout3(P, d.two_word).total : nerf::delta_layout(P).total;
 }
 
-// the save buffer a dgrad is about to read: written by a forward of the same family (fp32 rows vs split-bf16 tiles: the
-// ReLU bitmasks differ) for the same point count?  0 = fine / unknown buffer
-static int check_act_for_dgrad(const char* fn, const void* act, bool split_bf16, int n_rays, int n_samples, int two_word = -1) {
+// the save buffer dp's dgrad is about to read: written by a forward of the same family (fp32 rows vs split tiles: the ReLU
+// bitmasks differ; one-word vs two-word saves) for the same point count?  0 = fine / unknown buffer
+static int check_act_for_dgrad(const char* fn, const void* act, Datapath dp, int n_rays, int n_samples) {
     BufTag t;
     if (!tag_lookup(act, &t)) return 0;
     if (t.is_delta) return fail_arg(fn, "`act` is a buffer this library last wrote DELTAS into");
-    if (two_word >= 0 && (t.kind == ACT_TILE16_F16X2) != (two_word == 1))
+    const DatapathDesc &d = nerf::desc(dp), &a = nerf::desc(t.dp);
+    if (d.split && a.two_word != d.two_word)
         return fail_arg(fn, "`act` and this dgrad disagree about two-word saves (split = 5 on both the forward and the dgrad, or on neither): "
                             "the three-term weight-gradient GEMM contracts the lo deltas with the lo rows only a split = 5 forward saved");
-    if ((t.kind != ACT_ROWS_F32) != split_bf16)
-        return fail_arg(fn, split_bf16 ? "`act` was saved by the exact-fp32 forward (point-major rows, fp32 bitmask order): not readable by a split datapath's dgrad"
-                                       : "`act` was saved by a split datapath's forward (tiles, its bitmask order): not readable by the fp32 dgrad");
+    if (a.split != d.split)
+        return fail_arg(fn, d.split ? "`act` was saved by the exact-fp32 forward (point-major rows, fp32 bitmask order): not readable by a split datapath's dgrad"
+                                    : "`act` was saved by a split datapath's forward (tiles, its bitmask order): not readable by the fp32 dgrad");
     if (t.n_rays != n_rays || t.n_samples != n_samples) {
         snprintf(g_err, sizeof(g_err), "%s: `act` was saved for %d rays x %d samples, this call says %d x %d", fn, t.n_rays, t.n_samples, n_rays, n_samples);
         return NERF_E_BADARG;
@@ -183,21 +187,19 @@ int nerf_sample_coarse(const float* rays, int ray_stride, int n_rays, const floa
 }
 
 size_t nerf_act_floats_dp(int n_rays, int n_samples, int datapath) {
-    if (n_rays <= 0 || n_samples <= 0 || datapath < 0 || datapath > 2) return 0;
-    const size_t P = (size_t)n_rays * n_samples;
-    return datapath == 0 ? nerf::act_layout(P, (size_t)n_rays).total : nerf::act_layout3(P, (size_t)n_rays, datapath == 2).total;
+    Datapath dp;
+    return decode_family(datapath, &dp) ? act_floats(n_rays, n_samples, dp) : 0;
 }
 size_t nerf_delta_floats_dp(int n_rays, int n_samples, int datapath) {
-    if (n_rays <= 0 || n_samples <= 0 || datapath < 0 || datapath > 2) return 0;
-    const size_t P = (size_t)n_rays * n_samples;
-    return datapath == 0 ? nerf::delta_layout(P).total : nerf::delta_layout3(P, datapath == 2).total;
+    Datapath dp;
+    return decode_family(datapath, &dp) ? delta_floats(n_rays, n_samples, dp) : 0;
 }
 size_t nerf_act_floats(int n_rays, int n_samples) {       // a buffer either datapath may write
-    const size_t a = nerf_act_floats_dp(n_rays, n_samples, 0), b = nerf_act_floats_dp(n_rays, n_samples, 1);
+    const size_t a = act_floats(n_rays, n_samples, Datapath::F32), b = act_floats(n_rays, n_samples, Datapath::BF16X3);
     return a > b ? a : b;
 }
 size_t nerf_delta_floats(int n_rays, int n_samples) {
-    const size_t a = nerf_delta_floats_dp(n_rays, n_samples, 0), b = nerf_delta_floats_dp(n_rays, n_samples, 1);
+    const size_t a = delta_floats(n_rays, n_samples, Datapath::F32), b = delta_floats(n_rays, n_samples, Datapath::BF16X3);
     return a > b ? a : b;
 }
 size_t nerf_wgrad_partial_floats(int n_rays, int n_samples) {
@@ -212,36 +214,36 @@ size_t nerf_workspace_floats(int n_rays, int n_coarse, int n_fine, int training)
            nerf_delta_floats(n_rays, s_big) + nerf_wgrad_partial_floats(n_rays, s_big);
 }
 size_t nerf_workspace_floats_dp(int n_rays, int n_coarse, int n_fine, int training, int datapath) {
-    if (!training || n_rays <= 0 || n_coarse <= 0 || n_fine < 0 || datapath < 0 || datapath > 2) return 0;
+    Datapath dp;
+    if (!training || n_rays <= 0 || n_coarse <= 0 || n_fine < 0 || !decode_family(datapath, &dp)) return 0;
     const int s_big = n_coarse + n_fine;
-    return nerf_act_floats_dp(n_rays, n_coarse, datapath) + (n_fine > 0 ? nerf_act_floats_dp(n_rays, s_big, datapath) : 0) +
-           nerf_delta_floats_dp(n_rays, s_big, datapath) + nerf_wgrad_partial_floats(n_rays, s_big);
+    return act_floats(n_rays, n_coarse, dp) + (n_fine > 0 ? act_floats(n_rays, s_big, dp) : 0) +
+           delta_floats(n_rays, s_big, dp) + nerf_wgrad_partial_floats(n_rays, s_big);
 }
 
 int nerf_debug_layout(int n_rays, int n_samples, int family, int is_delta, long long* out_host) {
     REQUIRE(out_host, "null pointer");
-    REQUIRE(n_rays > 0 && n_samples > 0 && family >= 0 && family <= 2, "bad size / family (0 fp32 rows, 1 split tiles, 2 split tiles with two-word saves)");
+    Datapath dp;
+    REQUIRE(n_rays > 0 && n_samples > 0 && decode_family(family, &dp), "bad size / family (0 fp32 rows, 1 split tiles, 2 split tiles with two-word saves)");
+    const DatapathDesc& d = nerf::desc(dp);
     const size_t P = (size_t)n_rays * n_samples;
     for (int i = 0; i < 16; ++i) out_host[i] = -1;
     auto put = [&](int i, size_t v) { out_host[i] = (long long)v; };
-    if (!is_delta && family == 0) {
-        const nerf::ActLayout a = nerf::act_layout(P, (size_t)n_rays);
-        for (int l = 0; l < nerf::D; ++l) put(l, a.h[l]);
-        put(8, a.feat); put(9, a.hv); put(10, a.enc); put(11, a.dir); put(12, a.dir_pt); put(13, a.mask); put(14, a.total);
-    } else if (!is_delta) {
-        const nerf::ActLayout3 a = nerf::act_layout3(P, (size_t)n_rays, family == 2);
-        for (int l = 0; l < nerf::D; ++l) put(l, a.h[l]);
-        put(8, a.feat); put(9, a.hv); put(10, a.enc); put(11, a.dir); put(12, a.dir_pt); put(13, a.mask); put(14, a.total);
-        if (family == 2) put(15, a.lo);
-    } else if (family == 0) {
-        const nerf::DeltaLayout a = nerf::delta_layout(P);
+    auto rows = [&](const auto& a) {        // the regions every layout has
         for (int l = 0; l < nerf::D; ++l) put(l, a.h[l]);
         put(8, a.feat); put(9, a.hv); put(14, a.total);
+    };
+    auto saved = [&](const auto& a) { rows(a); put(10, a.enc); put(11, a.dir); put(12, a.dir_pt); put(13, a.mask); };
+    if (!d.split) {
+        if (is_delta) rows(nerf::delta_layout(P)); else saved(nerf::act_layout(P, (size_t)n_rays));
+    } else if (is_delta) {
+        const nerf::DeltaLayout3 a = nerf::delta_layout3(P, d.two_word);
+        rows(a); put(10, a.graw); put(11, a.scale);
+        if (d.two_word) put(15, a.lo);
     } else {
-        const nerf::DeltaLayout3 a = nerf::delta_layout3(P, family == 2);
-        for (int l = 0; l < nerf::D; ++l) put(l, a.h[l]);
-        put(8, a.feat); put(9, a.hv); put(10, a.graw); put(11, a.scale); put(14, a.total);
-        if (family == 2) put(15, a.lo);
+        const nerf::ActLayout3 a = nerf::act_layout3(P, (size_t)n_rays, d.two_word);
+        saved(a);
+        if (d.two_word) put(15, a.lo);
     }
     return 0;
 }
@@ -252,7 +254,7 @@ int nerf_buffer_layout(const float* buf, int* is_delta, int* n_rays, int* n_samp
     if (is_delta) *is_delta = t.is_delta;
     if (n_rays) *n_rays = t.n_rays;
     if (n_samples) *n_samples = t.n_samples;
-    return t.kind;
+    return tag_kind(t);
 }
 
 int nerf_field_fwd(const float* packed, const float* rays, int ray_stride, const float* z_vals, int n_rays,
@@ -260,9 +262,8 @@ int nerf_field_fwd(const float* packed, const float* rays, int ray_stride, const
     REQUIRE(packed && rays && z_vals && raw, "null pointer");
     REQUIRE(ray_stride >= 11, "rays must carry view directions (ray_stride >= 11): use_viewdirs=True architecture");
     REQUIRE(n_rays >= 0 && n_samples >= 1, "bad size");
-    REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(raw) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(act) & 15) == 0, "packed/raw/act must be 16-byte aligned");
-    if (act) tag_record(act, 0, ACT_ROWS_F32, n_rays, n_samples);
+    REQUIRE(aligned16(packed, raw, act), "packed/raw/act must be 16-byte aligned");
+    tag_record(act, 0, Datapath::F32, n_rays, n_samples);
     return done(__func__, nerf::launch_field_fwd(packed, rays, ray_stride, z_vals, n_rays, n_samples, raw, act,
                                                  (hipStream_t)stream));
 }
@@ -348,11 +349,9 @@ int nerf_field_bwd(const float* packed, const float* act, const float* d_raw, in
                    float* delta, float* partial, float* grad, int accumulate, void* stream) {
     REQUIRE(packed && act && d_raw && delta && partial && grad, "null pointer");
     REQUIRE(n_rays >= 0 && n_samples >= 1, "bad size");
-    REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(act) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(d_raw) & 15) == 0 && (reinterpret_cast<uintptr_t>(delta) & 15) == 0,
-            "packed/act/d_raw/delta must be 16-byte aligned");
-    if (int rc = check_act_for_dgrad(__func__, act, false, n_rays, n_samples)) return rc;
-    tag_record(delta, 1, DELTA_ROWS_F32, n_rays, n_samples);
+    REQUIRE(aligned16(packed, act, d_raw, delta), "packed/act/d_raw/delta must be 16-byte aligned");
+    if (int rc = check_act_for_dgrad(__func__, act, Datapath::F32, n_rays, n_samples)) return rc;
+    tag_record(delta, 1, Datapath::F32, n_rays, n_samples);
     return done(__func__, nerf::launch_field_bwd(packed, act, d_raw, n_rays, n_samples, delta, partial, grad, accumulate,
                                                  (hipStream_t)stream));
 }
@@ -361,11 +360,9 @@ int nerf_field_dgrad(const float* packed, const float* act, const float* d_raw, 
                      float* delta, void* stream) {
     REQUIRE(packed && act && d_raw && delta, "null pointer");
     REQUIRE(n_rays >= 0 && n_samples >= 1, "bad size");
-    REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(act) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(d_raw) & 15) == 0 && (reinterpret_cast<uintptr_t>(delta) & 15) == 0,
-            "packed/act/d_raw/delta must be 16-byte aligned");
-    if (int rc = check_act_for_dgrad(__func__, act, false, n_rays, n_samples)) return rc;
-    tag_record(delta, 1, DELTA_ROWS_F32, n_rays, n_samples);
+    REQUIRE(aligned16(packed, act, d_raw, delta), "packed/act/d_raw/delta must be 16-byte aligned");
+    if (int rc = check_act_for_dgrad(__func__, act, Datapath::F32, n_rays, n_samples)) return rc;
+    tag_record(delta, 1, Datapath::F32, n_rays, n_samples);
     return done(__func__, nerf::launch_field_dgrad(packed, act, d_raw, n_rays, n_samples, delta, (hipStream_t)stream));
 }
 
@@ -373,31 +370,30 @@ int nerf_field_wgrad(const float* act, const float* delta, const float* d_raw, i
                      float* partial, float* grad, int accumulate, void* stream) {
     REQUIRE(act && delta && d_raw && partial && grad, "null pointer");
     REQUIRE(n_rays >= 0 && n_samples >= 1, "bad size");
-    return done(__func__, nerf::launch_field_wgrad(act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate, 0, 7,
+    return done(__func__, nerf::launch_field_wgrad(act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate, Datapath::F32, 7,
                                                    (hipStream_t)stream, nullptr));
 }
 
-// the datapath the (act, delta) pair of a weight-gradient call needs, from what the library wrote into them; -1 = unknown
+// the datapath the (act, delta) pair of a weight-gradient call needs, from what the library wrote into them; false = unknown
 // buffers.  *rc != 0: the pair is known and impossible (or of another point count): refused.
-static int datapath_from_tags(const char* fn, const void* act, const void* delta, int n_rays, int n_samples, int* rc) {
+static bool datapath_from_tags(const char* fn, const void* act, const void* delta, int n_rays, int n_samples, Datapath* dp, int* rc) {
     BufTag ta, td;
     *rc = 0;
     const bool ka = tag_lookup(act, &ta), kd = tag_lookup(delta, &td);
-    if (ka && ta.is_delta) { *rc = fail_arg(fn, "`act` is a buffer this library last wrote deltas into"); return -1; }
-    if (kd && !td.is_delta) { *rc = fail_arg(fn, "`delta` is a buffer this library last wrote saved activations into"); return -1; }
+    if (ka && ta.is_delta) { *rc = fail_arg(fn, "`act` is a buffer this library last wrote deltas into"); return false; }
+    if (kd && !td.is_delta) { *rc = fail_arg(fn, "`delta` is a buffer this library last wrote saved activations into"); return false; }
     if ((ka && (ta.n_rays != n_rays || ta.n_samples != n_samples)) || (kd && (td.n_rays != n_rays || td.n_samples != n_samples))) {
         *rc = fail_arg(fn, "act / delta were written for another ray or sample count than this call's");
-        return -1;
+        return false;
     }
-    if (!(ka && kd)) return -1;
-    const int dp = datapath_of(ta.kind, td.kind);
-    if (dp < 0) {
-        snprintf(g_err, sizeof(g_err), "%s: act layout %d (0 fp32 rows, 4 / 5 = 16-point tiles of bf16 / fp16) cannot be "
-                 "contracted with delta kind %d (0 fp32 rows, 2 / 3 = tiles of bf16 / fp16): the forward and the dgrad that wrote them belong to different datapaths",
-                 fn, ta.kind, td.kind);
-        *rc = NERF_E_BADARG;
-    }
-    return dp;
+    if (!(ka && kd)) return false;
+    *dp = ta.dp;
+    if (ta.dp == td.dp) return true;
+    snprintf(g_err, sizeof(g_err), "%s: act layout %d (0 fp32 rows, 4 / 5 = 16-point tiles of bf16 / fp16) cannot be "
+             "contracted with delta kind %d (0 fp32 rows, 2 / 3 = tiles of bf16 / fp16): the forward and the dgrad that wrote them belong to different datapaths",
+             fn, tag_kind(ta), tag_kind(td));
+    *rc = NERF_E_BADARG;
+    return false;
 }
 
 // NERF_BWD_SKIP_DEAD=0 in the environment (read once per process): the *_live entry points ignore their list -- the dense forms
@@ -405,16 +401,6 @@ static int datapath_from_tags(const char* fn, const void* act, const void* delta
 static bool skip_dead_enabled() {
     static const bool on = [] { const char* e = getenv("NERF_BWD_SKIP_DEAD"); return !(e && e[0] == '0'); }();
     return on;
-}
-
-static int field_wgrad_phase(const char* fn, const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
-                             float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
-                             const unsigned* live, void* stream);
-
-int nerf_field_wgrad_phase(const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
-                           float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
-                           void* stream) {
-    return field_wgrad_phase(__func__, act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate, datapath, phases, params, nullptr, stream);
 }
 
 size_t nerf_live_tiles_words(int n_rays, int n_samples) {
@@ -430,63 +416,68 @@ size_t nerf_live_tiles_words(int n_rays, int n_samples) {
 
 int nerf_bwd_skip_dead(void) { return skip_dead_enabled() ? 1 : 0; }
 
-int nerf_field_wgrad_phase_live(const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
-                                float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
-                                const unsigned* live, void* stream) {
-    REQUIRE((reinterpret_cast<uintptr_t>(live) & 15) == 0, "live must be 16-byte aligned");
-    REQUIRE(!live || datapath != 0, "the fp32 datapath has no sparse form: live must be NULL");
-    return field_wgrad_phase(__func__, act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate, datapath, phases, params,
-                             skip_dead_enabled() ? live : nullptr, stream);
-}
-
-int nerf_field_dgrad_split_live(const float* packed3, const float* act, const float* d_raw, int n_rays, int n_samples,
-                                float* delta, int split, unsigned* live, void* stream) {
-    REQUIRE(packed3 && act && d_raw && delta, "null pointer");
-    REQUIRE(n_rays >= 0 && n_samples >= 1 && (split == 0 || split == 1 || split == 5), "bad size / split (0 bf16, 1 fp16, 5 fp16 with two-word saves)");
-    REQUIRE((reinterpret_cast<uintptr_t>(packed3) & 15) == 0 && (reinterpret_cast<uintptr_t>(act) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(d_raw) & 15) == 0 && (reinterpret_cast<uintptr_t>(delta) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(live) & 15) == 0,
-            "packed/act/d_raw/delta/live must be 16-byte aligned");
-    if (int rc = check_act_for_dgrad(__func__, act, true, n_rays, n_samples, split == 5 ? 1 : 0)) return rc;
-    tag_record(delta, 1, split == 5 ? DELTA_TILE32_F16X2 : split ? DELTA_TILE32_F16 : DELTA_TILE32_BF16, n_rays, n_samples);
-    return done(__func__, nerf::launch_field_dgrad3r(packed3, act, d_raw, n_rays, n_samples, delta, split, (hipStream_t)stream,
-                                                     skip_dead_enabled() ? live : nullptr));
-}
-
+// the bodies of the entry points that exist with and without a live-tile list (live = NULL: dense; checked as given, then ignored
+// when the lists are switched off)
 #define REQUIRE_FN(cond, what) do { if (!(cond)) return nerf_api::fail_arg(fn, what); } while (0)
 static int field_wgrad_phase(const char* fn, const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
                              float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
                              const unsigned* live, void* stream) {
+    REQUIRE_FN(aligned16(live), "live must be 16-byte aligned");
     REQUIRE_FN(act && delta && d_raw && partial && grad, "null pointer");
-    REQUIRE_FN(n_rays >= 0 && n_samples >= 1 && phases >= 1 && phases <= 7 && (datapath == -1 || datapath == 0 || (datapath >= 4 && datapath <= 6)), "bad size / datapath (-1, 0, 4, 5, 6)");
+    Datapath dp = Datapath::F32, recorded;
+    const bool as_recorded = datapath == -1;
+    REQUIRE_FN(n_rays >= 0 && n_samples >= 1 && phases >= 1 && phases <= 7 && (as_recorded || decode_wgrad_datapath(datapath, &dp)), "bad size / datapath (-1, 0, 4, 5, 6)");
     int rc;
-    const int recorded = datapath_from_tags(fn, act, delta, n_rays, n_samples, &rc);
+    const bool known = datapath_from_tags(fn, act, delta, n_rays, n_samples, &recorded, &rc);
     if (rc) return rc;
-    if (datapath < 0) {
-        REQUIRE_FN(recorded >= 0, "datapath = -1 (as recorded) needs act and delta written by this library's forward / dgrad entry points");
-        datapath = recorded;
-    } else if (recorded >= 0 && recorded != datapath) {
+    if (as_recorded) {
+        REQUIRE_FN(known, "datapath = -1 (as recorded) needs act and delta written by this library's forward / dgrad entry points");
+        dp = recorded;
+    } else if (known && recorded != dp) {
         snprintf(g_err, sizeof(g_err), "%s: datapath %d requested, but act / delta were written for datapath %d (the tiling and element type of "
-                 "the saved rows and deltas follow from the forward and dgrad entry points that produced them)", fn, datapath, recorded);
+                 "the saved rows and deltas follow from the forward and dgrad entry points that produced them)", fn, datapath, CODES[(int)recorded].wgrad);
         return NERF_E_BADARG;
     }
-    REQUIRE_FN(datapath == 0 || params, "the split datapaths need the canonical parameters (folded feature layer)");
-    REQUIRE_FN(!live || datapath != 0, "the fp32 datapath has no sparse form: live must be NULL");
+    REQUIRE_FN(!nerf::desc(dp).split || params, "the split datapaths need the canonical parameters (folded feature layer)");
+    REQUIRE_FN(!live || nerf::desc(dp).split, "the fp32 datapath has no sparse form: live must be NULL");
     return done(fn, nerf::launch_field_wgrad(act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate,
-                                                   datapath, phases, (hipStream_t)stream, params, live));
+                                                   dp, phases, (hipStream_t)stream, params, skip_dead_enabled() ? live : nullptr));
+}
+
+static int field_dgrad_split(const char* fn, const float* packed3, const float* act, const float* d_raw, int n_rays, int n_samples,
+                             float* delta, int split, unsigned* live, void* stream) {
+    REQUIRE_FN(packed3 && act && d_raw && delta, "null pointer");
+    const SplitCode c = decode_split(split);
+    const Datapath dp = c.dp;
+    REQUIRE_FN(n_rays >= 0 && n_samples >= 1 && c.ok && c.mode == FwdMode::Full, "bad size / split (0 bf16, 1 fp16, 5 fp16 with two-word saves)");
+    REQUIRE_FN(aligned16(packed3, act, d_raw, delta, live), "packed/act/d_raw/delta/live must be 16-byte aligned");
+    if (int rc = check_act_for_dgrad(fn, act, dp, n_rays, n_samples)) return rc;
+    tag_record(delta, 1, dp, n_rays, n_samples);
+    return done(fn, nerf::launch_field_dgrad3r(packed3, act, d_raw, n_rays, n_samples, delta, dp, (hipStream_t)stream,
+                                               skip_dead_enabled() ? live : nullptr));
 }
 #undef REQUIRE_FN
 
+int nerf_field_wgrad_phase(const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
+                           float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
+                           void* stream) {
+    return field_wgrad_phase(__func__, act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate, datapath, phases, params, nullptr, stream);
+}
+
+int nerf_field_wgrad_phase_live(const float* act, const float* delta, const float* d_raw, int n_rays, int n_samples,
+                                float* partial, float* grad, int accumulate, int datapath, int phases, const float* params,
+                                const unsigned* live, void* stream) {
+    return field_wgrad_phase(__func__, act, delta, d_raw, n_rays, n_samples, partial, grad, accumulate, datapath, phases, params, live, stream);
+}
+
 int nerf_field_dgrad_split(const float* packed3, const float* act, const float* d_raw, int n_rays, int n_samples,
                            float* delta, int split, void* stream) {
-    REQUIRE(packed3 && act && d_raw && delta, "null pointer");
-    REQUIRE(n_rays >= 0 && n_samples >= 1 && (split == 0 || split == 1 || split == 5), "bad size / split (0 bf16, 1 fp16, 5 fp16 with two-word saves)");
-    REQUIRE((reinterpret_cast<uintptr_t>(packed3) & 15) == 0 && (reinterpret_cast<uintptr_t>(act) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(d_raw) & 15) == 0 && (reinterpret_cast<uintptr_t>(delta) & 15) == 0,
-            "packed/act/d_raw/delta must be 16-byte aligned");
-    if (int rc = check_act_for_dgrad(__func__, act, true, n_rays, n_samples, split == 5 ? 1 : 0)) return rc;
-    tag_record(delta, 1, split == 5 ? DELTA_TILE32_F16X2 : split ? DELTA_TILE32_F16 : DELTA_TILE32_BF16, n_rays, n_samples);
-    return done(__func__, nerf::launch_field_dgrad3r(packed3, act, d_raw, n_rays, n_samples, delta, split, (hipStream_t)stream));
+    return field_dgrad_split(__func__, packed3, act, d_raw, n_rays, n_samples, delta, split, nullptr, stream);
+}
+
+int nerf_field_dgrad_split_live(const float* packed3, const float* act, const float* d_raw, int n_rays, int n_samples,
+                                float* delta, int split, unsigned* live, void* stream) {
+    return field_dgrad_split(__func__, packed3, act, d_raw, n_rays, n_samples, delta, split, live, stream);
 }
 
 /* ---- three-term split datapaths (bf16 / fp16 parts) */
@@ -508,23 +499,23 @@ int nerf_field_fwd_split(const float* packed3, const float* rays, int ray_stride
                          int n_samples, float* raw, float* act, int split, void* stream) {
     REQUIRE(packed3 && rays && z_vals && raw, "null pointer");
     REQUIRE(ray_stride >= 11, "rays must carry view directions (ray_stride >= 11): use_viewdirs=True architecture");
-    REQUIRE(n_rays >= 0 && n_samples >= 1 && ((split >= 0 && split <= 3) || split == 5), "bad size / split (0, 1, 2, 3, 5)");
-    REQUIRE(split < 2 || split == 5 || !act, "split = 2 / 3 (fp16 main term + fp8 corrections) is an inference form: act must be NULL");
+    const SplitCode c = decode_split(split);
+    REQUIRE(n_rays >= 0 && n_samples >= 1 && c.ok, "bad size / split (0, 1, 2, 3, 5)");
+    REQUIRE(c.mode == FwdMode::Full || !act, "split = 2 / 3 (fp16 main term + fp8 corrections) is an inference form: act must be NULL");
     REQUIRE((long)n_rays * n_samples <= nerf::FWD16R_MAX_POINTS && (!act || (long)n_rays * n_samples <= nerf::FWD16R_MAX_SAVED_POINTS),
             "too many points for one launch (2^31 - 1; 2^26 when saving): split the ray batch");
-    REQUIRE((reinterpret_cast<uintptr_t>(packed3) & 15) == 0 && (reinterpret_cast<uintptr_t>(raw) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(act) & 15) == 0, "packed/raw/act must be 16-byte aligned");
-    if (act) tag_record(act, 0, split == 5 ? ACT_TILE16_F16X2 : split ? ACT_TILE16_F16 : ACT_TILE16_BF16, n_rays, n_samples);
-    return done(__func__, nerf::launch_field_fwd16r(packed3, rays, ray_stride, z_vals, n_rays, n_samples, raw, act, split,
+    REQUIRE(aligned16(packed3, raw, act), "packed/raw/act must be 16-byte aligned");
+    tag_record(act, 0, c.dp, n_rays, n_samples);
+    return done(__func__, nerf::launch_field_fwd16r(packed3, rays, ray_stride, z_vals, n_rays, n_samples, raw, act, c.dp, c.mode,
                                                     (hipStream_t)stream));
 }
 
 int nerf_range_scan(const float* buf, int n_rays, int n_samples, unsigned* words, void* stream) {
     REQUIRE(buf && words, "null pointer");
     REQUIRE(n_rays >= 0 && n_samples >= 1, "bad size");
-    REQUIRE((reinterpret_cast<uintptr_t>(buf) & 15) == 0 && (reinterpret_cast<uintptr_t>(words) & 3) == 0, "buf must be 16-byte, words 4-byte aligned");
+    REQUIRE(aligned16(buf) && (reinterpret_cast<uintptr_t>(words) & 3) == 0, "buf must be 16-byte, words 4-byte aligned");
     BufTag t;
-    REQUIRE(tag_lookup(buf, &t) && (t.is_delta ? (t.kind == DELTA_TILE32_F16 || t.kind == DELTA_TILE32_F16X2) : (t.kind == ACT_TILE16_F16 || t.kind == ACT_TILE16_F16X2)),
+    REQUIRE(tag_lookup(buf, &t) && nerf::desc(t.dp).f16,
             "`buf` must be a save buffer an fp16 forward (split = 1 / 5) or a delta buffer an fp16 dgrad of this library wrote: only fp16 "
             "rows and deltas have a range to check");
     REQUIRE(t.n_rays == n_rays && t.n_samples == n_samples, "`buf` was written for another ray / sample count");
@@ -546,25 +537,29 @@ int nerf_field_fwd_last_sample(const float* packed3, const float* rays, int ray_
     REQUIRE(packed3 && rays && z_vals && raw, "null pointer");
     REQUIRE(ray_stride >= 11, "rays must carry view directions (ray_stride >= 11): use_viewdirs=True architecture");
     REQUIRE(n_rays >= 0 && n_samples >= 1, "bad size");
-    REQUIRE((reinterpret_cast<uintptr_t>(packed3) & 15) == 0 && (reinterpret_cast<uintptr_t>(raw) & 15) == 0, "packed/raw must be 16-byte aligned");
+    REQUIRE(aligned16(packed3, raw), "packed/raw must be 16-byte aligned");
     REQUIRE(!packed3_next || (raw_next && n_samples_next >= n_samples), "packed3_next needs raw_next and the refining pass's sample count");
-    REQUIRE((reinterpret_cast<uintptr_t>(packed3_next) & 15) == 0 && (reinterpret_cast<uintptr_t>(raw_next) & 15) == 0, "packed/raw must be 16-byte aligned");
+    REQUIRE(aligned16(packed3_next, raw_next), "packed/raw must be 16-byte aligned");
     return done(__func__, nerf::launch_field_fwd16r_last(packed3, rays, ray_stride, z_vals, n_rays, n_samples, raw, packed3_next, raw_next,
                                                          n_samples_next, (hipStream_t)stream));
 }
 
 int nerf_pack_params_split(const float* params, float* packed3, int streams, int split, void* stream) {
     REQUIRE(params && packed3, "null pointer");
-    REQUIRE(streams >= 0 && (streams & ~5) == 0 && split >= 0 && split <= 2, "streams is a mask of 1 (forward stream) and 4 (transposed streams of the delta chain); split 0 (bf16), 1 (fp16) or 2 (reduced inference stream)");
-    REQUIRE(split != 2 || (streams & 1), "split = 2 refills the 16-point forward stream: streams must include bit 0");
-    return done(__func__, nerf::launch_pack3_sel(params, packed3, streams, (hipStream_t)stream, split));
+    const SplitCode c = decode_split(split);
+    REQUIRE(streams >= 0 && (streams & ~5) == 0 && c.ok && !nerf::desc(c.dp).two_word && c.mode != FwdMode::ReducedSkipLast,
+            "streams is a mask of 1 (forward stream) and 4 (transposed streams of the delta chain); split 0 (bf16), 1 (fp16) or 2 (reduced inference stream)");
+    REQUIRE(c.mode == FwdMode::Full || (streams & 1), "split = 2 refills the 16-point forward stream: streams must include bit 0");
+    return done(__func__, nerf::launch_pack3_sel(params, packed3, streams, (hipStream_t)stream, c.dp, c.mode));
 }
 
 int nerf_pack_params_split_pair(const float* params_a, float* packed3_a, const float* params_b, float* packed3_b, int streams, int split, void* stream) {
     REQUIRE(params_a && packed3_a && params_b && packed3_b, "null pointer");
     REQUIRE(packed3_a != packed3_b, "the two networks need their own packed buffers");
-    REQUIRE(streams >= 0 && (streams & ~5) == 0 && (split == 0 || split == 1), "streams is a mask of 1 (forward stream) and 4 (transposed streams); split 0 (bf16) or 1 (fp16)");
-    return done(__func__, nerf::launch_pack3_pair(params_a, packed3_a, params_b, packed3_b, streams, (hipStream_t)stream, split));
+    const SplitCode c = decode_split(split);
+    REQUIRE(streams >= 0 && (streams & ~5) == 0 && c.ok && !nerf::desc(c.dp).two_word && c.mode == FwdMode::Full,
+            "streams is a mask of 1 (forward stream) and 4 (transposed streams); split 0 (bf16) or 1 (fp16)");
+    return done(__func__, nerf::launch_pack3_pair(params_a, packed3_a, params_b, packed3_b, streams, (hipStream_t)stream, c.dp));
 }
 
 

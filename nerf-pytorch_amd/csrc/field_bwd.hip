@@ -961,77 +961,71 @@ __global__ void replicate_dir_bf16_kernel(const float* __restrict__ dir_ray, u32
     dir_rep[i] = pack8_sp<SP>(v);
 }
 
-// phases: bit 0 = full-width jobs, bit 1 = narrow jobs, bit 2 = chunk reduction (7 = everything)
-hipError_t launch_field_wgrad(const float* act, const float* delta, const float* d_raw, int n_rays, int S,
-                              float* partial, float* grad, int accumulate, int datapath, int phases, hipStream_t stream,
-                              const float* params, const unsigned* live) {
-    // datapath: 0 = fp32 (point-major rows); 4 = bf16 operands, rows saved by the 16-point forward (16-point tiles, row16h order),
-    // deltas in 32-point tiles; 5 = the same with fp16 elements (deltas scaled by the launch's power of two, removed in the reduction);
-    // 6 = fp16 TWO-WORD operands (hi and lo words saved by the SAVE = 3 forward and the TWO dgrad: three MFMAs per product)
-    if (datapath != 0 && datapath != 4 && datapath != 5 && datapath != 6) return hipErrorInvalidValue;
-    const bool two = datapath == 6;
-    const bool f16 = datapath == 5 || two;
-    const bool split16 = datapath != 0;      // split datapaths: 16-bit operands streamed by wgrad1_kernel,
-    const bool fold = split16;               //   feature layer folded into the view branch (nerf_common.h)
-    if (fold && !params) return hipErrorInvalidValue;
-    if (live && !split16) return hipErrorInvalidValue;      // the fp32 anchor stays dense
-    const long P = (long)n_rays * S;
-    if (P <= 0) return hipSuccess;
-    hipError_t e;
-    constexpr Canon cn = canon();
-    // operand bases.  fp32 datapath: point-major rows (lda = row pitch); split datapaths: 32-point feature-major tiles
-    // (lda = features per tile, a feature offset f0 is folded into the base as f0 * 32)
+// ---- the weight-gradient GEMM.  Split datapaths: 16-bit operands streamed by wgrad1_kernel, rows saved by the 16-point forward (16-point
+// tiles, row16h order), deltas in 32-point tiles, feature layer folded into the view branch (nerf_common.h); fp16 parts: deltas scaled by the
+// launch's power of two, removed in the reduction; two-word: hi and lo words (SAVE = 3 forward, TWO dgrad), three MFMAs per product.
+// operand bases.  fp32 datapath: point-major rows (lda = row pitch); split datapaths: 32-point feature-major tiles
+// (lda = features per tile, a feature offset f0 is folded into the base as f0 * 32)
+struct WgradOperands {
     const float *d_h[D], *d_feat, *d_hv, *d_rgb, *d_sigma, *x_h[D], *x_feat, *x_hv, *x_enc, *x_dir;
-    const unsigned* amax = nullptr;
-    int ld_graw;
-    long lo_a = 0, lo_b = 0;        // two-word operands: bytes from the hi words of a delta / save region to its lo words
-    if (split16) {
-        const ActLayout3 al = act_layout3((size_t)P, (size_t)n_rays, two);
-        const DeltaLayout3 dl = delta_layout3((size_t)P, two);
-        lo_a = 4 * (long)dl.lo;
-        lo_b = 4 * (long)al.lo;
-        if (f16) amax = reinterpret_cast<const unsigned*>(delta + dl.scale);
-        for (int l = 0; l < D; ++l) { d_h[l] = delta + dl.h[l]; x_h[l] = act + al.h[l]; }
-        d_feat = delta + dl.feat; d_hv = delta + dl.hv; d_rgb = delta + dl.graw;
+    const float* dir;               // the per-ray direction encoding the forward saved, and where its expansion goes (scratch inside act)
+    float *dir_pt, *dir_pt_lo;
+    const unsigned* amax;           // fp16 parts: the scale word of the launch
+    long lo_a, lo_b;                // two-word operands: bytes from the hi words of a delta / save region to its lo words
+};
+static WgradOperands wgrad_operands(const DatapathDesc& dp, const float* act, const float* delta, const float* d_raw, long P, int n_rays) {
+    WgradOperands o{};
+    float* act_w = const_cast<float*>(act);     // act is written by the forward; the expanded copy is scratch inside the same buffer
+    if (dp.split) {
+        const ActLayout3 al = act_layout3((size_t)P, (size_t)n_rays, dp.two_word);
+        const DeltaLayout3 dl = delta_layout3((size_t)P, dp.two_word);
+        o.lo_a = 4 * (long)dl.lo;
+        o.lo_b = 4 * (long)al.lo;
+        if (dp.f16) o.amax = reinterpret_cast<const unsigned*>(delta + dl.scale);
+        for (int l = 0; l < D; ++l) { o.d_h[l] = delta + dl.h[l]; o.x_h[l] = act + al.h[l]; }
+        o.d_feat = delta + dl.feat; o.d_hv = delta + dl.hv; o.d_rgb = delta + dl.graw;
         // feature 3 of the 4-wide tile: 3 rows of 32 two-byte elements
-        d_sigma = reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(delta + dl.graw) + 3 * 32);
-        x_feat = act + al.feat; x_hv = act + al.hv; x_enc = act + al.enc; x_dir = act + al.dir_pt;
-        ld_graw = 4;
-        if (phases & 1) {   // act is written by the forward; the expanded copy is scratch inside the same buffer
-            if (S % 32 == 0) {
-                const dim3 grid((unsigned)(((long)n_rays * 32 + 255) / 256));
-                u32x4* dst = reinterpret_cast<u32x4*>(const_cast<float*>(act) + al.dir_pt);
-                if (f16) hipLaunchKernelGGL(replicate_dir_bf16_kernel<SplitF16>, grid, dim3(256), 0, stream, act + al.dir, dst, (long)n_rays * 32);
-                else hipLaunchKernelGGL(replicate_dir_bf16_kernel<SplitBF16>, grid, dim3(256), 0, stream, act + al.dir, dst, (long)n_rays * 32);
-                if (two) hipLaunchKernelGGL((replicate_dir_bf16_kernel<SplitF16, true>), grid, dim3(256), 0, stream, act + al.dir,
-                                            reinterpret_cast<u32x4*>(const_cast<float*>(act) + al.lo + al.dir_pt), (long)n_rays * 32);
-            } else {
-                const long n_thr = ((P + 31) >> 5) * 128;
-                const dim3 grid((unsigned)((n_thr + 255) / 256));
-                u32x4* dst = reinterpret_cast<u32x4*>(const_cast<float*>(act) + al.dir_pt);
-                if (f16) hipLaunchKernelGGL(expand_dir_tiles_bf16_kernel<SplitF16>, grid, dim3(256), 0, stream, act + al.dir, dst, P, S);
-                else hipLaunchKernelGGL(expand_dir_tiles_bf16_kernel<SplitBF16>, grid, dim3(256), 0, stream, act + al.dir, dst, P, S);
-                if (two) hipLaunchKernelGGL((expand_dir_tiles_bf16_kernel<SplitF16, true>), grid, dim3(256), 0, stream, act + al.dir,
-                                            reinterpret_cast<u32x4*>(const_cast<float*>(act) + al.lo + al.dir_pt), P, S);
-            }
-            e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
+        o.d_sigma = reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(delta + dl.graw) + 3 * 32);
+        o.x_feat = act + al.feat; o.x_hv = act + al.hv; o.x_enc = act + al.enc; o.x_dir = act + al.dir_pt;
+        o.dir = act + al.dir; o.dir_pt = act_w + al.dir_pt; o.dir_pt_lo = act_w + al.lo + al.dir_pt;
     } else {
         const ActLayout al = act_layout((size_t)P, (size_t)n_rays);
         const DeltaLayout dl = delta_layout((size_t)P);
-        for (int l = 0; l < D; ++l) { d_h[l] = delta + dl.h[l]; x_h[l] = act + al.h[l]; }
-        d_feat = delta + dl.feat; d_hv = delta + dl.hv; d_rgb = d_raw; d_sigma = d_raw + 3;
-        x_feat = act + al.feat; x_hv = act + al.hv; x_enc = act + al.enc; x_dir = act + al.dir_pt;
-        ld_graw = 4;
-        if (phases & 1) {
-            hipLaunchKernelGGL(expand_dir_kernel, dim3((unsigned)((P * 8 + 255) / 256)), dim3(256), 0, stream,
-                               reinterpret_cast<const f32x4*>(act + al.dir), reinterpret_cast<f32x4*>(const_cast<float*>(act) + al.dir_pt), P, S);
-            e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
+        for (int l = 0; l < D; ++l) { o.d_h[l] = delta + dl.h[l]; o.x_h[l] = act + al.h[l]; }
+        o.d_feat = delta + dl.feat; o.d_hv = delta + dl.hv; o.d_rgb = d_raw; o.d_sigma = d_raw + 3;
+        o.x_feat = act + al.feat; o.x_hv = act + al.hv; o.x_enc = act + al.enc; o.x_dir = act + al.dir_pt;
+        o.dir = act + al.dir; o.dir_pt = act_w + al.dir_pt;
     }
-    WgradArgs wa{};
+    return o;
+}
+
+// the per-ray direction encoding -> the operand of the (delta_hv, direction) job
+static hipError_t wgrad_expand_dir(const DatapathDesc& dp, const WgradOperands& o, long P, int n_rays, int S, hipStream_t stream) {
+    u32x4* dst = reinterpret_cast<u32x4*>(o.dir_pt);
+    u32x4* dst_lo = reinterpret_cast<u32x4*>(o.dir_pt_lo);
+    if (dp.split && S % 32 == 0) {
+        const dim3 grid((unsigned)(((long)n_rays * 32 + 255) / 256));
+        if (dp.f16) hipLaunchKernelGGL(replicate_dir_bf16_kernel<SplitF16>, grid, dim3(256), 0, stream, o.dir, dst, (long)n_rays * 32);
+        else hipLaunchKernelGGL(replicate_dir_bf16_kernel<SplitBF16>, grid, dim3(256), 0, stream, o.dir, dst, (long)n_rays * 32);
+        if (dp.two_word) hipLaunchKernelGGL((replicate_dir_bf16_kernel<SplitF16, true>), grid, dim3(256), 0, stream, o.dir, dst_lo, (long)n_rays * 32);
+    } else if (dp.split) {
+        const long n_thr = ((P + 31) >> 5) * 128;
+        const dim3 grid((unsigned)((n_thr + 255) / 256));
+        if (dp.f16) hipLaunchKernelGGL(expand_dir_tiles_bf16_kernel<SplitF16>, grid, dim3(256), 0, stream, o.dir, dst, P, S);
+        else hipLaunchKernelGGL(expand_dir_tiles_bf16_kernel<SplitBF16>, grid, dim3(256), 0, stream, o.dir, dst, P, S);
+        if (dp.two_word) hipLaunchKernelGGL((expand_dir_tiles_bf16_kernel<SplitF16, true>), grid, dim3(256), 0, stream, o.dir, dst_lo, P, S);
+    } else {
+        hipLaunchKernelGGL(expand_dir_kernel, dim3((unsigned)((P * 8 + 255) / 256)), dim3(256), 0, stream,
+                           reinterpret_cast<const f32x4*>(o.dir), reinterpret_cast<f32x4*>(o.dir_pt), P, S);
+    }
+    return hipGetLastError();
+}
+
+// the job table: the same for both families except the folded feature layer and the merged alpha row.  Returns the job count.
+static int wgrad_jobs(const DatapathDesc& dp, const WgradOperands& o, int S, WgradArgs& wa) {
+    constexpr Canon cn = canon();
+    constexpr int ld_graw = 4;
+    const bool split16 = dp.split, fold = dp.split;
     int nj = 0, tiles = 0;
     auto add = [&](const float* A, int lda, int nA, const float* B, int ldb, int nB, int rowdiv, int c_off, int ldc, int bias_off) {
         if (nj >= WG_MAX_JOBS) { ++nj; return; }
@@ -1048,44 +1042,52 @@ hipError_t launch_field_wgrad(const float* act, const float* delta, const float*
         j.vecA = ((reinterpret_cast<uintptr_t>(A) & 15) == 0 && lda % 4 == 0) ? 1 : 0;
         j.vecB = ((reinterpret_cast<uintptr_t>(B) & 15) == 0 && ldb % 4 == 0) ? 1 : 0;
     };
-    add(d_h[0], W, W, x_enc, 64, IN_XYZ, 1, cn.w[0], IN_XYZ, cn.b[0]);
+    add(o.d_h[0], W, W, o.x_enc, 64, IN_XYZ, 1, cn.w[0], IN_XYZ, cn.b[0]);
     for (int l = 1; l < D; ++l) {
         if (l == SKIP + 1) {
-            add(d_h[l], W, W, x_enc, 64, IN_XYZ, 1, cn.w[l], W + IN_XYZ, cn.b[l]);
-            add(d_h[l], W, W, x_h[l - 1], W, W, 1, cn.w[l] + IN_XYZ, W + IN_XYZ, -1);
+            add(o.d_h[l], W, W, o.x_enc, 64, IN_XYZ, 1, cn.w[l], W + IN_XYZ, cn.b[l]);
+            add(o.d_h[l], W, W, o.x_h[l - 1], W, W, 1, cn.w[l] + IN_XYZ, W + IN_XYZ, -1);
         } else {
-            add(d_h[l], W, W, x_h[l - 1], W, W, 1, cn.w[l], W, cn.b[l]);
+            add(o.d_h[l], W, W, o.x_h[l - 1], W, W, 1, cn.w[l], W, cn.b[l]);
         }
     }
-    if (!fold) add(d_feat, W, W, x_h[D - 1], W, W, 1, cn.wf, W, cn.bf);
+    if (!fold) add(o.d_feat, W, W, o.x_h[D - 1], W, W, 1, cn.wf, W, cn.bf);
     // (the merged job addresses d_sigma through a 32-bit lane offset from d_hv: kept below 2 GiB -- launches beyond ~9 M points keep
     // the alpha head as a job of its own)
     // ... and the kernel's wrap-around arithmetic (a2_off + tile * (a2_tile_bytes - tile_bytes)) wants the graw region BEHIND hv, as
     // delta_layout3 lays them out: a reordered layout falls back to 13 jobs instead of reading the wrong rows
     // (NERF_WG_MERGE_ALPHA=0 in the environment, read per call: the 13-job plan, for the test that pins the merged row against it)
     const char* merge_env = getenv("NERF_WG_MERGE_ALPHA");
-    const bool merge_alpha = split16 && NERF_WG_MERGE_ALPHA && !(merge_env && merge_env[0] == '0') && d_sigma > d_hv &&
-                             reinterpret_cast<const char*>(d_sigma) - reinterpret_cast<const char*>(d_hv) < (1L << 31);
-    if (!merge_alpha) add(d_sigma, ld_graw, 1, x_h[D - 1], W, W, 1, cn.wa, W, cn.ba);           // alpha_linear (A = d_sigma, one row)
+    const bool merge_alpha = split16 && NERF_WG_MERGE_ALPHA && !(merge_env && merge_env[0] == '0') && o.d_sigma > o.d_hv &&
+                             reinterpret_cast<const char*>(o.d_sigma) - reinterpret_cast<const char*>(o.d_hv) < (1L << 31);
+    if (!merge_alpha) add(o.d_sigma, ld_graw, 1, o.x_h[D - 1], W, W, 1, cn.wa, W, cn.ba);           // alpha_linear (A = d_sigma, one row)
     // fold: G = delta_hv^T h7 lands in the slot of Wv[:, :256]; wgrad_fold_kernel turns it into dWv[:, :256], dWf, dbf
     if (fold) {
-        add(d_hv, WV, WV, x_h[D - 1], W, W, 1, cn.wv, W + IN_DIR, cn.bv);
+        add(o.d_hv, WV, WV, o.x_h[D - 1], W, W, 1, cn.wv, W + IN_DIR, cn.bv);
         if (merge_alpha) {
             // the alpha head's one row rides on the view layer's job (both contract against h7: 512 B per point read once instead of
             // twice): row 128 of A = d_sigma = feature 3 of the 4-wide graw tiles of the same delta buffer
             WgradJob& j = wa.job[nj - 1];
             j.nA = WV + 1;
             j.a2_row = WV;
-            j.a2_off = (unsigned)((reinterpret_cast<const char*>(d_sigma) - reinterpret_cast<const char*>(d_hv)));
+            j.a2_off = (unsigned)((reinterpret_cast<const char*>(o.d_sigma) - reinterpret_cast<const char*>(o.d_hv)));
             j.a2_tile_bytes = 64 * ld_graw;
             j.c_off2 = cn.wa;
             j.bias_off2 = cn.ba;
         }
-    } else add(d_hv, WV, WV, x_feat, W, W, 1, cn.wv, W + IN_DIR, cn.bv);
-    add(d_hv, WV, WV, x_dir, 32, IN_DIR, 1, cn.wv + W, W + IN_DIR, -1);
+    } else add(o.d_hv, WV, WV, o.x_feat, W, W, 1, cn.wv, W + IN_DIR, cn.bv);
+    add(o.d_hv, WV, WV, o.x_dir, 32, IN_DIR, 1, cn.wv + W, W + IN_DIR, -1);
     if (split16 && S % 32 == 0 && nj <= WG_MAX_JOBS) wa.job[nj - 1].b_ray_tiles = S / 32;       // direction encoding: one record per ray
-    add(d_rgb, ld_graw, 3, x_hv, WV, WV, 1, cn.wr, WV, cn.br);
-    if (nj != WG_MAX_JOBS - (fold ? 1 : 0) - (merge_alpha ? 1 : 0)) return hipErrorInvalidValue;
+    add(o.d_rgb, ld_graw, 3, o.x_hv, WV, WV, 1, cn.wr, WV, cn.br);
+    if (nj != WG_MAX_JOBS - (fold ? 1 : 0) - (merge_alpha ? 1 : 0)) return -1;
+    return nj;
+}
+
+// the launches of a family over the job table `wa`: the GEMM (phases bits 0, 1), then the chunk reduction (bit 2)
+static hipError_t wgrad_launch(const DatapathDesc& dp, const WgradArgs& wa, int nj, const WgradOperands& o, long P, float* partial, float* grad,
+                               int accumulate, int phases, hipStream_t stream, const float* params, const unsigned* live) {
+    const bool split16 = dp.split, fold = dp.split;
+    hipError_t e;
     // full-width jobs -> wgrad256_kernel (whole 256x256 output per workgroup); the rest -> 128x128 tiles
     WgradArgs big{}, small{};
     int small_tiles = 0;
@@ -1106,8 +1108,8 @@ hipError_t launch_field_wgrad(const float* act, const float* delta, const float*
     big.chunk_pts = small.chunk_pts = chunk_pts;
     big.n_chunks = small.n_chunks = n_chunks;
     big.partial = small.partial = partial;
-    big.a_lo_bytes = lo_a;
-    big.b_lo_bytes = lo_b;
+    big.a_lo_bytes = o.lo_a;
+    big.b_lo_bytes = o.lo_b;
     big.live = live;
     big.group = live ? live_group() : 32;
     small.total_tiles = small_tiles;
@@ -1128,8 +1130,8 @@ hipError_t launch_field_wgrad(const float* act, const float* delta, const float*
         attr1_set = true;
     }
     if (big.n_jobs > 0 && split16 && (phases & 1)) {
-        if (two) hipLaunchKernelGGL((wgrad1_kernel<SplitF16, 3>), dim3((unsigned)(big.n_jobs * n_chunks)), dim3(512), WG1_LDS_BYTES, stream, big);
-        else if (f16) hipLaunchKernelGGL(wgrad1_kernel<SplitF16>, dim3((unsigned)(big.n_jobs * n_chunks)), dim3(512), WG1_LDS_BYTES, stream, big);
+        if (dp.two_word) hipLaunchKernelGGL((wgrad1_kernel<SplitF16, 3>), dim3((unsigned)(big.n_jobs * n_chunks)), dim3(512), WG1_LDS_BYTES, stream, big);
+        else if (dp.f16) hipLaunchKernelGGL(wgrad1_kernel<SplitF16>, dim3((unsigned)(big.n_jobs * n_chunks)), dim3(512), WG1_LDS_BYTES, stream, big);
         else hipLaunchKernelGGL(wgrad1_kernel<SplitBF16>, dim3((unsigned)(big.n_jobs * n_chunks)), dim3(512), WG1_LDS_BYTES, stream, big);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -1146,7 +1148,7 @@ hipError_t launch_field_wgrad(const float* act, const float* delta, const float*
     if (phases & 4) {
         float* scratch = partial + wgrad_partial_floats(P) - N_DERIVED;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((N_PARAMS + 255) / 256), dim3(256), 0, stream,
-                           (const float*)partial, n_chunks, grad, accumulate, fold ? 1 : 0, scratch, amax);
+                           (const float*)partial, n_chunks, grad, accumulate, fold ? 1 : 0, scratch, o.amax);
         if (fold)
             hipLaunchKernelGGL(wgrad_fold_kernel, dim3((WV * W + W * W + W + 255) / 256), dim3(256), 0, stream,
                                params, (const float*)scratch, grad, accumulate);
@@ -1154,11 +1156,31 @@ hipError_t launch_field_wgrad(const float* act, const float* delta, const float*
     return hipGetLastError();
 }
 
+// phases: bit 0 = full-width jobs, bit 1 = narrow jobs, bit 2 = chunk reduction (7 = everything)
+hipError_t launch_field_wgrad(const float* act, const float* delta, const float* d_raw, int n_rays, int S,
+                              float* partial, float* grad, int accumulate, Datapath datapath, int phases, hipStream_t stream,
+                              const float* params, const unsigned* live) {
+    const DatapathDesc& dp = desc(datapath);
+    if (dp.split && !params) return hipErrorInvalidValue;       // the folded feature layer needs the canonical parameters
+    if (live && !dp.split) return hipErrorInvalidValue;         // the fp32 anchor stays dense
+    const long P = (long)n_rays * S;
+    if (P <= 0) return hipSuccess;
+    const WgradOperands o = wgrad_operands(dp, act, delta, d_raw, P, n_rays);
+    if (phases & 1) {
+        hipError_t e = wgrad_expand_dir(dp, o, P, n_rays, S, stream);
+        if (e != hipSuccess) return e;
+    }
+    WgradArgs wa{};
+    const int nj = wgrad_jobs(dp, o, S, wa);
+    if (nj < 0) return hipErrorInvalidValue;
+    return wgrad_launch(dp, wa, nj, o, P, partial, grad, accumulate, phases, stream, params, live);
+}
+
 hipError_t launch_field_bwd(const float* packed, const float* act, const float* d_raw, int n_rays, int S,
                             float* delta, float* partial, float* grad, int accumulate, hipStream_t stream) {
     hipError_t e = launch_field_dgrad(packed, act, d_raw, n_rays, S, delta, stream);
     if (e != hipSuccess) return e;
-    return launch_field_wgrad(act, delta, d_raw, n_rays, S, partial, grad, accumulate, 0, 7, stream, nullptr);
+    return launch_field_wgrad(act, delta, d_raw, n_rays, S, partial, grad, accumulate, Datapath::F32, 7, stream, nullptr);
 }
 
 }  // namespace nerf

@@ -354,19 +354,21 @@ static hipError_t launch_dgrad_one(const FieldBwdRingArgs& ba, unsigned blocks, 
     return hipGetLastError();
 }
 
-// split: 0 bf16, 1 fp16 parts (of the products and of the stored deltas); 5 = fp16 with two-word deltas (and a two-word save buffer)
+// dp: a split datapath -- bf16 or fp16 parts (of the products and of the stored deltas); F16X3W: two-word deltas (and a two-word save buffer)
 // live (nullable, live_tiles(P).total words): the launch writes the live-tile list there and skips the dead tiles
 // (NERF_LIVE_GROUPS builds with live_group() = 16 / 8: `live` has live_groups(P).total words and also receives the group masks, read by
 // the weight-gradient GEMM; the delta chain itself works on whole tiles)
 hipError_t launch_field_dgrad3r(const float* packed3, const float* act, const float* d_raw, int n_rays, int S,
-                                float* delta, int split, hipStream_t stream, unsigned* live) {
+                                float* delta, Datapath dp, hipStream_t stream, unsigned* live) {
+    const DatapathDesc& d = desc(dp);
+    if (!d.split) return hipErrorInvalidValue;
     const int group = live_group();
     const long P = (long)n_rays * S;
     if (P <= 0) return hipSuccess;
     FieldBwdRingArgs ba{packed3, act, d_raw, delta, n_rays, S, live};
     const unsigned blocks = (unsigned)((P + PTS_PER_WG3 - 1) / PTS_PER_WG3);
     unsigned* slot = nullptr;
-    if (split) {
+    if (d.f16) {
         // (the scale word sits in the hi part of the layout: at the same offset in the one- and the two-word layout)
         slot = reinterpret_cast<unsigned*>(delta + delta_layout3((size_t)P).scale);
         hipError_t e = hipMemsetAsync(slot, 0, 16, stream);
@@ -382,11 +384,11 @@ hipError_t launch_field_dgrad3r(const float* packed3, const float* act, const fl
         hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, stream, live, lt.n_tiles, groups ? (unsigned)group : 0u);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-    } else if (split) {
+    } else if (d.f16) {
         const unsigned sb = (unsigned)min((long)1024, (P + 1023) / 1024);      // one 16-byte load per thread: the launch is latency, not bytes
         hipLaunchKernelGGL(delta_amax_kernel<false>, dim3(sb), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot, (unsigned*)nullptr, (unsigned*)nullptr);
     }
-    if (split) return split == 5 ? launch_dgrad_one<SplitF16, true>(ba, blocks, stream) : launch_dgrad_one<SplitF16>(ba, blocks, stream);
+    if (d.f16) return d.two_word ? launch_dgrad_one<SplitF16, true>(ba, blocks, stream) : launch_dgrad_one<SplitF16>(ba, blocks, stream);
     return launch_dgrad_one<SplitBF16>(ba, blocks, stream);
 }
 

@@ -52,7 +52,7 @@ __device__ __forceinline__ void posenc_bwd3(const float x[3], G g, int L, float 
     }
 }
 
-// KIND: nerf_api::DeltaKind -- 0 fp32 point-major rows, 2 bf16 32-point tiles, 3 fp16 tiles (scaled), 4 fp16 hi + lo tiles (scaled)
+// KIND: DeltaKind (launchers.h) -- 0 fp32 point-major rows, 2 bf16 32-point tiles, 3 fp16 tiles (scaled), 4 fp16 hi + lo tiles (scaled)
 template <int KIND>
 struct DeltaRead {
     const float* base;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void field_input_grad_kernel(const float* __re
     for (int c = 0; c < 11; ++c) dst[c] = accumulate ? dst[c] + out[c] : out[c];
 }
 
-hipError_t launch_field_input_grad(const float* params, const float* delta, int kind, const float* rays, int ray_stride,
+hipError_t launch_field_input_grad(const float* params, const float* delta, DeltaKind kind, const float* rays, int ray_stride,
                                    const float* z_vals, int n_rays, int S, float* d_rays, int accumulate, hipStream_t stream) {
     if (n_rays <= 0) return hipSuccess;
     const bool pt = S == 1;
@@ -164,10 +164,10 @@ hipError_t launch_field_input_grad(const float* params, const float* delta, int 
     else hipLaunchKernelGGL((field_input_grad_kernel<K, false>), grid, block, 0, stream, params, delta, rays, ray_stride, z_vals,  \
                             n_rays, S, d_rays, accumulate);
     switch (kind) {
-        case 0: NERF_IG(0) break;
-        case 2: NERF_IG(2) break;
-        case 3: NERF_IG(3) break;
-        case 4: NERF_IG(4) break;
+        case DELTA_ROWS_F32: NERF_IG(DELTA_ROWS_F32) break;
+        case DELTA_TILE32_BF16: NERF_IG(DELTA_TILE32_BF16) break;
+        case DELTA_TILE32_F16: NERF_IG(DELTA_TILE32_F16) break;
+        case DELTA_TILE32_F16X2: NERF_IG(DELTA_TILE32_F16X2) break;
         default: return hipErrorInvalidValue;
     }
 #undef NERF_IG
@@ -208,9 +208,7 @@ int nerf_field_input_grad(const float* params, const float* delta, const float* 
     BufTag t;
     REQUIRE(tag_lookup(delta, &t) && t.is_delta, "delta is not a buffer this library's dgrad wrote (no layout record)");
     REQUIRE(t.n_rays == n_rays && t.n_samples == n_samples, "delta buffer was written for another ray / sample count");
-    REQUIRE(t.kind == DELTA_ROWS_F32 || t.kind == DELTA_TILE32_BF16 || t.kind == DELTA_TILE32_F16 || t.kind == DELTA_TILE32_F16X2,
-            "delta buffer layout has no input-gradient reader");
-    return done(__func__, nerf::launch_field_input_grad(params, delta, t.kind, rays, ray_stride, z_vals, n_rays, n_samples, d_rays,
+    return done(__func__, nerf::launch_field_input_grad(params, delta, nerf::desc(t.dp).delta, rays, ray_stride, z_vals, n_rays, n_samples, d_rays,
                                                         accumulate, (hipStream_t)stream));
 }
 

@@ -7,6 +7,31 @@
 
 namespace nerf {
 
+// ---- the datapaths.  The public integer codes (the table at the top of include/nerf_hip.h) are decoded once, at the extern "C"
+// boundary (api_util.h); everything below it speaks these.  ActLayoutKind / DeltaKind: what nerf_buffer_layout reports (public values).
+enum ActLayoutKind { ACT_ROWS_F32 = 0, ACT_TILE16_BF16 = 4, ACT_TILE16_F16 = 5, ACT_TILE16_F16X2 = 6 /* hi + lo words (two-word saves) */ };
+enum DeltaKind { DELTA_ROWS_F32 = 0, DELTA_TILE32_BF16 = 2, DELTA_TILE32_F16 = 3, DELTA_TILE32_F16X2 = 4 };
+enum class Datapath { F32, BF16X3, F16X3, F16X3W };
+constexpr int N_DATAPATHS = 4;
+// the reduced inference forward ("fp16_fp8c": fp16 main term + fp8 corrections, field_ring8.h) is F16X3 in a forward-only mode: it
+// saves nothing, and its repack is the third pack form.  ReducedSkipLast leaves every ray's last sample to launch_field_fwd16r_last.
+enum class FwdMode { Full, Reduced, ReducedSkipLast };
+struct DatapathDesc {
+    bool split;             // on the weight-ring kernels: three-term split products, folded feature layer, tiled 16-bit saves
+    bool f16;               // fp16 parts (else bf16; csrc/split_types.h)
+    bool two_word;          // hi + lo words saved, three-term weight-gradient GEMM
+    ActLayoutKind act;      // what its forward writes
+    DeltaKind delta;        // what its dgrad writes
+    int family;             // layout family of the *_dp size entry points: 0 fp32 rows, 1 16-bit tiles, 2 hi + lo tiles
+};
+constexpr DatapathDesc DATAPATHS[N_DATAPATHS] = {
+    {false, false, false, ACT_ROWS_F32, DELTA_ROWS_F32, 0},
+    {true, false, false, ACT_TILE16_BF16, DELTA_TILE32_BF16, 1},
+    {true, true, false, ACT_TILE16_F16, DELTA_TILE32_F16, 1},
+    {true, true, true, ACT_TILE16_F16X2, DELTA_TILE32_F16X2, 2},
+};
+constexpr const DatapathDesc& desc(Datapath dp) { return DATAPATHS[(int)dp]; }
+
 struct CompositeArgs {
     const float* raw;       // [N][S][4]
     const float* z;         // [N][S]
@@ -81,7 +106,7 @@ struct RenderInferArgs {
     float *z_c, *raw_c, *w_c, *rgb_c, *disp_c, *acc_c;
     // fine pass
     float *z_f, *z_std, *raw_f, *rgb_f, *disp_f, *acc_f;
-    int split;              // 16-bit type of the three-term split the packed buffers were made for: 0 bf16, 1 fp16
+    int split;              // 16-bit type of the three-term split the packed buffers were made for: DatapathDesc::f16
 };
 bool render_infer_fused_ok(int n_c, int n_f);
 hipError_t launch_render_infer(const RenderInferArgs& a, hipStream_t stream);
@@ -96,8 +121,8 @@ hipError_t launch_mse_fwd(const float* x, const float* y, long n, float* scratch
 hipError_t launch_mse_bwd(const float* x, const float* y, long n, const float* g, float* dx, hipStream_t stream);
 hipError_t launch_embed(const float* x, long n_pts, int n_freqs, float* out, hipStream_t stream);
 hipError_t launch_embed_bwd(const float* x, long n_pts, int n_freqs, const float* d_out, float* d_x, int accumulate, hipStream_t stream);
-// input gradients of one field evaluation from its deltas (field_input_grad.hip); kind = the delta buffer's DeltaKind (api_util.h)
-hipError_t launch_field_input_grad(const float* params, const float* delta, int kind, const float* rays, int ray_stride,
+// input gradients of one field evaluation from its deltas (field_input_grad.hip); kind = what the dgrad wrote there
+hipError_t launch_field_input_grad(const float* params, const float* delta, DeltaKind kind, const float* rays, int ray_stride,
                                    const float* z_vals, int n_rays, int S, float* d_rays, int accumulate, hipStream_t stream);
 hipError_t launch_make_rays(int H, int W, const float* K9, const float* pose12, const float* pose_static12, int ndc,
                             float near, float far, float* rays, int ray_stride, hipStream_t stream);
@@ -124,7 +149,7 @@ hipError_t launch_field_dgrad(const float* packed, const float* act, const float
                               float* delta, hipStream_t stream);
 // live (split datapaths, nullable): the live-tile list the delta chain of the same pass wrote; the GEMM streams the live tiles only
 hipError_t launch_field_wgrad(const float* act, const float* delta, const float* d_raw, int n_rays, int S,
-                              float* partial, float* grad, int accumulate, int datapath /* 0 fp32, 4 bf16 operands, 5 fp16 operands */,
+                              float* partial, float* grad, int accumulate, Datapath dp,
                               int phases, hipStream_t stream, const float* params,      // canonical parameters: required by the split datapaths
                               const unsigned* live = nullptr);
 size_t wgrad_partial_floats(long P);
@@ -133,18 +158,19 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, int n, floa
 void pack_table_host(int* out);
 void pack3_table_host(int* out);
 void pack16_table_host(int* out);
-hipError_t launch_pack3_sel(const float* canon_params, float* packed, int streams, hipStream_t stream, int split = 0);
-hipError_t launch_pack3_pair(const float* params_a, float* packed_a, const float* params_b, float* packed_b, int streams, hipStream_t stream, int split);
+// the (hi, lo) fragment repack of a split datapath; mode Reduced: the reduced inference stream on top of F16X3's
+hipError_t launch_pack3_sel(const float* canon_params, float* packed, int streams, hipStream_t stream, Datapath dp, FwdMode mode);
+hipError_t launch_pack3_pair(const float* params_a, float* packed_a, const float* params_b, float* packed_b, int streams, hipStream_t stream, Datapath dp);
 // largest launches of the 16-point forward: n_rays * S points in all, and with saving (4.8 KB per point: 2^26 points = 320 GB)
 constexpr long FWD16R_MAX_POINTS = (1L << 31) - 1, FWD16R_MAX_SAVED_POINTS = 1L << 26;
-// split (ring kernels, repack, streaming weight-gradient GEMM): 0 = bf16 three-term split, 1 = fp16 (csrc/split_types.h)
+// dp: a split datapath (its repack in packed3); a mode other than Full needs F16X3 and act == nullptr
 hipError_t launch_field_fwd16r(const float* packed3, const float* rays, int ray_stride, const float* z_vals,
-                               int n_rays, int S, float* raw, float* act, int split, hipStream_t stream);
+                               int n_rays, int S, float* raw, float* act, Datapath dp, FwdMode mode, hipStream_t stream);
 hipError_t launch_field_fwd16r_last(const float* packed3, const float* rays, int ray_stride, const float* z_vals,
                                     int n_rays, int S, float* raw, const float* packed3_next, float* raw_next, int S_next,
                                     hipStream_t stream);
 hipError_t launch_field_dgrad3r(const float* packed3, const float* act, const float* d_raw, int n_rays, int S,
-                                float* delta, int split, hipStream_t stream, unsigned* live = nullptr);
+                                float* delta, Datapath dp, hipStream_t stream, unsigned* live = nullptr);
 
 // The live-tile list of one backward pass (caller-owned words; written by launch_field_dgrad3r, read by the delta chain and the
 // weight-gradient GEMM).  Tile t = points 32 t .. 32 t + 31 of the launch; dead = all 128 words of its d_raw are +-0.

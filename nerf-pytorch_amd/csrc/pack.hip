@@ -323,7 +323,7 @@ __global__ void pack8_kernel(const float* __restrict__ canon_params, const float
 }
 
 // one or two networks (params_b == nullptr: one) in the same two launches: derive_folded, then every selected stream
-hipError_t launch_pack3_pair(const float* params_a, float* packed_a, const float* params_b, float* packed_b, int streams, hipStream_t stream, int split) {
+hipError_t launch_pack3_pair(const float* params_a, float* packed_a, const float* params_b, float* packed_b, int streams, hipStream_t stream, Datapath dp) {
     const int threads = 256;
     const unsigned nets = params_b ? 2 : 1;
     PackPair pp{{params_a, params_b ? params_b : params_a}, {packed_a, params_b ? packed_b : packed_a}};
@@ -331,15 +331,16 @@ hipError_t launch_pack3_pair(const float* params_a, float* packed_a, const float
     const int n16f = (streams & 1) ? 2 * P16F_WORDS : 0, n3b = (streams & 4) ? 2 * (P3B_END - P3B_VIEWS) : 0;
     const long total = (long)n16f + n3b + (PACKED_FLOATS - SM_BIAS);
     const dim3 grid((unsigned)((total + threads - 1) / threads), nets);
-    if (split) hipLaunchKernelGGL(pack3_all_kernel<SplitF16>, grid, dim3(threads), 0, stream, pp, n16f, n3b);
+    if (desc(dp).f16) hipLaunchKernelGGL(pack3_all_kernel<SplitF16>, grid, dim3(threads), 0, stream, pp, n16f, n3b);
     else hipLaunchKernelGGL(pack3_all_kernel<SplitBF16>, grid, dim3(threads), 0, stream, pp, n16f, n3b);
     return hipGetLastError();
 }
 
-hipError_t launch_pack3_sel(const float* canon_params, float* packed, int streams, hipStream_t stream, int split) {
-    hipError_t e = launch_pack3_pair(canon_params, packed, nullptr, nullptr, streams, stream, split);
+hipError_t launch_pack3_sel(const float* canon_params, float* packed, int streams, hipStream_t stream, Datapath dp, FwdMode mode) {
+    if (mode != FwdMode::Full && dp != Datapath::F16X3) return hipErrorInvalidValue;
+    hipError_t e = launch_pack3_pair(canon_params, packed, nullptr, nullptr, streams, stream, dp);
     if (e != hipSuccess) return e;
-    if (split == 2) {       // reduced inference stream on top of the fp16 three-term stream (its narrow units and small parameters stay)
+    if (mode != FwdMode::Full) {       // reduced inference stream on top of the fp16 three-term stream (its narrow units and small parameters stay)
         const int threads = 256;
         const float* derived = packed + P3_DERIVED;
         hipLaunchKernelGGL(weight_scale_kernel, dim3(N_RED_MATRICES), dim3(1024), 0, stream, canon_params, derived, packed);

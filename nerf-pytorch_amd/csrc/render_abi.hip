@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 #include "nerf_common.h"
 #include "api_util.h"
-#include "launchers.h"
 
 using namespace nerf_api;
 
@@ -23,8 +22,7 @@ struct RenderWs {
     size_t zero_rgb;                // training only: [N][3] zeros, the d_rgb of a pass that receives only d_disp / d_acc
     size_t total;
 };
-RenderWs render_ws(int n_rays, int Sc, int Sf, int training, int precision) {
-    const int dp = precision == 0 ? 0 : (precision == 5 ? 2 : 1);      // scratch regions sized for the configured datapath (16-bit tiles on the split ones, hi + lo on 5)
+RenderWs render_ws(int n_rays, int Sc, int Sf, int training, Datapath dp) {     // scratch regions sized for the configured datapath's layouts
     RenderWs w{};
     const size_t N = (size_t)n_rays;
     const int S2 = Sc + Sf;
@@ -36,10 +34,10 @@ RenderWs render_ws(int n_rays, int Sc, int Sf, int training, int precision) {
     w.w_c = o;   o += up4(N * Sc);
     w.z_f = o;   o += up4(Sf > 0 ? N * S2 : 0);
     if (training) {
-        w.act_c = o; o += up4(nerf_act_floats_dp(n_rays, Sc, dp));
-        w.act_f = o; o += up4(Sf > 0 ? nerf_act_floats_dp(n_rays, S2, dp) : 0);
+        w.act_c = o; o += up4(act_floats(n_rays, Sc, dp));
+        w.act_f = o; o += up4(Sf > 0 ? act_floats(n_rays, S2, dp) : 0);
         w.d_raw = o; o += up4(N * (size_t)S2 * 4);
-        w.delta = o; o += up4(nerf_delta_floats_dp(n_rays, S2, dp));
+        w.delta = o; o += up4(delta_floats(n_rays, S2, dp));
         w.partial = o; o += up4(nerf_wgrad_partial_floats(n_rays, S2));
         w.zero_rgb = o; o += up4(N * 3);
     }
@@ -62,51 +60,28 @@ __global__ void add_inplace_kernel(float* dst, const float* src, size_t n) {
     if (i < n) dst[i] += src[i];
 }
 
-bool cfg_ok(const NerfRenderCfg* c) {
-    return c && c->n_coarse >= 3 && c->n_fine >= 0 && c->n_coarse + c->n_fine <= 4096 && (c->precision == 0 || c->precision == 1 || c->precision == 3 || c->precision == 5) &&
+// *dp: the datapath the configuration names
+bool cfg_ok(const NerfRenderCfg* c, Datapath* dp) {
+    return c && c->n_coarse >= 3 && c->n_fine >= 0 && c->n_coarse + c->n_fine <= 4096 && decode_precision(c->precision, dp) &&
            c->raw_noise_std >= 0.0f;
 }
 
-// field evaluation of one pass in the configured datapath; act == nullptr: inference
-hipError_t field_forward(const NerfRenderCfg* c, const float* packed, const float* rays, int stride, const float* z, int n, int S,
+// field evaluation of one pass on datapath dp; act == nullptr: inference
+hipError_t field_forward(Datapath dp, const float* packed, const float* rays, int stride, const float* z, int n, int S,
                          float* raw, float* act, hipStream_t st) {
-    if (c->precision == 0) {
-        if (act) tag_record(act, 0, ACT_ROWS_F32, n, S);
-        return nerf::launch_field_fwd(packed, rays, stride, z, n, S, raw, act, st);
-    }
-    if (c->precision == 5) {        // fp16 split, two-word saves
-        if (act) tag_record(act, 0, ACT_TILE16_F16X2, n, S);
-        return nerf::launch_field_fwd16r(packed, rays, stride, z, n, S, raw, act, act ? 5 : 1, st);
-    }
-    if (c->precision == 3) {        // fp16 split: 16-bit (fp16) rows always
-        if (act) tag_record(act, 0, ACT_TILE16_F16, n, S);
-        return nerf::launch_field_fwd16r(packed, rays, stride, z, n, S, raw, act, 1, st);
-    }
-    if (act) tag_record(act, 0, ACT_TILE16_BF16, n, S);
-    return nerf::launch_field_fwd16r(packed, rays, stride, z, n, S, raw, act, 0, st);
+    tag_record(act, 0, dp, n, S);
+    if (!nerf::desc(dp).split) return nerf::launch_field_fwd(packed, rays, stride, z, n, S, raw, act, st);
+    return nerf::launch_field_fwd16r(packed, rays, stride, z, n, S, raw, act, dp, FwdMode::Full, st);
 }
 
 // parameter gradient of one pass: dgrad + weight gradients into `grad`
-hipError_t field_backward(const NerfRenderCfg* c, const float* packed, const float* params, const float* act, const float* d_raw, int n, int S,
+hipError_t field_backward(Datapath dp, const float* packed, const float* params, const float* act, const float* d_raw, int n, int S,
                           float* delta, float* partial, float* grad, int accumulate, hipStream_t st) {
-    if (c->precision == 0) return nerf::launch_field_bwd(packed, act, d_raw, n, S, delta, partial, grad, accumulate, st);
-    hipError_t e;
-    if (c->precision == 5) {
-        e = nerf::launch_field_dgrad3r(packed, act, d_raw, n, S, delta, 5, st);
-        if (e != hipSuccess) return e;
-        tag_record(delta, 1, DELTA_TILE32_F16X2, n, S);
-        return nerf::launch_field_wgrad(act, delta, d_raw, n, S, partial, grad, accumulate, 6, 7, st, params);
-    }
-    if (c->precision == 3) {
-        e = nerf::launch_field_dgrad3r(packed, act, d_raw, n, S, delta, 1, st);
-        if (e != hipSuccess) return e;
-        tag_record(delta, 1, DELTA_TILE32_F16, n, S);
-        return nerf::launch_field_wgrad(act, delta, d_raw, n, S, partial, grad, accumulate, 5, 7, st, params);
-    }
-    e = nerf::launch_field_dgrad3r(packed, act, d_raw, n, S, delta, 0, st);
+    if (!nerf::desc(dp).split) return nerf::launch_field_bwd(packed, act, d_raw, n, S, delta, partial, grad, accumulate, st);
+    hipError_t e = nerf::launch_field_dgrad3r(packed, act, d_raw, n, S, delta, dp, st);
     if (e != hipSuccess) return e;
-    tag_record(delta, 1, DELTA_TILE32_BF16, n, S);
-    return nerf::launch_field_wgrad(act, delta, d_raw, n, S, partial, grad, accumulate, 4, 7, st, params);
+    tag_record(delta, 1, dp, n, S);
+    return nerf::launch_field_wgrad(act, delta, d_raw, n, S, partial, grad, accumulate, dp, 7, st, params);
 }
 
 }  // namespace
@@ -114,15 +89,17 @@ hipError_t field_backward(const NerfRenderCfg* c, const float* packed, const flo
 extern "C" {
 
 size_t nerf_render_workspace_floats(const NerfRenderCfg* cfg, int n_rays, int training) {
-    if (!cfg_ok(cfg) || n_rays <= 0) return 0;
-    return render_ws(n_rays, cfg->n_coarse, cfg->n_fine, training, cfg->precision).total;
+    Datapath dp;
+    if (!cfg_ok(cfg, &dp) || n_rays <= 0) return 0;
+    return render_ws(n_rays, cfg->n_coarse, cfg->n_fine, training, dp).total;
 }
 
 int nerf_render_rays_fwd(const NerfRenderCfg* cfg, const float* packed_c, const float* packed_f, const float* rays, int ray_stride,
                          int n_rays, const float* t_rand, const float* noise_c, const float* u, const float* noise_f,
                          float* rgb, float* disp, float* acc, float* raw, float* rgb0, float* disp0, float* acc0, float* z_std,
                          float* workspace, int training, void* stream) {
-    REQUIRE(cfg_ok(cfg), "bad NerfRenderCfg (n_coarse >= 3, n_fine >= 0, precision 0 / 1 / 3 / 5, raw_noise_std >= 0)");
+    Datapath dp;
+    REQUIRE(cfg_ok(cfg, &dp), "bad NerfRenderCfg (n_coarse >= 3, n_fine >= 0, precision 0 / 1 / 3 / 5, raw_noise_std >= 0)");
     REQUIRE(packed_c && rays && rgb && disp && acc && raw && workspace, "null pointer");
     REQUIRE(ray_stride >= 11, "rays must carry view directions (ray_stride >= 11): use_viewdirs=True architecture");
     REQUIRE(n_rays >= 0, "bad size");
@@ -130,11 +107,10 @@ int nerf_render_rays_fwd(const NerfRenderCfg* cfg, const float* packed_c, const 
     const bool fine = Sf > 0;
     REQUIRE(!fine || (rgb0 && disp0 && acc0 && z_std), "n_fine > 0 needs the coarse outputs rgb0 / disp0 / acc0 and z_std");
     REQUIRE(!(cfg->raw_noise_std > 0.0f) || (noise_c && (!fine || noise_f)), "raw_noise_std > 0 needs the noise draws");
-    REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(raw) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(packed_c) & 15) == 0, "workspace / raw / packed must be 16-byte aligned");
+    REQUIRE(aligned16(workspace, raw, packed_c), "workspace / raw / packed must be 16-byte aligned");
     if (n_rays == 0) return 0;
     const float* pf = (fine && packed_f) ? packed_f : packed_c;          // network_fine == None: the coarse network (run_nerf.py:400)
-    const RenderWs w = render_ws(n_rays, Sc, Sf, training, cfg->precision);
+    const RenderWs w = render_ws(n_rays, Sc, Sf, training, dp);
     hipStream_t st = (hipStream_t)stream;
     float* ws = workspace;
     hipLaunchKernelGGL(linspace01_kernel, dim3((Sc + 255) / 256), dim3(256), 0, st, ws + w.t_lin, Sc);
@@ -145,7 +121,7 @@ int nerf_render_rays_fwd(const NerfRenderCfg* cfg, const float* packed_c, const 
     e = nerf::launch_sample_coarse(rays, ray_stride, n_rays, ws + w.t_lin, Sc, cfg->lindisp, t_rand, ws + w.z_c, st);
     if (e != hipSuccess) return done(__func__, e);
     float* raw_c = fine ? ws + w.raw_c : raw;
-    e = field_forward(cfg, packed_c, rays, ray_stride, ws + w.z_c, n_rays, Sc, raw_c, training ? ws + w.act_c : nullptr, st);
+    e = field_forward(dp, packed_c, rays, ray_stride, ws + w.z_c, n_rays, Sc, raw_c, training ? ws + w.act_c : nullptr, st);
     if (e != hipSuccess) return done(__func__, e);
     {
         nerf::CompositeArgs a{raw_c, ws + w.z_c, rays + 3, cfg->raw_noise_std > 0.0f ? noise_c : nullptr, cfg->raw_noise_std,
@@ -162,7 +138,7 @@ int nerf_render_rays_fwd(const NerfRenderCfg* cfg, const float* packed_c, const 
         e = nerf::launch_sample_fine(a, st);
         if (e != hipSuccess) return done(__func__, e);
     }
-    e = field_forward(cfg, pf, rays, ray_stride, ws + w.z_f, n_rays, S2, raw, training ? ws + w.act_f : nullptr, st);
+    e = field_forward(dp, pf, rays, ray_stride, ws + w.z_f, n_rays, S2, raw, training ? ws + w.act_f : nullptr, st);
     if (e != hipSuccess) return done(__func__, e);
     nerf::CompositeArgs a{raw, ws + w.z_f, rays + 3, cfg->raw_noise_std > 0.0f ? noise_f : nullptr, cfg->raw_noise_std,
                           ray_stride, n_rays, S2, cfg->white_bkgd, rgb, disp, acc, nullptr, nullptr,
@@ -171,14 +147,16 @@ int nerf_render_rays_fwd(const NerfRenderCfg* cfg, const float* packed_c, const 
 }
 
 int nerf_render_infer_supported(const NerfRenderCfg* cfg) {
-    return cfg_ok(cfg) && cfg->precision != 0 && nerf::render_infer_fused_ok(cfg->n_coarse, cfg->n_fine) ? 1 : 0;
+    Datapath dp;
+    return cfg_ok(cfg, &dp) && nerf::desc(dp).split && nerf::render_infer_fused_ok(cfg->n_coarse, cfg->n_fine) ? 1 : 0;
 }
 
 int nerf_render_rays_infer(const NerfRenderCfg* cfg, const float* packed_c, const float* packed_f, const float* rays, int ray_stride,
                            int n_rays, const float* t_rand, const float* noise_c, const float* u, const float* noise_f,
                            float* rgb, float* disp, float* acc, float* raw, float* rgb0, float* disp0, float* acc0, float* z_std,
                            float* workspace, void* stream) {
-    REQUIRE(cfg_ok(cfg), "bad NerfRenderCfg (n_coarse >= 3, n_fine >= 0, precision 0 / 1 / 3 / 5, raw_noise_std >= 0)");
+    Datapath dp;
+    REQUIRE(cfg_ok(cfg, &dp), "bad NerfRenderCfg (n_coarse >= 3, n_fine >= 0, precision 0 / 1 / 3 / 5, raw_noise_std >= 0)");
     REQUIRE(nerf_render_infer_supported(cfg), "one-launch inference: a three-term split datapath (precision 1 / 3), 16 * n_coarse and 16 * (n_coarse + n_fine) "
             "multiples of 128, n_coarse + n_fine <= 1024 (use nerf_render_rays_fwd(training = 0) otherwise)");
     REQUIRE(packed_c && rays && rgb && disp && acc && raw && workspace, "null pointer");
@@ -188,10 +166,9 @@ int nerf_render_rays_infer(const NerfRenderCfg* cfg, const float* packed_c, cons
     const bool fine = Sf > 0;
     REQUIRE(!fine || (rgb0 && disp0 && acc0 && z_std), "n_fine > 0 needs the coarse outputs rgb0 / disp0 / acc0 and z_std");
     REQUIRE(!(cfg->raw_noise_std > 0.0f) || (noise_c && (!fine || noise_f)), "raw_noise_std > 0 needs the noise draws");
-    REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(raw) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(packed_c) & 15) == 0, "workspace / raw / packed must be 16-byte aligned");
+    REQUIRE(aligned16(workspace, raw, packed_c), "workspace / raw / packed must be 16-byte aligned");
     if (n_rays == 0) return 0;
-    const RenderWs w = render_ws(n_rays, Sc, Sf, 0, cfg->precision);
+    const RenderWs w = render_ws(n_rays, Sc, Sf, 0, dp);
     float* ws = workspace;
     const bool noisy = cfg->raw_noise_std > 0.0f;
     nerf::RenderInferArgs a{};
@@ -204,7 +181,7 @@ int nerf_render_rays_infer(const NerfRenderCfg* cfg, const float* packed_c, cons
     a.raw_c = fine ? ws + w.raw_c : raw;
     a.rgb_c = fine ? rgb0 : rgb; a.disp_c = fine ? disp0 : disp; a.acc_c = fine ? acc0 : acc;
     a.z_f = ws + w.z_f; a.z_std = z_std; a.raw_f = raw; a.rgb_f = rgb; a.disp_f = disp; a.acc_f = acc;
-    a.split = (cfg->precision == 3 || cfg->precision == 5) ? 1 : 0;
+    a.split = nerf::desc(dp).f16 ? 1 : 0;
     return done(__func__, nerf::launch_render_infer(a, (hipStream_t)stream));
 }
 
@@ -213,17 +190,19 @@ int nerf_render_rays_bwd(const NerfRenderCfg* cfg, const float* packed_c, const 
                          const float* noise_f, const float* raw, const float* d_rgb, const float* d_disp, const float* d_acc,
                          const float* d_raw_out, const float* d_rgb0, const float* d_disp0, const float* d_acc0,
                          float* workspace, float* grad_c, float* grad_f, int accumulate, void* stream) {
-    REQUIRE(cfg_ok(cfg), "bad NerfRenderCfg");
+    Datapath dp;
+    REQUIRE(cfg_ok(cfg, &dp), "bad NerfRenderCfg");
+    const bool split = nerf::desc(dp).split;
     REQUIRE(packed_c && rays && raw && workspace && grad_c, "null pointer");
-    REQUIRE(cfg->precision == 0 || params_c, "the split datapaths need the canonical parameters (folded feature layer)");
+    REQUIRE(!split || params_c, "the split datapaths need the canonical parameters (folded feature layer)");
     REQUIRE(ray_stride >= 11 && n_rays >= 0, "bad size");
     REQUIRE(!(cfg->raw_noise_std > 0.0f) || noise_c, "raw_noise_std > 0 needs the noise draws of the forward");
     if (n_rays == 0) return 0;
     const int Sc = cfg->n_coarse, Sf = cfg->n_fine, S2 = Sc + Sf;
     const bool fine = Sf > 0;
     const bool same_net = !fine || !packed_f || packed_f == packed_c;
-    REQUIRE(same_net || (grad_f && (cfg->precision == 0 || params_f)), "a separate fine network needs grad_f (and params_f)");
-    const RenderWs w = render_ws(n_rays, Sc, Sf, 1, cfg->precision);
+    REQUIRE(same_net || (grad_f && (!split || params_f)), "a separate fine network needs grad_f (and params_f)");
+    const RenderWs w = render_ws(n_rays, Sc, Sf, 1, dp);
     hipStream_t st = (hipStream_t)stream;
     float* ws = workspace;
     hipError_t e;
@@ -251,7 +230,7 @@ int nerf_render_rays_bwd(const NerfRenderCfg* cfg, const float* packed_c, const 
             hipError_t err = hipMemcpyAsync(d_raw, g_raw, n4 * sizeof(float), hipMemcpyDeviceToDevice, st);
             if (err != hipSuccess) return err;
         }
-        return field_backward(cfg, packed, params, act, d_raw, n_rays, S, ws + w.delta, ws + w.partial, grad, accum, st);
+        return field_backward(dp, packed, params, act, d_raw, n_rays, S, ws + w.delta, ws + w.partial, grad, accum, st);
     };
     bool wrote_c = false;
     if (fine) {

@@ -213,7 +213,7 @@ def packed_params_pair(model_a, model_b, precision):
     """(model_a.packed_params(precision), model_b.packed_params(precision)); when BOTH repacks are stale -- every training step, after
     the optimizer step -- the two networks are repacked in the two launches one takes (hb.pack_params_pair) instead of four."""
     precision = hb.PACK_OF.get(precision, precision)
-    if model_a is model_b or precision not in ("fp16x3", "bf16x3") or not (isinstance(model_a, NeRF) and isinstance(model_b, NeRF)):
+    if model_a is model_b or hb.DATAPATHS[precision].pack_streams != hb.PACK_ALL_STREAMS or not (isinstance(model_a, NeRF) and isinstance(model_b, NeRF)):
         return model_a.packed_params(precision), model_b.packed_params(precision)
     fa, fb = model_a._refresh_packed_cache(), model_b._refresh_packed_cache()
     if precision not in model_a._packed and precision not in model_b._packed and fa.device == fb.device:

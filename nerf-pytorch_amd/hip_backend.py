@@ -8,6 +8,7 @@ There is no fallback: if the library is missing or a call fails, this raises.
 """
 import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import torch  # import torch BEFORE loading the library: one HIP runtime per process (torch's bundled one)
 
@@ -280,9 +281,56 @@ def pack_table():
 # next to the hi words and the GEMM contracts d_hi X_hi + d_hi X_lo + d_lo X_hi (the forward's product class, ~2^-22, instead of 11-bit
 # operands) at twice the saved bytes and three times the GEMM's MFMAs.  Forward values are bit-identical to fp16x3's.  Not the default:
 # it is the instrument that prices the one-word operand storage (profiles/r06_*).
-PRECISIONS = ("fp32", "fp16x3", "bf16x3", "fp16_fp8c", "fp16x3w")
-SPLIT = ("fp16x3", "bf16x3", "fp16_fp8c", "fp16x3w")       # datapaths on the three-term-split kernels (folded feature layer, tiled saves)
-PACK_OF = {"fp16x3w": "fp16x3"}                 # datapaths that read another datapath's fragment repack
+class Datapath(NamedTuple):
+    """One precision name in every vocabulary of the C ABI (the table at the top of include/nerf_hip.h) and of the timer.  None = the
+    datapath has no such form: the fp32 entry points carry no code, the reduced inference class saves and trains nothing."""
+    family: int                     # layout family of nerf_*_floats_dp / nerf_debug_layout: 0 fp32 rows, 1 16-bit tiles, 2 hi + lo tiles
+    fwd_split: Optional[int]        # `split` of nerf_field_fwd_split without a save buffer
+    save_split: Optional[int]       # ... with one, and of nerf_field_dgrad_split[_live]
+    pack_of: str                    # whose fragment repack its kernels read: that datapath's ...
+    pack_streams: int               # ... `streams` and
+    pack_split: Optional[int]       # ... `split` of nerf_pack_params_split[_pair]
+    cfg: Optional[int]              # NerfRenderCfg.precision
+    wgrad: Optional[int]            # `datapath` of nerf_field_wgrad_phase[_live] (the binding itself passes -1, "as recorded")
+    elem16: Optional[torch.dtype]   # element type of the saved rows and deltas
+    fwd_label: str                  # KernelTimer labels: the forward without ...
+    save_label: Optional[str]       # ... and with saving,
+    dgrad_label: Optional[str]      # the delta chain,
+    gemm_label: Optional[str]       # the streaming weight-gradient GEMM
+    bytes_save: float = 0.0         # algorithmic HBM bytes per point: a saving forward,
+    bytes_dgrad: float = 0.0        # the delta chain,
+    bytes_gemm: float = 0.0         # the GEMM
+
+    @property
+    def fp16_saves(self):
+        """saves fp16 rows and deltas: the datapaths the RangeMonitor watches"""
+        return self.save_split is not None and self.elem16 is torch.float16
+
+
+PACK_ALL_STREAMS = 1 | 4        # the 16-point forward stream and the transposed streams of the delta chain
+DATAPATHS = {
+    "fp32": Datapath(0, None, None, "fp32", 0, None, 0, 0, None, "field_fwd_kernel", "field_fwd_kernel<save>", "field_dgrad_kernel", None,
+                     BYTES_ACT_PER_POINT, BYTES_DELTA_PER_POINT),
+    "fp16x3": Datapath(1, 1, 1, "fp16x3", PACK_ALL_STREAMS, 1, 3, 5, torch.float16, "field_fwd16r_kernel<fp16>", "field_fwd16r_kernel<fp16, save>",
+                       "field_dgrad3r_kernel<fp16>", "wgrad1_kernel<fp16>", BYTES_ACT3_BF16_PER_POINT, BYTES_DELTA3_BF16_PER_POINT, BYTES_WGRAD_MIXED_PER_POINT),
+    "bf16x3": Datapath(1, 0, 0, "bf16x3", PACK_ALL_STREAMS, 0, 1, 4, torch.bfloat16, "field_fwd16r_kernel", "field_fwd16r_kernel<save bf16>",
+                       "field_dgrad3r_kernel<bf16 out>", "wgrad1_kernel", BYTES_ACT3_BF16_PER_POINT, BYTES_DELTA3_BF16_PER_POINT, BYTES_WGRAD_MIXED_PER_POINT),
+    # the reduced inference stream (fp16 main + fp8 correction fragments) in the 16-point forward stream's slot; 3 = last sample left out
+    "fp16_fp8c": Datapath(1, 3, None, "fp16_fp8c", 1, 2, None, None, torch.float16, "field_fwd16r_kernel<fp16 + fp8c>", None, None, None),
+    # (5: two-word saves; the inference forward and the repack are fp16x3's)
+    "fp16x3w": Datapath(2, 1, 5, "fp16x3", PACK_ALL_STREAMS, 1, 5, 6, torch.float16, "field_fwd16r_kernel<fp16>", "field_fwd16r_kernel<fp16, save hi+lo>",
+                        "field_dgrad3r_kernel<fp16, hi+lo>", "wgrad1_kernel<fp16, 3 terms>", BYTES_ACT3_BF16_PER_POINT + BYTES_ACT3_LO_PER_POINT,
+                        2 * BYTES_DELTA3_BF16_PER_POINT, 2 * BYTES_WGRAD_MIXED_PER_POINT),
+}
+PRECISIONS = tuple(DATAPATHS)
+SPLIT = tuple(p for p, d in DATAPATHS.items() if d.family)     # datapaths on the three-term-split kernels (folded feature layer, tiled saves)
+PACK_OF = {p: d.pack_of for p, d in DATAPATHS.items() if d.pack_of != p}    # datapaths that read another datapath's fragment repack
+
+
+def _datapath(precision):
+    if precision not in DATAPATHS:
+        raise ValueError(f"precision must be one of {PRECISIONS}")
+    return DATAPATHS[precision]
 
 
 def pack_table3():
@@ -317,35 +365,26 @@ def _small_offset():
 
 def pack_params(flat, out=None, precision="fp32"):
     L = lib()
-    precision = PACK_OF.get(precision, precision)
-    if precision == "fp16_fp8c":    # the reduced inference stream (fp16 main + fp8 correction fragments) in the 16-point forward stream's slot
-        if out is None:
-            out = torch.empty(L.nerf_packed3_floats(), dtype=torch.float32, device=flat.device)
-        _check(L.nerf_pack_params_split(_ptr(flat, "params"), _ptr(out, "packed"), 1, 2, _stream()), "nerf_pack_params_split")
-        return out
-    if precision == "fp16x3":       # fp16 (hi, lo) fragments: the 16-point forward stream and the transposed streams of the delta chain
-        if out is None:
-            out = torch.empty(L.nerf_packed3_floats(), dtype=torch.float32, device=flat.device)
-        _check(L.nerf_pack_params_split(_ptr(flat, "params"), _ptr(out, "packed"), 1 | 4, 1, _stream()), "nerf_pack_params_split")
-        return out
-    if precision == "bf16x3":       # bf16 (hi, lo) fragments of the same two streams
-        if out is None:
-            out = torch.empty(L.nerf_packed3_floats(), dtype=torch.float32, device=flat.device)
-        _check(L.nerf_pack_params_split(_ptr(flat, "params"), _ptr(out, "packed"), 1 | 4, 0, _stream()), "nerf_pack_params_split")
-        return out
+    dp = DATAPATHS.get(precision, DATAPATHS["fp32"])
+    split = dp.pack_split is not None       # the (hi, lo) fragments of the split's type, in the streams its kernels read
     if out is None:
-        out = torch.empty(L.nerf_packed_floats(), dtype=torch.float32, device=flat.device)
-    _check(L.nerf_pack_params(_ptr(flat, "params"), _ptr(out, "packed"), _stream()), "nerf_pack_params")
+        out = torch.empty(L.nerf_packed3_floats() if split else L.nerf_packed_floats(), dtype=torch.float32, device=flat.device)
+    if split:
+        _check(L.nerf_pack_params_split(_ptr(flat, "params"), _ptr(out, "packed"), dp.pack_streams, dp.pack_split, _stream()), "nerf_pack_params_split")
+    else:
+        _check(L.nerf_pack_params(_ptr(flat, "params"), _ptr(out, "packed"), _stream()), "nerf_pack_params")
     return out
 
 
 def pack_params_pair(flat_a, flat_b, precision):
     """the (hi, lo) fragment repack of two networks in the two launches one takes (nerf_pack_params_split_pair; fp16x3 / bf16x3)"""
     L = lib()
-    split = {"bf16x3": 0, "fp16x3": 1}[PACK_OF.get(precision, precision)]
+    dp = DATAPATHS[precision]
+    if dp.pack_streams != PACK_ALL_STREAMS:
+        raise NerfHipError(f"pack_params_pair: {precision!r} has no paired repack")
     out_a = torch.empty(L.nerf_packed3_floats(), dtype=torch.float32, device=flat_a.device)
     out_b = torch.empty(L.nerf_packed3_floats(), dtype=torch.float32, device=flat_a.device)
-    _check(L.nerf_pack_params_split_pair(_ptr(flat_a, "params"), _ptr(out_a, "packed"), _ptr(flat_b, "params"), _ptr(out_b, "packed"), 1 | 4, split,
+    _check(L.nerf_pack_params_split_pair(_ptr(flat_a, "params"), _ptr(out_a, "packed"), _ptr(flat_b, "params"), _ptr(out_b, "packed"), dp.pack_streams, dp.pack_split,
                                          _stream()), "nerf_pack_params_split_pair")
     return out_a, out_b
 
@@ -474,26 +513,19 @@ def ray_pose_grad(W, K, d_rays, pixels, views, n_views, d_pose=None, accumulate=
     return d_pose
 
 
-def _dp(precision):
-    """datapath index of the *_dp size entry points: 0 = fp32 rows, 1 = 16-bit tiles of the split datapaths, 2 = hi + lo tiles"""
-    if precision not in PRECISIONS:
-        raise ValueError(f"precision must be one of {PRECISIONS}")
-    return 0 if precision == "fp32" else (2 if precision == "fp16x3w" else 1)
-
-
 def act_floats(n_rays, n_samples, precision=None):
     """floats of a save buffer: for `precision`'s layout (fp32 rows: 10.6 KB / point; split datapaths' 16-bit tiles: 4.8 KB / point), or,
     without a precision, the larger of the two (a buffer any datapath may write)"""
     if precision is None:
         return lib().nerf_act_floats(int(n_rays), int(n_samples))
-    return lib().nerf_act_floats_dp(int(n_rays), int(n_samples), _dp(precision))
+    return lib().nerf_act_floats_dp(int(n_rays), int(n_samples), _datapath(precision).family)
 
 
 def delta_floats(n_rays, n_samples, precision=None):
     """floats of the delta scratch of one backward pass (see act_floats)"""
     if precision is None:
         return lib().nerf_delta_floats(int(n_rays), int(n_samples))
-    return lib().nerf_delta_floats_dp(int(n_rays), int(n_samples), _dp(precision))
+    return lib().nerf_delta_floats_dp(int(n_rays), int(n_samples), _datapath(precision).family)
 
 
 class Workspace:
@@ -551,7 +583,7 @@ def workspace_floats(n_rays, n_coarse, n_fine, training=True, precision=None):
     passes + deltas + partial gradients of the larger pass) on `precision`'s layouts (None: the larger of the two); 0 for inference."""
     if precision is None:
         return lib().nerf_workspace_floats(int(n_rays), int(n_coarse), int(n_fine), int(bool(training)))
-    return lib().nerf_workspace_floats_dp(int(n_rays), int(n_coarse), int(n_fine), int(bool(training)), _dp(precision))
+    return lib().nerf_workspace_floats_dp(int(n_rays), int(n_coarse), int(n_fine), int(bool(training)), _datapath(precision).family)
 
 
 def max_saved_rays(n_coarse, n_fine, precision=None):
@@ -610,15 +642,6 @@ def buffer_regions(n_rays, n_samples, split, is_delta=False):
     return reg
 
 
-def _family(precision):
-    """nerf_debug_layout family of a datapath"""
-    return 0 if precision not in SPLIT else (2 if precision == "fp16x3w" else 1)
-
-
-def _elem16(precision):
-    return torch.bfloat16 if precision == "bf16x3" else torch.float16
-
-
 def _tile32(flat16, Pa, F, P):
     """32-point feature-major tiles of 16-bit elements -> point-major [P, F] fp32"""
     return flat16[:Pa * F].float().view(Pa // 32, F, 32).permute(0, 2, 1).reshape(Pa, F)[:P]
@@ -631,7 +654,7 @@ def saved_rows(buf, n_rays, n_samples, region, precision="fp32", part="hi"):
     with the row16h row order, the encoding in 32-point feature-major tiles (csrc/nerf_common.h)."""
     split = precision in SPLIT
     P = n_rays * n_samples
-    reg = buffer_regions(n_rays, n_samples, _family(precision))
+    reg = buffer_regions(n_rays, n_samples, DATAPATHS[precision].family)
     F = 64 if region == "enc" else _REGIONS[region][1]
     off = reg[region] + (reg["lo"] if part == "lo" else 0)      # part="lo" ("fp16x3w" only): the remainders T(v - hi)
     if part == "lo" and not reg["lo"]:
@@ -639,7 +662,7 @@ def saved_rows(buf, n_rays, n_samples, region, precision="fp32", part="hi"):
     if not split:
         return buf[off:off + P * F].view(P, F)
     Pa = (P + 31) // 32 * 32
-    flat = buf[off:off + (Pa * F + 1) // 2].view(_elem16(precision))
+    flat = buf[off:off + (Pa * F + 1) // 2].view(DATAPATHS[precision].elem16)
     if region == "enc":
         return _tile32(flat, Pa, F, P)
     rows = flat[:Pa * F].float().view(Pa // 16, F, 16).permute(0, 2, 1).reshape(Pa, F)[:P]      # [P, row]
@@ -648,7 +671,7 @@ def saved_rows(buf, n_rays, n_samples, region, precision="fp32", part="hi"):
 
 def saved_dir(buf, n_rays, n_samples, precision="fp32"):
     """the per-ray direction encoding a saving forward wrote: [n_rays, 32] fp32 (27 used)"""
-    off = buffer_regions(n_rays, n_samples, _family(precision))["dir"]
+    off = buffer_regions(n_rays, n_samples, DATAPATHS[precision].family)["dir"]
     return buf[off:off + n_rays * 32].view(n_rays, 32)
 
 
@@ -656,7 +679,7 @@ def saved_masks(buf, n_rays, n_samples, precision="fp32"):
     """the ReLU bitmask words of a save buffer as int32 [9, P, 8] (layers 0..7 + view branch; 256 bits per point and layer, in the
     lane order of the datapath's kernels: csrc/nerf_common.h)"""
     P = n_rays * n_samples
-    off = buffer_regions(n_rays, n_samples, _family(precision))["mask"]
+    off = buffer_regions(n_rays, n_samples, DATAPATHS[precision].family)["mask"]
     return buf[off:off + 9 * P * 8].view(torch.int32).view(9, P, 8)
 
 
@@ -690,7 +713,7 @@ def delta_rows(buf, n_rays, n_samples, region, precision="fp32", part="hi"):
     "graw" (split datapaths: the tiled 4-wide copy of the scaled d_raw)."""
     split = precision in SPLIT
     P = n_rays * n_samples
-    reg = buffer_regions(n_rays, n_samples, _family(precision), is_delta=True)
+    reg = buffer_regions(n_rays, n_samples, DATAPATHS[precision].family, is_delta=True)
     F = 4 if region == "graw" else _REGIONS[region][1]
     off = reg[region] + (reg["lo"] if part == "lo" else 0)
     if part == "lo" and not reg["lo"]:
@@ -698,7 +721,7 @@ def delta_rows(buf, n_rays, n_samples, region, precision="fp32", part="hi"):
     if not split:
         return buf[off:off + P * F].view(P, F)
     Pa = (P + 31) // 32 * 32
-    flat = buf[off:off + (Pa * F + 1) // 2].view(_elem16(precision))
+    flat = buf[off:off + (Pa * F + 1) // 2].view(DATAPATHS[precision].elem16)
     return _tile32(flat, Pa, F, P)
 
 
@@ -722,7 +745,7 @@ def render_cfg(n_coarse, n_fine, lindisp, white_bkgd, raw_noise_std, precision):
         raise NerfHipError("render_cfg: the one-call entry points run the fp32 / bf16x3 / fp16x3 datapaths; the reduced inference class "
                            "\"fp16_fp8c\" is a chain of launches with its last-sample guard in between (render._field_pass)")
     return NerfRenderCfg(int(n_coarse), int(n_fine), int(bool(lindisp)), int(bool(white_bkgd)), float(raw_noise_std),
-                         {"fp32": 0, "bf16x3": 1, "fp16x3": 3, "fp16x3w": 5}[precision], 1)
+                         DATAPATHS[precision].cfg, 1)
 
 
 def render_infer_supported(n_coarse, n_fine, precision):
@@ -867,40 +890,27 @@ def field_fwd(packed, rays, z_vals, save_act=False, precision="fp32", guard_pack
         act = WORKSPACE.take(act_floats(n, S, precision), rays.device)
     elif act.numel() < act_floats(n, S, precision) or act.dtype != torch.float32 or not act.is_contiguous():
         raise NerfHipError(f"field_fwd: act= must be a contiguous float32 buffer of at least {act_floats(n, S, precision)} floats")
-    nbytes = BYTES_ACT_PER_POINT * n * S if save_act else 16.0 * n * S
-    if precision in SPLIT:
-        nbytes = BYTES_ACT3_PER_POINT * n * S if save_act else 16.0 * n * S
-    if precision == "fp16_fp8c":
-        if save_act:
-            raise NerfHipError("field_fwd: \"fp16_fp8c\" is an inference class (no saved activations); train on \"fp16x3\"")
-        if guard_packed is None:
-            raise NerfHipError("field_fwd: \"fp16_fp8c\" needs guard_packed= (the fp16x3 repack) for the last-sample guard")
-        with _timed("field_fwd16r_kernel<fp16 + fp8c>", FLOP_FWD3_PER_POINT * n * S, nbytes):
-            _check(lib().nerf_field_fwd_split(_ptr(packed, "packed3"), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"),
-                                              n, S, _ptr(raw), None, 3, _stream()), "nerf_field_fwd_split")
+    dp = DATAPATHS.get(precision, DATAPATHS["fp32"])
+    if save_act and dp.save_label is None:
+        raise NerfHipError(f"field_fwd: \"{precision}\" is an inference class (no saved activations); train on \"fp16x3\"")
+    if precision == "fp16_fp8c" and guard_packed is None:
+        raise NerfHipError("field_fwd: \"fp16_fp8c\" needs guard_packed= (the fp16x3 repack) for the last-sample guard")
+    with _timed(dp.save_label if save_act else dp.fwd_label, (FLOP_FWD3_PER_POINT if dp.family else FLOP_FWD_PER_POINT) * n * S,
+                (dp.bytes_save if save_act else 16.0) * n * S):
+        if dp.family:
+            _check(lib().nerf_field_fwd_split(_ptr(packed, "packed3"), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"), n, S,
+                                              _ptr(raw), _ptr(act, "act", True), dp.save_split if save_act else dp.fwd_split, _stream()),
+                   "nerf_field_fwd_split")
+        else:
+            _check(lib().nerf_field_fwd(_ptr(packed, "packed"), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"), n, S,
+                                        _ptr(raw), _ptr(act, "act", True), _stream()), "nerf_field_fwd")
+    if precision == "fp16_fp8c":        # the guard of the reduced class: every ray's last sample on the three-term fp16 products
         if not (isinstance(guard_packed, str) and guard_packed == "done"):
             nxt, raw_n, S_n = (None, None, 0) if next_guard is None else (next_guard[0], next_guard[1], next_guard[1].shape[1])
             with _timed("field_fwd16r_kernel<fp16> (last samples)", FLOP_FWD3_PER_POINT * n * (1 if nxt is None else 2), 16.0 * n):
                 _check(lib().nerf_field_fwd_last_sample(_ptr(guard_packed, "packed3"), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"),
                                                         n, S, _ptr(raw), _ptr(nxt, "packed3", True), _ptr(raw_n, "raw", True), S_n,
                                                         _stream()), "nerf_field_fwd_last_sample")
-        return raw, act
-    if precision in ("fp16x3", "fp16x3w"):
-        two = precision == "fp16x3w" and save_act
-        with _timed("field_fwd16r_kernel<fp16" + (", save hi+lo>" if two else ", save>" if save_act else ">"), FLOP_FWD3_PER_POINT * n * S,
-                    (BYTES_ACT3_BF16_PER_POINT + (BYTES_ACT3_LO_PER_POINT if two else 0)) * n * S if save_act else nbytes):
-            _check(lib().nerf_field_fwd_split(_ptr(packed, "packed3"), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"),
-                                              n, S, _ptr(raw), _ptr(act, "act", True), 5 if two else 1, _stream()), "nerf_field_fwd_split")
-        return raw, act
-    if precision == "bf16x3":
-        with _timed("field_fwd16r_kernel" + ("<save bf16>" if save_act else ""), FLOP_FWD3_PER_POINT * n * S,
-                    BYTES_ACT3_BF16_PER_POINT * n * S if save_act else nbytes):
-            _check(lib().nerf_field_fwd_split(_ptr(packed, "packed3"), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"),
-                                              n, S, _ptr(raw), _ptr(act, "act", True), 0, _stream()), "nerf_field_fwd_split")
-        return raw, act
-    with _timed("field_fwd_kernel<save>" if save_act else "field_fwd_kernel", FLOP_FWD_PER_POINT * n * S, nbytes):
-        _check(lib().nerf_field_fwd(_ptr(packed, "packed"), _ptr(rays, "rays"), stride, _ptr(z_vals, "z_vals"), n, S,
-                                    _ptr(raw), _ptr(act, "act", True), _stream()), "nerf_field_fwd")
     return raw, act
 
 
@@ -1091,7 +1101,7 @@ def field_input_grad(params, delta, rays, z_vals, d_rays, accumulate, precision=
     n, S = z_vals.shape
     P = n * S
     with _timed("field_input_grad_kernel", 2.0 * P * (2 * 63 * 256 + 27 * 128),
-                BYTES_INPUT_GRAD_PER_POINT * P * (1 if precision in ("bf16x3", "fp16x3", "fp16_fp8c") else 2)):
+                BYTES_INPUT_GRAD_PER_POINT * P * (1 if DATAPATHS[precision].family == 1 else 2)):
         _check(lib().nerf_field_input_grad(_ptr(params, "params"), _ptr(delta, "delta"), _ptr(rays, "rays"), rays.shape[1],
                                            _ptr(z_vals, "z_vals"), n, S, _ptr(d_rays, "d_rays"), int(bool(accumulate)), _stream()),
                "nerf_field_input_grad")
@@ -1108,8 +1118,10 @@ def embed_bwd(x, n_freqs, d_out):
 
 
 def _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partial, n, S, params, input_grad=None):
-    split = {"bf16x3": 0, "fp16x3": 1, "fp16x3w": 5}.get(precision)
-    two = split == 5
+    dp = DATAPATHS.get(precision, DATAPATHS["fp32"])
+    if dp.save_split is None:       # nothing trains on it: the fp32 entry points
+        dp = DATAPATHS["fp32"]
+    split = dp.save_split
     # what the forward wrote into `act` (the library's own record, nerf_buffer_layout); the weight-gradient call below passes
     # datapath = -1 ("as recorded"), and a mismatched pairing is refused by the library (NERF_E_BADARG)
     kind = buffer_layout(act)[0]
@@ -1121,23 +1133,20 @@ def _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partia
     # meet the tiles nobody wrote
     global LAST_LIVE
     live = None
-    if split is not None and BWD_SKIP_DEAD and input_grad is None and not (split in (1, 5) and RANGE_MONITOR.delta_scans_due > 0):
+    if split is not None and BWD_SKIP_DEAD and input_grad is None and not (dp.fp16_saves and RANGE_MONITOR.delta_scans_due > 0):
         live = live_list(n, S, d_raw.device)
     LAST_LIVE = live
-    if split is not None:
-        with _timed("field_dgrad3r_kernel<fp16, hi+lo>" if two else "field_dgrad3r_kernel<fp16>" if split else "field_dgrad3r_kernel<bf16 out>",
-                    FLOP_DGRAD3_PER_POINT * P, BYTES_DELTA3_BF16_PER_POINT * P * (2 if two else 1)):
-            if live is not None:
-                _check(L.nerf_field_dgrad_split_live(_ptr(packed, "packed3"), _ptr(act, "act"), _ptr(d_raw, "d_raw"), n, S, _ptr(delta), split,
-                                                     live.data_ptr(), _stream()), "nerf_field_dgrad_split_live")
-            else:
-                _check(L.nerf_field_dgrad_split(_ptr(packed, "packed3"), _ptr(act, "act"), _ptr(d_raw, "d_raw"), n, S, _ptr(delta), split, _stream()),
-                       "nerf_field_dgrad_split")
-    else:
-        with _timed("field_dgrad_kernel", FLOP_DGRAD_PER_POINT * P, BYTES_DELTA_PER_POINT * P):
+    with _timed(dp.dgrad_label, (FLOP_DGRAD3_PER_POINT if dp.family else FLOP_DGRAD_PER_POINT) * P, dp.bytes_dgrad * P):
+        if live is not None:
+            _check(L.nerf_field_dgrad_split_live(_ptr(packed, "packed3"), _ptr(act, "act"), _ptr(d_raw, "d_raw"), n, S, _ptr(delta), split,
+                                                 live.data_ptr(), _stream()), "nerf_field_dgrad_split_live")
+        elif split is not None:
+            _check(L.nerf_field_dgrad_split(_ptr(packed, "packed3"), _ptr(act, "act"), _ptr(d_raw, "d_raw"), n, S, _ptr(delta), split, _stream()),
+                   "nerf_field_dgrad_split")
+        else:
             _check(L.nerf_field_dgrad(_ptr(packed, "packed"), _ptr(act, "act"), _ptr(d_raw, "d_raw"), n, S, _ptr(delta),
                                       _stream()), "nerf_field_dgrad")
-    if split in (1, 5):
+    if dp.fp16_saves:
         RANGE_MONITOR.after_dgrad(delta, n, S)      # (scans the deltas on the steps whose forward was scanned; nothing otherwise)
     if input_grad is not None:
         rays, z_vals, d_rays, acc_rays = input_grad
@@ -1157,8 +1166,7 @@ def _field_bwd(L, packed, act, d_raw, grad, accumulate, precision, delta, partia
         _check(wgrad_phase(*args, 7, *tail), "nerf_field_wgrad_phase")
         return grad
     if gemm16:      # all 12 jobs stream 16-bit operands straight into the MFMA
-        with _timed("wgrad1_kernel<fp16, 3 terms>" if two else "wgrad1_kernel<fp16>" if split else "wgrad1_kernel", FLOP_WGRAD3_PER_POINT * P,
-                    BYTES_WGRAD_MIXED_PER_POINT * P * (2 if two else 1)):
+        with _timed(dp.gemm_label, FLOP_WGRAD3_PER_POINT * P, dp.bytes_gemm * P):
             _check(wgrad_phase(*args, 3, *tail), "nerf_field_wgrad_phase")
     else:
         with _timed("wgrad256_kernel", FLOP_WGRAD_BIG_PER_POINT * P, BYTES_WGRAD_BIG_PER_POINT * P):

@@ -286,7 +286,7 @@ class _RenderRays(torch.autograd.Function):
             else:
                 out_keys = ("rgb_c", "disp_c", "acc_c", "raw_c") if n_f <= 0 else ("rgb_f", "disp_f", "acc_f", "raw_f", "rgb_c", "disp_c", "acc_c", "z_std")
                 r = {k_: torch.cat([p_[k_] for p_ in parts], 0) for k_ in out_keys + (("distortion",) if dist else ()) + (("interlevel",) if inter else ())}
-        if need and not ctx.checkpoint and prec in ("fp16x3", "fp16x3w"):
+        if need and not ctx.checkpoint and hb.DATAPATHS[prec].fp16_saves:
             # the fp16 split's range guard rail: every RANGE_MONITOR.every-th training render scans what the forward saved
             # (hb.RangeMonitor; replaces run_nerf.py:414-416's DEBUG-gated NaN / Inf check)
             for r_, n_ in ([(r, n)] if ctx.tiles is None else [(p_, hi - lo) for p_, (lo, hi) in zip(parts, ctx.tiles)]):
@@ -971,7 +971,7 @@ class _RenderRaysGrid(torch.autograd.Function):
             raise
         _grid_stats(grid, stats, torch.stack(n_stopped).sum() if n_stopped else None, torch.stack(n_truncated).sum() if n_truncated else None,
                     torch.stack(n_refit).sum() if n_refit else None)
-        if prec in ("fp16x3", "fp16x3w"):       # the fp16 split's range guard rail sees the compacted passes' saved activations
+        if hb.DATAPATHS[prec].fp16_saves:       # the fp16 split's range guard rail sees the compacted passes' saved activations
             for passes in parts:
                 acts = [(p["act"], 1) for p in passes if p["act"] is not None]
                 if acts:

@@ -293,7 +293,7 @@ def _one_call_step(npa, dev, flat_c, flat_f, rays, rnd, target, precision, lr_st
     n = rays.shape[0]
     s = torch.cuda.current_stream().cuda_stream
     ptr = lambda t: None if t is None else t.data_ptr()
-    prec = {"fp32": 0, "bf16x3": 1, "fp16x3": 3, "fp16x3w": 5}[precision]
+    prec = hb.DATAPATHS[precision].cfg
     cfg = hb.NerfRenderCfg(64, 128, 0, 1, 1.0 if "noise_c" in rnd else 0.0, prec, 0)
     packed = []
     for flat in (flat_c, flat_f):

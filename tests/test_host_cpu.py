@@ -500,6 +500,62 @@ def test_buffer_tags_refuse_mismatched_pairings():
     assert L.nerf_field_wgrad_phase(0x900000, 0xA00000, d_raw, 0, 64, partial, grad, 0, -1, 7, params, None) == -1
 
 
+def test_datapath_table_and_library_agree_on_every_pairing():
+    """Characterisation of the pairing rules, walked over hip_backend.DATAPATHS: which save-buffer kind each forward records, which
+    (forward, dgrad) pairs the dgrad accepts and which delta kind it records, which weight-gradient codes each accepted pair takes,
+    the forward-only `split` codes, the buffer sizes and the NerfRenderCfg codes.  The expectations are spelled per precision NAME, so
+    a datapath added to the table or to the library alone fails here.  Host-only (n_rays = 0, fake aligned addresses)."""
+    import nerf_pytorch_amd as npa
+    hb = npa.hip_backend
+    L = hb.lib()
+    ACT_KIND = {"fp32": 0, "bf16x3": 4, "fp16x3": 5, "fp16x3w": 6}
+    DELTA_KIND = {"fp32": 0, "bf16x3": 2, "fp16x3": 3, "fp16x3w": 4}
+    WGRAD = {"fp32": 0, "bf16x3": 4, "fp16x3": 5, "fp16x3w": 6}
+    CFG = {"fp32": 0, "bf16x3": 1, "fp16x3": 3, "fp16x3w": 5}
+    ACCEPTED = {("fp32", "fp32"), ("bf16x3", "bf16x3"), ("bf16x3", "fp16x3"), ("fp16x3", "bf16x3"), ("fp16x3", "fp16x3"), ("fp16x3w", "fp16x3w")}
+    SIZES = {"fp32": (182320, 170240), "fp16x3": (124656, 114884), "bf16x3": (124656, 114884), "fp16_fp8c": (124656, 114884),
+             "fp16x3w": (249312, 229768)}
+    train = {p: d for p, d in hb.DATAPATHS.items() if d.wgrad is not None}
+    assert set(train) == set(ACT_KIND) and set(hb.DATAPATHS) == set(SIZES) == set(hb.PRECISIONS)
+    packed, rays, z, raw, d_raw, partial, grad, params = (0x10000 * (k + 1) for k in range(8))
+    fresh = iter(range(0x1000000, 0x2000000, 0x10000))
+    kind = lambda buf: L.nerf_buffer_layout(buf, None, None, None)
+
+    def fwd(dp, act):
+        if dp.save_split is None:
+            return L.nerf_field_fwd(packed, rays, 11, z, 0, 64, raw, act, None)
+        return L.nerf_field_fwd_split(packed, rays, 11, z, 0, 64, raw, act, dp.save_split, None)
+
+    def dgrad(dp, act, delta):
+        if dp.save_split is None:
+            return L.nerf_field_dgrad(packed, act, d_raw, 0, 64, delta, None)
+        return L.nerf_field_dgrad_split(packed, act, d_raw, 0, 64, delta, dp.save_split, None)
+    for f, dp_f in train.items():
+        assert (dp_f.wgrad, dp_f.cfg) == (WGRAD[f], CFG[f]) and hb.render_cfg(64, 128, False, False, 0.0, f).precision == CFG[f]
+        for d, dp_d in train.items():
+            act, delta = next(fresh), next(fresh)
+            assert fwd(dp_f, act) == 0 and kind(act) == ACT_KIND[f], (f, d)
+            rc = dgrad(dp_d, act, delta)
+            assert rc == (0 if (f, d) in ACCEPTED else -1), (f, d)
+            if rc:
+                continue
+            assert kind(delta) == DELTA_KIND[d], (f, d)
+            wgrad = lambda code: L.nerf_field_wgrad_phase(act, delta, d_raw, 0, 64, partial, grad, 0, code, 7, params, None)
+            assert wgrad(-1) == (0 if f == d else -1), (f, d)
+            assert f == d or b"different datapaths" in L.nerf_last_error()
+            for c in train:
+                assert wgrad(WGRAD[c]) == (0 if f == d == c else -1), (f, d, c)
+    # the forward-only codes: the reduced inference form saves nothing and has no dgrad
+    reduced = hb.DATAPATHS["fp16_fp8c"]
+    assert (reduced.fwd_split, reduced.pack_split, reduced.save_split) == (3, 2, None)
+    for split, want in ((2, 0), (3, 0), (4, -1), (6, -1), (-1, -1)):
+        assert L.nerf_field_fwd_split(packed, rays, 11, z, 0, 64, raw, None, split, None) == want, split
+        assert L.nerf_field_dgrad_split(packed, next(fresh), d_raw, 0, 64, next(fresh), split, None) == -1, split
+    assert L.nerf_field_fwd_split(packed, rays, 11, z, 0, 64, raw, next(fresh), 2, None) == -1
+    for p in hb.DATAPATHS:
+        assert (hb.act_floats(10, 7, p), hb.delta_floats(10, 7, p)) == SIZES[p], p
+
+
 # ---------------------------------------------------------------- build hygiene: no heavy kernel spills
 HEAVY_KERNELS = ["field_fwd16r_kernel<2, nerf::SplitF16, false>", "field_fwd16r_kernel<0, nerf::SplitF16, false>",
                  "field_fwd16r_kernel<0, nerf::SplitF16, true>", "field_fwd16r_last2_kernel<nerf::SplitF16>",

@@ -84,14 +84,15 @@ def main():
         partial = torch.empty(L.nerf_wgrad_partial_floats(n, S), device=dev)
         grad = torch.empty(hb.N_PARAMS, device=dev)
         s = torch.cuda.current_stream().cuda_stream
-        split = {"bf16x3": 0, "fp16x3": 1, "fp16x3w": 5}.get(prec)       # (5: two-word saves; the inference forward is split 1's)
+        dp = hb.DATAPATHS[prec]
+        split = dp.save_split
         flat = net.flat_params()
         if split is None:
             fwd_i = lambda: L.nerf_field_fwd(packed.data_ptr(), rays.data_ptr(), 11, z.data_ptr(), n, S, raw.data_ptr(), None, s)
             fwd_s = lambda: L.nerf_field_fwd(packed.data_ptr(), rays.data_ptr(), 11, z.data_ptr(), n, S, raw.data_ptr(), act.data_ptr(), s)
             dgrad = lambda: L.nerf_field_dgrad(packed.data_ptr(), act.data_ptr(), d_raw.data_ptr(), n, S, delta.data_ptr(), s)
         else:
-            fwd_i = lambda: L.nerf_field_fwd_split(packed.data_ptr(), rays.data_ptr(), 11, z.data_ptr(), n, S, raw.data_ptr(), None, split, s)
+            fwd_i = lambda: L.nerf_field_fwd_split(packed.data_ptr(), rays.data_ptr(), 11, z.data_ptr(), n, S, raw.data_ptr(), None, dp.fwd_split, s)
             fwd_s = lambda: L.nerf_field_fwd_split(packed.data_ptr(), rays.data_ptr(), 11, z.data_ptr(), n, S, raw.data_ptr(), act.data_ptr(), split, s)
             dgrad = lambda: L.nerf_field_dgrad_split(packed.data_ptr(), act.data_ptr(), d_raw.data_ptr(), n, S, delta.data_ptr(), split, s)
         wargs = (act.data_ptr(), delta.data_ptr(), d_raw.data_ptr(), n, S, partial.data_ptr(), grad.data_ptr(), 0, -1)
