@@ -717,6 +717,43 @@ int nerf_baked_render(const NerfOccGrid* grid, const int* node_index, const void
                       float stop_eps, int white_bkgd, float* rgb_map, float* disp_map, float* acc_map, float* depth_map,
                       int* n_samples, void* stream);
 
+/* ---- baked field, training (additive in ABI v10): the render above with stop_eps = 0 and its backward to the table's rows
+ * (baked.BakedTrainer; BakedTrainer.render_rays_reference is the definition, DESIGN.md 3.23 the closed form).  No atomics anywhere:
+ * every contribution is stored once and summed per destination in a fixed order, so the same inputs give the same bits.
+ *   nerf_baked_count: counts [n] = the kept candidates of every ray -- nerf_baked_render's walk without the table, never a stop.
+ *   nerf_baked_train_fwd: rgb_map, acc_map, depth_map as nerf_baked_render writes them with stop_eps = 0, bit for bit, and one record
+ *     per kept sample at offsets[ray] + (its rank among the ray's kept samples): ray-major, sample-minor.  offsets int [n + 1] is the
+ *     exclusive running sum of nerf_baked_count's counts, offsets[n] = total <= 2^30; records [total][12] words, 16-byte aligned:
+ *       cell = (ix Ry + iy) Rz + iz and ray (int32), fx, fy, fz, z, e = expf(-sigma step_size), T, c_R, c_G, c_B, gate (1 where the
+ *       blended v0 >= 0, else 0).
+ *     A position outside [0, total) is not written.
+ *   nerf_baked_train_bwd_samples: sample_grads [total][4] = (dL/dv0, dL/dl_R, dL/dl_G, dL/dl_B) of every sample from the upstream
+ *     g_rgb [n][3], g_acc [n], g_depth [n]: with alpha = 1 - e, t = 1 - alpha + 1e-10, w = alpha T, g_acc' = g_acc - (G_R + G_G + G_B)
+ *     under white_bkgd, q = G . c + g_acc' + g_depth z and S_k = sum_{j > k} q_j w_j (summed back to front, a suffix, never a total
+ *     minus a prefix): dL/dalpha = q T - S / t, dL/dv0 = gate dL/dalpha step_size e, dL/dl_c = w G_c c (1 - c).
+ *   nerf_baked_train_bwd_rows: grad fp32 [n_rows][W] (W as above), every element written: row_node [n_rows] is the lattice node of a
+ *     row (the inverse of node_index; -1 for row 0); order [total] holds the samples sorted by cell, stable (so ascending (ray, k)
+ *     inside a cell), cell_start [Rx Ry Rz + 1] the first entry of every cell.  A row's columns are summed over its adjacent cells in
+ *     corner order 000 001 .. 111 and each cell's samples in the order of `order`: term = ((wx wy) wz) * contribution, contribution =
+ *     dL/dv0 for column 0 and dL/dl_c * Y_b(viewdir of the sample's ray) for column 1 + c B + b, one product and one addition per
+ *     term, in three levels of that same order: the consecutive samples of one ray in a cell are summed, these runs are added to
+ *     the cell's sum, the cells' sums to the row's.  Row 0, rows without a node and the padding columns are zero.  total == 0 or
+ *     n_rays == 0 writes zeros.
+ * ray_stride >= 11; sh_degree 0, 1 or 2; step_size finite and > 0; 1 <= max_steps <= 2^24; 1 <= n_rows (<= 2^26 in bwd_rows);
+ * 0 <= total <= 2^30; table, records and sample_grads 16-byte aligned.  n_rays == 0 is a no-op in the first three (in bwd_rows rays may
+ * then be null). */
+int nerf_baked_count(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* u /* nullable: 0.5 */, int n_rays,
+                     float step_size, int max_steps, int* counts, void* stream);
+int nerf_baked_train_fwd(const NerfOccGrid* grid, const int* node_index, const void* table /* fp16 rows */, int n_rows, int sh_degree,
+                         const float* rays, int ray_stride, const float* u /* nullable: 0.5 */, int n_rays, float step_size, int max_steps,
+                         int white_bkgd, const int* offsets, int total, float* records, float* rgb_map, float* acc_map, float* depth_map,
+                         void* stream);
+int nerf_baked_train_bwd_samples(const float* records, const int* offsets, int n_rays, int total, float step_size, int white_bkgd,
+                                 const float* g_rgb, const float* g_acc, const float* g_depth, float* sample_grads, void* stream);
+int nerf_baked_train_bwd_rows(const NerfOccGrid* grid, const int* row_node, int n_rows, int sh_degree, const float* rays, int ray_stride,
+                              int n_rays, const float* records, const float* sample_grads, const int* order, const int* cell_start,
+                              int total, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,13 @@ occupancy grid instead (PlenOctrees, Yu et al. 2021; SNeRG, Hedman et al. 2021):
 density and the coefficients of the colour logits in the real spherical harmonics of degree <= 2, and a ray is rendered by marching
 the grid in world-space steps, blending the eight nodes of each kept sample's cell and compositing on the spot (csrc/baked.hip,
 nerf_baked_render).  ``BakedField.render_rays_reference`` is the definition the kernel is tested against; ``render_rays(...,
-baked=field)`` and ``render_kwargs_test["baked"] = field`` are the ways in.  No gradients: a baked field is an inference artefact.
+baked=field)`` and ``render_kwargs_test["baked"] = field`` are the ways in.  A ``BakedField`` itself has no gradients: it is an inference
+artefact.  Its trainable twin is ``BakedTrainer`` (``field.trainable()``): an fp32 master copy of the table, the same render with a
+deterministic backward to the table's rows (csrc/baked_train.hip: every contribution stored once and summed per row in a fixed order, no
+atomics), so the table can be fitted to images through the renderer (PlenOctrees' fine-tuning, Plenoxels) and written back with
+``to_field()``.
 """
+import copy
 import math
 
 import numpy as np
@@ -84,6 +89,85 @@ def fibonacci_sphere(n, dtype=torch.float64, device=None):
     phi = i * (math.pi * (3.0 - math.sqrt(5.0)))
     s = torch.sqrt(torch.clamp(1.0 - z * z, min=0.0))
     return torch.stack([s * torch.cos(phi), s * torch.sin(phi), z], -1).to(dtype=dtype, device=device)
+
+
+def _render_reference(who, grid, index, table, sh_degree, step_size, stop_eps, rays, u, white_bkgd, max_steps, dtype, values):
+    """BakedField.render_rays_reference's body (its docstring is the definition), shared with BakedTrainer.render_rays_reference: `values`
+    [n_rows, >= 1 + 3B] stands in for the table where it is not None, and may require grad -- everything behind the gather is ordinary
+    differentiable torch"""
+    max_steps = _check_max_steps(max_steps, who)
+    r, ok, uu, dn, M, _ = OccupancyGrid._march_rays(who, rays, u, max_steps, 1)
+    if rays.shape[1] < 11:
+        raise ValueError(f"{who}: rays [N, >= 11] (o, d, near, far, viewdir)")
+    dev = rays.device
+    N = r.shape[0]
+    ds32 = torch.tensor(step_size, dtype=torch.float32, device=dev)
+    dz = ds32 / dn
+    ok = ok & (dz[:, 0] > 0) & torch.isfinite(dz[:, 0])
+    out_rgb = torch.zeros((N, 3), dtype=dtype, device=dev)
+    out_acc = torch.zeros(N, dtype=dtype, device=dev)
+    out_depth = torch.zeros(N, dtype=dtype, device=dev)
+    n_samples = torch.zeros(N, dtype=torch.int32, device=dev)
+    stopped = torch.zeros(N, dtype=torch.bool, device=dev)
+    if N > 0:
+        z, valid = OccupancyGrid._world_steps(r, ok, uu, dz, M)
+        K = z.shape[1]
+        pts = r[:, None, 0:3] + r[:, None, 3:6] * z[:, :, None]
+        f32 = lambda a: torch.tensor(np.asarray(a, dtype=np.float32), device=dev)
+        t = (pts - f32(grid.lo)) * f32(grid.scale)
+        inside, _, bit = grid._classify(pts)
+        keep = valid & inside & bit
+        Y = sh_basis(rays.detach()[:, 8:11].to(torch.float32).to(dtype), sh_degree)       # [N, B]
+        B = (sh_degree + 1) ** 2
+        index = index.to(dev).to(torch.int64)
+        table = table.to(dev)
+        ny, nz = grid.resolution[1] + 1, grid.resolution[2] + 1
+        rows, cols = keep.nonzero(as_tuple=True)
+        tk = t[rows, cols]
+        cell = torch.floor(tk)
+        f = (tk - cell).to(dtype)
+        ci = cell.to(torch.int64)
+        val = torch.zeros((rows.numel(), 1 + 3 * B), dtype=dtype, device=dev)
+        for c in range(8):
+            ox, oy, oz = (c >> 2) & 1, (c >> 1) & 1, c & 1
+            node = ((ci[:, 0] + ox) * ny + (ci[:, 1] + oy)) * nz + (ci[:, 2] + oz)
+            w = (f[:, 0] if ox else 1.0 - f[:, 0]) * (f[:, 1] if oy else 1.0 - f[:, 1]) * (f[:, 2] if oz else 1.0 - f[:, 2])
+            corner = table[index[node]][:, :1 + 3 * B].to(dtype) if values is None else values[index[node]][:, :1 + 3 * B].to(dtype)
+            val = val + w[:, None] * corner
+        sigma = torch.clamp(val[:, 0], min=0.0)
+        Yk = Y[rows]
+        logits = torch.zeros((rows.numel(), 3), dtype=dtype, device=dev)
+        for b in range(B):
+            logits = logits + val[:, 1 + b:1 + 3 * B:B] * Yk[:, b:b + 1]
+        rgb_k = torch.sigmoid(logits)
+        alpha_k = 1.0 - torch.exp(-sigma * ds32.to(dtype))
+        alpha = torch.zeros((N, K), dtype=dtype, device=dev)
+        alpha[rows, cols] = alpha_k
+        step_t = 1.0 - alpha + 1e-10
+        step_t = torch.where(keep, step_t, torch.ones_like(step_t))
+        incl = torch.cumprod(step_t, -1)
+        T = torch.cat([torch.ones((N, 1), dtype=dtype, device=dev), incl[:, :-1]], -1)
+        live = keep
+        if stop_eps > 0.0:         # the rounds: T at the end of round j is incl[:, 64 j + 63] (or the last column)
+            ends = torch.arange(_ROUND - 1, K + _ROUND - 1, _ROUND, device=dev).clamp(max=K - 1)
+            kept_in = torch.stack([keep[:, e0:e0 + _ROUND].any(-1) for e0 in range(0, K, _ROUND)], -1)
+            below = (incl[:, ends] < np.float32(stop_eps).item()) & kept_in        # (a round that keeps nothing changes nothing)
+            stopped = below.any(-1)
+            first = torch.where(stopped, below.to(torch.uint8).argmax(-1), torch.full((N,), ends.numel(), device=dev))
+            live = keep & (torch.arange(K, device=dev)[None, :] < ((first + 1) * _ROUND)[:, None])
+        w = torch.where(live, alpha * T, torch.zeros_like(T))
+        rgb_full = torch.zeros((N, K, 3), dtype=dtype, device=dev)
+        rgb_full[rows, cols] = rgb_k
+        out_rgb = (w[:, :, None] * rgb_full).sum(1)
+        out_acc = w.sum(-1)
+        out_depth = (w * torch.where(live, z, torch.zeros_like(z)).to(dtype)).sum(-1)       # (a candidate that is not kept may lie at inf)
+        n_samples = live.sum(-1).to(torch.int32)
+    if white_bkgd:
+        out_rgb = out_rgb + (1.0 - out_acc)[:, None]
+    ratio = out_depth / out_acc
+    disp = 1.0 / torch.max(torch.full_like(ratio, 1e-10), ratio)
+    return {"rgb_map": out_rgb, "disp_map": disp, "acc_map": out_acc, "depth_map": out_depth, "n_samples": n_samples,
+            "rays_stopped": int(stopped.sum())}
 
 
 class BakedField:
@@ -289,79 +373,8 @@ class BakedField:
         The stop (stop_eps > 0), in units of the kernel's rounds: the candidates are taken 64 at a time; behind the first round at
         whose end the running T -- the product over everything kept so far -- is below stop_eps no further round is walked.
         "rays_stopped" counts the rays with such a round (never one with stop_eps = 0); n_samples counts what was composited."""
-        max_steps = _check_max_steps(max_steps, "BakedField.render_rays_reference")
-        grid = self.grid
-        r, ok, uu, dn, M, _ = OccupancyGrid._march_rays("BakedField.render_rays_reference", rays, u, max_steps, 1)
-        if rays.shape[1] < 11:
-            raise ValueError("BakedField.render_rays_reference: rays [N, >= 11] (o, d, near, far, viewdir)")
-        dev = rays.device
-        N = r.shape[0]
-        ds32 = torch.tensor(self.step_size, dtype=torch.float32, device=dev)
-        dz = ds32 / dn
-        ok = ok & (dz[:, 0] > 0) & torch.isfinite(dz[:, 0])
-        out_rgb = torch.zeros((N, 3), dtype=dtype, device=dev)
-        out_acc = torch.zeros(N, dtype=dtype, device=dev)
-        out_depth = torch.zeros(N, dtype=dtype, device=dev)
-        n_samples = torch.zeros(N, dtype=torch.int32, device=dev)
-        stopped = torch.zeros(N, dtype=torch.bool, device=dev)
-        if N > 0:
-            z, valid = OccupancyGrid._world_steps(r, ok, uu, dz, M)
-            K = z.shape[1]
-            pts = r[:, None, 0:3] + r[:, None, 3:6] * z[:, :, None]
-            f32 = lambda a: torch.tensor(np.asarray(a, dtype=np.float32), device=dev)
-            t = (pts - f32(grid.lo)) * f32(grid.scale)
-            inside, _, bit = grid._classify(pts)
-            keep = valid & inside & bit
-            Y = sh_basis(rays.detach()[:, 8:11].to(torch.float32).to(dtype), self.sh_degree)       # [N, B]
-            B = self.n_basis
-            index = self.index.to(dev).to(torch.int64)
-            table = self.table.to(dev)
-            ny, nz = grid.resolution[1] + 1, grid.resolution[2] + 1
-            rows, cols = keep.nonzero(as_tuple=True)
-            tk = t[rows, cols]
-            cell = torch.floor(tk)
-            f = (tk - cell).to(dtype)
-            ci = cell.to(torch.int64)
-            val = torch.zeros((rows.numel(), 1 + 3 * B), dtype=dtype, device=dev)
-            for c in range(8):
-                ox, oy, oz = (c >> 2) & 1, (c >> 1) & 1, c & 1
-                node = ((ci[:, 0] + ox) * ny + (ci[:, 1] + oy)) * nz + (ci[:, 2] + oz)
-                w = (f[:, 0] if ox else 1.0 - f[:, 0]) * (f[:, 1] if oy else 1.0 - f[:, 1]) * (f[:, 2] if oz else 1.0 - f[:, 2])
-                val = val + w[:, None] * table[index[node]][:, :1 + 3 * B].to(dtype)
-            sigma = torch.clamp(val[:, 0], min=0.0)
-            Yk = Y[rows]
-            logits = torch.zeros((rows.numel(), 3), dtype=dtype, device=dev)
-            for b in range(B):
-                logits = logits + val[:, 1 + b:1 + 3 * B:B] * Yk[:, b:b + 1]
-            rgb_k = torch.sigmoid(logits)
-            alpha_k = 1.0 - torch.exp(-sigma * ds32.to(dtype))
-            alpha = torch.zeros((N, K), dtype=dtype, device=dev)
-            alpha[rows, cols] = alpha_k
-            step_t = 1.0 - alpha + 1e-10
-            step_t = torch.where(keep, step_t, torch.ones_like(step_t))
-            incl = torch.cumprod(step_t, -1)
-            T = torch.cat([torch.ones((N, 1), dtype=dtype, device=dev), incl[:, :-1]], -1)
-            live = keep
-            if self.stop_eps > 0.0:         # the rounds: T at the end of round j is incl[:, 64 j + 63] (or the last column)
-                ends = torch.arange(_ROUND - 1, K + _ROUND - 1, _ROUND, device=dev).clamp(max=K - 1)
-                kept_in = torch.stack([keep[:, e0:e0 + _ROUND].any(-1) for e0 in range(0, K, _ROUND)], -1)
-                below = (incl[:, ends] < np.float32(self.stop_eps).item()) & kept_in        # (a round that keeps nothing changes nothing)
-                stopped = below.any(-1)
-                first = torch.where(stopped, below.to(torch.uint8).argmax(-1), torch.full((N,), ends.numel(), device=dev))
-                live = keep & (torch.arange(K, device=dev)[None, :] < ((first + 1) * _ROUND)[:, None])
-            w = torch.where(live, alpha * T, torch.zeros_like(T))
-            rgb_full = torch.zeros((N, K, 3), dtype=dtype, device=dev)
-            rgb_full[rows, cols] = rgb_k
-            out_rgb = (w[:, :, None] * rgb_full).sum(1)
-            out_acc = w.sum(-1)
-            out_depth = (w * torch.where(live, z, torch.zeros_like(z)).to(dtype)).sum(-1)       # (a candidate that is not kept may lie at inf)
-            n_samples = live.sum(-1).to(torch.int32)
-        if white_bkgd:
-            out_rgb = out_rgb + (1.0 - out_acc)[:, None]
-        ratio = out_depth / out_acc
-        disp = 1.0 / torch.max(torch.full_like(ratio, 1e-10), ratio)
-        return {"rgb_map": out_rgb, "disp_map": disp, "acc_map": out_acc, "depth_map": out_depth, "n_samples": n_samples,
-                "rays_stopped": int(stopped.sum())}
+        return _render_reference("BakedField.render_rays_reference", self.grid, self.index, self.table, self.sh_degree, self.step_size,
+                                 self.stop_eps, rays, u, white_bkgd, max_steps, dtype, None)
 
     # ------------------------------------------------------------------ the kernel
     def render_rays(self, rays, u=None, white_bkgd=False, max_steps=1 << 14):
@@ -379,3 +392,179 @@ class BakedField:
             n = rays.shape[0]
             self.last_stats = {"rays": n, "samples": int(n_samples.sum()) if n else 0, "rays_stopped": int(stopped.sum()) if n else 0}
         return {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "depth_map": depth}
+
+    def trainable(self):
+        """the trainable twin of this field: ``BakedTrainer(self)``"""
+        return BakedTrainer(self)
+
+
+# ---------------------------------------------------------------------------------------------------- fine-tuning
+def inverted_index(cells, n_cells):
+    """(order int32 [S], cell_start int32 [n_cells + 1]) of the cell numbers `cells` (int32 [S], one per sample record): ``order`` lists the
+    samples sorted by cell with a STABLE sort -- records come ray-major and sample-minor, so the samples of a cell stand in ascending
+    (ray, k) --, and the samples of cell c are order[cell_start[c] : cell_start[c + 1]].  Plain torch on cells' device: this is the
+    inverted index nerf_baked_train_bwd_rows sums through, and its order is the order of that sum."""
+    cells = cells.reshape(-1)
+    sorted_cells, order = torch.sort(cells, stable=True)
+    bounds = torch.arange(int(n_cells) + 1, dtype=sorted_cells.dtype, device=cells.device)
+    cell_start = torch.searchsorted(sorted_cells, bounds)
+    return order.to(torch.int32), cell_start.to(torch.int32)
+
+
+class _BakedRender(torch.autograd.Function):
+    """rgb_map, acc_map, depth_map of the trainer's fp16 table with the gradient handed to ``values`` (straight-through): count, forward
+    and, in backward, the sample pass, the inverted index and the row pass"""
+
+    @staticmethod
+    def forward(ctx, values, trainer, rays, u, white_bkgd, max_steps):
+        desc = trainer.grid._desc()
+        counts = hb.baked_count(desc, rays, u, trainer.step_size, max_steps)
+        offsets = torch.zeros(rays.shape[0] + 1, dtype=torch.int64, device=rays.device)
+        offsets[1:] = torch.cumsum(counts, 0)
+        total = int(offsets[-1])
+        if total > hb.BAKED_MAX_SAMPLES:
+            raise ValueError(f"BakedTrainer.render_rays: {total} samples in one call, at most 2^30 (render fewer rays at a time)")
+        offsets = offsets.to(torch.int32)
+        rgb, acc, depth, records = hb.baked_train_fwd(desc, trainer.index, trainer.table, trainer.sh_degree, rays, u, trainer.step_size,
+                                                      max_steps, white_bkgd, offsets, total)
+        trainer.last_stats = {"rays": int(rays.shape[0]), "samples": total}
+        ctx.trainer, ctx.rays, ctx.white_bkgd, ctx.total = trainer, rays, bool(white_bkgd), total
+        ctx.save_for_backward(records, offsets)
+        return rgb, acc, depth
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_acc, g_depth):
+        records, offsets = ctx.saved_tensors
+        trainer, total = ctx.trainer, ctx.total
+        f32 = lambda g: g.detach().to(torch.float32).contiguous()
+        grads = hb.baked_train_bwd_samples(records, offsets, total, trainer.step_size, ctx.white_bkgd, f32(g_rgb), f32(g_acc), f32(g_depth))
+        if total > 0:
+            order, cell_start = inverted_index(records[:total, 0].view(torch.int32), trainer.grid.n_cells)
+        else:
+            order = torch.zeros(1, dtype=torch.int32, device=records.device)
+            cell_start = torch.zeros(trainer.grid.n_cells + 1, dtype=torch.int32, device=records.device)
+        grad = hb.baked_train_bwd_rows(trainer.grid._desc(), trainer.row_node, trainer.sh_degree, ctx.rays, records, grads, order, cell_start,
+                                       total)
+        return grad, None, None, None, None, None
+
+
+class BakedTrainer:
+    """The trainable twin of a ``BakedField``: the table fitted to images through the renderer.
+
+    ``values`` is an fp32 ``torch.nn.Parameter`` [n_rows, W], the master copy, initialised from the field's table; ``table`` is the fp16
+    table the kernels read; ``grid``, ``index``, ``sh_degree`` and ``step_size`` are copies of the field's; ``row_node`` (int32
+    [n_rows]) is the inverse of ``index``: the lattice node of every row, -1 for row 0.  The trainer shares nothing mutable with the
+    field it was made from.
+
+    ``render_rays`` renders exactly the fp16 table that inference renders and hands the gradient of that render, taken at the table's
+    values, to ``values`` (straight-through); ``commit()`` after ``optimizer.step()`` rounds the master into the table again.
+    Training uses stop_eps = 0: a field with stop_eps > 0 is accepted and its stop_eps is carried over to ``to_field()``, but the training
+    render never stops a ray, so the set of kept samples is purely geometric -- it depends on the rays and the grid's bits, never on the
+    values being trained.  The outputs are rgb_map, acc_map and depth_map; there is no disp_map (its 0 / 0 on empty rays has no useful
+    gradient).  ``last_stats`` = {"rays", "samples"} of the last ``render_rays`` call.
+
+        trainer = field.trainable()
+        opt = torch.optim.Adam(trainer.parameters(), lr=1e-2)
+        loss = ((trainer.render_rays(rays)["rgb_map"] - target) ** 2).mean(); loss.backward(); opt.step(); opt.zero_grad(); trainer.commit()
+        field = trainer.to_field()"""
+
+    def __init__(self, field):
+        if not isinstance(field, BakedField):
+            raise ValueError("BakedTrainer: field must be a baked.BakedField")
+        self._field = BakedField(copy.deepcopy(field.grid), field.index.clone(), field.table.clone(), field.sh_degree, field.step_size,
+                                 field.stop_eps)
+        self.values = torch.nn.Parameter(self._field.table.to(torch.float32))
+        self._set_row_node()
+        self.last_stats = None
+
+    def _set_row_node(self):
+        index = self._field.index.to(torch.int64)
+        row_node = torch.full((self._field.n_rows,), -1, dtype=torch.int32, device=index.device)
+        stored = index > 0
+        row_node[index[stored]] = torch.arange(index.numel(), dtype=torch.int32, device=index.device)[stored]
+        self.row_node = row_node
+
+    # ------------------------------------------------------------------ the field's side
+    grid = property(lambda self: self._field.grid)
+    index = property(lambda self: self._field.index)
+    table = property(lambda self: self._field.table)
+    sh_degree = property(lambda self: self._field.sh_degree)
+    step_size = property(lambda self: self._field.step_size)
+    stop_eps = property(lambda self: self._field.stop_eps)
+    n_basis = property(lambda self: self._field.n_basis)
+    n_rows = property(lambda self: self._field.n_rows)
+    device = property(lambda self: self._field.device)
+
+    def to(self, device):
+        """moves everything; ``values`` becomes a new Parameter, so move the trainer before handing ``parameters()`` to an optimiser"""
+        self._field.to(device)
+        self.row_node = self.row_node.to(device)
+        with torch.no_grad():
+            self.values = torch.nn.Parameter(self.values.detach().to(device))
+        return self
+
+    def parameters(self):
+        return [self.values]
+
+    def commit(self):
+        """After ``optimizer.step()``: under no_grad, zeroes row 0 and the padding columns of ``values``, clamps ``values`` to the finite
+        fp16 range and rounds it into ``table``.  The master keeps its fp32 digits."""
+        with torch.no_grad():
+            V = 1 + 3 * self.n_basis
+            self.values[0].zero_()
+            self.values[:, V:].zero_()
+            top = float(torch.finfo(torch.float16).max)
+            self.values.clamp_(min=-top, max=top)
+            self._field.table.copy_(self.values)
+        return self
+
+    def to_field(self):
+        """A ``BakedField`` of the table as it stands (copies: later steps do not change it), with the stop_eps of the field the trainer
+        was made from.  Its ``render_rays`` gives the bits of the trainer's forward (where no ray stops)."""
+        f = self._field
+        return BakedField(copy.deepcopy(f.grid), f.index.clone(), f.table.clone(), f.sh_degree, f.step_size, f.stop_eps)
+
+    def state_dict(self):
+        state = self._field.state_dict()
+        state["values"] = self.values.detach().cpu().clone()
+        return state
+
+    def load_state_dict(self, state):
+        """Takes the state of a trainer (or, without "values", of a field: the master is then the table) of the same sh_degree and grid
+        resolution"""
+        dev = self.device
+        values = state.get("values")
+        if values is not None and tuple(values.shape) != tuple(torch.as_tensor(state["table"]).shape):
+            raise ValueError("BakedTrainer.load_state_dict: values must have the table's shape")
+        self._field.load_state_dict(state)
+        self._field.to(dev)
+        with torch.no_grad():
+            src = self._field.table if values is None else torch.as_tensor(values)
+            self.values = torch.nn.Parameter(src.to(device=dev, dtype=torch.float32).clone())
+        self._set_row_node()
+        return self
+
+    # ------------------------------------------------------------------ the definition
+    def render_rays_reference(self, rays, u=None, white_bkgd=False, max_steps=1 << 14, dtype=torch.float64, values=None):
+        """The definition of the training render, in plain torch on rays' device: ``BakedField.render_rays_reference``'s arithmetic (one
+        body, _render_reference) with stop_eps = 0 -> {"rgb_map" [N, 3], "acc_map", "depth_map" [N] in `dtype`, "n_samples" int32 [N]}.
+        `values` stands in for the table: None is the fp16 table cast to `dtype`; a tensor [n_rows, W] may require grad, and the result
+        is differentiable with respect to it by ordinary autograd.  The gradient the kernels produce is autograd's gradient of this
+        function at the fp16 table's values."""
+        out = _render_reference("BakedTrainer.render_rays_reference", self.grid, self.index, self.table, self.sh_degree, self.step_size, 0.0,
+                                rays, u, white_bkgd, max_steps, dtype, values)
+        return {k: out[k] for k in ("rgb_map", "acc_map", "depth_map", "n_samples")}
+
+    # ------------------------------------------------------------------ the kernels
+    def render_rays(self, rays, u=None, white_bkgd=False, max_steps=1 << 14):
+        """{"rgb_map" fp32 [N, 3], "acc_map", "depth_map" fp32 [N]} of rays [N, >= 11] on the GPU: nerf_baked_render's bits with stop_eps
+        = 0, carrying grad to ``values`` (nerf_baked_count, nerf_baked_train_fwd; in backward nerf_baked_train_bwd_samples, a stable sort
+        of the samples' cells, nerf_baked_train_bwd_rows).  Two backward calls on the same inputs give the same bits.  The rays are
+        detached: gradients to rays and poses are not part of this.  Under no_grad only the count and the forward run."""
+        max_steps = _check_max_steps(max_steps, "BakedTrainer.render_rays")
+        if rays.dim() != 2 or rays.shape[1] < 11:
+            raise ValueError("BakedTrainer.render_rays: rays [N, >= 11] (o, d, near, far, viewdir)")
+        rays = rays.detach().to(torch.float32).contiguous()
+        u = None if u is None else u.detach().to(device=rays.device, dtype=torch.float32).contiguous()
+        rgb, acc, depth = _BakedRender.apply(self.values, self, rays, u, bool(white_bkgd), max_steps)
+        return {"rgb_map": rgb, "acc_map": acc, "depth_map": depth}

@@ -18,20 +18,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "api_util.h"
-#include "grid_device.h"
-#include "ray_device.h"
+#include "baked_device.h"
 
 using namespace nerf_api;
 using namespace nerf_grid;
+using namespace nerf_baked;
 
 namespace {
 
-constexpr int BAKED_THREADS = 256;
-constexpr int BAKED_RAYS = BAKED_THREADS / 64;
 constexpr int BAKED_STOPPED = 1 << 30;          // the flag in n_samples (include/nerf_hip.h)
-
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 
 struct BakedArgs {
     const int* node_index;
@@ -52,134 +47,41 @@ struct BakedArgs {
     int* n_samples;
 };
 
-// B = (DEG + 1)^2 basis functions; a row is sigma, then B coefficients per colour channel, zero-padded to W halves
-template <int DEG> struct RowOf {
-    static constexpr int B = (DEG + 1) * (DEG + 1);
-    static constexpr int V = 1 + 3 * B;                 // values used
-    static constexpr int W = DEG == 0 ? 4 : (DEG == 1 ? 16 : 32);
-};
-
-// acc[0 .. V) += w * row[0 .. V): one product, one addition per value (no contraction)
-template <int DEG>
-__device__ __forceinline__ void add_row(const _Float16* __restrict__ row, float w, float* acc) {
-    constexpr int V = RowOf<DEG>::V;
-    if (DEG == 0) {
-        const half4_t h = *reinterpret_cast<const half4_t*>(row);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = acc[j] + w * (float)h[j];
-    } else {
-#pragma unroll
-        for (int q = 0; q < RowOf<DEG>::W / 8; ++q) {
-            const half8_t h = *reinterpret_cast<const half8_t*>(row + 8 * q);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (8 * q + j < V) acc[8 * q + j] = acc[8 * q + j] + w * (float)h[j];
-        }
-    }
-}
-
-// The real spherical harmonics of degree <= DEG at (x, y, z), in the order and with the signs of baked.sh_basis
-template <int DEG>
-__device__ __forceinline__ void sh_basis(float x, float y, float z, float* Y) {
-    Y[0] = 0.28209479177387814f;
-    if (DEG >= 1) {
-        Y[1] = -0.4886025119029199f * y;
-        Y[2] = 0.4886025119029199f * z;
-        Y[3] = -0.4886025119029199f * x;
-    }
-    if (DEG >= 2) {
-        const float xx = x * x, yy = y * y, zz = z * z;
-        Y[4] = 1.0925484305920792f * (x * y);
-        Y[5] = -1.0925484305920792f * (y * z);
-        Y[6] = 0.31539156525252005f * (2.0f * zz - xx - yy);
-        Y[7] = -1.0925484305920792f * (x * z);
-        Y[8] = 0.5462742152960396f * (xx - yy);
-    }
-}
-
+// (the row layout, the ray's set-up, the candidates and the arithmetic of a kept sample: baked_device.h, shared with baked_train.hip)
 template <int DEG>
 __global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(GridArgs g, BakedArgs a) {
-    constexpr int B = RowOf<DEG>::B, V = RowOf<DEG>::V, W = RowOf<DEG>::W;
+    constexpr int B = RowOf<DEG>::B;
     const int ray = blockIdx.x * BAKED_RAYS + (threadIdx.x >> 6);
     if (ray >= a.n_rays) return;        // (whole waves leave: the ballots and shuffles below see full waves)
     const int lane = threadIdx.x & 63;
     const float* ray_in = a.rays + (size_t)ray * a.ray_stride;
-    const float near = ray_in[6], far = ray_in[7];
-    bool ok = near < far;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) ok = ok && fabsf(ray_in[c]) < INFINITY;     // (a NaN fails the comparison)
-    // o and d in scalar registers: the wave has one ray
-    float r[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) r[c] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ray_in[c])));
-    const float dz = a.ds / dir_norm(r);                    // (IEEE division: hipcc's default for fp32)
-    ok = ok && dz > 0.0f && dz < INFINITY;                  // (d = 0, an overflowing |d|, a NaN: no step)
+    RaySetup rs;
+    const bool ok = ray_setup(ray_in, a.ds, &rs);
     float Y[B];
     sh_basis<DEG>(ray_in[8], ray_in[9], ray_in[10], Y);
-    float T = 1.0f, s_r = 0.0f, s_g = 0.0f, s_b = 0.0f, s_acc = 0.0f, s_depth = 0.0f;
+    RayIntegrals A;
     int count = 0, stopped = 0;
     if (ok) {
         const float uu = a.u ? a.u[ray] : 0.5f;
         const int ny = g.res[1] + 1, nz = g.res[2] + 1;     // nodes per axis
         for (int k0 = 0; k0 < a.M; k0 += 64) {
-            const int k = k0 + lane;
-            const float z = near + ((float)k + uu) * dz;    // (no contraction)
-            const bool valid = k < a.M && z < far;          // (a NaN fails the comparison)
-            const unsigned long long vm = __ballot(valid);
+            const Candidate cd = candidate(g, rs, uu, k0 + lane, a.M);
+            const float z = cd.z;
+            const bool keep = cd.keep;
+            const unsigned long long vm = __ballot(cd.valid);
             if (!(vm & 1ull)) break;
-            const Pt p = sample_point(r, z);
-            float tx, ty, tz;
-            const bool inside = grid_coords(g, p, &tx, &ty, &tz);
-            bool keep = false;
-            int ix = 0, iy = 0, iz = 0;
-            if (valid && inside) {
-                ix = (int)floorf(tx); iy = (int)floorf(ty); iz = (int)floorf(tz);
-                keep = cell_bit(g, cell_index(g, ix, iy, iz));
-            }
             const unsigned long long km = __ballot(keep);
             if (km) {
                 float alpha = 0.0f, t1 = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
                 if (keep) {
-                    const float fx = tx - floorf(tx), fy = ty - floorf(ty), fz = tz - floorf(tz);     // (exact)
-                    const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy}, wz[2] = {1.0f - fz, fz};
-                    const unsigned n0 = ((unsigned)ix * (unsigned)ny + (unsigned)iy) * (unsigned)nz + (unsigned)iz;
-                    unsigned row[8];
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {
-                        const unsigned n = n0 + ((unsigned)((c >> 2) & 1) * (unsigned)ny + (unsigned)((c >> 1) & 1)) * (unsigned)nz + (unsigned)(c & 1);
-                        const unsigned i = (unsigned)a.node_index[n];
-                        row[c] = i < a.n_rows ? i : 0u;
-                    }
-                    float v[V];
-#pragma unroll
-                    for (int j = 0; j < V; ++j) v[j] = 0.0f;
-#pragma unroll
-                    for (int c = 0; c < 8; ++c)
-                        add_row<DEG>(a.table + (size_t)row[c] * W, wx[(c >> 2) & 1] * wy[(c >> 1) & 1] * wz[c & 1], v);
-                    const float sg = fmaxf(v[0], 0.0f);
-                    float l0 = 0.0f, l1 = 0.0f, l2 = 0.0f;
-#pragma unroll
-                    for (int b = 0; b < B; ++b) {
-                        l0 = l0 + v[1 + b] * Y[b];
-                        l1 = l1 + v[1 + B + b] * Y[b];
-                        l2 = l2 + v[1 + 2 * B + b] * Y[b];
-                    }
-                    c0 = nerf::sigmoidf_(l0); c1 = nerf::sigmoidf_(l1); c2 = nerf::sigmoidf_(l2);
-                    alpha = 1.0f - expf(-sg * a.ds);
-                    t1 = 1.0f - alpha + 1e-10f;
+                    const Sample sm = sample_value<DEG>(a.node_index, a.table, a.n_rows, ny, nz, cd, Y, a.ds);
+                    c0 = sm.c0; c1 = sm.c1; c2 = sm.c2;
+                    alpha = sm.alpha;
+                    t1 = sm.t1;
                 }
-                const float incl = nerf::wave_incl_scan_mul(t1, lane);
-                float excl = __shfl_up(incl, 1);
-                if (lane == 0) excl = 1.0f;
-                const float w = alpha * (T * excl);
-                s_r = s_r + nerf::wave_sum(w * c0);
-                s_g = s_g + nerf::wave_sum(w * c1);
-                s_b = s_b + nerf::wave_sum(w * c2);
-                s_acc = s_acc + nerf::wave_sum(w);
-                s_depth = s_depth + nerf::wave_sum(keep ? w * z : 0.0f);     // (a candidate that is not kept may lie at inf)
-                T = T * __shfl(incl, 63);
+                composite_round(A, alpha, t1, c0, c1, c2, keep, z, lane);
                 count += __popcll(km);
-                if (T < a.stop_eps) {           // (stop_eps = 0: never)
+                if (A.T < a.stop_eps) {           // (stop_eps = 0: never)
                     stopped = 1;
                     break;
                 }
@@ -188,14 +90,14 @@ __global__ __launch_bounds__(BAKED_THREADS) void baked_render_kernel(GridArgs g,
         }
     }
     if (lane == 0) {
-        const float bg = a.white_bkgd ? 1.0f - s_acc : 0.0f;
-        a.rgb[(size_t)ray * 3] = s_r + bg; a.rgb[(size_t)ray * 3 + 1] = s_g + bg; a.rgb[(size_t)ray * 3 + 2] = s_b + bg;
-        const float ratio = s_depth / s_acc;
+        const float bg = a.white_bkgd ? 1.0f - A.acc : 0.0f;
+        a.rgb[(size_t)ray * 3] = A.r + bg; a.rgb[(size_t)ray * 3 + 1] = A.g + bg; a.rgb[(size_t)ray * 3 + 2] = A.b + bg;
+        const float ratio = A.depth / A.acc;
         // torch.max(1e-10, ratio) propagates NaN (0/0 on empty rays): composite_ray's expression
         const float m = (ratio != ratio) ? ratio : fmaxf(1e-10f, ratio);
         a.disp[ray] = 1.0f / m;
-        a.acc[ray] = s_acc;
-        a.depth[ray] = s_depth;
+        a.acc[ray] = A.acc;
+        a.depth[ray] = A.depth;
         a.n_samples[ray] = count | (stopped ? BAKED_STOPPED : 0);
     }
 }

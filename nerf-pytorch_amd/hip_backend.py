@@ -108,6 +108,10 @@ def _declare(lib):
         "nerf_iso_count": (i, [p, i, i, i, f, p, p, p, p]),
         "nerf_iso_emit": (i, [p, i, i, i, f, p, p, p, p, p, p, p]),
         "nerf_baked_render": (i, [p, p, p, i, i, p, i, p, i, f, i, f, i, p, p, p, p, p, p]),
+        "nerf_baked_count": (i, [p, p, i, p, i, f, i, p, p]),
+        "nerf_baked_train_fwd": (i, [p, p, p, i, i, p, i, p, i, f, i, i, p, i, p, p, p, p, p]),
+        "nerf_baked_train_bwd_samples": (i, [p, p, i, i, f, i, p, p, p, p, p]),
+        "nerf_baked_train_bwd_rows": (i, [p, p, i, i, p, i, i, p, p, p, p, i, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -137,6 +141,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_occ_stop_depth", "nerf_occ_compact_stop", "nerf_occ_march", "nerf_occ_march_stop", "nerf_occ_march_step",
            "nerf_occ_view_carve",
            "nerf_iso_scratch_words", "nerf_iso_count", "nerf_iso_emit", "nerf_baked_render",
+           "nerf_baked_count", "nerf_baked_train_fwd", "nerf_baked_train_bwd_samples", "nerf_baked_train_bwd_rows",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live",
            "nerf_distortion_fwd", "nerf_distortion_bwd", "nerf_interlevel_fwd", "nerf_interlevel_bwd"]
 
@@ -1536,6 +1541,100 @@ def baked_render(desc, node_index, table, sh_degree, rays, u, step_size, max_ste
                                            _stream()), "nerf_baked_render")
     stopped = (n_samples & BAKED_STOPPED) != 0
     return rgb, disp, acc, depth, n_samples & (BAKED_STOPPED - 1), stopped
+
+
+# ---- baked field, training (csrc/baked_train.hip; the user-facing object is baked.BakedTrainer)
+BAKED_RECORD_WORDS = 12             # fp32 words per sample record of nerf_baked_train_fwd
+BAKED_MAX_SAMPLES = 1 << 30         # records of one call
+
+
+def _baked_rays(who, rays, u):
+    if not (isinstance(rays, torch.Tensor) and rays.is_cuda) or rays.dim() != 2 or rays.shape[1] < 11:
+        raise NerfHipError(f"{who}: rays [n, >= 11] (o, d, near, far, viewdir) on the GPU")
+    if u is not None and tuple(u.shape) != (rays.shape[0],):
+        raise NerfHipError(f"{who}: u must hold one offset per ray")
+    return int(rays.shape[0]), int(rays.shape[1])
+
+
+def baked_count(desc, rays, u, step_size, max_steps):
+    """nerf_baked_count: int32 [n], the kept candidates of every ray [n, >= 11] -- baked_render's n_samples with stop_eps = 0, without
+    reading a table"""
+    n, stride = _baked_rays("baked_count", rays, u)
+    counts = torch.zeros(n, dtype=torch.int32, device=rays.device)
+    if n > 0:
+        with _timed("baked_count_kernel", 0.0, 48.0 * n):
+            _check(lib().nerf_baked_count(ctypes.byref(desc), _ptr(rays, "rays"), stride, _ptr(u, "u", True), n, float(step_size),
+                                          int(max_steps), counts.data_ptr(), _stream()), "nerf_baked_count")
+    return counts
+
+
+def baked_train_fwd(desc, node_index, table, sh_degree, rays, u, step_size, max_steps, white_bkgd, offsets, total):
+    """nerf_baked_train_fwd: (rgb_map fp32 [n, 3], acc_map, depth_map fp32 [n], records fp32 [max(total, 1), 12]) -- baked_render's bits
+    with stop_eps = 0 and one record per kept sample, ray-major; offsets int32 [n + 1] = the exclusive running sum of baked_count's
+    counts, total = offsets[n] as a Python int"""
+    deg = int(sh_degree)
+    if deg not in (0, 1, 2):
+        raise NerfHipError(f"baked_train_fwd: sh_degree must be 0, 1 or 2, got {sh_degree!r}")
+    n, stride = _baked_rays("baked_train_fwd", rays, u)
+    nodes = (desc.res[0] + 1) * (desc.res[1] + 1) * (desc.res[2] + 1)
+    if node_index.numel() != nodes:
+        raise NerfHipError(f"baked_train_fwd: node_index holds one entry per lattice node, {nodes}")
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float16 and table.is_contiguous() and table.dim() == 2
+            and table.shape[0] >= 1 and table.shape[1] == BAKED_ROW_HALVES[deg]):
+        raise NerfHipError(f"baked_train_fwd: table must be a contiguous fp16 tensor [rows >= 1, {BAKED_ROW_HALVES[deg]}] on the GPU")
+    total = int(total)
+    if offsets.numel() != n + 1 or not (0 <= total <= BAKED_MAX_SAMPLES):
+        raise NerfHipError(f"baked_train_fwd: offsets holds n + 1 entries and 0 <= total <= 2^30 samples, got {offsets.numel()} and {total}")
+    dev = rays.device
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    acc, depth = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+    records = torch.empty((max(total, 1), BAKED_RECORD_WORDS), dtype=torch.float32, device=dev)
+    if n > 0:
+        # per ray 48 B in and 20 B out, per sample a 48-byte record out; what the samples gather depends on the scene and is not counted
+        with _timed("baked_train_fwd_kernel", 0.0, 68.0 * n + 48.0 * total):
+            _check(lib().nerf_baked_train_fwd(ctypes.byref(desc), _words(node_index, "node_index"), table.data_ptr(), int(table.shape[0]), deg,
+                                              _ptr(rays, "rays"), stride, _ptr(u, "u", True), n, float(step_size), int(max_steps),
+                                              int(bool(white_bkgd)), _words(offsets, "offsets"), total, _ptr(records), _ptr(rgb), _ptr(acc),
+                                              _ptr(depth), _stream()), "nerf_baked_train_fwd")
+    return rgb, acc, depth, records
+
+
+def baked_train_bwd_samples(records, offsets, total, step_size, white_bkgd, g_rgb, g_acc, g_depth):
+    """nerf_baked_train_bwd_samples: fp32 [max(total, 1), 4] = (dL/dv0, dL/dl_R, dL/dl_G, dL/dl_B) per sample record from the upstream
+    gradients g_rgb [n, 3], g_acc [n], g_depth [n] of baked_train_fwd's outputs"""
+    n = offsets.numel() - 1
+    total = int(total)
+    if tuple(g_rgb.shape) != (n, 3) or tuple(g_acc.shape) != (n,) or tuple(g_depth.shape) != (n,) or records.shape[0] < total:
+        raise NerfHipError("baked_train_bwd_samples: g_rgb [n, 3], g_acc [n], g_depth [n] and `total` records")
+    grads = torch.empty((max(total, 1), 4), dtype=torch.float32, device=records.device)
+    if n > 0 and total > 0:
+        with _timed("baked_train_bwd_samples_kernel", 0.0, 20.0 * n + 48.0 * total):       # 32 B of a record in, 16 B out
+            _check(lib().nerf_baked_train_bwd_samples(_ptr(records, "records"), _words(offsets, "offsets"), n, total, float(step_size),
+                                                      int(bool(white_bkgd)), _ptr(g_rgb, "g_rgb"), _ptr(g_acc, "g_acc"),
+                                                      _ptr(g_depth, "g_depth"), _ptr(grads), _stream()), "nerf_baked_train_bwd_samples")
+    return grads
+
+
+def baked_train_bwd_rows(desc, row_node, sh_degree, rays, records, sample_grads, order, cell_start, total):
+    """nerf_baked_train_bwd_rows: fp32 [n_rows, W], the gradient of the table: per row the sum over its adjacent cells (corner order) and
+    each cell's samples (the order of `order`: int32 [total], the samples sorted by cell, stable; cell_start int32 [cells + 1]) of
+    corner weight x contribution.  Two calls give the same bits."""
+    deg = int(sh_degree)
+    if deg not in (0, 1, 2):
+        raise NerfHipError(f"baked_train_bwd_rows: sh_degree must be 0, 1 or 2, got {sh_degree!r}")
+    n, stride = _baked_rays("baked_train_bwd_rows", rays, None)
+    total = int(total)
+    cells = desc.res[0] * desc.res[1] * desc.res[2]
+    if order.numel() < total or cell_start.numel() != cells + 1 or records.shape[0] < total or sample_grads.shape[0] < total:
+        raise NerfHipError(f"baked_train_bwd_rows: `total` records, sample gradients and entries of order, and cell_start [{cells + 1}]")
+    n_rows = int(row_node.numel())
+    grad = torch.empty((n_rows, BAKED_ROW_HALVES[deg]), dtype=torch.float32, device=rays.device)
+    # per term a 32-byte piece of a record, 16 B of sample gradients and 12 B of the ray; per row 4 W bytes out
+    with _timed("baked_train_bwd_rows_kernel", 0.0, 4.0 * grad.numel() + 8.0 * 64.0 * total):
+        _check(lib().nerf_baked_train_bwd_rows(ctypes.byref(desc), _words(row_node, "row_node"), n_rows, deg, _ptr(rays, "rays"), stride, n,
+                                               _ptr(records, "records"), _ptr(sample_grads, "sample_grads"), _words(order, "order"),
+                                               _words(cell_start, "cell_start"), total, _ptr(grad), _stream()), "nerf_baked_train_bwd_rows")
+    return grad
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not
