@@ -754,6 +754,30 @@ int nerf_baked_train_bwd_rows(const NerfOccGrid* grid, const int* row_node, int 
                               int n_rays, const float* records, const float* sample_grads, const int* order, const int* cell_start,
                               int total, float* grad, void* stream);
 
+/* ---- baked field, regularisers (additive in ABI v10): total variation and Cauchy sparsity of the fp32 master table over the stored
+ * lattice nodes (baked.BakedTrainer.regularizers; baked.regularizer_reference is the definition).  values is fp32
+ * [n_rows][W] (W = 4 / 16 / 32 floats for sh_degree 0 / 1 / 2, 16-byte aligned), column 0 the density before the ReLU, columns 1 .. 3B
+ * the colour coefficients, the rest padding; node_index and row_node as above.  With n + e_a the next node along axis a,
+ *   D_a[n][c] = s_a (v[n + e_a][c] - v[n][c])  where n + e_a lies in the lattice and is stored, else 0     (a missing neighbour is
+ *                                                                                                 left out, not taken as zero)
+ *   t[n][c]   = sqrtf(((D_x^2 + D_y^2) + D_z^2) + eps)
+ * and s_a = (sx, sy, sz) = min(cell edge) / (cell edge along a).
+ *   nerf_baked_reg_fwd: terms [n_rows][3], every element written: per stored row (t[n][0], the sum of t[n][c] over c = 1 .. 3B,
+ *     log1pf(2 max(v[n][0], 0)^2)); zeros for row 0 and rows without a node.  The colour sum is a butterfly over the row's W lanes,
+ *     partners at distance 1, 2, 4, .. W/2 in turn.  The caller sums the rows.
+ *   nerf_baked_reg_bwd: grad [n_rows][W], every element written: the gradient of g[0] sum_n t[n][0] + g[1] sum_n sum_c t[n][c] + g[2]
+ *     sum_n log1p(..) (g: three floats on the device), gathered per stored row and column -- no atomics --
+ *       w_c ( - sum_a s_a D_a[n][c] / t[n][c]  +  sum_a [m = n - e_a stored] s_a D_a[m][c] / t[m][c] )  +  (c == 0) g[2] 4 sg / (1 + 2 sg^2),
+ *     w_0 = g[0], w_c = g[1], sg = max(v[n][0], 0): at most 13 rows read per row (n; n + e_a; n - e_a and its two other forward
+ *     neighbours), in that written order, the six terms added in that order (own x, y, z, then behind x, y, z).  Row 0, rows without
+ *     a node and the padding columns are zero.  The same inputs give the same bits.
+ * sh_degree 0, 1 or 2; 1 <= n_rows <= 2^26 (n_rows == 1: all zeros); eps and the three scales finite and > 0; values and grad 16-byte
+ * aligned.  An index read from memory that does not address its buffer counts as "not stored". */
+int nerf_baked_reg_fwd(const NerfOccGrid* grid, const int* node_index, const int* row_node, const float* values, int n_rows, int sh_degree,
+                       float sx, float sy, float sz, float eps, float* terms, void* stream);
+int nerf_baked_reg_bwd(const NerfOccGrid* grid, const int* node_index, const int* row_node, const float* values, int n_rows, int sh_degree,
+                       float sx, float sy, float sz, float eps, const float* g /* device, 3 floats */, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,9 @@ baked=field)`` and ``render_kwargs_test["baked"] = field`` are the ways in.  A `
 artefact.  Its trainable twin is ``BakedTrainer`` (``field.trainable()``): an fp32 master copy of the table, the same render with a
 deterministic backward to the table's rows (csrc/baked_train.hip: every contribution stored once and summed per row in a fixed order, no
 atomics), so the table can be fitted to images through the renderer (PlenOctrees' fine-tuning, Plenoxels) and written back with
-``to_field()``.
+``to_field()``.  ``BakedTrainer.regularizers()`` adds what ties a node to its neighbours: the total variation of the density and of the
+colour coefficients between stored nodes and Plenoxels' Cauchy sparsity of the density, on the fp32 master, with a gradient that is a
+gather (csrc/baked_reg.hip); ``regularizer_reference`` is their definition.
 """
 import copy
 import math
@@ -448,6 +450,88 @@ class _BakedRender(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
+def _check_eps(eps, who):
+    real = not isinstance(eps, (bool, np.bool_)) and isinstance(eps, (int, float, np.integer, np.floating))
+    if real:
+        with np.errstate(all="ignore"):
+            real = 0.0 < float(np.float32(eps)) < float("inf")         # (the kernels' eps is fp32(eps); also refuses NaN)
+    if not real:
+        raise ValueError(f"{who}: eps must be a finite real number > 0 (as an fp32 value), got {eps!r}")
+    return float(eps)
+
+
+def regularizer_reference(values, index, node_resolution, sh_degree, axis_scale, eps=1e-9, dtype=torch.float64):
+    """The definition of the table's regularisers, in plain torch on values' device, differentiable in `values` by ordinary autograd ->
+    {"tv_sigma", "tv_sh", "sparsity"}, 0-d tensors in `dtype`.
+
+    values [n_rows, >= 1 + 3B] are the rows of a table (column 0 the density before the ReLU, columns 1 .. 3B the colour coefficients, B =
+    (sh_degree + 1)^2; row 0 and further columns take no part); index (one entry per node of the (Nx, Ny, Nz) = node_resolution lattice,
+    n = (i Ny + j) Nz + k) is a node's row, or 0: the node is not stored.  With s = axis_scale, three floats (BakedTrainer passes
+    min(cell edge) / (cell edge along the axis)), and n + e_a the next node along axis a:
+        D_a[n][c] = s_a (v[n + e_a][c] - v[n][c])   where n + e_a lies in the lattice and is stored, else 0
+        t[n][c]   = sqrt(D_x^2 + D_y^2 + D_z^2 + eps)
+        tv_sigma  = 1 / M       sum over the stored n of t[n][0]
+        tv_sh     = 1 / (3B M)  sum over the stored n and c = 1 .. 3B of t[n][c]
+        sparsity  = 1 / M       sum over the stored n of log1p(2 max(v[n][0], 0)^2)          (Plenoxels' Cauchy prior)
+    M = n_rows - 1 is the number of stored nodes; with M = 0 all three are 0.  A difference to a missing neighbour is left out, not
+    taken against zero: every corner of an occupied cell has a row, the render never reads a missing node, and pulling the hull towards
+    0 would be wrong."""
+    who = "regularizer_reference"
+    sh_degree = _check_degree(sh_degree, who)
+    eps = _check_eps(eps, who)
+    nx, ny, nz = (int(r) for r in node_resolution)
+    V = 1 + 3 * (sh_degree + 1) ** 2
+    index = torch.as_tensor(index).reshape(-1).to(device=values.device, dtype=torch.int64)
+    if values.dim() != 2 or values.shape[0] < 1 or values.shape[1] < V or index.numel() != nx * ny * nz:
+        raise ValueError(f"{who}: values [n_rows >= 1, >= {V}] and one index entry per lattice node ({nx * ny * nz})")
+    scale = [float(s) for s in axis_scale]
+    if len(scale) != 3 or not all(0.0 < s < float("inf") for s in scale):
+        raise ValueError(f"{who}: axis_scale must hold three finite numbers > 0, got {axis_scale!r}")
+    M = int(values.shape[0]) - 1
+    if M == 0:
+        zero = torch.zeros((), dtype=dtype, device=values.device)
+        return {"tv_sigma": zero, "tv_sh": zero.clone(), "sparsity": zero.clone()}
+    stored = (index > 0).view(nx, ny, nz)
+    v = values.to(dtype)[index][:, :V].view(nx, ny, nz, V)          # (a node that is not stored reads row 0 and is masked below)
+    square = torch.zeros_like(v)
+    for a, n in enumerate((nx, ny, nz)):
+        if n < 2:
+            continue
+        there = stored.narrow(a, 1, n - 1)[..., None]               # the forward neighbour is stored
+        d = torch.where(there, scale[a] * (v.narrow(a, 1, n - 1) - v.narrow(a, 0, n - 1)), torch.zeros((), dtype=dtype, device=v.device))
+        last = list(v.shape)
+        last[a] = 1
+        d = torch.cat([d, torch.zeros(last, dtype=dtype, device=v.device)], a)     # the last plane has no forward neighbour
+        square = square + d * d
+    t = torch.sqrt(square + eps) * stored[..., None].to(dtype)
+    cauchy = torch.log1p(2.0 * torch.clamp(v[..., 0], min=0.0) ** 2) * stored.to(dtype)
+    return {"tv_sigma": t[..., 0].sum() / M, "tv_sh": t[..., 1:].sum() / (3 * (sh_degree + 1) ** 2 * M), "sparsity": cauchy.sum() / M}
+
+
+class _BakedRegularizers(torch.autograd.Function):
+    """(tv_sigma, tv_sh, sparsity) of the trainer's fp32 master: nerf_baked_reg_fwd and a float64 sum of its rows; in backward
+    nerf_baked_reg_bwd with the three upstream gradients, divided by the counts, in a device buffer"""
+
+    @staticmethod
+    def forward(ctx, values, trainer, eps):
+        scales = trainer.axis_scale
+        terms = hb.baked_reg_fwd(trainer.grid._desc(), trainer.index, trainer.row_node, values, trainer.sh_degree, scales, eps)
+        M = max(trainer.n_rows - 1, 1)
+        counts = (float(M), float(3 * trainer.n_basis * M), float(M))
+        sums = terms.sum(0, dtype=torch.float64)
+        ctx.trainer, ctx.scales, ctx.eps, ctx.counts = trainer, scales, eps, counts
+        ctx.save_for_backward(values)
+        return tuple((sums[i] / counts[i]).to(torch.float32) for i in range(3))
+
+    @staticmethod
+    def backward(ctx, g_sigma, g_sh, g_sparsity):
+        values, = ctx.saved_tensors
+        trainer = ctx.trainer
+        g = torch.stack([u.detach().to(torch.float32) / c for u, c in zip((g_sigma, g_sh, g_sparsity), ctx.counts)]).contiguous()
+        grad = hb.baked_reg_bwd(trainer.grid._desc(), trainer.index, trainer.row_node, values, trainer.sh_degree, ctx.scales, ctx.eps, g)
+        return grad, None, None
+
+
 class BakedTrainer:
     """The trainable twin of a ``BakedField``: the table fitted to images through the renderer.
 
@@ -466,7 +550,9 @@ class BakedTrainer:
         trainer = field.trainable()
         opt = torch.optim.Adam(trainer.parameters(), lr=1e-2)
         loss = ((trainer.render_rays(rays)["rgb_map"] - target) ** 2).mean(); loss.backward(); opt.step(); opt.zero_grad(); trainer.commit()
-        field = trainer.to_field()"""
+        field = trainer.to_field()
+
+    ``regularizers()`` gives the total variation and the sparsity of the master, to be weighted and added to the loss."""
 
     def __init__(self, field):
         if not isinstance(field, BakedField):
@@ -568,3 +654,28 @@ class BakedTrainer:
         u = None if u is None else u.detach().to(device=rays.device, dtype=torch.float32).contiguous()
         rgb, acc, depth = _BakedRender.apply(self.values, self, rays, u, bool(white_bkgd), max_steps)
         return {"rgb_map": rgb, "acc_map": acc, "depth_map": depth}
+
+    # ------------------------------------------------------------------ regularisers
+    @property
+    def axis_scale(self):
+        """(sx, sy, sz) = min(cell edge) / (cell edge along the axis), computed in float64: 1 on cubic cells"""
+        g = self.grid
+        edge = (np.asarray(g.hi, dtype=np.float64) - np.asarray(g.lo, dtype=np.float64)) / np.asarray(g.resolution, dtype=np.float64)
+        return tuple(float(edge.min() / e) for e in edge)
+
+    def regularizers_reference(self, values=None, eps=1e-9, dtype=torch.float64):
+        """``regularizer_reference`` (the definition) on this trainer's index and grid; `values` None: the master"""
+        values = self.values if values is None else values
+        return regularizer_reference(values, self.index, self._field.node_resolution, self.sh_degree, self.axis_scale, eps, dtype)
+
+    def regularizers(self, eps=1e-9):
+        """{"tv_sigma", "tv_sh", "sparsity"}, fp32 0-d tensors on the GPU carrying grad to ``values``: ``regularizer_reference`` of the fp32
+        MASTER (not of the fp16 table: the loss is a plain function of the parameter, nothing is straight-through, and a small gradient
+        does not vanish in fp16 rounding) within fp32 rounding -- the total variation of the density and of the colour coefficients
+        between stored neighbours and Plenoxels' Cauchy sparsity of the density (nerf_baked_reg_fwd, a float64 sum over the rows; in
+        backward nerf_baked_reg_bwd, a gather without atomics: two calls give the same bits).  Under no_grad only the forward runs.
+
+            reg = trainer.regularizers(); loss = mse + 1e-3 * reg["tv_sigma"] + 1e-4 * reg["tv_sh"] + 1e-5 * reg["sparsity"]"""
+        eps = _check_eps(eps, "BakedTrainer.regularizers")
+        tv_sigma, tv_sh, sparsity = _BakedRegularizers.apply(self.values, self, eps)
+        return {"tv_sigma": tv_sigma, "tv_sh": tv_sh, "sparsity": sparsity}

@@ -112,6 +112,8 @@ def _declare(lib):
         "nerf_baked_train_fwd": (i, [p, p, p, i, i, p, i, p, i, f, i, i, p, i, p, p, p, p, p]),
         "nerf_baked_train_bwd_samples": (i, [p, p, i, i, f, i, p, p, p, p, p]),
         "nerf_baked_train_bwd_rows": (i, [p, p, i, i, p, i, i, p, p, p, p, i, p, p]),
+        "nerf_baked_reg_fwd": (i, [p, p, p, p, i, i, f, f, f, f, p, p]),
+        "nerf_baked_reg_bwd": (i, [p, p, p, p, i, i, f, f, f, f, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -142,6 +144,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_occ_view_carve",
            "nerf_iso_scratch_words", "nerf_iso_count", "nerf_iso_emit", "nerf_baked_render",
            "nerf_baked_count", "nerf_baked_train_fwd", "nerf_baked_train_bwd_samples", "nerf_baked_train_bwd_rows",
+           "nerf_baked_reg_fwd", "nerf_baked_reg_bwd",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live",
            "nerf_distortion_fwd", "nerf_distortion_bwd", "nerf_interlevel_fwd", "nerf_interlevel_bwd"]
 
@@ -1634,6 +1637,50 @@ def baked_train_bwd_rows(desc, row_node, sh_degree, rays, records, sample_grads,
         _check(lib().nerf_baked_train_bwd_rows(ctypes.byref(desc), _words(row_node, "row_node"), n_rows, deg, _ptr(rays, "rays"), stride, n,
                                                _ptr(records, "records"), _ptr(sample_grads, "sample_grads"), _words(order, "order"),
                                                _words(cell_start, "cell_start"), total, _ptr(grad), _stream()), "nerf_baked_train_bwd_rows")
+    return grad
+
+
+# ---- baked field, regularisers (csrc/baked_reg.hip; the user-facing method is baked.BakedTrainer.regularizers)
+def _baked_reg_args(who, desc, node_index, row_node, values, sh_degree, scales, eps):
+    deg = int(sh_degree)
+    if deg not in (0, 1, 2):
+        raise NerfHipError(f"{who}: sh_degree must be 0, 1 or 2, got {sh_degree!r}")
+    W = BAKED_ROW_HALVES[deg]
+    if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float32 and values.is_contiguous()
+            and values.dim() == 2 and values.shape[0] >= 1 and values.shape[1] == W):
+        raise NerfHipError(f"{who}: values must be a contiguous fp32 tensor [rows >= 1, {W}] on the GPU")
+    nodes = (desc.res[0] + 1) * (desc.res[1] + 1) * (desc.res[2] + 1)
+    n_rows = int(values.shape[0])
+    if node_index.numel() != nodes or row_node.numel() != n_rows:
+        raise NerfHipError(f"{who}: node_index holds one entry per lattice node, {nodes}, and row_node one per row, {n_rows}")
+    sx, sy, sz = (float(s) for s in scales)
+    return deg, W, n_rows, nodes, sx, sy, sz, float(eps)
+
+
+def baked_reg_fwd(desc, node_index, row_node, values, sh_degree, scales, eps):
+    """nerf_baked_reg_fwd: terms fp32 [n_rows, 3] of the fp32 table `values` [n_rows, W]: per stored row the total-variation term of the
+    density column, the sum of the colour columns' terms and the Cauchy term log1p(2 max(sigma, 0)^2); zeros for row 0.  scales = (sx, sy,
+    sz), min(cell edge) / (cell edge along the axis)."""
+    deg, W, n_rows, nodes, sx, sy, sz, eps = _baked_reg_args("baked_reg_fwd", desc, node_index, row_node, values, sh_degree, scales, eps)
+    terms = torch.empty((n_rows, 3), dtype=torch.float32, device=values.device)
+    # the table in once (the three forward neighbours come from cache), 12 B per row out, both index arrays in
+    with _timed("baked_reg_fwd_kernel", 0.0, 4.0 * W * n_rows + 12.0 * n_rows + 4.0 * n_rows + 4.0 * nodes):
+        _check(lib().nerf_baked_reg_fwd(ctypes.byref(desc), _words(node_index, "node_index"), _words(row_node, "row_node"), _ptr(values, "values"),
+                                        n_rows, deg, sx, sy, sz, eps, _ptr(terms), _stream()), "nerf_baked_reg_fwd")
+    return terms
+
+
+def baked_reg_bwd(desc, node_index, row_node, values, sh_degree, scales, eps, g):
+    """nerf_baked_reg_bwd: fp32 [n_rows, W], the gradient with respect to `values` of g[0] sum(terms[:, 0]) + g[1] sum(terms[:, 1]) +
+    g[2] sum(terms[:, 2]) (g: fp32 [3] on the GPU), gathered per row without atomics.  Two calls give the same bits."""
+    deg, W, n_rows, nodes, sx, sy, sz, eps = _baked_reg_args("baked_reg_bwd", desc, node_index, row_node, values, sh_degree, scales, eps)
+    if tuple(g.shape) != (3,):
+        raise NerfHipError("baked_reg_bwd: g holds the three upstream gradients")
+    grad = torch.empty((n_rows, W), dtype=torch.float32, device=values.device)
+    # the table in once if the 13-row gather is served by cache, the gradient out, both index arrays in
+    with _timed("baked_reg_bwd_kernel", 0.0, 4.0 * W * n_rows + 4.0 * W * n_rows + 4.0 * n_rows + 4.0 * nodes):
+        _check(lib().nerf_baked_reg_bwd(ctypes.byref(desc), _words(node_index, "node_index"), _words(row_node, "row_node"), _ptr(values, "values"),
+                                        n_rows, deg, sx, sy, sz, eps, _ptr(g, "g"), _ptr(grad), _stream()), "nerf_baked_reg_bwd")
     return grad
 
 
