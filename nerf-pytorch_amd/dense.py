@@ -214,54 +214,48 @@ def _freqs_of(ch):
 def _render_no_rays(cfg, rays, model_c, model_f):
     """render_rays_dense for an empty batch: the per-ray kernels have nothing to launch, but the networks still see their (empty)
     inputs, so the outputs stay in the graph as the reference's do and a backward leaves exact zeros in every used parameter."""
-    n_c, n_f, dev = cfg["N_samples"], cfg["N_importance"], rays.device
+    n_c, n_f, dev = cfg.N_samples, cfg.N_importance, rays.device
     empty = torch.zeros(0, dtype=torch.float32, device=dev)
 
     def one_pass(model, S):
         raw = model.query(rays, torch.zeros((0, S), dtype=torch.float32, device=dev))
         return raw[..., :3].sum(1), raw[..., 3].sum(1), raw[..., 3].sum(1), raw
     rgb, disp, acc, raw = one_pass(model_c, n_c)
-    ret = {}
+    coarse = ()
     if n_f > 0:
-        ret.update(rgb0=rgb, disp0=disp, acc0=acc)
+        coarse = (rgb, disp, acc, empty)
         rgb, disp, acc, raw = one_pass(model_c if model_f is None else model_f, n_c + n_f)
-        ret["z_std"] = empty
-    ret.update(rgb_map=rgb, disp_map=disp, acc_map=acc, raw=raw)
-    if cfg.get("distortion", False):
-        ret["distortion"] = empty
-    if cfg.get("interlevel", False):
-        ret["interlevel"] = empty
-    return ret
+    return (rgb, disp, acc, raw) + coarse + (empty,) * (int(cfg.distortion) + int(cfg.interlevel))
 
 
 def render_rays_dense(cfg, rays, rnd, model_c, model_f):
     """run_nerf.py:351-412 for DenseNeRF networks: the same per-ray kernels as the fused path around DenseNeRF.query; autograd
-    through the compositing (render._Composite) and the layer stack (_DenseMLP).  Returns the reference's dict."""
+    through the compositing (render._Composite) and the layer stack (_DenseMLP).  Returns the output tuple (rgb, disp, acc, raw[, rgb0,
+    disp0, acc0, z_std][, distortion][, interlevel]) that render_options.result_dict names."""
     from .render import _Composite, _linspace01
-    n_c, n_f = cfg["N_samples"], cfg["N_importance"]
-    std, wb, dev = cfg["raw_noise_std"], cfg["white_bkgd"], rays.device
+    n_c, n_f = cfg.N_samples, cfg.N_importance
+    std, wb, dev = cfg.raw_noise_std, cfg.white_bkgd, rays.device
     if model_c.use_viewdirs and rays.shape[1] < 11:
         raise ValueError("render_rays: a network with view directions needs ray records with 11 columns")
     if rays.shape[0] == 0:
         return _render_no_rays(cfg, rays, model_c, model_f)
     rays_d = rays[:, 3:6].contiguous()
-    z = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
+    z = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg.lindisp, rnd.get("t_rand"))
     raw = model_c.query(rays, z)
     rgb, disp, acc, weights, _ = _Composite.apply(raw[..., :4].contiguous(), z, rays_d, rnd.get("noise_c"), std, wb)
     w_c, z_c = weights, z
-    ret = {}
+    coarse = ()
     if n_f > 0:
-        ret.update(rgb0=rgb, disp0=disp, acc0=acc)
         u = rnd.get("u")
         z, z_std, _ = hb.sample_fine(z, weights.detach().contiguous(), n_f, u, None if u is not None else _linspace01(n_f, dev))
+        coarse = (rgb, disp, acc, z_std)
         raw = (model_c if model_f is None else model_f).query(rays, z)
         rgb, disp, acc, weights, _ = _Composite.apply(raw[..., :4].contiguous(), z, rays_d, rnd.get("noise_f"), std, wb)
-        ret["z_std"] = z_std
-    ret.update(rgb_map=rgb, disp_map=disp, acc_map=acc, raw=raw)
-    if cfg.get("distortion", False):        # of the last pass's weights (differentiable through _Composite); the key comes last
+    outs = (rgb, disp, acc, raw) + coarse
+    if cfg.distortion:        # of the last pass's weights (differentiable through _Composite)
         from .render import distortion_loss
-        ret["distortion"] = distortion_loss(weights, z, rays[:, 6], rays[:, 7])
-    if cfg.get("interlevel", False):        # the coarse pass's weights against the refining pass's; behind "distortion"
+        outs += (distortion_loss(weights, z, rays[:, 6], rays[:, 7]),)
+    if cfg.interlevel:        # the coarse pass's weights against the refining pass's; behind the distortion loss
         from .render import interlevel_loss
-        ret["interlevel"] = interlevel_loss(w_c, z_c, weights, z)
-    return ret
+        outs += (interlevel_loss(w_c, z_c, weights, z),)
+    return outs

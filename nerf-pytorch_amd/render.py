@@ -7,12 +7,14 @@ Random draws (stratified jitter, density noise, CDF samples) are made here with
 torch, in the reference's order and shapes, and handed to the
 kernels, so a seeded run consumes the generator exactly like the reference.
 """
+import dataclasses
 from functools import partial
 
 import numpy as np
 import torch
 
 from . import hip_backend as hb
+from . import render_options as ro
 from .field import NeRF, packed_params_pair
 
 _LINSPACE_CACHE = {}
@@ -154,12 +156,12 @@ def _field_pass(cfg, rays, rnd, model_c, model_f, save):
     """One evaluation of render_rays' pipeline (run_nerf.py:351-412) on `rays`: coarse depths -> field -> composite
     [-> hierarchical depths -> field -> composite].  save=True leases workspace buffers for the saved activations
     (hb.Workspace) and returns them in the dict; everything else is small ([N,S]-sized)."""
-    n_c, n_f = cfg["N_samples"], cfg["N_importance"]
+    n_c, n_f = cfg.N_samples, cfg.N_importance
     dev = rays.device
-    std, wb, prec = cfg["raw_noise_std"], cfg["white_bkgd"], cfg.get("precision", "fp32")
+    std, wb, prec = cfg.raw_noise_std, cfg.white_bkgd, cfg.precision
     r = {}
     guard = (lambda m: m.packed_params("fp16x3")) if prec == "fp16_fp8c" else (lambda m: None)
-    r["z_c"] = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
+    r["z_c"] = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg.lindisp, rnd.get("t_rand"))
     mf = model_c if (model_f is None or model_f is model_c) else model_f
     nxt = raw_f = None
     # The reduced inference class with a refining pass: hierarchical sampling divides by ~1e-5 in bins the coarse pass found empty
@@ -177,8 +179,8 @@ def _field_pass(cfg, rays, rnd, model_c, model_f, save):
         nxt = (guard(mf), raw_f)
     r["raw_c"], r["act_c"] = hb.field_fwd(r["packed_c"], rays, r["z_c"], save_act=save, precision=prec_c,
                                           guard_packed=guard(model_c) if prec_c == "fp16_fp8c" else None, next_guard=nxt)
-    dist = cfg.get("distortion", False)     # the last pass also hands out its weights (one more store, every other output keeps its bits)
-    inter = cfg.get("interlevel", False)    # likewise, and the coarse weights are kept too (render_rays refuses it without a refining pass)
+    dist = cfg.distortion     # the last pass also hands out its weights (one more store, every other output keeps its bits)
+    inter = cfg.interlevel    # likewise, and the coarse weights are kept too (render_rays refuses it without a refining pass)
     r["rgb_c"], r["disp_c"], r["acc_c"], w_c, _ = hb.raw2outputs(r["raw_c"], r["z_c"], rays, rays.shape[1], rnd.get("noise_c"), std, wb,
                                                               want_weights=n_f > 0 or dist, want_depth=False, rays_d_offset=3)
     if n_f <= 0:
@@ -224,19 +226,19 @@ class _RenderRays(torch.autograd.Function):
     saving and the backward re-runs it, with saving, one sub-chunk at a time (the kernels are deterministic, so the
     recomputed pass is bit-identical to the first): bounded memory for +1 inference-speed forward.
 
-    cfg["distortion"]: one trailing differentiable output, the distortion loss [N] of the last pass's weights (_field_pass), which stay
+    cfg.distortion: one trailing differentiable output, the distortion loss [N] of the last pass's weights (_field_pass), which stay
     among the saved tensors; its upstream gradient enters the last pass's compositing backward as d_weights (nerf_distortion_bwd), in
-    all three plans.  cfg["interlevel"]: one trailing differentiable output (behind the distortion loss), the interlevel loss [N] of the
+    all three plans.  cfg.interlevel: one trailing differentiable output (behind the distortion loss), the interlevel loss [N] of the
     coarse pass's weights against the refining pass's; both passes' weights stay among the saved tensors (the recompute plan recomputes
     them) and its upstream gradient enters the COARSE pass's compositing backward as d_weights (nerf_interlevel_bwd): it reaches model_c
     through the coarse pass only, and alone it runs no backward of the refining pass."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, *params):
-        n_f = cfg["N_importance"]
-        need = cfg["need_grad"]
+        n_f = cfg.N_importance
+        need = cfg.need_grad
         n = rays.shape[0]
-        sub = hb.max_saved_rays(cfg["N_samples"], n_f, cfg.get("precision", "fp32")) if need else n
+        sub = hb.max_saved_rays(cfg.N_samples, n_f, cfg.precision) if need else n
         ctx.checkpoint = bool(need and n > sub)
         ctx.tiles = None
         if ctx.checkpoint:
@@ -246,23 +248,23 @@ class _RenderRays(torch.autograd.Function):
             # + the pool's idle leases LARGE ENOUGH to hold a sub-chunk's saved activations (smaller ones serve nothing) + half of
             # what torch's caching allocator holds without using (cached blocks are fragmented: only part of them can back a
             # multi-GB request).  The estimate can still be wrong: the forward below falls back to recomputation on out-of-memory.
-            prec_ = cfg.get("precision", "fp32")
-            lease = min(hb.act_floats(sub, cfg["N_samples"], prec_), hb.act_floats(sub, cfg["N_samples"] + n_f, prec_) if n_f > 0 else 1 << 62)
+            prec_ = cfg.precision
+            lease = min(hb.act_floats(sub, cfg.N_samples, prec_), hb.act_floats(sub, cfg.N_samples + n_f, prec_) if n_f > 0 else 1 << 62)
             cached = torch.cuda.memory_reserved(rays.device) - torch.cuda.memory_allocated(rays.device)
             free_now = torch.cuda.mem_get_info(rays.device)[0] + cached // 2 + hb.WORKSPACE.idle_bytes(rays.device, lease)
-            if hb.saved_bytes(sub, cfg["N_samples"], n_f, prec_) * ceil_div(n, sub) <= min(hb.SAVE_TOTAL_BYTES, int(0.9 * free_now)):
+            if hb.saved_bytes(sub, cfg.N_samples, n_f, prec_) * ceil_div(n, sub) <= min(hb.SAVE_TOTAL_BYTES, int(0.9 * free_now)):
                 ctx.checkpoint = False
                 ctx.tiles = [(lo, min(lo + sub, n)) for lo in range(0, n, sub)]
         global LAST_BACKWARD_PLAN
         LAST_BACKWARD_PLAN = ("recompute" if ctx.checkpoint else "resident sub-chunks" if ctx.tiles is not None else "one launch", n, sub)
         ctx.sub_rays = sub
-        prec = cfg.get("precision", "fp32")
-        dist, inter = cfg.get("distortion", False), cfg.get("interlevel", False)
-        if not need and not dist and not inter and hb.INFER_ONE_LAUNCH and hb.render_infer_supported(cfg["N_samples"], n_f, prec):
+        prec = cfg.precision
+        dist, inter = cfg.distortion, cfg.interlevel
+        if not need and not dist and not inter and hb.INFER_ONE_LAUNCH and hb.render_infer_supported(cfg.N_samples, n_f, prec):
             # no gradients: coarse depths -> network -> compositing -> hierarchical depths -> network -> compositing in ONE launch
             mf = None if (model_f is None or model_f is model_c or n_f <= 0) else model_f
-            r = hb.render_rays_infer(model_c.packed_params(prec), None if mf is None else mf.packed_params(prec), rays, cfg["N_samples"],
-                                     n_f, cfg["lindisp"], cfg["white_bkgd"], cfg["raw_noise_std"], prec, rnd)
+            r = hb.render_rays_infer(model_c.packed_params(prec), None if mf is None else mf.packed_params(prec), rays, cfg.N_samples,
+                                     n_f, cfg.lindisp, cfg.white_bkgd, cfg.raw_noise_std, prec, rnd)
         elif ctx.tiles is None:
             r = _field_pass(cfg, rays, rnd, model_c, model_f, save=need and not ctx.checkpoint)
         else:
@@ -290,7 +292,7 @@ class _RenderRays(torch.autograd.Function):
             # the fp16 split's range guard rail: every RANGE_MONITOR.every-th training render scans what the forward saved
             # (hb.RangeMonitor; replaces run_nerf.py:414-416's DEBUG-gated NaN / Inf check)
             for r_, n_ in ([(r, n)] if ctx.tiles is None else [(p_, hi - lo) for p_, (lo, hi) in zip(parts, ctx.tiles)]):
-                hb.RANGE_MONITOR.after_forward([(r_[k_], s_) for k_, s_ in (("act_c", cfg["N_samples"]), ("act_f", cfg["N_samples"] + n_f))
+                hb.RANGE_MONITOR.after_forward([(r_[k_], s_) for k_, s_ in (("act_c", cfg.N_samples), ("act_f", cfg.N_samples + n_f))
                                                 if r_.get(k_) is not None], n_)
         ctx.cfg, ctx.model_c, ctx.model_f = cfg, model_c, model_f
         ctx.same_net = model_f is None or model_f is model_c
@@ -312,8 +314,8 @@ class _RenderRays(torch.autograd.Function):
             keep = ("packed_c", "z_c", "act_c", "raw_c", "packed_f", "z_f", "act_f", "raw_f", "w", "w_c")
             ctx.saved = [{k_: p_[k_] for k_ in keep if k_ in p_} for p_ in parts]     # per-sub-chunk tensors, none is an output
         elif need and not ctx.checkpoint:
-            # ("w": the last pass's weights under cfg["distortion"] or cfg["interlevel"], N S 4 bytes, "w_c": the coarse pass's under
-            # cfg["interlevel"], N N_samples 4 bytes; neither is an output)
+            # ("w": the last pass's weights under cfg.distortion or cfg.interlevel, N S 4 bytes, "w_c": the coarse pass's under
+            # cfg.interlevel, N N_samples 4 bytes; neither is an output)
             keep = ("packed_c", "z_c", "act_c", "packed_f", "z_f", "act_f", "w", "w_c") + (("raw_c",) if n_f > 0 else ())
             ctx.saved = {k: r[k] for k in keep if k in r}
             ctx.save_for_backward(r["raw_f"] if n_f > 0 else r["raw_c"])
@@ -340,18 +342,18 @@ class _RenderRays(torch.autograd.Function):
         if not ctx.need:
             return none_all
         now = tuple(_param_state(m) for m in (ctx.model_c, ctx.model_f) if m is not None)
-        if cfg.get("precision", "fp32") != "fp32" and now != ctx.param_state:
+        if cfg.precision != "fp32" and now != ctx.param_state:
             raise RuntimeError(_STALE_MSG)
         rays_all, rnd_all = ctx.rays, ctx.rnd
-        std, wb, prec = cfg["raw_noise_std"], cfg["white_bkgd"], cfg.get("precision", "fp32")
+        std, wb, prec = cfg.raw_noise_std, cfg.white_bkgd, cfg.precision
         dev = rays_all.device
         n_all = rays_all.shape[0]
-        n_f = cfg["N_importance"]
+        n_f = cfg.N_importance
         fine = n_f > 0
         # upstream gradients of (rgb, disp, acc, raw, distortion, interlevel) of the fine (or only) pass and of the coarse pass; the two
         # losses are the trailing outputs: the distortion loss belongs to the last pass, the interlevel loss to the coarse one
-        inter = cfg.get("interlevel", False)
-        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-2 if inter else -1] if cfg.get("distortion", False) else None, None)
+        inter = cfg.interlevel
+        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-2 if inter else -1] if cfg.distortion else None, None)
         up_c = (gouts[4], gouts[5], gouts[6], None, None, gouts[-1] if inter else None) if fine else None
         if not fine:
             up_c, up_f = up_f, None
@@ -765,10 +767,10 @@ def _grid_pass(cfg, desc, rays, z_vals, model, noise, want_weights, z_stop=None,
     others' on an error.  budget = {"rays_grad": bool, "resident": bytes the call keeps so far, "rays": rays of the whole call} goes with
     it: beyond hb.SAVE_TOTAL_BYTES in total the pass raises.
     The compacted raw and the M zero depths live inside the pass and are plain torch allocations on both paths.
-    keep_weights (cfg["distortion"], the last pass; cfg["interlevel"], both passes): the record also keeps the pass's compositing weights as "w" for the backward."""
+    keep_weights (cfg.distortion, the last pass; cfg.interlevel, both passes): the record also keeps the pass's compositing weights as "w" for the backward."""
     n, S = z_vals.shape
     P = n * S
-    dev, prec = rays.device, cfg["precision"]
+    dev, prec = rays.device, cfg.precision
     p = {"z": z_vals, "slot": hb.WORKSPACE.take(P, dev), "act": None, "rec": None, "m": 0}
     if passes is not None:
         passes.append(p)
@@ -801,7 +803,7 @@ def _grid_pass(cfg, desc, rays, z_vals, model, noise, want_weights, z_stop=None,
     p["raw"] = raw
     stats["evaluated"] += m
     stats["total"] += P
-    outs = hb.raw2outputs(raw, z_vals, rays, rays.shape[1], noise, cfg["raw_noise_std"], cfg["white_bkgd"], want_weights=want_weights,
+    outs = hb.raw2outputs(raw, z_vals, rays, rays.shape[1], noise, cfg.raw_noise_std, cfg.white_bkgd, want_weights=want_weights,
                           want_depth=False, rays_d_offset=3)
     if keep_weights:
         p["w"] = outs[3]
@@ -812,51 +814,51 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
     """THE stages of a grid render on one ray chunk or sub-chunk -- _render_rays_hooked's chain with device code where the hook sits --
     with run_pass(rays, z_vals, model, noise, want_weights, z_stop) = _grid_pass bound to the caller's cfg, desc and bookkeeping.
     Everything option-dependent is read from cfg, which render_rays fills once for both paths:
-      cfg["march_steps"] (proposal="march"): the depths are the grid's own (nerf_occ_march: march_steps candidates, N_samples slots) and
+      cfg.march_steps (proposal="march"): the depths are the grid's own (nerf_occ_march: march_steps candidates, N_samples slots) and
         the chunk is ONE pass of model_c on them, compacted with the march's stop depth (the caller hands the evaluated network as
-        model_c, N_importance = 0 and the pass's noise as noise_c); with cfg["march_stop_eps"] the depths are nerf_occ_march_stop's, the
-        march that also stops on the DensityGrid's own transmittance -- nothing else of the chunk changes (cfg["march_step_size"]: below);
-      else coarse depths (nerf_sample_coarse) and their weights: cfg["proposal"] ("grid") takes the grid's own
+        model_c, N_importance = 0 and the pass's noise as noise_c); with cfg.march_stop_eps the depths are nerf_occ_march_stop's, the
+        march that also stops on the DensityGrid's own transmittance -- nothing else of the chunk changes (cfg.march_step_size: below);
+      else coarse depths (nerf_sample_coarse) and their weights: cfg.proposal ("grid") takes the grid's own
         (DensityGrid.proposal_weights: one launch, no network, no read-back; the evaluated network is model_c), otherwise a pass of
         model_c, which is the whole chunk when N_importance = 0;
-      cfg["early_stop_eps"]: the coarse weights give one stop depth per ray (nerf_occ_stop_depth), with which the refining pass compacts;
+      cfg.early_stop_eps: the coarse weights give one stop depth per ray (nerf_occ_stop_depth), with which the refining pass compacts;
       nerf_sample_fine, and the refining pass on model_f (model_c without one).
     One host synchronisation per pass and none of its own.  Returns the output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std][, distortion][, interlevel])
     and the device counters (stopped rays, truncated rays, refit rays; None without the option), which the caller reads back after its
-    passes.  cfg["march_step_size"] (with cfg["march_fit"]): the march's depths are nerf_occ_march_step's -- steps of one length in the
+    passes.  cfg.march_step_size (with cfg.march_fit): the march's depths are nerf_occ_march_step's -- steps of one length in the
     scene, march_steps the cap on candidates, the step doubled per ray until it fits the slots -- and nothing else of the chunk changes."""
-    n_c, n_f = cfg["N_samples"], cfg["N_importance"]
+    n_c, n_f = cfg.N_samples, cfg.N_importance
     dev = rays.device
-    # cfg["distortion"]: the LAST pass hands out and keeps its weights, and the chain's tuple ends with their distortion loss on the depths
+    # cfg.distortion: the LAST pass hands out and keeps its weights, and the chain's tuple ends with their distortion loss on the depths
     # the pass was given and the near / far of `rays` (the clipped ones under clip_to_occupancy)
-    # cfg["interlevel"] (two passes, no proposal: render_rays refuses the rest): BOTH passes hand out and keep their weights, and the tuple
+    # cfg.interlevel (two passes, no proposal: render_rays refuses the rest): BOTH passes hand out and keep their weights, and the tuple
     # ends with the interlevel loss of the coarse pass's weights against the refining pass's (skipped and stopped samples: weight 0)
-    dist, inter = cfg.get("distortion", False), cfg.get("interlevel", False)
+    dist, inter = cfg.distortion, cfg.interlevel
     last_kw = {"keep_weights": True} if dist or inter else {}
     loss_of = lambda w, z: (hb.distortion(w, z, rays, nf_stride=rays.shape[1], nf_offset=6),) if dist else ()
-    if cfg["march_steps"] is not None:
+    if cfg.march_steps is not None:
         n_stopped = n_refit = None
-        if cfg["march_step_size"] is not None:      # world-space steps, march_steps is the cap: one kernel for both forms
-            dens = cfg["march_stop_eps"] is not None
+        if cfg.march_step_size is not None:      # world-space steps, march_steps is the cap: one kernel for both forms
+            dens = cfg.march_stop_eps is not None
             z_m, z_stop, truncated, level, stopped = hb.occ_march_step(
                 desc, grid.density if dens else None, grid.outside_sigma() if dens else 0.0, rays, rnd.get("u_march"),
-                cfg["march_step_size"], cfg["march_steps"], n_c, cfg["march_fit"], cfg["march_stop_eps"])
+                cfg.march_step_size, cfg.march_steps, n_c, cfg.march_fit, cfg.march_stop_eps)
             if dens:
                 n_stopped = stopped.sum()
-            if cfg["march_fit"] > 0:
+            if cfg.march_fit > 0:
                 n_refit = (level > 0).sum()
-        elif cfg["march_stop_eps"] is not None:
+        elif cfg.march_stop_eps is not None:
             z_m, z_stop, truncated, stopped = hb.occ_march_stop(desc, grid.density, grid.outside_sigma(), rays, rnd.get("u_march"),
-                                                                cfg["march_steps"], n_c, cfg["march_stop_eps"])
+                                                                cfg.march_steps, n_c, cfg.march_stop_eps)
             n_stopped = stopped.sum()
         else:
-            z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), cfg["march_steps"], n_c)
+            z_m, z_stop, truncated = hb.occ_march(desc, rays, rnd.get("u_march"), cfg.march_steps, n_c)
         n_truncated = truncated.sum()
         raw, (rgb, disp, acc, w_m, _) = run_pass(rays, z_m, model_c, rnd.get("noise_c"), dist, z_stop, **last_kw)
         return (rgb, disp, acc, raw) + loss_of(w_m, z_m), n_stopped, n_truncated, n_refit
-    z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg["lindisp"], rnd.get("t_rand"))
+    z_c = hb.sample_coarse(rays, _linspace01(n_c, dev), cfg.lindisp, rnd.get("t_rand"))
     coarse = ()
-    if cfg["proposal"] is not None:
+    if cfg.proposal is not None:
         w_c = grid.proposal_weights(rays, z_c)
     else:
         raw_c, (rgb_c, disp_c, acc_c, w_c, _) = run_pass(rays, z_c, model_c, rnd.get("noise_c"), n_f > 0 or dist, None,
@@ -865,8 +867,8 @@ def _grid_chain(cfg, desc, grid, rays, rnd, model_c, model_f, run_pass):
             return (rgb_c, disp_c, acc_c, raw_c) + loss_of(w_c, z_c), None, None, None
         coarse = (rgb_c, disp_c, acc_c)
     z_stop = n_stopped = None
-    if cfg["early_stop_eps"] is not None:
-        z_stop = hb.occ_stop_depth(z_c, w_c, cfg["early_stop_eps"])
+    if cfg.early_stop_eps is not None:
+        z_stop = hb.occ_stop_depth(z_c, w_c, cfg.early_stop_eps)
         n_stopped = torch.isfinite(z_stop).sum()
     u = rnd.get("u")
     z_f, z_std, _ = hb.sample_fine(z_c, w_c, n_f, u, None if u is not None else _linspace01(n_f, dev))
@@ -916,25 +918,25 @@ class _RenderRaysGrid(torch.autograd.Function):
     back by the backward or freed with a dropped graph.  Calls above hb.max_saved_rays(...) rays run in equal ray sub-chunks, every
     one resident with leases of its own M; beyond hb.SAVE_TOTAL_BYTES in total the call raises (no recompute plan on this path).
 
-    The options of _grid_chain as the backward sees them.  cfg["proposal"] ("grid"): the coarse weights are a constant of the graph,
-    nothing saved, and the node has ONE pass, the refining one on model_c; outputs (rgb, disp, acc, raw, z_std).  cfg["early_stop_eps"]:
+    The options of _grid_chain as the backward sees them.  cfg.proposal ("grid"): the coarse weights are a constant of the graph,
+    nothing saved, and the node has ONE pass, the refining one on model_c; outputs (rgb, disp, acc, raw, z_std).  cfg.early_stop_eps:
     z_stop is a constant of the graph, computed per sub-chunk; a stopped sample has slot -1 like a skipped one -- raw = 0, no gradient
-    -- so nothing beyond slot is kept for it and the backward is unchanged.  cfg["march_steps"]: depths and stop depth are constants of
+    -- so nothing beyond slot is kept for it and the backward is unchanged.  cfg.march_steps: depths and stop depth are constants of
     the graph, computed per sub-chunk; with N_importance = 0 the backward is the coarse-only one; outputs (rgb, disp, acc, raw) --
-    cfg["march_stop_eps"], cfg["march_step_size"] and cfg["march_fit"] change which kernel computes those constants and nothing of the
-    backward.  cfg["distortion"]: the tuple ends with the distortion loss [N] of the last pass's weights, which that pass's record keeps
-    as "w"; its upstream gradient enters the pass's compositing backward as d_weights, in front of nerf_occ_gather.  cfg["interlevel"] (the
+    cfg.march_stop_eps, cfg.march_step_size and cfg.march_fit change which kernel computes those constants and nothing of the
+    backward.  cfg.distortion: the tuple ends with the distortion loss [N] of the last pass's weights, which that pass's record keeps
+    as "w"; its upstream gradient enters the pass's compositing backward as d_weights, in front of nerf_occ_gather.  cfg.interlevel (the
     two-pass form only): the tuple ends with the interlevel loss [N] of the coarse pass's weights against the refining pass's, both
     records keep their "w", and its upstream gradient enters the COARSE pass's compositing backward as d_weights (nerf_interlevel_bwd):
     alone it runs no backward of the refining pass."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
-        n_c, n_f = cfg["N_samples"], cfg["N_importance"]
-        prec = cfg["precision"]
+        n_c, n_f = cfg.N_samples, cfg.N_importance
+        prec = cfg.precision
         n = rays.shape[0]
         desc = grid._desc()
-        ctx.proposal = cfg["proposal"] is not None
+        ctx.proposal = cfg.proposal is not None
         ctx.same_net = model_f is None or model_f is model_c
         ctx.n_params_c = len(_param_slices(model_c))
         ctx.rays_grad = rays_grad = bool(ctx.needs_input_grad[1])
@@ -988,7 +990,7 @@ class _RenderRaysGrid(torch.autograd.Function):
         ctx.consumed = False
         ctx.set_materialize_grads(False)
         if n_f > 0:     # z_std (in front of the trailing losses if there are any): the reference detaches z_samples (run_nerf.py:394)
-            ctx.mark_non_differentiable(out[-1 - int(cfg.get("distortion", False)) - int(cfg.get("interlevel", False))])
+            ctx.mark_non_differentiable(out[-1 - int(cfg.distortion) - int(cfg.interlevel)])
         return tuple(out)
 
     @staticmethod
@@ -999,16 +1001,16 @@ class _RenderRaysGrid(torch.autograd.Function):
         none_c = (None,) * ctx.n_params_c
         none_all = (None,) * 6 + none_c + (() if ctx.same_net else none_c)
         now = tuple(_param_state(m) for m in (ctx.model_c, ctx.model_f) if m is not None)
-        std, wb, prec = cfg["raw_noise_std"], cfg["white_bkgd"], cfg["precision"]
+        std, wb, prec = cfg.raw_noise_std, cfg.white_bkgd, cfg.precision
         if prec != "fp32" and now != ctx.param_state:
             raise RuntimeError(_STALE_MSG)
         rays_all, rnd_all = ctx.rays, ctx.rnd
         dev = rays_all.device
         n_all = rays_all.shape[0]
-        fine = cfg["N_importance"] > 0
+        fine = cfg.N_importance > 0
         # (the losses are the trailing outputs: the distortion loss belongs to the last pass, the interlevel loss behind it to the coarse one)
-        inter = cfg.get("interlevel", False)
-        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-2 if inter else -1] if cfg.get("distortion", False) else None, None)
+        inter = cfg.interlevel
+        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-2 if inter else -1] if cfg.distortion else None, None)
         if ctx.proposal:        # one pass, the refining one: there is no coarse image
             up_c = None
         else:
@@ -1098,159 +1100,12 @@ class _RenderRaysGrid(torch.autograd.Function):
         return lead + out_c + (_grad_views(ctx.model_f, grad_f) if wrote["f"] else none_c)
 
 
-def _check_grid_options(N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal, early_stop_eps, march_steps,
-                        march_stop_eps=None, march_step_size=None, march_fit=0):
-    """render_rays' checks of its grid options, in front of everything else (a refused call launches nothing, not even hb.lib()).
-    Returns (march, early_stop_eps as a float or None, march_steps as an int or None, march_stop_eps as a float or None,
-    march_step_size as a float or None, march_fit as an int)."""
-    if clip_to_occupancy and occupancy is None:
-        raise ValueError("render_rays: clip_to_occupancy=True needs an occupancy grid (occupancy=)")
-    march = isinstance(proposal, str) and proposal == "march"
-    if march_steps is not None and not march:
-        raise ValueError("render_rays: march_steps belongs to proposal=\"march\"")
-    if march_stop_eps is not None and not march:
-        raise ValueError("render_rays: march_stop_eps belongs to proposal=\"march\"")
-    if march_step_size is not None and not march:
-        raise ValueError("render_rays: march_step_size belongs to proposal=\"march\"")
-    fit_off = march_fit is None or (not isinstance(march_fit, (bool, np.bool_)) and isinstance(march_fit, (int, np.integer)) and int(march_fit) == 0)
-    if not fit_off and not march:
-        raise ValueError("render_rays: march_fit belongs to proposal=\"march\"")
-    if march:
-        if occupancy is None:
-            raise ValueError("render_rays: proposal=\"march\" walks an occupancy grid (occupancy=): none was given")
-        if isinstance(march_steps, bool) or not isinstance(march_steps, (int, np.integer)) or not (1 <= int(march_steps) <= 16384):
-            raise ValueError(f"render_rays: proposal=\"march\" needs march_steps, an int with 1 <= march_steps <= 16384, got {march_steps!r}")
-        if early_stop_eps is not None:
-            raise ValueError("render_rays: early_stop_eps together with proposal=\"march\": there are no coarse weights to stop on")
-        if int(N_samples) + max(int(N_importance), 0) > 4096:
-            raise ValueError("render_rays: proposal=\"march\" fills at most 4096 slots per ray (N_samples + N_importance)")
-        if int(N_samples) + max(int(N_importance), 0) < 1:
-            raise ValueError("render_rays: proposal=\"march\" needs at least one slot per ray (N_samples + N_importance)")
-        if lindisp:
-            raise NotImplementedError("render_rays: proposal=\"march\" with lindisp=True is not implemented (the steps are equal in depth)")
-        march_steps = int(march_steps)
-        if march_step_size is not None or not fit_off:
-            from .occupancy import _check_march_step
-            if march_step_size is None:
-                _check_march_step(1.0, march_fit, "render_rays")
-                raise ValueError("render_rays: march_fit doubles the world-space step of a ray: it needs march_step_size")
-            march_step_size, march_fit = _check_march_step(march_step_size, march_fit, "render_rays")
-        if march_stop_eps is not None:
-            from .occupancy import DensityGrid, _check_march_eps
-            march_stop_eps = _check_march_eps(march_stop_eps, "render_rays")
-            if not isinstance(occupancy, DensityGrid):
-                raise ValueError("render_rays: march_stop_eps reads the densities of an occupancy.DensityGrid (occupancy=); "
-                                 "a plain OccupancyGrid has none")
-    if early_stop_eps is not None:
-        early_stop_eps = float(early_stop_eps)
-        if not (0.0 < early_stop_eps < 1.0):        # (also refuses NaN)
-            raise ValueError(f"render_rays: early_stop_eps must be None or a float with 0 < eps < 1, got {early_stop_eps!r}")
-        if occupancy is None:
-            raise ValueError("render_rays: early_stop_eps needs an occupancy grid (occupancy=): the stop is applied by the grid's compaction")
-        if int(N_importance) <= 0:
-            raise ValueError("render_rays: early_stop_eps stops the refining pass from the coarse pass's weights: N_importance must be > 0")
-    if not march and proposal not in (None, "grid"):
-        raise ValueError(f"render_rays: proposal must be None, \"grid\" or \"march\", got {proposal!r}")
-    if proposal is not None and not march:
-        from .occupancy import DensityGrid
-        if not isinstance(occupancy, DensityGrid):
-            raise ValueError("render_rays: proposal=\"grid\" reads the densities of an occupancy.DensityGrid (occupancy=); "
-                             + ("none was given" if occupancy is None else "a plain OccupancyGrid has none"))
-        if int(N_importance) <= 0:
-            raise ValueError("render_rays: proposal=\"grid\" draws importance samples: N_importance must be > 0")
-    return march, early_stop_eps, march_steps, march_stop_eps, march_step_size, 0 if fit_off else int(march_fit)
-
-
-def _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march):
-    """render_rays' random tensors for n rays, injected (``randoms``: the keys the options read, checked for their row count) or drawn in
-    the reference's order and shapes.  Returns (rnd, the noise scale the kernels apply)."""
-    rnd = {}
-    if randoms is not None:
-        keys = (["t_rand"] if perturb > 0. else []) + (["noise_c"] if raw_noise_std > 0. and proposal is None else [])
-        if n_f > 0:
-            keys += (["u"] if perturb > 0. else []) + (["noise_f"] if raw_noise_std > 0. else [])
-        if march:
-            keys = (["u_march"] if perturb > 0. else []) + (["noise_f"] if raw_noise_std > 0. else [])
-        rnd = {k: randoms[k].to(device=dev, dtype=torch.float32).contiguous() for k in keys}
-        for k, v in rnd.items():
-            if v.shape[0] != n:
-                raise ValueError(f"render_rays: randoms[{k!r}] has {v.shape[0]} rows for {n} rays")
-        perturb_draw = 0.
-    else:
-        perturb_draw = perturb
-    # draw order of the reference: t_rand (:371) -> noise coarse (:285) -> u (helpers:208) -> noise fine (:285)
-    if perturb_draw > 0. and not march:
-        rnd["t_rand"] = torch.rand((n, N_samples), device=dev)
-        if pytest:
-            np.random.seed(0)
-            rnd["t_rand"] = torch.Tensor(np.random.rand(n, N_samples)).to(dev)
-    std = float(raw_noise_std)
-
-    def draw_noise(S):
-        nz = torch.randn((n, S), device=dev)
-        if pytest:
-            np.random.seed(0)
-            nz = torch.Tensor(np.random.rand(n, S) * raw_noise_std).to(dev)
-        return nz.contiguous()
-    if raw_noise_std > 0. and randoms is None and proposal is None:
-        rnd["noise_c"] = draw_noise(N_samples)
-    if march:       # draw order: u_march (one offset per ray) -> noise of the one pass
-        if perturb_draw > 0.:
-            rnd["u_march"] = torch.rand(n, device=dev)
-            if pytest:
-                np.random.seed(0)
-                rnd["u_march"] = torch.Tensor(np.random.rand(n)).to(dev)
-        if raw_noise_std > 0. and randoms is None:
-            rnd["noise_f"] = draw_noise(N_samples + max(n_f, 0))
-    elif n_f > 0:
-        if perturb_draw > 0.:
-            rnd["u"] = torch.rand((n, n_f), device=dev)
-            if pytest:
-                np.random.seed(0)
-                rnd["u"] = torch.Tensor(np.random.rand(n, n_f)).to(dev)
-        elif pytest and randoms is None:
-            # det + pytest: the reference builds u with np.linspace in float64 and casts it (helpers:213-215), which is NOT
-            # torch.linspace's fp32 sequence (one ulp apart in 30 of 64 / 8 of 128 entries: tests/test_host_cpu.py) -- hand the
-            # kernel the reference's numbers as explicit draws
-            rnd["u"] = torch.Tensor(np.broadcast_to(np.linspace(0., 1., n_f), (n, n_f)).copy()).to(dev)
-        if raw_noise_std > 0. and randoms is None:
-            rnd["noise_f"] = draw_noise(N_samples + n_f)
-    if pytest and raw_noise_std > 0. and randoms is None:
-        std = 1.0       # pytest noise is pre-scaled in float64 like the reference (run_nerf.py:290)
-    return rnd, std
-
-
-def _result_dict(outs, retraw, coarse_first, distortion=False, interlevel=False):
-    """the returned dict of an output tuple (rgb, disp, acc, raw[, rgb0, disp0, acc0][, z_std][, distortion][, interlevel]).  coarse_first: the key
-    order of _render_rays_hooked, which the grid paths share (the coarse image and z_std in front); else the fused dense path's, which
-    the empty batch has always had.  distortion: the tuple ends with the distortion loss, whose key comes last; interlevel: with the interlevel loss, behind it"""
-    last = {}
-    if interlevel:
-        outs, last = outs[:-1], {"interlevel": outs[-1]}
-    if distortion:
-        outs, last = outs[:-1], {"distortion": outs[-1], **last}
-    fine = dict(rgb_map=outs[0], disp_map=outs[1], acc_map=outs[2], **({"raw": outs[3]} if retraw else {}))
-    coarse = dict(zip(("rgb0", "disp0", "acc0"), outs[4:7])) if len(outs) == 8 else {}
-    if len(outs) > 4:
-        coarse["z_std"] = outs[-1]
-    return {**coarse, **fine, **last} if coarse_first else {**fine, **coarse, **last}
-
-
-def _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal, march_stop_eps=None, march_fit=0):
-    """the last_stats keys the grid options add to "evaluated" and "total" (render_rays' keyword arguments, checked or not)"""
-    march = isinstance(proposal, str) and proposal == "march"
-    refit = march and not isinstance(march_fit, (bool, np.bool_)) and isinstance(march_fit, (int, np.integer)) and march_fit > 0
-    return ((("rays_hit", "rays") if clip_to_occupancy else ()) + (("rays_stopped",) if early_stop_eps is not None else ())
-            + (("rays_truncated",) if march else ()) + (("rays_stopped",) if march and march_stop_eps is not None else ())
-            + (("rays_refit",) if refit else ()))
-
-
-def _render_rays_baked(ray_batch, baked, network_query_fn, perturb, white_bkgd, pytest, refused):
-    """render_rays(baked=field): the guards (`refused`: option name -> whether the call set it), the one draw, the field's own launch"""
+def _render_rays_baked(ray_batch, baked, network_query_fn, perturb, white_bkgd, pytest, given):
+    """render_rays(baked=field): the guards (`given`: render_rays' option arguments as they came), the one draw, the field's own launch"""
     from .baked import BakedField
+    bad = ro.options_set(**given)
     if not isinstance(baked, BakedField):
         raise ValueError(f"render_rays: baked must be None or a baked.BakedField, got {type(baked).__name__}")
-    bad = [k for k, v in refused.items() if v]
     if bad:
         raise ValueError(f"render_rays: baked= renders from the baked field alone and cannot be combined with {', '.join(bad)}")
     if not _is_builtin_query(network_query_fn):
@@ -1414,30 +1269,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     occupancy, clip_to_occupancy, proposal, early_stop_eps, the march options, distortion, interlevel, retraw, randoms,
     raw_noise_std > 0, a user network_query_fn, and -- in grad mode -- rays that require grad (there is no backward).  Clipping stays
     possible by hand: baked.grid.clip_rays(rays)[0].  None: nothing changes -- same launches, same bits, same draws."""
-    if baked is not None:
-        return _render_rays_baked(ray_batch, baked, network_query_fn, perturb, white_bkgd, pytest,
-                                  dict(retraw=bool(retraw), raw_noise_std=raw_noise_std > 0., randoms=randoms is not None,
-                                       occupancy=occupancy is not None, clip_to_occupancy=bool(clip_to_occupancy), proposal=proposal is not None,
-                                       early_stop_eps=early_stop_eps is not None, march_steps=march_steps is not None,
-                                       march_stop_eps=march_stop_eps is not None, march_step_size=march_step_size is not None,
-                                       march_fit=not (march_fit is None or (isinstance(march_fit, (int, np.integer)) and int(march_fit) == 0)),
-                                       distortion=distortion is not False, interlevel=interlevel is not False))
-    if not isinstance(distortion, (bool, np.bool_)):
-        raise ValueError(f"render_rays: distortion must be a bool, got {distortion!r}")
-    distortion = bool(distortion)
-    if not isinstance(interlevel, (bool, np.bool_)):
-        raise ValueError(f"render_rays: interlevel must be a bool, got {interlevel!r}")
-    interlevel = bool(interlevel)
-    if interlevel:
-        if proposal is not None:
-            raise ValueError(f"render_rays: interlevel=True fits the coarse network's weights to the refining pass's; proposal={proposal!r} "
-                             "has no coarse network pass")
-        if int(N_importance) <= 0:
-            raise ValueError("render_rays: interlevel=True needs a refining pass to fit the coarse weights to: N_importance must be > 0")
-    march, early_stop_eps, march_steps, march_stop_eps, march_step_size, march_fit = _check_grid_options(
-        N_samples, N_importance, lindisp, occupancy, clip_to_occupancy, proposal, early_stop_eps, march_steps, march_stop_eps, march_step_size,
-        march_fit)
-    from .dense import DenseNeRF
+    given = dict(N_samples=N_samples, retraw=retraw, lindisp=lindisp, perturb=perturb, N_importance=N_importance, white_bkgd=white_bkgd,
+                 raw_noise_std=raw_noise_std, pytest=pytest, randoms=randoms, occupancy=occupancy, clip_to_occupancy=clip_to_occupancy,
+                 proposal=proposal, early_stop_eps=early_stop_eps, march_steps=march_steps, march_stop_eps=march_stop_eps,
+                 march_step_size=march_step_size, march_fit=march_fit, distortion=distortion, interlevel=interlevel)
+    if baked is not None:       # (in front of every check: whatever else is wrong with the call, the field refuses the options it was given)
+        return _render_rays_baked(ray_batch, baked, network_query_fn, perturb, white_bkgd, pytest, given)
+    opt = ro.ray_options(**given)
+    from .dense import DenseNeRF, render_rays_dense
     nets = [network_fn] + ([network_fine] if network_fine is not None else [])
     dense = all(isinstance(m, DenseNeRF) for m in nets)         # architectures outside the fused kernels: layer by layer (dense.py)
     if not dense and not all(isinstance(m, NeRF) for m in nets):
@@ -1453,67 +1292,44 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     rays = ray_batch.to(torch.float32).contiguous()
     if not rays_grad:
         rays = rays.detach()
-    n = rays.shape[0]
-    dev = rays.device
-    n_f = int(N_importance)
-    if n == 0 and dense and occupancy is None and _is_builtin_query(network_query_fn):
-        # general networks: the dense path's own keys and order, outputs attached to the networks (dense._render_no_rays)
-        from .dense import render_rays_dense
-        ret = render_rays_dense(dict(N_samples=int(N_samples), N_importance=n_f, raw_noise_std=0., white_bkgd=bool(white_bkgd),
-                                     distortion=distortion, interlevel=interlevel), rays, {}, network_fn, network_fine if n_f > 0 else None)
-        if not retraw:
-            ret.pop("raw")
-        return ret
+    n, dev, n_f = rays.shape[0], rays.device, opt.N_importance
+    builtin = _is_builtin_query(network_query_fn)
+    # THE cfg of the call; its path says which noise scale the kernels apply and whether a backward can follow
+    cfg_of = partial(ro.RenderCfg.of, opt, precision=_PRECISION, grid=occupancy is not None)
+    wants_grad = lambda params: torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for p in params))
+    if n == 0 and dense and occupancy is None and builtin:
+        # general networks: the dense path's own order, outputs attached to the networks (dense._render_no_rays)
+        cfg = cfg_of(raw_noise_std=0., need_grad=wants_grad(p for m in nets for p in m.parameters()))
+        return ro.result_dict(opt, render_rays_dense(cfg, rays, {}, network_fn, network_fine if n_f > 0 else None), coarse_first=True)
     if n == 0:      # empty batch: the reference returns empty tensors of the right trailing shapes
-        e = lambda *tail: torch.zeros((0,) + tail, dtype=torch.float32, device=dev)
-        outs = (e(3), e(), e(), e(N_samples + max(n_f, 0) if march else N_samples + n_f, 4))
-        if n_f > 0 and not march:
-            outs += ((e(3), e(), e()) if proposal is None else ()) + (e(),)
-        outs += (e(),) * (int(distortion) + int(interlevel))
         if occupancy is not None:       # nothing was evaluated; the grid is validated as on the staged path
             occupancy._desc()
-            occupancy.last_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(clip_to_occupancy, early_stop_eps, proposal,
-                                                                                             march_stop_eps, march_fit), 0)
-        return _result_dict(outs, retraw, coarse_first=False, distortion=distortion, interlevel=interlevel)
-    rnd, std = _draw_randoms(n, dev, N_samples, n_f, perturb, raw_noise_std, pytest, randoms, proposal, march)
-    cfg = dict(N_samples=int(N_samples), N_importance=n_f, lindisp=bool(lindisp), white_bkgd=bool(white_bkgd),
-               raw_noise_std=std, precision=_PRECISION)
-    if distortion:      # (the key exists only with the option: the passes read cfg.get("distortion", False))
-        cfg["distortion"] = True
-    if interlevel:
-        cfg["interlevel"] = True
+            occupancy.last_stats = dict.fromkeys(("evaluated", "total") + opt.stats_keys, 0)
+        return ro.result_dict(opt, opt.empty_outputs(dev), coarse_first=False)
+    rnd, std = ro.draw_randoms(opt, n, dev)
     if occupancy is not None:
-        if not _is_builtin_query(network_query_fn):
+        if not builtin:
             raise NotImplementedError("render_rays: occupancy= together with a user network_query_fn is not implemented (mask inside the "
                                       "hook with occupancy.occupied(pts) instead)")
         if dense:
             raise NotImplementedError("render_rays: occupancy= together with general (DenseNeRF) networks is not implemented; the grid "
                                       "path runs the fused NeRF architecture only")
-        evaluated = nets if proposal is None else nets[-1:]        # (proposal: network_fine if given, else network_fn)
-        if torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for m in evaluated for p in m.parameters())):
-            from .occupancy import DensityGrid
-            if not isinstance(occupancy, DensityGrid):
-                raise NotImplementedError("render_rays: a plain OccupancyGrid together with a needed gradient (grad mode on and parameters or "
-                                          "rays that require grad) is not implemented: a static grid would hide what the network has not "
-                                          "learnt yet.  Render under torch.no_grad(), or train through an occupancy.DensityGrid (the grid "
-                                          "that follows the network: maybe_update every step)")
-            grid_grad = True
-        else:
-            grid_grad = False
-        # what _grid_chain reads, set once for both paths; the reduced class is an inference form whose last-sample fix-up is per ray: the
-        # compacted points, and gradients anyway, run on the fp16x3 products
-        cfg.update(proposal=None if march else proposal, early_stop_eps=early_stop_eps, march_steps=march_steps, march_stop_eps=march_stop_eps,
-                   march_step_size=march_step_size, march_fit=march_fit)
-        if cfg["precision"] == "fp16_fp8c":
-            cfg["precision"] = "fp16x3"
-        if march:       # ONE pass over all the slots: what the two paths below run as a coarse-only call on the march's depths
-            cfg.update(N_samples=int(N_samples) + max(n_f, 0), N_importance=0)
+        evaluated = nets[-1:] if opt.one_pass else nets        # (one pass: network_fine if given, else network_fn)
+        grid_grad = wants_grad(p for m in evaluated for p in m.parameters())
+        if grid_grad and not isinstance(occupancy, ro.DensityGrid):
+            raise NotImplementedError("render_rays: a plain OccupancyGrid together with a needed gradient (grad mode on and parameters or "
+                                      "rays that require grad) is not implemented: a static grid would hide what the network has not "
+                                      "learnt yet.  Render under torch.no_grad(), or train through an occupancy.DensityGrid (the grid "
+                                      "that follows the network: maybe_update every step)")
+        cfg = cfg_of(raw_noise_std=std, need_grad=grid_grad)        # what _grid_chain reads, once for both paths
+        if opt.march:       # ONE pass over all the slots: what the two paths below run as a coarse-only call on the march's depths
+            cfg = dataclasses.replace(cfg, N_samples=opt.slots, N_importance=0)
             rnd = {k_: v for k_, v in (("u_march", rnd.get("u_march")), ("noise_c", rnd.get("noise_f"))) if v is not None}
         n_hit = None
         if clip_to_occupancy:       # (after the guards: a refused call launches nothing; the draws above do not depend on near / far)
             rays, hit = occupancy.clip_rays(rays)
             n_hit = hit.sum()       # read back after the passes, which synchronise anyway
-        if proposal is not None:        # one network, handed on as model_c
+        if opt.one_pass:        # one network, handed on as model_c
             model_c, model_f = evaluated[0], None
         else:
             same = n_f <= 0 or network_fine is None or network_fine is network_fn
@@ -1523,63 +1339,34 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             outs = _RenderRaysGrid.apply(cfg, rays, rnd, model_c, model_f, occupancy, *params)
         else:
             outs = _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, occupancy)
-        ret = _result_dict(outs, retraw, coarse_first=True, distortion=distortion, interlevel=interlevel)
         if n_hit is not None:
             occupancy.last_stats = dict(occupancy.last_stats, rays_hit=int(n_hit.item()), rays=n)
-        return ret
-    if not _is_builtin_query(network_query_fn):
-        return _render_rays_hooked(rays, rnd, network_fn, network_query_fn, int(N_samples), n_f, network_fine if n_f > 0 else None,
-                                   bool(lindisp), white_bkgd, std, retraw, distortion, interlevel)
+        return ro.result_dict(opt, outs, coarse_first=True)
+    if not builtin:
+        return _render_rays_hooked(rays, rnd, network_fn, network_query_fn, opt.N_samples, n_f, network_fine if n_f > 0 else None,
+                                   opt.lindisp, opt.white_bkgd, std, opt.retraw, opt.distortion, opt.interlevel)
     if dense:
-        from .dense import render_rays_dense
-        ret = render_rays_dense(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None)
-        if not retraw:
-            ret.pop("raw")
-        return ret
+        cfg = cfg_of(raw_noise_std=std, need_grad=wants_grad(p for m in nets for p in m.parameters()))
+        return ro.result_dict(opt, render_rays_dense(cfg, rays, rnd, network_fn, network_fine if n_f > 0 else None), coarse_first=True)
     params = network_fn.param_list()
     same = network_fine is None or network_fine is network_fn
     if n_f > 0 and not same:
         params = params + network_fine.param_list()
     # activations are saved only when a backward can follow (Function.forward itself always runs in no-grad mode)
-    cfg["need_grad"] = torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for p in params))
-    if cfg["precision"] == "fp16_fp8c" and cfg["need_grad"]:
-        cfg["precision"] = "fp16x3"         # the reduced class is an inference form; gradients: the fp16x3 datapath, unchanged
+    cfg = cfg_of(raw_noise_std=std, need_grad=wants_grad(params))
     outs = _RenderRays.apply(cfg, rays, rnd, network_fn, None if (same or n_f <= 0) else network_fine, *params)
-    last = {}
-    if interlevel:      # the node's trailing outputs; their keys come last
-        outs, last = outs[:-1], {'interlevel': outs[-1]}
-    if distortion:
-        outs, last = outs[:-1], {'distortion': outs[-1], **last}
-    if n_f <= 0:
-        rgb_map, disp_map, acc_map, raw = outs
-        ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map}
-        if retraw:
-            ret['raw'] = raw
-        ret.update(last)
-        return ret
-    rgb_map, disp_map, acc_map, raw, rgb0, disp0, acc0, z_std = outs
-    ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map}
-    if retraw:
-        ret['raw'] = raw
-    ret['rgb0'] = rgb0
-    ret['disp0'] = disp0
-    ret['acc0'] = acc0
-    ret['z_std'] = z_std
-    ret.update(last)
-    return ret
+    return ro.result_dict(opt, outs, coarse_first=False)
 
 
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """run_nerf.py:54-66.  Injected ``randoms`` (one row per ray) are sliced with the rays, so a chunked call consumes
-    the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks (with ``clip_to_occupancy``
-    its "rays_hit" / "rays" too, with ``early_stop_eps`` its "rays_stopped", with ``proposal="march"`` its "rays_truncated" and with
-    ``march_stop_eps`` its "rays_stopped", with ``march_fit`` > 0 its "rays_refit"); so are a ``baked`` field's."""
+    the same draws as an unchunked one.  An ``occupancy`` grid's last_stats are summed over the chunks: "evaluated", "total" and the keys
+    the call's options add, which render_options._stats_keys names once for render_rays and for this function
+    (unchecked_stats_keys: the keywords are forwarded as given, nothing is validated here); so are a ``baked`` field's."""
     all_ret = {}
     randoms = kwargs.pop("randoms", None)
     occ = kwargs.get("occupancy")
-    occ_stats = dict.fromkeys(("evaluated", "total") + _option_stats_keys(kwargs.get("clip_to_occupancy"), kwargs.get("early_stop_eps"),
-                                                                          kwargs.get("proposal"), kwargs.get("march_stop_eps"),
-                                                                          kwargs.get("march_fit", 0)), 0)
+    occ_stats = dict.fromkeys(("evaluated", "total") + ro.unchecked_stats_keys(kwargs), 0)
     if randoms is not None:
         for k, v in randoms.items():
             if v.shape[0] != rays_flat.shape[0]:
