@@ -212,6 +212,155 @@ def _release(r):
 LAST_BACKWARD_PLAN = None
 
 
+# ---- what _RenderRays and _RenderRaysGrid share: sub-chunking, the forward's bookkeeping, and ONE backward (_backward) over pass records.
+# A pass record is a dict: z, raw, packed, act, w (the pass's compositing weights where the forward kept them; cfg.distortion /
+# cfg.interlevel), on the grid path also slot, rec, m.  _grid_pass appends it; the dense node makes it from _field_pass's dict.
+def _sub_chunks(n, sub):
+    """n rays in sub-chunks of at most `sub`: (rays per sub-chunk, [(lo, hi)]).  More than one: equal sub-chunks, multiples of 64 rays
+    (the last one takes what is left); n <= sub: `sub` as given and the one tile."""
+    if n > sub:
+        ceil_div = lambda a, b: -(-a // b)
+        sub = min(sub, 64 * ceil_div(ceil_div(n, ceil_div(n, sub)), 64))
+    return sub, [(lo, min(lo + sub, n)) for lo in range(0, n, sub)]
+
+
+def _pass_records(r):
+    """_field_pass's flat dict as pass records, [coarse, fine] or [only]; the last pass's weights are r["w"], the coarse ones r["w_c"]"""
+    rec = lambda s, w: {"z": r["z_" + s], "raw": r["raw_" + s], "packed": r["packed_" + s], "act": r["act_" + s], "w": r.get(w)}
+    return [rec("c", "w_c"), rec("f", "w")] if "z_f" in r else [rec("c", "w")]
+
+
+def _give_leases(records):
+    """hand the hb.WORKSPACE leases of pass records back (give ignores None: a dense record has no slot / rec, a freed one nothing)"""
+    for p in records:
+        for k_ in ("slot", "act", "rec"):
+            hb.WORKSPACE.give(p.get(k_))
+            p[k_] = None
+
+
+def _resident_tiles(tiles, rays, rnd, parts):
+    """the backward's tiles (lo, hi, rays, rnd, records, last) of a forward that kept every sub-chunk's records"""
+    for i, ((lo, hi), records) in enumerate(zip(tiles, parts)):
+        yield lo, hi, rays[lo:hi], rnd if len(tiles) == 1 else {k_: v[lo:hi] for k_, v in rnd.items()}, records, i == len(tiles) - 1
+
+
+def _keep_for_backward(ctx, cfg, rays, rnd, model_c, model_f, first_param):
+    """the forward's bookkeeping for _backward; the networks' parameters are the node's inputs from `first_param` on"""
+    ctx.cfg, ctx.model_c, ctx.model_f = cfg, model_c, model_f
+    ctx.same_net = model_f is None or model_f is model_c
+    ctx.n_params_c = len(_param_slices(model_c))
+    # which gradients the backward computes: the ray records' (input-gradient kernel), each network's parameters' (weight
+    # gradient; a frozen network gets none: no wgrad launch, no _grad_ready, .grad stays None)
+    ctx.rays_grad = bool(ctx.needs_input_grad[1])
+    ctx.wgrad_c = any(ctx.needs_input_grad[first_param:first_param + ctx.n_params_c])
+    ctx.wgrad_f = ctx.wgrad_c if ctx.same_net else any(ctx.needs_input_grad[first_param + ctx.n_params_c:])
+    ctx.set_materialize_grads(False)
+    ctx.rays, ctx.rnd = rays.detach(), rnd
+    # the folded feature layer of the split datapaths' backward reads the LIVE parameters (Wf, bf, Wv) next to
+    # fragments packed at forward time: remember which parameter state this forward saw
+    ctx.param_state = tuple(_param_state(m) for m in (model_c, model_f) if m is not None)
+    ctx.consumed = False
+
+
+def _upstream(cfg, gouts, coarse_image):
+    """(up_c, up_f): the upstream gradients of (rgb, disp, acc, raw, distortion, interlevel) of the coarse pass and of the fine one, None
+    for a pass the call does not have.  The two losses are the trailing outputs: the distortion loss belongs to the last pass, the
+    interlevel loss behind it to the coarse one.  coarse_image False (cfg.proposal: one pass, the refining one): there is no coarse image."""
+    fine, inter = cfg.N_importance > 0, cfg.interlevel
+    up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-2 if inter else -1] if cfg.distortion else None, None)
+    up_c = (gouts[4], gouts[5], gouts[6], None, None, gouts[-1] if inter else None) if fine and coarse_image else None
+    if not fine:
+        up_c, up_f = up_f, None
+    return up_c, up_f
+
+
+def _composite_adjoint(cfg, rays, p, raw, noise, up, target, rays_grad):
+    """(d_raw, d_dn) of pass record p on the ray tile `rays`: the compositing backward with the losses' adjoints as its d_weights.  `up`:
+    the tile's rows of the six upstream gradients (_upstream); target: the record whose (w, z) the interlevel loss fits p's weights to;
+    d_dn [n, 3], the compositing's |d| term (dists = dz |d|), when the rays need a gradient and the compositing ran, else None."""
+    d_rgb, d_disp, d_acc, d_raw_up, d_dist, d_inter = up
+    n, dev, z = rays.shape[0], rays.device, p["z"]
+    if d_rgb is None and (d_disp is not None or d_acc is not None or d_dist is not None or d_inter is not None):
+        d_rgb = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+    c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
+    if d_rgb is None:       # only `raw` itself (extras['raw'], e.g. a sigma regulariser) carries a gradient
+        return c(d_raw_up), None
+    d_dn = torch.empty((n, 3), dtype=torch.float32, device=dev) if rays_grad else None
+    # the distortion loss reaches raw (and |d|) through the weights' adjoint: d_weights of the compositing backward
+    extra = {} if d_dist is None else {"d_weights": hb.distortion_bwd(p["w"], z, rays, c(d_dist), nf_stride=rays.shape[1], nf_offset=6)}
+    if d_inter is not None:     # the interlevel loss, likewise: p is the proposal, target the refining pass
+        extra = {"d_weights": hb.interlevel_bwd(p["w"], z, target["w"], target["z"], c(d_inter))}
+    d_raw = hb.raw2outputs_bwd(raw, z, rays, rays.shape[1], noise, cfg.raw_noise_std, cfg.white_bkgd, c(d_rgb), c(d_acc), c(d_disp),
+                               rays_d_offset=3, d_rays_d=d_dn, **extra)
+    if d_raw_up is not None:
+        d_raw += d_raw_up
+    return d_raw, d_dn
+
+
+def _backward(ctx, gouts, n_lead, tiles, field_step, after_pass, release):
+    """THE backward of both nodes; n_lead: the node's inputs in front of the networks' parameters.  tiles: an iterable of (lo, hi, rays, rnd, records, last), asked for one tile at a time (the dense
+    node's recompute plan runs a sub-chunk's forward when its tile is asked for); field_step(record, rays, d_raw, model, grad,
+    accumulate, d_rays) -> whether it wrote `grad`: the path's field backward from d_raw on; after_pass(record): the path is done with
+    a pass of a tile (called for the coarse pass before the fine pass's backward, with or without an upstream gradient); release():
+    nothing of the forward is needed any more.  Per tile coarse, then fine; a network's _grad_ready fires once, with the final flat
+    vector, behind its last launch: after the coarse pass of the last tile -- unless the fine pass adds into the same vector --, and
+    after the fine pass of the last tile."""
+    if ctx.consumed:
+        raise RuntimeError(_FREED_MSG)
+    cfg = ctx.cfg
+    none_c = (None,) * ctx.n_params_c
+    none_all = (None,) * n_lead + none_c + (() if ctx.same_net else none_c)
+    if not cfg.need_grad:
+        return none_all
+    now = tuple(_param_state(m) for m in (ctx.model_c, ctx.model_f) if m is not None)
+    if cfg.precision != "fp32" and now != ctx.param_state:
+        raise RuntimeError(_STALE_MSG)
+    fine = cfg.N_importance > 0
+    up_c, up_f = _upstream(cfg, gouts, coarse_image=cfg.proposal is None)
+    has = lambda up: up is not None and any(g is not None for g in up)
+    if not has(up_c) and not has(up_f):
+        ctx.consumed = True
+        release()
+        return none_all
+    dev = ctx.rays.device
+    grad_c = torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev) if ctx.wgrad_c else None
+    grad_f = None if (ctx.same_net or not fine or not ctx.wgrad_f) else torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev)
+    wrote = {"c": False, "f": False}
+    # dL/d(ray records), summed over both passes (near / far: zero -- render() builds them from Python floats)
+    d_rays_all = torch.zeros((ctx.rays.shape[0], 11), dtype=torch.float32, device=dev) if ctx.rays_grad else None
+    shared = ctx.same_net and fine and has(up_f)      # the fine pass adds into the coarse network's gradient
+    raw_last = (ctx.saved_tensors or (None,))[0]        # one tile: the last pass's raw is an output (save_for_backward)
+
+    def pass_grad(p, rays, noise, up, lo, hi, target, model, grad, key):
+        d_rays = None if d_rays_all is None else d_rays_all[lo:hi]
+        d_raw, d_dn = _composite_adjoint(cfg, rays, p, raw_last if p.get("raw") is None else p["raw"], noise,
+                                         tuple(None if g is None else g[lo:hi] for g in up), target, d_rays is not None)
+        if (grad is not None or d_rays is not None) and field_step(p, rays, d_raw, model, grad, wrote[key], d_rays):
+            wrote[key] = True
+        if d_dn is not None:
+            d_rays[:, 3:6] += d_dn          # the compositing's |d| term
+
+    for lo, hi, rays, rnd, records, last in tiles:
+        if has(up_c):
+            pass_grad(records[0], rays, rnd.get("noise_c"), up_c, lo, hi, records[-1], ctx.model_c, grad_c, "c")
+            if last and not shared and grad_c is not None:     # final: its all-reduce may start under the fine network's backward
+                _grad_ready(ctx.model_c, grad_c)
+        after_pass(records[0])
+        if fine and has(up_f):
+            model, grad, key = (ctx.model_c, grad_c, "c") if ctx.same_net else (ctx.model_f, grad_f, "f")
+            pass_grad(records[-1], rays, rnd.get("noise_f"), up_f, lo, hi, None, model, grad, key)
+            if last and grad is not None:
+                _grad_ready(model, grad)
+        after_pass(records[-1])
+    ctx.consumed = True
+    release()
+    lead = (None, d_rays_all) + (None,) * (n_lead - 2)
+    out_c = _grad_views(ctx.model_c, grad_c) if wrote["c"] else none_c
+    if ctx.same_net:
+        return lead + out_c
+    return lead + out_c + (_grad_views(ctx.model_f, grad_f) if wrote["f"] else none_c)
+
+
 class _RenderRays(torch.autograd.Function):
     """The whole of render_rays (run_nerf.py:308-418) as one autograd node.
 
@@ -226,24 +375,23 @@ class _RenderRays(torch.autograd.Function):
     saving and the backward re-runs it, with saving, one sub-chunk at a time (the kernels are deterministic, so the
     recomputed pass is bit-identical to the first): bounded memory for +1 inference-speed forward.
 
-    cfg.distortion: one trailing differentiable output, the distortion loss [N] of the last pass's weights (_field_pass), which stay
-    among the saved tensors; its upstream gradient enters the last pass's compositing backward as d_weights (nerf_distortion_bwd), in
-    all three plans.  cfg.interlevel: one trailing differentiable output (behind the distortion loss), the interlevel loss [N] of the
-    coarse pass's weights against the refining pass's; both passes' weights stay among the saved tensors (the recompute plan recomputes
-    them) and its upstream gradient enters the COARSE pass's compositing backward as d_weights (nerf_interlevel_bwd): it reaches model_c
-    through the coarse pass only, and alone it runs no backward of the refining pass."""
+    The backward is _backward, shared with _RenderRaysGrid; the three plans are its three tile sources.  cfg.distortion: one trailing
+    differentiable output, the distortion loss [N] of the last pass's weights (_field_pass), which that pass's record keeps as "w"; its
+    upstream gradient enters the last pass's compositing backward as d_weights (_composite_adjoint: nerf_distortion_bwd).
+    cfg.interlevel: one trailing differentiable output (behind the distortion loss), the interlevel loss [N] of the coarse pass's weights
+    against the refining pass's; both records keep their "w" (the recompute plan recomputes them) and its upstream gradient enters the
+    COARSE pass's compositing backward as d_weights (nerf_interlevel_bwd): it reaches model_c through the coarse pass only, and alone
+    it runs no backward of the refining pass."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, *params):
         n_f = cfg.N_importance
         need = cfg.need_grad
         n = rays.shape[0]
-        sub = hb.max_saved_rays(cfg.N_samples, n_f, cfg.precision) if need else n
-        ctx.checkpoint = bool(need and n > sub)
+        sub, ctx.sub_tiles = _sub_chunks(n, hb.max_saved_rays(cfg.N_samples, n_f, cfg.precision) if need else n)
+        ctx.checkpoint = len(ctx.sub_tiles) > 1
         ctx.tiles = None
         if ctx.checkpoint:
-            ceil_div = lambda a, b: -(-a // b)
-            sub = min(sub, 64 * ceil_div(ceil_div(n, ceil_div(n, sub)), 64))        # equal sub-chunks, multiples of 64 rays
             # resident sub-chunks only if they fit the budget AND what the device actually has free right now: what the driver reports
             # + the pool's idle leases LARGE ENOUGH to hold a sub-chunk's saved activations (smaller ones serve nothing) + half of
             # what torch's caching allocator holds without using (cached blocks are fragmented: only part of them can back a
@@ -252,12 +400,11 @@ class _RenderRays(torch.autograd.Function):
             lease = min(hb.act_floats(sub, cfg.N_samples, prec_), hb.act_floats(sub, cfg.N_samples + n_f, prec_) if n_f > 0 else 1 << 62)
             cached = torch.cuda.memory_reserved(rays.device) - torch.cuda.memory_allocated(rays.device)
             free_now = torch.cuda.mem_get_info(rays.device)[0] + cached // 2 + hb.WORKSPACE.idle_bytes(rays.device, lease)
-            if hb.saved_bytes(sub, cfg.N_samples, n_f, prec_) * ceil_div(n, sub) <= min(hb.SAVE_TOTAL_BYTES, int(0.9 * free_now)):
+            if hb.saved_bytes(sub, cfg.N_samples, n_f, prec_) * len(ctx.sub_tiles) <= min(hb.SAVE_TOTAL_BYTES, int(0.9 * free_now)):
                 ctx.checkpoint = False
-                ctx.tiles = [(lo, min(lo + sub, n)) for lo in range(0, n, sub)]
+                ctx.tiles = ctx.sub_tiles
         global LAST_BACKWARD_PLAN
         LAST_BACKWARD_PLAN = ("recompute" if ctx.checkpoint else "resident sub-chunks" if ctx.tiles is not None else "one launch", n, sub)
-        ctx.sub_rays = sub
         prec = cfg.precision
         dist, inter = cfg.distortion, cfg.interlevel
         if not need and not dist and not inter and hb.INFER_ONE_LAUNCH and hb.render_infer_supported(cfg.N_samples, n_f, prec):
@@ -294,37 +441,20 @@ class _RenderRays(torch.autograd.Function):
             for r_, n_ in ([(r, n)] if ctx.tiles is None else [(p_, hi - lo) for p_, (lo, hi) in zip(parts, ctx.tiles)]):
                 hb.RANGE_MONITOR.after_forward([(r_[k_], s_) for k_, s_ in (("act_c", cfg.N_samples), ("act_f", cfg.N_samples + n_f))
                                                 if r_.get(k_) is not None], n_)
-        ctx.cfg, ctx.model_c, ctx.model_f = cfg, model_c, model_f
-        ctx.same_net = model_f is None or model_f is model_c
-        ctx.n_params_c = len(_param_slices(model_c))
-        # which gradients the backward computes: the ray records' (input-gradient kernel), each network's parameters' (weight
-        # gradient; a frozen network gets none: no wgrad launch, no _grad_ready, .grad stays None)
-        ctx.rays_grad = bool(ctx.needs_input_grad[1])
-        ctx.wgrad_c = any(ctx.needs_input_grad[5:5 + ctx.n_params_c])
-        ctx.wgrad_f = ctx.wgrad_c if ctx.same_net else any(ctx.needs_input_grad[5 + ctx.n_params_c:])
-        ctx.need = need
-        ctx.set_materialize_grads(False)
-        ctx.rays, ctx.rnd = rays.detach(), rnd
         # What the backward needs, WITHOUT the node's own outputs: an output carries grad_fn = this node, so keeping it
         # in ctx.__dict__ is a node -> ctx -> output -> node cycle the garbage collector cannot break (a graph dropped
         # without backward would pin its ~11 GB of saved activations for good).  The one output the backward reads,
         # `raw` of the last pass, goes through save_for_backward, which autograd knows how to hold without a cycle.
+        # ctx.saved: the pass records of every tile ("w": a pass's weights under cfg.distortion / cfg.interlevel; not an output)
         ctx.saved = None
         if ctx.tiles is not None:
-            keep = ("packed_c", "z_c", "act_c", "raw_c", "packed_f", "z_f", "act_f", "raw_f", "w", "w_c")
-            ctx.saved = [{k_: p_[k_] for k_ in keep if k_ in p_} for p_ in parts]     # per-sub-chunk tensors, none is an output
+            ctx.saved = [_pass_records(p_) for p_ in parts]     # per-sub-chunk tensors, none is an output
         elif need and not ctx.checkpoint:
-            # ("w": the last pass's weights under cfg.distortion or cfg.interlevel, N S 4 bytes, "w_c": the coarse pass's under
-            # cfg.interlevel, N N_samples 4 bytes; neither is an output)
-            keep = ("packed_c", "z_c", "act_c", "packed_f", "z_f", "act_f", "w", "w_c") + (("raw_c",) if n_f > 0 else ())
-            ctx.saved = {k: r[k] for k in keep if k in r}
-            ctx.save_for_backward(r["raw_f"] if n_f > 0 else r["raw_c"])
+            ctx.saved = [_pass_records(r)]
+            ctx.save_for_backward(ctx.saved[0][-1].pop("raw"))
         elif not need:
             _release(r)
-        # the folded feature layer of the split datapaths' backward reads the LIVE parameters (Wf, bf, Wv) next to
-        # fragments packed at forward time: remember which parameter state this forward saw
-        ctx.param_state = tuple(_param_state(m) for m in (model_c, model_f) if m is not None)
-        ctx.consumed = False
+        _keep_for_backward(ctx, cfg, rays, rnd, model_c, model_f, 5)
         tail = ((r["distortion"],) if dist else ()) + ((r["interlevel"],) if inter else ())      # trailing differentiable outputs
         if n_f <= 0:
             return (r["rgb_c"], r["disp_c"], r["acc_c"], r["raw_c"]) + tail
@@ -333,124 +463,27 @@ class _RenderRays(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        if ctx.consumed:
-            raise RuntimeError(_FREED_MSG)
         cfg = ctx.cfg
-        n_lead = 5
-        none_c = (None,) * ctx.n_params_c
-        none_all = (None,) * n_lead + none_c + (() if ctx.same_net else none_c)
-        if not ctx.need:
-            return none_all
-        now = tuple(_param_state(m) for m in (ctx.model_c, ctx.model_f) if m is not None)
-        if cfg.precision != "fp32" and now != ctx.param_state:
-            raise RuntimeError(_STALE_MSG)
-        rays_all, rnd_all = ctx.rays, ctx.rnd
-        std, wb, prec = cfg.raw_noise_std, cfg.white_bkgd, cfg.precision
-        dev = rays_all.device
-        n_all = rays_all.shape[0]
-        n_f = cfg.N_importance
-        fine = n_f > 0
-        # upstream gradients of (rgb, disp, acc, raw, distortion, interlevel) of the fine (or only) pass and of the coarse pass; the two
-        # losses are the trailing outputs: the distortion loss belongs to the last pass, the interlevel loss to the coarse one
-        inter = cfg.interlevel
-        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-2 if inter else -1] if cfg.distortion else None, None)
-        up_c = (gouts[4], gouts[5], gouts[6], None, None, gouts[-1] if inter else None) if fine else None
-        if not fine:
-            up_c, up_f = up_f, None
-        has = lambda up: up is not None and any(g is not None for g in up)
-        if not has(up_c) and not has(up_f):
-            ctx.consumed = True
-            if ctx.saved is not None:
-                for r_ in (ctx.saved if isinstance(ctx.saved, list) else [ctx.saved]):
-                    _release(r_)
-                ctx.saved = None
-            return none_all
-        grad_c = torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev) if ctx.wgrad_c else None
-        grad_f = None if (ctx.same_net or not fine or not ctx.wgrad_f) else torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev)
-        wrote = {"c": False, "f": False}
-        # dL/d(ray records), summed over both passes (near / far: zero -- render() builds them from Python floats)
-        d_rays_all = torch.zeros((n_all, 11), dtype=torch.float32, device=dev) if ctx.rays_grad else None
 
-        def field_grad(rays, model, packed, act, raw, z, noise, up, lo, hi, grad, key, w=None, target=None):
-            d_rgb, d_disp, d_acc, d_raw_up, d_dist, d_inter = (None if g is None else g[lo:hi] for g in up)
-            m = hi - lo
-            if d_rgb is None and (d_disp is not None or d_acc is not None or d_dist is not None or d_inter is not None):
-                d_rgb = torch.zeros((m, 3), dtype=torch.float32, device=dev)
-            c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
-            d_rays = None if d_rays_all is None else d_rays_all[lo:hi]
-            d_dn = None
-            if d_rgb is None:       # only `raw` itself (extras['raw'], e.g. a sigma regulariser) carries a gradient
-                d_raw = c(d_raw_up)
-            else:
-                if d_rays is not None:
-                    d_dn = torch.empty((m, 3), dtype=torch.float32, device=dev)
-                # the distortion loss reaches raw (and |d|) through the weights' adjoint: d_weights of the compositing backward
-                extra = {} if d_dist is None else {"d_weights": hb.distortion_bwd(w, z, rays, c(d_dist), nf_stride=rays.shape[1], nf_offset=6)}
-                if d_inter is not None:     # the interlevel loss, likewise: w, z are the proposal, target = the refining pass's (weights, depths)
-                    extra = {"d_weights": hb.interlevel_bwd(w, z, target[0], target[1], c(d_inter))}
-                d_raw = hb.raw2outputs_bwd(raw, z, rays, rays.shape[1], noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
-                                           rays_d_offset=3, d_rays_d=d_dn, **extra)
-                if d_raw_up is not None:
-                    d_raw += d_raw_up
-            if grad is None and d_rays is None:
-                return
-            hb.field_bwd(packed, act, d_raw, grad, wrote[key], precision=prec, params=model.flat_params(),
-                         input_grad=None if d_rays is None else (rays, z, d_rays, True))
-            if d_dn is not None:
-                d_rays[:, 3:6] += d_dn          # the compositing's |d| term (dists = dz |d|)
-            if grad is not None:
-                wrote[key] = True
+        def recomputed():       # the recompute plan: a sub-chunk's forward runs, with saving, when _backward asks for its tile
+            for lo, hi in ctx.sub_tiles:
+                rays, rnd = ctx.rays[lo:hi], {k: v[lo:hi] for k, v in ctx.rnd.items()}
+                yield lo, hi, rays, rnd, _pass_records(_field_pass(cfg, rays, rnd, ctx.model_c, ctx.model_f, save=True)), hi == ctx.rays.shape[0]
 
-        shared = ctx.same_net and fine and has(up_f)      # the fine pass adds into the coarse network's gradient
+        def field_step(p, rays, d_raw, model, grad, accumulate, d_rays):
+            hb.field_bwd(p["packed"], p["act"], d_raw, grad, accumulate, precision=cfg.precision, params=model.flat_params(),
+                         input_grad=None if d_rays is None else (rays, p["z"], d_rays, True))
+            return grad is not None
 
-        def backprop(r, rays, rnd, lo, hi, last=True):
-            if has(up_c):
-                field_grad(rays, ctx.model_c, r["packed_c"], r["act_c"], r["raw_c"], r["z_c"], rnd.get("noise_c"), up_c, lo, hi, grad_c, "c",
-                           r.get("w_c") if fine else r.get("w"), (r.get("w"), r.get("z_f")))
-                if last and not shared and grad_c is not None:     # final: its all-reduce may start under the fine network's backward
-                    _grad_ready(ctx.model_c, grad_c)
-            hb.WORKSPACE.give(r["act_c"])
-            r["act_c"] = None
-            if fine and has(up_f):
-                if ctx.same_net:
-                    field_grad(rays, ctx.model_c, r["packed_f"], r["act_f"], r["raw_f"], r["z_f"], rnd.get("noise_f"), up_f, lo, hi, grad_c, "c",
-                               r.get("w"))
-                    if last and grad_c is not None:
-                        _grad_ready(ctx.model_c, grad_c)
-                else:
-                    field_grad(rays, ctx.model_f, r["packed_f"], r["act_f"], r["raw_f"], r["z_f"], rnd.get("noise_f"), up_f, lo, hi, grad_f, "f",
-                               r.get("w"))
-                    if last and grad_f is not None:
-                        _grad_ready(ctx.model_f, grad_f)
-            _release(r)
+        def release():
+            for records in ctx.saved or ():
+                _give_leases(records)
+            ctx.saved = None
 
-        if ctx.tiles is not None:
-            for i, (lo, hi) in enumerate(ctx.tiles):
-                backprop(ctx.saved[i], rays_all[lo:hi], {k: v[lo:hi] for k, v in rnd_all.items()}, lo, hi, last=i == len(ctx.tiles) - 1)
-        elif not ctx.checkpoint:
-            r = dict(ctx.saved)
-            r["raw_f" if fine else "raw_c"] = ctx.saved_tensors[0]
-            backprop(r, rays_all, rnd_all, 0, n_all)
-            ctx.saved["act_c"] = ctx.saved["act_f"] = None
-        else:
-            step = ctx.sub_rays
-            for lo in range(0, n_all, step):
-                hi = min(lo + step, n_all)
-                rays = rays_all[lo:hi]
-                rnd = {k: v[lo:hi] for k, v in rnd_all.items()}
-                backprop(_field_pass(cfg, rays, rnd, ctx.model_c, ctx.model_f, save=True), rays, rnd, lo, hi, last=hi == n_all)
-        ctx.saved = None
-        ctx.consumed = True
-        out_c = none_c
-        if wrote["c"]:
-            out_c = _grad_views(ctx.model_c, grad_c)
-        lead = (None, d_rays_all) + (None,) * (n_lead - 2)
-        if ctx.same_net:
-            return lead + out_c
-        out_f = none_c
-        if wrote["f"]:
-            out_f = _grad_views(ctx.model_f, grad_f)
-        return lead + out_c + out_f
+        # (a pass's act goes back to the pool right behind that pass's backward, in front of the next pass's: a training loop finds the
+        # same buffers every step)
+        return _backward(ctx, gouts, 5, recomputed() if ctx.checkpoint else _resident_tiles(ctx.sub_tiles, ctx.rays, ctx.rnd, ctx.saved or ()),
+                         field_step, lambda p: _give_leases([p]), release)
 
 
 class _Composite(torch.autograd.Function):
@@ -902,16 +935,15 @@ def _render_rays_occupancy(cfg, rays, rnd, model_c, model_f, grid):
 
 
 class _RenderRaysGrid(torch.autograd.Function):
-    """render_rays through an occupancy.DensityGrid WITH gradients, as one autograd node shaped like _RenderRays (one _grad_ready per
-    network per backward with the final flat vector, a shared network accumulated in the kernel, no weight-gradient launch for a frozen
-    network, the stale-parameter and freed-graph checks, no saved output in ctx).
+    """render_rays through an occupancy.DensityGrid WITH gradients, as one autograd node with _RenderRays' backward (_backward: one
+    _grad_ready per network with the final flat vector, a shared network accumulated in the kernel, no weight-gradient launch for a
+    frozen network, the stale-parameter and freed-graph checks; no saved output in ctx).
 
-    Forward: _grid_chain -- the stages of the no-grad grid render -- per ray sub-chunk, every pass a saving _grid_pass (depths ->
-    nerf_occ_compact -> ONE read-back of M -> the field on the M one-sample records with saved activations -> nerf_occ_expand, zeros for
-    skipped samples -> nerf_raw2outputs).  Backward, per pass: nerf_raw2outputs_bwd -> nerf_occ_gather
-    (d_raw of the M points) -> delta chain / weight gradient on the M records, the input gradient in point mode when the rays need one
-    -> nerf_occ_fold_rays (per-point [M, 11] -> per-ray [N, 11]) + the compositing's |d| term.  A skipped sample has raw = 0 and no
-    gradient: what a network_query_fn that evaluates only the occupied points computes.
+    Forward: _grid_chain -- the stages of the no-grad grid render -- per ray sub-chunk, every pass a saving _grid_pass.  Backward, per
+    pass: _composite_adjoint (nerf_raw2outputs_bwd) -> this node's field_step: nerf_occ_gather (d_raw of the M points) -> delta chain /
+    weight gradient on the M records, the input gradient in point mode when the rays need one -> nerf_occ_fold_rays (per-point [M, 11]
+    -> per-ray [N, 11]); then the compositing's |d| term.  A skipped sample has raw = 0 and no gradient: what a network_query_fn that
+    evaluates only the occupied points computes.
 
     Kept from forward to backward, per pass: slot (4 B per sample point), the saved activations of M points (leased at
     _grid_pass_lease's size), z, raw, and the M records (44 B each) only when the rays need a gradient -- hb.WORKSPACE leases, given
@@ -924,11 +956,8 @@ class _RenderRaysGrid(torch.autograd.Function):
     -- so nothing beyond slot is kept for it and the backward is unchanged.  cfg.march_steps: depths and stop depth are constants of
     the graph, computed per sub-chunk; with N_importance = 0 the backward is the coarse-only one; outputs (rgb, disp, acc, raw) --
     cfg.march_stop_eps, cfg.march_step_size and cfg.march_fit change which kernel computes those constants and nothing of the
-    backward.  cfg.distortion: the tuple ends with the distortion loss [N] of the last pass's weights, which that pass's record keeps
-    as "w"; its upstream gradient enters the pass's compositing backward as d_weights, in front of nerf_occ_gather.  cfg.interlevel (the
-    two-pass form only): the tuple ends with the interlevel loss [N] of the coarse pass's weights against the refining pass's, both
-    records keep their "w", and its upstream gradient enters the COARSE pass's compositing backward as d_weights (nerf_interlevel_bwd):
-    alone it runs no backward of the refining pass."""
+    backward.  cfg.distortion, cfg.interlevel (the two-pass form only): the trailing outputs and their adjoints are _RenderRays'; the
+    d_weights enter the compositing backward in front of nerf_occ_gather."""
 
     @staticmethod
     def forward(ctx, cfg, rays, rnd, model_c, model_f, grid, *params):
@@ -936,23 +965,11 @@ class _RenderRaysGrid(torch.autograd.Function):
         prec = cfg.precision
         n = rays.shape[0]
         desc = grid._desc()
-        ctx.proposal = cfg.proposal is not None
-        ctx.same_net = model_f is None or model_f is model_c
-        ctx.n_params_c = len(_param_slices(model_c))
-        ctx.rays_grad = rays_grad = bool(ctx.needs_input_grad[1])
-        ctx.wgrad_c = any(ctx.needs_input_grad[6:6 + ctx.n_params_c])
-        ctx.wgrad_f = ctx.wgrad_c if ctx.same_net else any(ctx.needs_input_grad[6 + ctx.n_params_c:])
-        sub = hb.max_saved_rays(n_c, n_f, prec)
-        if n > sub:
-            ceil_div = lambda a, b: -(-a // b)
-            sub = min(sub, 64 * ceil_div(ceil_div(n, ceil_div(n, sub)), 64))        # equal sub-chunks, multiples of 64 rays
-            tiles = [(lo, min(lo + sub, n)) for lo in range(0, n, sub)]
-        else:
-            sub, tiles = n, [(0, n)]
+        sub, tiles = _sub_chunks(n, hb.max_saved_rays(n_c, n_f, prec))
         global LAST_BACKWARD_PLAN
-        LAST_BACKWARD_PLAN = ("resident sub-chunks" if len(tiles) > 1 else "one launch", n, sub)
+        LAST_BACKWARD_PLAN = ("resident sub-chunks" if len(tiles) > 1 else "one launch", n, min(n, sub))
         stats = {"evaluated": 0, "total": 0}
-        budget = {"rays_grad": rays_grad, "resident": 0, "rays": n}
+        budget = {"rays_grad": bool(ctx.needs_input_grad[1]), "resident": 0, "rays": n}
         n_stopped, n_truncated, n_refit = [], [], []
         parts, outs = [], []
         try:
@@ -967,9 +984,7 @@ class _RenderRaysGrid(torch.autograd.Function):
                 n_refit += [] if refit is None else [refit]
         except BaseException:
             for passes in parts:
-                for p in passes:
-                    for k_ in ("slot", "act", "rec"):
-                        hb.WORKSPACE.give(p.get(k_))
+                _give_leases(passes)
             raise
         _grid_stats(grid, stats, torch.stack(n_stopped).sum() if n_stopped else None, torch.stack(n_truncated).sum() if n_truncated else None,
                     torch.stack(n_refit).sum() if n_refit else None)
@@ -984,120 +999,40 @@ class _RenderRaysGrid(torch.autograd.Function):
             ctx.save_for_backward(parts[0][-1].pop("raw"))
         else:
             out = tuple(torch.cat([o[i] for o in outs], 0) for i in range(len(outs[0])))       # new tensors: the per-tile ones are no outputs
-        ctx.cfg, ctx.model_c, ctx.model_f, ctx.tiles, ctx.parts = cfg, model_c, model_f, tiles, parts
-        ctx.rays, ctx.rnd = rays.detach(), rnd
-        ctx.param_state = tuple(_param_state(m_) for m_ in (model_c, model_f) if m_ is not None)
-        ctx.consumed = False
-        ctx.set_materialize_grads(False)
+        ctx.tiles, ctx.parts = tiles, parts
+        _keep_for_backward(ctx, cfg, rays, rnd, model_c, model_f, 6)
         if n_f > 0:     # z_std (in front of the trailing losses if there are any): the reference detaches z_samples (run_nerf.py:394)
             ctx.mark_non_differentiable(out[-1 - int(cfg.distortion) - int(cfg.interlevel)])
         return tuple(out)
 
     @staticmethod
     def backward(ctx, *gouts):
-        if ctx.consumed:
-            raise RuntimeError(_FREED_MSG)
-        cfg = ctx.cfg
-        none_c = (None,) * ctx.n_params_c
-        none_all = (None,) * 6 + none_c + (() if ctx.same_net else none_c)
-        now = tuple(_param_state(m) for m in (ctx.model_c, ctx.model_f) if m is not None)
-        std, wb, prec = cfg.raw_noise_std, cfg.white_bkgd, cfg.precision
-        if prec != "fp32" and now != ctx.param_state:
-            raise RuntimeError(_STALE_MSG)
-        rays_all, rnd_all = ctx.rays, ctx.rnd
-        dev = rays_all.device
-        n_all = rays_all.shape[0]
-        fine = cfg.N_importance > 0
-        # (the losses are the trailing outputs: the distortion loss belongs to the last pass, the interlevel loss behind it to the coarse one)
-        inter = cfg.interlevel
-        up_f = (gouts[0], gouts[1], gouts[2], gouts[3], gouts[-2 if inter else -1] if cfg.distortion else None, None)
-        if ctx.proposal:        # one pass, the refining one: there is no coarse image
-            up_c = None
-        else:
-            up_c = (gouts[4], gouts[5], gouts[6], None, None, gouts[-1] if inter else None) if fine else None
-        if not fine:
-            up_c, up_f = up_f, None
-        has = lambda up: up is not None and any(g is not None for g in up)
+        prec = ctx.cfg.precision
+
+        def field_step(p, rays, d_raw, model, grad, accumulate, d_rays):
+            m, z, dev = p["m"], p["z"], rays.device
+            if m == 0:         # no point of this pass was evaluated: no field launch, zero gradient from it
+                if grad is not None and not accumulate:
+                    grad.zero_()
+                return grad is not None
+            slot = p["slot"][:z.numel()].view(torch.int32)
+            d_raw_c = hb.occ_gather(slot, d_raw, torch.empty((m, 1, 4), dtype=torch.float32, device=dev))
+            d_rec = rec = None
+            if d_rays is not None:
+                rec = p["rec"][:11 * m].view(m, 11)
+                d_rec = torch.empty((m, 11), dtype=torch.float32, device=dev)
+            hb.field_bwd(p["packed"], p["act"], d_raw_c, grad, accumulate, precision=prec, params=model.flat_params(),
+                         input_grad=None if d_rec is None else (rec, torch.zeros((m, 1), dtype=torch.float32, device=dev), d_rec, False))
+            if d_rec is not None:
+                hb.occ_fold_rays(slot, z, d_rec, d_rays, accumulate=True)
+            return grad is not None
 
         def release():
             for passes in ctx.parts:
-                for p in passes:
-                    for k_ in ("slot", "act", "rec"):
-                        hb.WORKSPACE.give(p.get(k_))
-                        p[k_] = None
+                _give_leases(passes)
             ctx.parts = None
-            ctx.consumed = True
 
-        if not has(up_c) and not has(up_f):
-            release()
-            return none_all
-        grad_c = torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev) if ctx.wgrad_c else None
-        grad_f = None if (ctx.same_net or not fine or not ctx.wgrad_f) else torch.empty(hb.N_PARAMS, dtype=torch.float32, device=dev)
-        wrote = {"c": False, "f": False}
-        d_rays_all = torch.zeros((n_all, 11), dtype=torch.float32, device=dev) if ctx.rays_grad else None
-
-        def field_grad(rays, model, p, raw, noise, up, lo, hi, grad, key, target=None):
-            d_rgb, d_disp, d_acc, d_raw_up, d_dist, d_inter = (None if g is None else g[lo:hi] for g in up)
-            nt, z, m = hi - lo, p["z"], p["m"]
-            if d_rgb is None and (d_disp is not None or d_acc is not None or d_dist is not None or d_inter is not None):
-                d_rgb = torch.zeros((nt, 3), dtype=torch.float32, device=dev)
-            c = lambda t: t.to(torch.float32).contiguous() if t is not None else None
-            d_rays = None if d_rays_all is None else d_rays_all[lo:hi]
-            d_dn = None
-            if d_rgb is None:       # only `raw` itself carries a gradient
-                d_raw = c(d_raw_up)
-            else:
-                if d_rays is not None:
-                    d_dn = torch.empty((nt, 3), dtype=torch.float32, device=dev)
-                # the distortion loss enters as d_weights of the compositing backward, in front of nerf_occ_gather
-                extra = {} if d_dist is None else {"d_weights": hb.distortion_bwd(p["w"], z, rays, c(d_dist), nf_stride=rays.shape[1], nf_offset=6)}
-                if d_inter is not None:     # the interlevel loss, likewise: this pass is the proposal, target = the refining pass's record
-                    extra = {"d_weights": hb.interlevel_bwd(p["w"], z, target["w"], target["z"], c(d_inter))}
-                d_raw = hb.raw2outputs_bwd(raw, z, rays, rays.shape[1], noise, std, wb, c(d_rgb), c(d_acc), c(d_disp),
-                                           rays_d_offset=3, d_rays_d=d_dn, **extra)
-                if d_raw_up is not None:
-                    d_raw += d_raw_up
-            if m == 0:         # no point of this pass was evaluated: no field launch, zero gradient from it
-                if grad is not None and not wrote[key]:
-                    grad.zero_()
-                    wrote[key] = True
-            elif grad is not None or d_rays is not None:
-                d_raw_c = hb.occ_gather(p["slot"][:nt * z.shape[1]].view(torch.int32), d_raw, torch.empty((m, 1, 4), dtype=torch.float32, device=dev))
-                d_rec = rec = None
-                if d_rays is not None:
-                    rec = p["rec"][:11 * m].view(m, 11)
-                    d_rec = torch.empty((m, 11), dtype=torch.float32, device=dev)
-                hb.field_bwd(p["packed"], p["act"], d_raw_c, grad, wrote[key], precision=prec, params=model.flat_params(),
-                             input_grad=None if d_rec is None else (rec, torch.zeros((m, 1), dtype=torch.float32, device=dev), d_rec, False))
-                if d_rec is not None:
-                    hb.occ_fold_rays(p["slot"][:nt * z.shape[1]].view(torch.int32), z, d_rec, d_rays, accumulate=True)
-                if grad is not None:
-                    wrote[key] = True
-            if d_dn is not None:
-                d_rays[:, 3:6] += d_dn          # the compositing's |d| term (dists = dz |d|)
-
-        shared = ctx.same_net and fine and has(up_f)      # the fine pass adds into the coarse network's gradient
-        raw_last = ctx.saved_tensors[0] if len(ctx.tiles) == 1 else None
-        for i, ((lo, hi), passes) in enumerate(zip(ctx.tiles, ctx.parts)):
-            last = i == len(ctx.tiles) - 1
-            rays = rays_all[lo:hi]
-            rnd = rnd_all if len(ctx.tiles) == 1 else {k: v[lo:hi] for k, v in rnd_all.items()}
-            raw_of = lambda p: p["raw"] if "raw" in p else raw_last
-            if has(up_c):
-                field_grad(rays, ctx.model_c, passes[0], raw_of(passes[0]), rnd.get("noise_c"), up_c, lo, hi, grad_c, "c", passes[-1])
-                if last and not shared and grad_c is not None:     # final: its all-reduce may start under the fine network's backward
-                    _grad_ready(ctx.model_c, grad_c)
-            if fine and has(up_f):
-                model, grad, key = (ctx.model_c, grad_c, "c") if ctx.same_net else (ctx.model_f, grad_f, "f")
-                field_grad(rays, model, passes[-1], raw_of(passes[-1]), rnd.get("noise_f"), up_f, lo, hi, grad, key)
-                if last and grad is not None:
-                    _grad_ready(model, grad)
-        release()
-        lead = (None, d_rays_all) + (None,) * 4
-        out_c = _grad_views(ctx.model_c, grad_c) if wrote["c"] else none_c
-        if ctx.same_net:
-            return lead + out_c
-        return lead + out_c + (_grad_views(ctx.model_f, grad_f) if wrote["f"] else none_c)
+        return _backward(ctx, gouts, 6, _resident_tiles(ctx.tiles, ctx.rays, ctx.rnd, ctx.parts), field_step, lambda p: None, release)
 
 
 def _render_rays_baked(ray_batch, baked, network_query_fn, perturb, white_bkgd, pytest, given):
