@@ -741,7 +741,25 @@ int nerf_baked_render(const NerfOccGrid* grid, const int* node_index, const void
  *     n_rays == 0 writes zeros.
  * ray_stride >= 11; sh_degree 0, 1 or 2; step_size finite and > 0; 1 <= max_steps <= 2^24; 1 <= n_rows (<= 2^26 in bwd_rows);
  * 0 <= total <= 2^30; table, records and sample_grads 16-byte aligned.  n_rays == 0 is a no-op in the first three (in bwd_rows rays may
- * then be null). */
+ * then be null).
+ *   nerf_baked_train_bwd_rays (csrc/baked_rays.hip; additive in ABI v10): d_rays fp32 [n_rays][11], every element written: the gradient
+ *     of the same render with respect to the ray records -- columns 0:3 (o), 3:6 (d) and 8:11 (viewdir); columns 6 and 7 (near, far) are
+ *     zeros.  BakedTrainer.render_rays_reference(ray_grad=True) is the definition: the depths z_k, the validity, the
+ *     kept set and every sample's cell are constants; f = (o + d z - lo) scale - cell and Y = sh_basis(viewdir) are differentiated, the
+ *     normalisation of viewdir is the caller's.  Per record, with a_0 = dL/dv0 (gated) and g_c = dL/dl_c from sample_grads, over the
+ *     eight corner rows of the fp16 table in corner order 000 001 .. 111:
+ *       m_q[b] = (g_R row_q[1 + b] + g_G row_q[1 + B + b]) + g_B row_q[1 + 2B + b],   r_q = a_0 row_q[0] + sum_b m_q[b] Y_b   (ascending b)
+ *       dL/df_x = sum_q (q_x ? + : -) (w_y w_z)_q r_q (likewise y, z),   dL/dY_b = sum_q ((w_x w_y) w_z)_q m_q[b]           (ascending q)
+ *       dL/dx = scale * dL/df;   d_o += dL/dx,   d_d += z dL/dx,   d_viewdir += (dY/dviewdir)^T dL/dY.
+ *     One wavefront per ray, lane = record, rounds of 64 over offsets[ray] .. offsets[ray + 1].  Order of summation: lane l adds the
+ *     records l, l + 64, l + 128, .. of its ray into nine accumulators (d_o, d_d, d_viewdir) in that order, then one xor butterfly over
+ *     the lanes, partners at distance 32, 16, 8, 4, 2, 1 in turn, finishes each sum: the same inputs give the same bits.  No atomics, no
+ *     LDS, no scratch.  Per record 32 B of the record, 16 B of sample_grads, 32 B of node_index and 8 rows of 2 W bytes are read (what
+ *     nerf_baked_train_fwd gathers, plus 16 B); per ray 8 B of offsets and 12 B of viewdir are read and 44 B written.  offsets, a
+ *     record's cell and a node's row are checked against their buffers (a record with a cell outside the grid adds nothing, a row
+ *     outside the table reads row 0).  Rays without records -- misses, invalid rays -- give zeros.  ray_stride >= 11; sh_degree 0, 1 or
+ *     2; n_rows >= 1; 0 <= total <= 2^30; table, records and sample_grads 16-byte aligned.  n_rays == 0 is a no-op; total == 0 writes
+ *     zeros. */
 int nerf_baked_count(const NerfOccGrid* grid, const float* rays, int ray_stride, const float* u /* nullable: 0.5 */, int n_rays,
                      float step_size, int max_steps, int* counts, void* stream);
 int nerf_baked_train_fwd(const NerfOccGrid* grid, const int* node_index, const void* table /* fp16 rows */, int n_rows, int sh_degree,
@@ -753,6 +771,9 @@ int nerf_baked_train_bwd_samples(const float* records, const int* offsets, int n
 int nerf_baked_train_bwd_rows(const NerfOccGrid* grid, const int* row_node, int n_rows, int sh_degree, const float* rays, int ray_stride,
                               int n_rays, const float* records, const float* sample_grads, const int* order, const int* cell_start,
                               int total, float* grad, void* stream);
+int nerf_baked_train_bwd_rays(const NerfOccGrid* grid, const int* node_index, const void* table /* fp16 rows */, int n_rows, int sh_degree,
+                              const float* rays, int ray_stride, int n_rays, const float* records, const float* sample_grads,
+                              const int* offsets, int total, float* d_rays /* [n_rays][11], every element written */, void* stream);
 
 /* ---- baked field, regularisers (additive in ABI v10): total variation and Cauchy sparsity of the fp32 master table over the stored
  * lattice nodes (baked.BakedTrainer.regularizers; baked.regularizer_reference is the definition).  values is fp32

@@ -11,7 +11,9 @@ deterministic backward to the table's rows (csrc/baked_train.hip: every contribu
 atomics), so the table can be fitted to images through the renderer (PlenOctrees' fine-tuning, Plenoxels) and written back with
 ``to_field()``.  ``BakedTrainer.regularizers()`` adds what ties a node to its neighbours: the total variation of the density and of the
 colour coefficients between stored nodes and Plenoxels' Cauchy sparsity of the density, on the fp32 master, with a gradient that is a
-gather (csrc/baked_reg.hip); ``regularizer_reference`` is their definition.
+gather (csrc/baked_reg.hip); ``regularizer_reference`` is their definition.  ``BakedTrainer.render_rays(ray_grad=True)`` also hands the
+gradient to the rays (csrc/baked_rays.hip; the depths are constants), and ``ray_records`` turns ``RayBatcher``'s batches into ray records
+inside the graph: a camera pose is refined against a baked field through ``PoseRefinement``.
 """
 import copy
 import math
@@ -93,12 +95,18 @@ def fibonacci_sphere(n, dtype=torch.float64, device=None):
     return torch.stack([s * torch.cos(phi), s * torch.sin(phi), z], -1).to(dtype=dtype, device=device)
 
 
-def _render_reference(who, grid, index, table, sh_degree, step_size, stop_eps, rays, u, white_bkgd, max_steps, dtype, values):
+def _render_reference(who, grid, index, table, sh_degree, step_size, stop_eps, rays, u, white_bkgd, max_steps, dtype, values,
+                      ray_grad=False, geometry=None):
     """BakedField.render_rays_reference's body (its docstring is the definition), shared with BakedTrainer.render_rays_reference: `values`
     [n_rows, >= 1 + 3B] stands in for the table where it is not None, and may require grad -- everything behind the gather is ordinary
-    differentiable torch"""
+    differentiable torch.  ray_grad=True: the definition of the gradient with respect to the rays (BakedField.render_rays_reference)"""
     max_steps = _check_max_steps(max_steps, who)
-    r, ok, uu, dn, M, _ = OccupancyGrid._march_rays(who, rays, u, max_steps, 1)
+    if geometry is not None and not ray_grad:
+        raise ValueError(f"{who}: geometry= belongs to ray_grad=True")
+    if geometry is not None and (not isinstance(geometry, torch.Tensor) or geometry.shape != rays.shape):
+        raise ValueError(f"{who}: geometry must be a tensor of rays' shape")
+    geo = rays if geometry is None else geometry.to(rays.device)
+    r, ok, uu, dn, M, _ = OccupancyGrid._march_rays(who, geo, u, max_steps, 1)
     if rays.shape[1] < 11:
         raise ValueError(f"{who}: rays [N, >= 11] (o, d, near, far, viewdir)")
     dev = rays.device
@@ -119,7 +127,6 @@ def _render_reference(who, grid, index, table, sh_degree, step_size, stop_eps, r
         t = (pts - f32(grid.lo)) * f32(grid.scale)
         inside, _, bit = grid._classify(pts)
         keep = valid & inside & bit
-        Y = sh_basis(rays.detach()[:, 8:11].to(torch.float32).to(dtype), sh_degree)       # [N, B]
         B = (sh_degree + 1) ** 2
         index = index.to(dev).to(torch.int64)
         table = table.to(dev)
@@ -127,8 +134,17 @@ def _render_reference(who, grid, index, table, sh_degree, step_size, stop_eps, r
         rows, cols = keep.nonzero(as_tuple=True)
         tk = t[rows, cols]
         cell = torch.floor(tk)
-        f = (tk - cell).to(dtype)
         ci = cell.to(torch.int64)
+        if ray_grad:
+            # the kept samples' rows of the live rays, picked before anything is computed from them: a ray that keeps nothing (a NaN
+            # among its components included) gets exact zeros
+            live = rays[rows]
+            x = live[:, 0:3].to(dtype) + live[:, 3:6].to(dtype) * z[rows, cols].to(dtype)[:, None]
+            f = (x - f32(grid.lo).to(dtype)) * f32(grid.scale).to(dtype) - cell.to(dtype)
+            Yk = sh_basis(live[:, 8:11].to(dtype), sh_degree)
+        else:
+            f = (tk - cell).to(dtype)
+            Yk = sh_basis(rays.detach()[:, 8:11].to(torch.float32).to(dtype), sh_degree)[rows]       # [S, B]
         val = torch.zeros((rows.numel(), 1 + 3 * B), dtype=dtype, device=dev)
         for c in range(8):
             ox, oy, oz = (c >> 2) & 1, (c >> 1) & 1, c & 1
@@ -137,7 +153,6 @@ def _render_reference(who, grid, index, table, sh_degree, step_size, stop_eps, r
             corner = table[index[node]][:, :1 + 3 * B].to(dtype) if values is None else values[index[node]][:, :1 + 3 * B].to(dtype)
             val = val + w[:, None] * corner
         sigma = torch.clamp(val[:, 0], min=0.0)
-        Yk = Y[rows]
         logits = torch.zeros((rows.numel(), 3), dtype=dtype, device=dev)
         for b in range(B):
             logits = logits + val[:, 1 + b:1 + 3 * B:B] * Yk[:, b:b + 1]
@@ -353,7 +368,7 @@ class BakedField:
         return self
 
     # ------------------------------------------------------------------ the definition
-    def render_rays_reference(self, rays, u=None, white_bkgd=False, max_steps=1 << 14, dtype=torch.float64):
+    def render_rays_reference(self, rays, u=None, white_bkgd=False, max_steps=1 << 14, dtype=torch.float64, ray_grad=False, geometry=None):
         """The definition of the baked render, in plain torch on rays' device: rays [N, >= 11] (o, d, near, far, viewdir), u fp32 [N] in
         [0, 1) or None (0.5) -> {"rgb_map" [N, 3], "disp_map", "acc_map", "depth_map" [N] in `dtype`, "n_samples" int32 [N],
         "rays_stopped" int}.  Every discrete decision is the fp32 expression of the march references; the continuous arithmetic runs in
@@ -374,9 +389,19 @@ class BakedField:
         nothing give the background, acc = depth = 0 and n_samples = 0.
         The stop (stop_eps > 0), in units of the kernel's rounds: the candidates are taken 64 at a time; behind the first round at
         whose end the running T -- the product over everything kept so far -- is below stop_eps no further round is walked.
-        "rays_stopped" counts the rays with such a round (never one with stop_eps = 0); n_samples counts what was composited."""
+        "rays_stopped" counts the rays with such a round (never one with stop_eps = 0); n_samples counts what was composited.
+
+        ray_grad=True is the definition of the GRADIENT with respect to the rays (the forward values stay those above within rounding;
+        with ray_grad=False the rays are detached and the function is what it always was, bit for bit).  The depths are constants,
+        as everywhere in this project: validity, z_k, valid_k, keep_k and every kept sample's cell come from `geometry` (a tensor of
+        rays' shape; None: rays.detach()) by the fp32 expressions above -- nothing discrete and no depth depends on the live rays.
+        The fractional coordinates come from the live rays in dtype, f = ((o + d z_k - lo) scale) - cell with z_k, lo, scale and cell
+        the fp32 values cast to dtype; f may fall a rounding error outside [0, 1], the blend is then an extrapolation of the same cell
+        and is continuous.  Y = sh_basis(rays[:, 8:11]) comes from the live rays as the polynomial it is: normalising the view direction
+        is the caller's torch op.  Everything behind that is unchanged.  Columns 6 and 7 (near, far), any column >= 11 and u get no
+        gradient; depth_map uses the constant z_k.  `geometry` exists for finite differences: without it a moved d would move z."""
         return _render_reference("BakedField.render_rays_reference", self.grid, self.index, self.table, self.sh_degree, self.step_size,
-                                 self.stop_eps, rays, u, white_bkgd, max_steps, dtype, None)
+                                 self.stop_eps, rays, u, white_bkgd, max_steps, dtype, None, ray_grad, geometry)
 
     # ------------------------------------------------------------------ the kernel
     def render_rays(self, rays, u=None, white_bkgd=False, max_steps=1 << 14):
@@ -413,12 +438,27 @@ def inverted_index(cells, n_cells):
     return order.to(torch.int32), cell_start.to(torch.int32)
 
 
+def ray_records(batch_rays, near, far):
+    """[N, 11] ray records (o, d, near, far, viewdir = d / |d|) of batch_rays [2, N, 3] -- origins and directions as ``RayBatcher.next``
+    returns them -- in plain differentiable torch: the glue between ``PoseRefinement`` / ``RayBatcher`` and
+    ``BakedTrainer.render_rays(ray_grad=True)``.  near and far are numbers; the normalisation of the view direction is part of the
+    graph, so d receives the gradient of viewdir as well.
+
+        rays, target = batcher.next(refine(poses)); out = trainer.render_rays(ray_records(rays, 2.0, 6.0), ray_grad=True)"""
+    if not isinstance(batch_rays, torch.Tensor) or batch_rays.dim() != 3 or batch_rays.shape[0] != 2 or batch_rays.shape[2] != 3:
+        raise ValueError("ray_records: batch_rays [2, N, 3] (origins, directions)")
+    o, d = batch_rays[0], batch_rays[1]
+    view = d / torch.norm(d, dim=-1, keepdim=True)
+    return torch.cat([o, d, torch.full_like(o[:, :1], float(near)), torch.full_like(o[:, :1], float(far)), view], -1)
+
+
 class _BakedRender(torch.autograd.Function):
-    """rgb_map, acc_map, depth_map of the trainer's fp16 table with the gradient handed to ``values`` (straight-through): count, forward
-    and, in backward, the sample pass, the inverted index and the row pass"""
+    """rgb_map, acc_map, depth_map of the trainer's fp16 table with the gradient handed to ``values`` (straight-through) and, where `live`
+    -- the caller's rays as they were given, or None -- is a tensor, to the rays: count, forward and, in backward, the sample pass once,
+    then for ``values`` the inverted index and the row pass and for the rays the ray pass, each only where ctx.needs_input_grad asks"""
 
     @staticmethod
-    def forward(ctx, values, trainer, rays, u, white_bkgd, max_steps):
+    def forward(ctx, values, live, trainer, rays, u, white_bkgd, max_steps):
         desc = trainer.grid._desc()
         counts = hb.baked_count(desc, rays, u, trainer.step_size, max_steps)
         offsets = torch.zeros(rays.shape[0] + 1, dtype=torch.int64, device=rays.device)
@@ -431,6 +471,7 @@ class _BakedRender(torch.autograd.Function):
                                                       max_steps, white_bkgd, offsets, total)
         trainer.last_stats = {"rays": int(rays.shape[0]), "samples": total}
         ctx.trainer, ctx.rays, ctx.white_bkgd, ctx.total = trainer, rays, bool(white_bkgd), total
+        ctx.live = None if live is None else (live.shape, live.dtype, live.device)
         ctx.save_for_backward(records, offsets)
         return rgb, acc, depth
 
@@ -440,14 +481,23 @@ class _BakedRender(torch.autograd.Function):
         trainer, total = ctx.trainer, ctx.total
         f32 = lambda g: g.detach().to(torch.float32).contiguous()
         grads = hb.baked_train_bwd_samples(records, offsets, total, trainer.step_size, ctx.white_bkgd, f32(g_rgb), f32(g_acc), f32(g_depth))
-        if total > 0:
-            order, cell_start = inverted_index(records[:total, 0].view(torch.int32), trainer.grid.n_cells)
-        else:
-            order = torch.zeros(1, dtype=torch.int32, device=records.device)
-            cell_start = torch.zeros(trainer.grid.n_cells + 1, dtype=torch.int32, device=records.device)
-        grad = hb.baked_train_bwd_rows(trainer.grid._desc(), trainer.row_node, trainer.sh_degree, ctx.rays, records, grads, order, cell_start,
-                                       total)
-        return grad, None, None, None, None, None
+        grad = d_live = None
+        if ctx.needs_input_grad[0]:
+            if total > 0:
+                order, cell_start = inverted_index(records[:total, 0].view(torch.int32), trainer.grid.n_cells)
+            else:
+                order = torch.zeros(1, dtype=torch.int32, device=records.device)
+                cell_start = torch.zeros(trainer.grid.n_cells + 1, dtype=torch.int32, device=records.device)
+            grad = hb.baked_train_bwd_rows(trainer.grid._desc(), trainer.row_node, trainer.sh_degree, ctx.rays, records, grads, order,
+                                           cell_start, total)
+        if ctx.needs_input_grad[1]:
+            shape, dtype, device = ctx.live
+            d_rays = hb.baked_train_bwd_rays(trainer.grid._desc(), trainer.index, trainer.table, trainer.sh_degree, ctx.rays, records, grads,
+                                             offsets, total)
+            d_live = torch.zeros(shape, dtype=torch.float32, device=d_rays.device)      # (the columns behind the record get none)
+            d_live[:, :11] = d_rays
+            d_live = d_live.to(device=device, dtype=dtype)
+        return grad, d_live, None, None, None, None, None
 
 
 def _check_eps(eps, who):
@@ -631,28 +681,39 @@ class BakedTrainer:
         return self
 
     # ------------------------------------------------------------------ the definition
-    def render_rays_reference(self, rays, u=None, white_bkgd=False, max_steps=1 << 14, dtype=torch.float64, values=None):
+    def render_rays_reference(self, rays, u=None, white_bkgd=False, max_steps=1 << 14, dtype=torch.float64, values=None, ray_grad=False,
+                              geometry=None):
         """The definition of the training render, in plain torch on rays' device: ``BakedField.render_rays_reference``'s arithmetic (one
         body, _render_reference) with stop_eps = 0 -> {"rgb_map" [N, 3], "acc_map", "depth_map" [N] in `dtype`, "n_samples" int32 [N]}.
         `values` stands in for the table: None is the fp16 table cast to `dtype`; a tensor [n_rows, W] may require grad, and the result
         is differentiable with respect to it by ordinary autograd.  The gradient the kernels produce is autograd's gradient of this
-        function at the fp16 table's values."""
+        function at the fp16 table's values.  ray_grad=True (and `geometry`): differentiable in the rays as well, by
+        ``BakedField.render_rays_reference``'s definition of that gradient -- what ``render_rays(ray_grad=True)`` hands to the rays."""
         out = _render_reference("BakedTrainer.render_rays_reference", self.grid, self.index, self.table, self.sh_degree, self.step_size, 0.0,
-                                rays, u, white_bkgd, max_steps, dtype, values)
+                                rays, u, white_bkgd, max_steps, dtype, values, ray_grad, geometry)
         return {k: out[k] for k in ("rgb_map", "acc_map", "depth_map", "n_samples")}
 
     # ------------------------------------------------------------------ the kernels
-    def render_rays(self, rays, u=None, white_bkgd=False, max_steps=1 << 14):
+    def render_rays(self, rays, u=None, white_bkgd=False, max_steps=1 << 14, ray_grad=False):
         """{"rgb_map" fp32 [N, 3], "acc_map", "depth_map" fp32 [N]} of rays [N, >= 11] on the GPU: nerf_baked_render's bits with stop_eps
         = 0, carrying grad to ``values`` (nerf_baked_count, nerf_baked_train_fwd; in backward nerf_baked_train_bwd_samples, a stable sort
-        of the samples' cells, nerf_baked_train_bwd_rows).  Two backward calls on the same inputs give the same bits.  The rays are
-        detached: gradients to rays and poses are not part of this.  Under no_grad only the count and the forward run."""
+        of the samples' cells, nerf_baked_train_bwd_rows).  Two backward calls on the same inputs give the same bits.  Under no_grad
+        only the count and the forward run.
+
+        ray_grad=False: the rays are detached, whether they require grad or not.  ray_grad=True: the same forward, bit for bit, and the
+        result also carries grad to `rays` (nerf_baked_train_bwd_rays: ``render_rays_reference(ray_grad=True)``'s gradient within fp32
+        rounding -- the depths are constants; columns 0:6 and 8:11 receive a gradient, near, far, further columns and u none), so a
+        loss reaches camera poses through ``ray_records`` and ``PoseRefinement``.  The backward runs only what is asked for: the sample
+        pass once, the sort and the row pass only if ``values`` requires grad, the ray pass only if `rays` does -- so
+        ``trainer.values.requires_grad_(False)`` localises a camera against a frozen table without a sort or a row pass.  The ray pass
+        reads ``table`` when backward runs: call backward before ``commit()``."""
         max_steps = _check_max_steps(max_steps, "BakedTrainer.render_rays")
         if rays.dim() != 2 or rays.shape[1] < 11:
             raise ValueError("BakedTrainer.render_rays: rays [N, >= 11] (o, d, near, far, viewdir)")
+        live = rays if ray_grad else None
         rays = rays.detach().to(torch.float32).contiguous()
         u = None if u is None else u.detach().to(device=rays.device, dtype=torch.float32).contiguous()
-        rgb, acc, depth = _BakedRender.apply(self.values, self, rays, u, bool(white_bkgd), max_steps)
+        rgb, acc, depth = _BakedRender.apply(self.values, live, self, rays, u, bool(white_bkgd), max_steps)
         return {"rgb_map": rgb, "acc_map": acc, "depth_map": depth}
 
     # ------------------------------------------------------------------ regularisers

@@ -112,6 +112,7 @@ def _declare(lib):
         "nerf_baked_train_fwd": (i, [p, p, p, i, i, p, i, p, i, f, i, i, p, i, p, p, p, p, p]),
         "nerf_baked_train_bwd_samples": (i, [p, p, i, i, f, i, p, p, p, p, p]),
         "nerf_baked_train_bwd_rows": (i, [p, p, i, i, p, i, i, p, p, p, p, i, p, p]),
+        "nerf_baked_train_bwd_rays": (i, [p, p, p, i, i, p, i, i, p, p, p, i, p, p]),
         "nerf_baked_reg_fwd": (i, [p, p, p, p, i, i, f, f, f, f, p, p]),
         "nerf_baked_reg_bwd": (i, [p, p, p, p, i, i, f, f, f, f, p, p, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
@@ -144,6 +145,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_occ_view_carve",
            "nerf_iso_scratch_words", "nerf_iso_count", "nerf_iso_emit", "nerf_baked_render",
            "nerf_baked_count", "nerf_baked_train_fwd", "nerf_baked_train_bwd_samples", "nerf_baked_train_bwd_rows",
+           "nerf_baked_train_bwd_rays",
            "nerf_baked_reg_fwd", "nerf_baked_reg_bwd",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live",
            "nerf_distortion_fwd", "nerf_distortion_bwd", "nerf_interlevel_fwd", "nerf_interlevel_bwd"]
@@ -1638,6 +1640,35 @@ def baked_train_bwd_rows(desc, row_node, sh_degree, rays, records, sample_grads,
                                                _ptr(records, "records"), _ptr(sample_grads, "sample_grads"), _words(order, "order"),
                                                _words(cell_start, "cell_start"), total, _ptr(grad), _stream()), "nerf_baked_train_bwd_rows")
     return grad
+
+
+def baked_train_bwd_rays(desc, node_index, table, sh_degree, rays, records, sample_grads, offsets, total):
+    """nerf_baked_train_bwd_rays (csrc/baked_rays.hip): fp32 [n, 11], the gradient of baked_train_fwd's outputs with respect to the ray
+    records -- columns 0:3 (o), 3:6 (d) and 8:11 (viewdir); columns 6 and 7 are zeros -- from the forward's records and
+    baked_train_bwd_samples' sample gradients.  Per ray a fixed order of summation: two calls give the same bits."""
+    deg = int(sh_degree)
+    if deg not in (0, 1, 2):
+        raise NerfHipError(f"baked_train_bwd_rays: sh_degree must be 0, 1 or 2, got {sh_degree!r}")
+    n, stride = _baked_rays("baked_train_bwd_rays", rays, None)
+    nodes = (desc.res[0] + 1) * (desc.res[1] + 1) * (desc.res[2] + 1)
+    if node_index.numel() != nodes:
+        raise NerfHipError(f"baked_train_bwd_rays: node_index holds one entry per lattice node, {nodes}")
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float16 and table.is_contiguous() and table.dim() == 2
+            and table.shape[0] >= 1 and table.shape[1] == BAKED_ROW_HALVES[deg]):
+        raise NerfHipError(f"baked_train_bwd_rays: table must be a contiguous fp16 tensor [rows >= 1, {BAKED_ROW_HALVES[deg]}] on the GPU")
+    total = int(total)
+    if offsets.numel() != n + 1 or not (0 <= total <= BAKED_MAX_SAMPLES) or records.shape[0] < total or sample_grads.shape[0] < total:
+        raise NerfHipError("baked_train_bwd_rays: offsets holds n + 1 entries, and `total` (0 .. 2^30) records and sample gradients")
+    d_rays = torch.empty((n, 11), dtype=torch.float32, device=rays.device)
+    if n > 0:
+        # per sample 32 B of the record, 16 B of sample gradients and 32 B of node indices (the rows it gathers depend on the scene and
+        # are not counted, as in baked_train_fwd); per ray 20 B in and 44 B out
+        with _timed("baked_train_bwd_rays_kernel", 0.0, 64.0 * n + 80.0 * total):
+            _check(lib().nerf_baked_train_bwd_rays(ctypes.byref(desc), _words(node_index, "node_index"), table.data_ptr(), int(table.shape[0]),
+                                                   deg, _ptr(rays, "rays"), stride, n, _ptr(records, "records"),
+                                                   _ptr(sample_grads, "sample_grads"), _words(offsets, "offsets"), total, _ptr(d_rays),
+                                                   _stream()), "nerf_baked_train_bwd_rays")
+    return d_rays
 
 
 # ---- baked field, regularisers (csrc/baked_reg.hip; the user-facing method is baked.BakedTrainer.regularizers)
