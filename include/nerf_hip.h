@@ -799,6 +799,46 @@ int nerf_baked_reg_fwd(const NerfOccGrid* grid, const int* node_index, const int
 int nerf_baked_reg_bwd(const NerfOccGrid* grid, const int* node_index, const int* row_node, const float* values, int n_rows, int sh_degree,
                        float sx, float sy, float sz, float eps, const float* g /* device, 3 floats */, float* grad, void* stream);
 
+/* ---- hash-grid encoding (additive in ABI v10; csrc/hash_encode.hip; hashgrid.HashEncoding): a multiresolution
+ * lattice over the box [lo, lo + 1 / inv_extent], level l with (R_l + 1)^3 nodes (corners aligned), every level's rows in ONE fp32
+ * table embeddings [rows_total][n_features].  The HOST computes the level tables (Python float64 and integers) and hands them down
+ * in this record; the library checks them against each other (level_dense[l] iff (R_l + 1)^3 <= T = 2^log2_hashmap_size;
+ * level_offset = prefix sum of the rows owned: (R_l + 1)^3 for a dense level, T for a hashed one; level_offset[n_levels] =
+ * rows_total) and computes none of them.  The record lives in host memory.
+ *   slot of node (ix, iy, iz):  dense   ix + iy (R + 1) + iz (R + 1)^2
+ *                               hashed  (ix ^ iy * 2654435761 ^ iz * 805459861) mod T     in wrapping uint32 arithmetic
+ *   per point and level, in fp32 without contraction:  u = clamp((x - lo) inv_extent, 0, 1),  p = u R,  i = min(int(floor(p)), R - 1),
+ *   f = p - i;  corner c (bit 0 x, bit 1 y, bit 2 z) has the weight (wx wy) wz, wx = c & 1 ? fx : 1 - fx, ..;
+ *   out[p][l F + k] = sum_c w_c E[level_offset[l] + slot_c][k], accumulated in ascending c from w_0 v_0.
+ * Points outside the box are clamped; a non-finite coordinate reads inside the table (its output is unspecified).
+ * The points are either `points` [n_points][3], or -- points NULL -- o + d z_vals of ray records [n_points / n_samples][ray_stride]
+ * (o3, d3, ..) and z_vals [n_points], a separate multiply and add as in nerf_build_inputs.
+ *   nerf_hash_encode_fwd: writes columns 0 .. L F of the row-major matrix `out` with leading dimension ld_out >= L F (point it at a
+ *     column of a wider matrix: the other columns are untouched).  n_points == 0 returns 0 and launches nothing.
+ *   nerf_hash_encode_bwd: d_embeddings [rows_total][F], every element written, from d_out [n_points][ld_d_out]; deterministic.  With
+ *     M = max |d_out| = m 2^e (frexp) found on the device and q = 61 - e - ceil(log2(max(n_points, 1))), every contribution
+ *     t = w_c g (one fp32 product) becomes k = llrint((double)t 2^q) and is added to scratch[row][k] by a 64-bit integer atomic add;
+ *     the finishing pass writes (float)((double)acc 2^-q) and zeroes the accumulator.  |sum| <= M P < 2^61: no overflow, and integer
+ *     addition does not depend on its order, so two calls give the same bits.  M == 0: all zeros.  M not finite: all NaN (decided on
+ *     the device, no host read-back).  scratch: nerf_hash_scratch_words(grid) 64-bit words, 8-byte aligned, ZERO before its first use;
+ *     a complete call (phases = 3, or 1 then 2) leaves the accumulator zero (the last word holds the bits of M and is rewritten by every call).  phases: 1 = the maximum and the scatter, 2 = the finishing pass,
+ *     3 = both (1 and 2 as two calls with the same arguments give the bits of 3; they exist so the two can be timed apart).
+ *     No gradient with respect to the points is computed. */
+#define NERF_HASH_MAX_LEVELS 32
+typedef struct NerfHashGrid {
+    int n_levels, n_features, log2_hashmap_size, reserved;
+    float lo[3], inv_extent[3];
+    int level_resolution[NERF_HASH_MAX_LEVELS];
+    int level_dense[NERF_HASH_MAX_LEVELS];
+    long long level_offset[NERF_HASH_MAX_LEVELS + 1];
+} NerfHashGrid;
+size_t nerf_hash_scratch_words(const NerfHashGrid* grid);
+int nerf_hash_encode_fwd(const NerfHashGrid* grid, const float* embeddings, const float* points /* nullable */, const float* rays /* nullable */,
+                         int ray_stride, const float* z_vals /* nullable */, int n_samples, long n_points, float* out, int ld_out, void* stream);
+int nerf_hash_encode_bwd(const NerfHashGrid* grid, const float* points /* nullable */, const float* rays /* nullable */, int ray_stride,
+                         const float* z_vals /* nullable */, int n_samples, long n_points, const float* d_out, int ld_d_out, long long* scratch,
+                         float* d_embeddings, int phases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,8 +22,11 @@ from .mesh import density_volume, extract_mesh, extract_mesh_reference, mesh_fro
 from . import mesh  # noqa: F401
 from .baked import BakedField, BakedTrainer, ray_records, regularizer_reference, sh_basis  # noqa: F401
 from . import baked  # noqa: F401
+from .hashgrid import HashEncoding, HashNeRF  # noqa: F401
+from . import hashgrid  # noqa: F401
 
 __all__ = ["density_volume", "extract_mesh", "extract_mesh_reference", "mesh_from_network", "write_ply", "mesh","Embedder", "NeRF", "get_embedder", "batchify", "batchify_rays", "get_rays", "get_rays_np", "img2mse",
            "mse2psnr", "ndc_rays", "query_points", "raw2outputs", "render", "render_path", "render_rays",
            "run_network", "sample_pdf", "to8b", "config_parser", "create_nerf", "hip_backend", "parallel", "set_precision", "get_precision", "FlatAdam", "sample_ray_batch", "RayBatcher", "PoseRefinement", "DEFAULT_PRECISION", "check_range", "OccupancyGrid", "DensityGrid", "occupancy",
-           "distortion_loss", "distortion_loss_reference", "interlevel_loss", "interlevel_loss_reference", "BakedField", "BakedTrainer", "sh_basis", "baked", "regularizer_reference", "ray_records"]
+           "distortion_loss", "distortion_loss_reference", "interlevel_loss", "interlevel_loss_reference", "BakedField", "BakedTrainer", "sh_basis", "baked", "regularizer_reference", "ray_records",
+           "HashEncoding", "HashNeRF", "hashgrid"]

@@ -30,10 +30,10 @@ def _fwd(x, x_lo, K, w, w_lo, bias, y, y_lo, N, accumulate=False, relu=False):
                                       int(accumulate), int(relu), hb._stream()), "nerf_dense_fwd")
 
 
-def _dgrad(dy, dy_lo, N, w, w_lo, dx, K, accumulate=False, act=None):
+def _dgrad(dy, dy_lo, N, w, w_lo, dx, K, accumulate=False, act=None, dx_lo=0):
     dyp, lddy = _cols(dy, dy_lo, N)
     wp, ldw = _cols(w, w_lo, K)
-    dxp, lddx = _cols(dx, 0, K)
+    dxp, lddx = _cols(dx, dx_lo, K)
     hb._check(hb.lib().nerf_dense_dgrad(dyp, lddy, N, wp, ldw, dxp, lddx, K, dy.shape[0], int(accumulate),
                                         None if act is None else act.data_ptr(), 0 if act is None else act.shape[1], hb._stream()),
               "nerf_dense_dgrad")
@@ -96,7 +96,8 @@ class _DenseMLP(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out):
         m = ctx.model
-        if not ctx.needs:
+        x_grad = ctx.needs_input_grad[1]        # a learned encoding in front of the stack (hashgrid.HashNeRF) asks for d_x
+        if not (ctx.needs or x_grad):
             return (None, None) + (None,) * len(ctx.names)
         saved = ctx.saved_tensors
         x = saved[0]
@@ -108,6 +109,10 @@ class _DenseMLP(torch.autograd.Function):
         g = {n: torch.empty_like(p) for n, p in m.named_parameters()}
         h = hs[-1]
         d_h = new(W)
+        # d_x [P, input_ch + input_ch_views], only when x requires grad: the first layer's dgrad plus that of every layer behind a
+        # skip (accumulated, deepest first), and the view branch's columns.  Otherwise: the same launches as without it.
+        d_x = new(x.shape[1]) if x_grad else None
+        x_acc = False
         if m.use_viewdirs:
             feat, hv = saved[1 + D], saved[2 + D]
             cd, Wh = m.input_ch_views, W // 2
@@ -117,6 +122,8 @@ class _DenseMLP(torch.autograd.Function):
             _dgrad(d_out, 0, 3, m.rgb_linear.weight, 0, d_hv, Wh, act=hv)
             _wgrad(d_hv, 0, Wh, feat, 0, W, g["views_linears.0.weight"], 0, g["views_linears.0.bias"])
             _wgrad(d_hv, 0, Wh, x, cx, cd, g["views_linears.0.weight"], W)
+            if x_grad:
+                _dgrad(d_hv, 0, Wh, vl.weight, W, d_x, cd, dx_lo=cx)
             d_feat = new(W)
             _dgrad(d_hv, 0, Wh, vl.weight, 0, d_feat, W)
             _wgrad(d_feat, 0, W, h, 0, W, g["feature_linear.weight"], 0, g["feature_linear.bias"])
@@ -128,22 +135,29 @@ class _DenseMLP(torch.autograd.Function):
             _wgrad(d_out, 0, oc, h, 0, W, g["output_linear.weight"], 0, g["output_linear.bias"])
             _dgrad(d_out, 0, oc, m.output_linear.weight, 0, d_h, W, act=h)
             g["views_linears.0.weight"] = g["views_linears.0.bias"] = None           # unused without view directions (helpers:82)
+            if x_grad and x.shape[1] > cx:
+                d_x[:, cx:] = 0.0           # (view columns the stack never reads)
         for i in range(D - 1, -1, -1):          # d_h = dL / d(pre-activation of layer i)
             lin = m.pts_linears[i]
             wn, bn = f"pts_linears.{i}.weight", f"pts_linears.{i}.bias"
             if i == 0:
                 _wgrad(d_h, 0, W, x, 0, cx, g[wn], 0, g[bn])
+                if x_grad:
+                    _dgrad(d_h, 0, W, lin.weight, 0, d_x, cx, accumulate=x_acc)
                 break
             d_prev = new(W)
             if (i - 1) in m.skips:
                 _wgrad(d_h, 0, W, x, 0, cx, g[wn], 0, g[bn])
+                if x_grad:
+                    _dgrad(d_h, 0, W, lin.weight, 0, d_x, cx, accumulate=x_acc)
+                    x_acc = True
                 _wgrad(d_h, 0, W, hs[i - 1], 0, W, g[wn], cx)
                 _dgrad(d_h, 0, W, lin.weight, cx, d_prev, W, act=hs[i - 1])
             else:
                 _wgrad(d_h, 0, W, hs[i - 1], 0, W, g[wn], 0, g[bn])
                 _dgrad(d_h, 0, W, lin.weight, 0, d_prev, W, act=hs[i - 1])
             d_h = d_prev
-        return (None, None) + tuple(g[n] for n in ctx.names)
+        return (None, d_x) + tuple(g[n] for n in ctx.names)
 
 
 class DenseNeRF(nn.Module):

@@ -55,8 +55,9 @@ class _Embed(torch.autograd.Function):
 
 
 def get_embedder(multires, i=0):
-    """run_nerf_helpers.py:48-63."""
-    if i == -1:
+    """run_nerf_helpers.py:48-63.  i = 1 (not in the reference): the points reach the network raw -- create_nerf builds
+    hashgrid.HashNeRF networks, whose learned hash encoding is part of the network, not of the embedder."""
+    if i == -1 or i == 1:
         return nn.Identity(), 3
     eo = Embedder(include_input=True, input_dims=3, max_freq_log2=multires - 1, num_freqs=multires,
                   log_sampling=True, periodic_fns=[torch.sin, torch.cos])

@@ -115,6 +115,9 @@ def _declare(lib):
         "nerf_baked_train_bwd_rays": (i, [p, p, p, i, i, p, i, i, p, p, p, i, p, p]),
         "nerf_baked_reg_fwd": (i, [p, p, p, p, i, i, f, f, f, f, p, p]),
         "nerf_baked_reg_bwd": (i, [p, p, p, p, i, i, f, f, f, f, p, p, p]),
+        "nerf_hash_scratch_words": (sz, [p]),
+        "nerf_hash_encode_fwd": (i, [p, p, p, p, i, p, i, l, p, i, p]),
+        "nerf_hash_encode_bwd": (i, [p, p, p, i, p, i, l, p, i, p, p, i, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -147,6 +150,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_baked_count", "nerf_baked_train_fwd", "nerf_baked_train_bwd_samples", "nerf_baked_train_bwd_rows",
            "nerf_baked_train_bwd_rays",
            "nerf_baked_reg_fwd", "nerf_baked_reg_bwd",
+           "nerf_hash_scratch_words", "nerf_hash_encode_fwd", "nerf_hash_encode_bwd",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live",
            "nerf_distortion_fwd", "nerf_distortion_bwd", "nerf_interlevel_fwd", "nerf_interlevel_bwd"]
 
@@ -1713,6 +1717,87 @@ def baked_reg_bwd(desc, node_index, row_node, values, sh_degree, scales, eps, g)
         _check(lib().nerf_baked_reg_bwd(ctypes.byref(desc), _words(node_index, "node_index"), _words(row_node, "row_node"), _ptr(values, "values"),
                                         n_rows, deg, sx, sy, sz, eps, _ptr(g, "g"), _ptr(grad), _stream()), "nerf_baked_reg_bwd")
     return grad
+
+
+# ---- hash-grid encoding (csrc/hash_encode.hip; hashgrid.HashEncoding builds the record)
+HASH_MAX_LEVELS = 32
+
+
+class NerfHashGrid(ctypes.Structure):
+    """include/nerf_hip.h NerfHashGrid"""
+    _fields_ = [("n_levels", ctypes.c_int), ("n_features", ctypes.c_int), ("log2_hashmap_size", ctypes.c_int), ("reserved", ctypes.c_int),
+                ("lo", ctypes.c_float * 3), ("inv_extent", ctypes.c_float * 3), ("level_resolution", ctypes.c_int * HASH_MAX_LEVELS),
+                ("level_dense", ctypes.c_int * HASH_MAX_LEVELS), ("level_offset", ctypes.c_longlong * (HASH_MAX_LEVELS + 1))]
+
+
+def _hash_points(who, points, rays, z_vals):
+    """(points pointer, rays pointer, ray stride, z pointer, samples per ray, number of points): points [P, 3], or rays [N, >= 6] with
+    z_vals [N, S] (the points o + d z)"""
+    if points is not None:
+        if rays is not None or z_vals is not None:
+            raise NerfHipError(f"{who}: give points or rays + z_vals, not both")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise NerfHipError(f"{who}: points must be [P, 3]")
+        P = int(points.shape[0])
+        return (_ptr(points, "points") if P else None), None, 0, None, 1, P
+    if rays is None or z_vals is None or rays.dim() != 2 or z_vals.dim() != 2 or rays.shape[0] != z_vals.shape[0] or rays.shape[1] < 6:
+        raise NerfHipError(f"{who}: rays [N, >= 6] and z_vals [N, S] are required without points")
+    P = int(z_vals.numel())
+    S = max(int(z_vals.shape[1]), 1)
+    return None, (_ptr(rays, "rays") if P else None), int(rays.shape[1]), (_ptr(z_vals, "z_vals") if P else None), S, P
+
+
+def _hash_cols(who, t, lo, width, P):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+            and t.shape[0] == P and 0 <= lo and lo + width <= t.shape[1]):
+        raise NerfHipError(f"{who}: needs a contiguous fp32 matrix [{P}, >= {lo + width}] on the GPU")
+    return (t.data_ptr() + 4 * lo if P else None), int(t.shape[1])
+
+
+def hash_encode_fwd(desc, embeddings, out, col=0, points=None, rays=None, z_vals=None):
+    """nerf_hash_encode_fwd: writes the encoding of the points into columns col .. col + L F of the row-major fp32 matrix `out` [P, >= col
+    + L F]; the other columns are untouched.  P == 0 launches nothing."""
+    pp, rp, stride, zp, S, P = _hash_points("hash_encode_fwd", points, rays, z_vals)
+    L, F = desc.n_levels, desc.n_features
+    if tuple(embeddings.shape) != (desc.level_offset[L], F):
+        raise NerfHipError(f"hash_encode_fwd: embeddings must be [{desc.level_offset[L]}, {F}]")
+    op, ld = _hash_cols("hash_encode_fwd", out, col, L * F, P)
+    # per point and level 8 rows in (random: whole 4 F byte rows), L F floats out
+    with _timed("hash_fwd_kernel", 0.0, P * L * (8.0 * 4 * F + 4.0 * F)):
+        _check(lib().nerf_hash_encode_fwd(ctypes.byref(desc), _ptr(embeddings, "embeddings"), pp, rp, stride, zp, S, P, op, ld, _stream()),
+               "nerf_hash_encode_fwd")
+    return out
+
+
+def hash_scratch(desc, device):
+    """a zeroed accumulator for hash_encode_bwd: int64 [nerf_hash_scratch_words]; a complete backward leaves it zero"""
+    return torch.zeros(lib().nerf_hash_scratch_words(ctypes.byref(desc)), dtype=torch.int64, device=device)
+
+
+def hash_encode_bwd(desc, d_out, col=0, points=None, rays=None, z_vals=None, scratch=None, phases=3, d_embeddings=None):
+    """nerf_hash_encode_bwd: fp32 [rows_total, F], the gradient of the table from columns col .. col + L F of d_out [P, >= col + L F],
+    accumulated in 64-bit fixed point (two calls give the same bits; M = max |d_out| == 0: zeros, not finite: NaN).  scratch: a
+    hash_scratch() the caller keeps (left zero), else a fresh one.  phases: 1 the maximum + the scatter (returns None), 2 the finishing
+    pass, 3 both."""
+    pp, rp, stride, zp, S, P = _hash_points("hash_encode_bwd", points, rays, z_vals)
+    L, F = desc.n_levels, desc.n_features
+    dp, ld = _hash_cols("hash_encode_bwd", d_out, col, L * F, P)
+    if scratch is None:
+        scratch = hash_scratch(desc, d_out.device)
+    rows = desc.level_offset[L]
+    if not (scratch.is_cuda and scratch.dtype == torch.int64 and scratch.is_contiguous() and scratch.numel() == rows * F + 1):
+        raise NerfHipError(f"hash_encode_bwd: scratch must be hash_scratch(desc, device): int64 [{rows * F + 1}] on the GPU")
+    if phases & 2 and d_embeddings is None:
+        d_embeddings = torch.empty((rows, F), dtype=torch.float32, device=d_out.device)
+    args = lambda ph: (ctypes.byref(desc), pp, rp, stride, zp, S, P, dp, ld, scratch.data_ptr(),
+                       None if d_embeddings is None else _ptr(d_embeddings, "d_embeddings"), ph, _stream())
+    if phases & 1:      # P L F words read twice (maximum, scatter), 8 F adds of 8 bytes per point and level
+        with _timed("hash_scatter_kernel", 0.0, P * L * (8.0 * F + 64.0 * F)):
+            _check(lib().nerf_hash_encode_bwd(*args(1)), "nerf_hash_encode_bwd")
+    if phases & 2:      # the accumulator in and out (zeroed), the gradient out
+        with _timed("hash_finish_kernel", 0.0, rows * F * 20.0):
+            _check(lib().nerf_hash_encode_bwd(*args(2)), "nerf_hash_encode_bwd")
+    return d_embeddings
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

@@ -36,7 +36,7 @@ _FLAGS = [
     ("N_importance", dict(type=int, default=0, help="number of additional fine samples per ray")),
     ("perturb", dict(type=float, default=1., help="set to 0. for no jitter, 1. for jitter")),
     ("use_viewdirs", dict(action="store_true", help="use full 5D input instead of 3D")),
-    ("i_embed", dict(type=int, default=0, help="set 0 for default positional encoding, -1 for none")),
+    ("i_embed", dict(type=int, default=0, help="set 0 for default positional encoding, -1 for none, 1 for a learned hash grid")),
     ("multires", dict(type=int, default=10, help="log2 of max freq for positional encoding (3D location)")),
     ("multires_views", dict(type=int, default=4, help="log2 of max freq for positional encoding (2D direction)")),
     ("raw_noise_std", dict(type=float, default=0., help="std dev of noise added to regularize sigma_a output")),
@@ -60,6 +60,16 @@ _FLAGS = [
     ("i_weights", dict(type=int, default=10000, help="frequency of weight ckpt saving")),
     ("i_testset", dict(type=int, default=50000, help="frequency of testset saving")),
     ("i_video", dict(type=int, default=50000, help="frequency of render_poses video saving")),
+]
+# --i_embed 1 (not in the reference): the hash-grid field of hashgrid.py.  create_nerf reads them with these defaults from any
+# namespace, so an args object built for the reference's flags keeps working.
+_HASH_FLAGS = [
+    ("hash_levels", dict(type=int, default=16, help="levels of the hash grid (--i_embed 1)")),
+    ("hash_features", dict(type=int, default=2, help="features per level and node: 1, 2 or 4")),
+    ("log2_hashmap_size", dict(type=int, default=19, help="log2 of the rows a hashed level owns")),
+    ("base_resolution", dict(type=int, default=16, help="cells per axis of the coarsest level")),
+    ("finest_resolution", dict(type=int, default=512, help="cells per axis of the finest level")),
+    ("hash_bound", dict(type=float, default=1.5, help="half side of the hash grid's cube about the origin")),
 ]
 
 
@@ -103,7 +113,7 @@ def config_parser():
     """run_nerf.py:421-531."""
     parser = _ConfigFileParser()
     parser.add_argument("--config", type=str, default=None, help="config file path")
-    for name, kw in _FLAGS:
+    for name, kw in _FLAGS + _HASH_FLAGS:
         parser.add_argument("--" + name, **kw)
     return parser
 
@@ -119,10 +129,13 @@ def create_nerf(args, device=None, fused_adam=None):
     embed_fn, input_ch = get_embedder(args.multires, args.i_embed)
     input_ch_views = 0
     embeddirs_fn = None
+    hashed = args.i_embed == 1      # a learned hash grid in front of a layer stack (hashgrid.HashNeRF); the views keep the positional encoding
     if args.use_viewdirs:
-        embeddirs_fn, input_ch_views = get_embedder(args.multires_views, args.i_embed)
+        embeddirs_fn, input_ch_views = get_embedder(args.multires_views, 0 if hashed else args.i_embed)
     output_ch = 5 if args.N_importance > 0 else 4
     skips = [4]
+    if hashed:
+        return _create_hash_nerf(args, device, embed_fn, embeddirs_fn, input_ch_views, output_ch)
     arch = lambda D, W: dict(D=D, W=W, input_ch=input_ch, output_ch=output_ch, skips=skips, input_ch_views=input_ch_views,
                              use_viewdirs=args.use_viewdirs)
     # render_rays evaluates a (coarse, fine) pair on ONE path: if only one of the two is the fused kernels' architecture
@@ -138,6 +151,30 @@ def create_nerf(args, device=None, fused_adam=None):
                           skips=skips, input_ch_views=input_ch_views, use_viewdirs=args.use_viewdirs, force_dense=mixed_pair).to(device)
         grad_vars += list(model_fine.parameters())
 
+    return _finish_create_nerf(args, device, model, model_fine, grad_vars, embed_fn, embeddirs_fn, fused_adam)
+
+
+def _create_hash_nerf(args, device, embed_fn, embeddirs_fn, input_ch_views, output_ch):
+    """create_nerf for --i_embed 1: HashNeRF networks of --netdepth x --netwidth layers (the skip connection of the reference only where
+    a layer 5 exists), each with a table of its own over the cube [-hash_bound, hash_bound]^3; torch.optim.Adam over layers and tables"""
+    from .hashgrid import HashNeRF
+    opt = {name: getattr(args, name, kw["default"]) for name, kw in _HASH_FLAGS}
+    bound = float(opt["hash_bound"])
+    grid = dict(n_levels=opt["hash_levels"], n_features=opt["hash_features"], log2_hashmap_size=opt["log2_hashmap_size"],
+                base_resolution=opt["base_resolution"], finest_resolution=opt["finest_resolution"])
+    make = lambda D, W: HashNeRF([-bound] * 3, [bound] * 3, D=D, W=W, input_ch_views=input_ch_views, output_ch=output_ch,
+                                 skips=[4] if D > 5 else [], use_viewdirs=args.use_viewdirs, **grid).to(device)
+    model = make(args.netdepth, args.netwidth)
+    grad_vars = list(model.parameters())
+    model_fine = None
+    if args.N_importance > 0:
+        model_fine = make(args.netdepth_fine, args.netwidth_fine)
+        grad_vars += list(model_fine.parameters())
+    return _finish_create_nerf(args, device, model, model_fine, grad_vars, embed_fn, embeddirs_fn, False)
+
+
+def _finish_create_nerf(args, device, model, model_fine, grad_vars, embed_fn, embeddirs_fn, fused_adam):
+    """the rest of run_nerf.py:178-259 behind the networks: the query function, the optimizer, the checkpoint, the two dictionaries"""
     netchunk = getattr(args, "netchunk", 1024 * 64)
     # (marked as the stock query function: render_rays evaluates it inside the fused kernels; a user's own callable in this slot of
     # render_kwargs is called per pass like the reference does, run_nerf.py:385 / :401)
