@@ -25,10 +25,10 @@ def four_level(F=2, seed=0):
     return enc
 
 
-def box_points(n, seed, spread=1.0):
-    """points over the box, `spread` > 1 reaching outside"""
+def box_points(n, seed, spread=1.0, lo=LO, hi=HI):
+    """points over the box [lo, hi], `spread` > 1 reaching outside"""
     u = torch.rand(n, 3, generator=torch.Generator().manual_seed(seed), dtype=F64)
-    lo, hi = torch.tensor(LO, dtype=F64), torch.tensor(HI, dtype=F64)
+    lo, hi = torch.tensor(lo, dtype=F64), torch.tensor(hi, dtype=F64)
     mid, half = 0.5 * (lo + hi), 0.5 * (hi - lo)
     return (mid + (2.0 * u - 1.0) * half * spread).float()
 
@@ -128,9 +128,10 @@ def test_the_hash_of_three_hand_written_coordinates():
 
 # ------------------------------------------------------------------------------------------------ encode_reference
 def node_points(enc, level):
+    """five lattice nodes of one level over the encoding's own box (indices capped at R: a level coarser than 3 cells has no node 3)"""
     R = enc.level_resolution[level]
-    idx = torch.tensor([[0, 0, 0], [1, 2, 3], [R, R, R], [R, 0, 1], [2, R - 1, R]], dtype=torch.int64)
-    lo, hi = torch.tensor(LO, dtype=F64), torch.tensor(HI, dtype=F64)
+    idx = torch.tensor([[0, 0, 0], [1, 2, 3], [R, R, R], [R, 0, 1], [2, R - 1, R]], dtype=torch.int64).clamp(max=R)
+    lo, hi = torch.tensor(enc.lo, dtype=F64), torch.tensor(enc.hi, dtype=F64)
     return idx, (lo + idx.to(F64) / R * (hi - lo)).float()
 
 
