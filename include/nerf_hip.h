@@ -349,6 +349,9 @@ int nerf_field_wgrad_phase(const float* act, const float* delta, const float* d_
  * nerf_field_wgrad_phase_live with the same list (nerf_field_input_grad, nerf_range_scan on the delta buffer) need the dense form.
  *   nerf_field_wgrad_phase_live: nerf_field_wgrad_phase whose GEMM streams the live tiles only (same chunk plan, same order of
  * summation inside every chunk: the same partial sums minus exact zeros).  datapath 0 (fp32) has no sparse form.
+ *   The two go together: when n_samples is a multiple of 32, nerf_field_dgrad_split_live (live != NULL) also writes the per-ray direction
+ * encoding, replicated for the GEMM, into scratch inside `act`, and nerf_field_wgrad_phase_live (live != NULL) reads it there instead
+ * of writing it itself: call it on the `act` of a nerf_field_dgrad_split_live call made since that buffer's forward.
  *   live = NULL in either: exactly the dense entry point.  NERF_BWD_SKIP_DEAD=0 in the environment (read once per process) makes both
  * ignore `live` (nerf_bwd_skip_dead() returns 0 then): the A/B switch. */
 size_t nerf_live_tiles_words(int n_rays, int n_samples);

@@ -801,12 +801,8 @@ __global__ __launch_bounds__(512) void wgrad1_kernel(WgradArgs a) {
 //   `scratch` ([128][256] | [128]) for wgrad_fold_kernel, and feature_linear.{weight,bias} / Wv[:, :256] are left to it.
 // amax (nullable): device word holding the bit pattern of the launch's max|d_raw| (fp16 split, DeltaLayout3::scale): every partial
 // sum carries the factor s = delta_scale_bits(amax) = 2^k, removed here exactly.
-__global__ void wgrad_reduce_kernel(const float* __restrict__ partial, int n_chunks, float* __restrict__ grad, int accumulate,
-                                    int fold, float* __restrict__ scratch, const unsigned* __restrict__ amax) {
-    constexpr Canon cn = canon();
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N_PARAMS) return;
-    if (fold && i >= cn.wf && i < cn.bf + W) return;                    // produced by wgrad_fold_kernel (no partials exist)
+// (the value of entry i: the one definition both reductions below use, so that they agree to the bit wherever a sum is formed)
+__device__ inline float reduce_chunks(const float* __restrict__ partial, int i, int n_chunks, const unsigned* __restrict__ amax) {
     // loads in batches of 8 (all issued before the first is added: the loop is latency-bound otherwise), sums in chunk order
     float s = 0.0f;
     const float* src = partial + i;
@@ -822,6 +818,15 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ partial, int n_chu
 #endif
     for (; cix < n_chunks; ++cix) s += src[(size_t)cix * N_PARAMS];
     if (amax) s *= __uint_as_float(delta_scale_bits(amax[0], true));
+    return s;
+}
+__global__ void wgrad_reduce_kernel(const float* __restrict__ partial, int n_chunks, float* __restrict__ grad, int accumulate,
+                                    int fold, float* __restrict__ scratch, const unsigned* __restrict__ amax) {
+    constexpr Canon cn = canon();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N_PARAMS) return;
+    if (fold && i >= cn.wf && i < cn.bf + W) return;                    // produced by wgrad_fold_kernel (no partials exist)
+    const float s = reduce_chunks(partial, i, n_chunks, amax);
     if (fold) {
         if (i >= cn.wv && i < cn.bv) {
             const int k = (i - cn.wv) / (W + IN_DIR), col = (i - cn.wv) % (W + IN_DIR);
@@ -867,6 +872,89 @@ __global__ void wgrad_fold_kernel(const float* __restrict__ params, const float*
         dst = cn.bf + i;
     } else return;
     grad[dst] = accumulate ? grad[dst] + v : v;
+}
+
+// Both of the above in ONE grid with no dependency between workgroups (split datapaths).  A fold workgroup forms the slice of G (and
+// of dbv) it needs itself, from the chunk partials, with reduce_chunks: the very sums wgrad_reduce_kernel parks in `scratch`, in the
+// same order and with the same power of two removed, so every value a fold output is made of has the bits it had -- and the FMA
+// chains below are wgrad_fold_kernel's, term for term.  Nothing is handed from one workgroup to another: no scratch, no tickets.
+//   workgroups [0, 128)      row k of G (256 sums, one per thread) and dbv[k] -> dWv[k][0..255], thread = i
+//   workgroups [128, 192)    columns 4 c .. 4 c + 3 of G (512 sums, two per thread; four neighbours share a 16-byte piece of a
+//                            partial row) -> dWf[0..255][4 c .. 4 c + 3], thread = i
+//   workgroup  192           dbv (128 sums) -> dbf
+//   workgroups [193, ...)    wgrad_reduce_kernel's grid without the entries above and without the stores to scratch
+// The fold workgroups come first in the grid: they are the long ones (277 / 554 loads and 256 / 512 FMAs a thread against 21 loads),
+// so the reductions fill in behind them instead of waiting for them.
+constexpr int FOLD_WGS = WV + W / 4 + 1;
+static_assert(W == 256 && 4 * WV == 2 * 256 && W % 4 == 0, "256 threads: one per column of a G row, two sums each of a 128 x 4 column block");
+__global__ __launch_bounds__(256) void wgrad_reduce_fold_kernel(const float* __restrict__ partial, int n_chunks, const float* __restrict__ params,
+                                                                float* __restrict__ grad, int accumulate, const unsigned* __restrict__ amax) {
+    constexpr Canon cn = canon();
+    constexpr int LDV = W + IN_DIR;
+    __shared__ __attribute__((aligned(16))) float sh[4 * WV + 4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    if (b >= FOLD_WGS) {
+        const int i = (b - FOLD_WGS) * 256 + tid;
+        if (i >= N_PARAMS) return;
+        if (i >= cn.wf && i < cn.bf + W) return;                                            // a fold workgroup's
+        if (i >= cn.wv && i < cn.bv && (i - cn.wv) % LDV < W) return;                       // G: likewise
+        const float s = reduce_chunks(partial, i, n_chunks, amax);
+        grad[i] = accumulate ? grad[i] + s : s;
+        return;
+    }
+    float v;
+    int dst;
+    if (b < WV) {                                       // dWv[k][i], i < 256
+        const int k = b, i = tid;
+        sh[tid] = reduce_chunks(partial, cn.wv + k * LDV + tid, n_chunks, amax);            // G[k][tid]
+        if (tid == 0) sh[W] = reduce_chunks(partial, cn.bv + k, n_chunks, amax);            // dbv[k]
+        __syncthreads();
+        const float* wf = params + cn.wf + i * W;
+        float acc = 0.0f;
+        if (cn.wf % 4 == 0 && (reinterpret_cast<uintptr_t>(params) & 15) == 0) {
+            for (int j = 0; j < W; j += 4) {
+                const f32x4 w = *reinterpret_cast<const f32x4*>(wf + j);
+                const f32x4 g = *reinterpret_cast<const f32x4*>(sh + j);
+                acc = fmaf(g[0], w[0], acc);
+                acc = fmaf(g[1], w[1], acc);
+                acc = fmaf(g[2], w[2], acc);
+                acc = fmaf(g[3], w[3], acc);
+            }
+        } else {
+            for (int j = 0; j < W; ++j) acc = fmaf(sh[j], wf[j], acc);
+        }
+        v = fmaf(sh[W], params[cn.bf + i], acc);
+        dst = cn.wv + k * LDV + i;
+        grad[dst] = accumulate ? grad[dst] + v : v;
+    } else if (b < WV + W / 4) {                        // dWf[i][j], j = j0 .. j0 + 3
+        const int j0 = 4 * (b - WV), i = tid;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int e = tid + 256 * t, k = e >> 2, c = e & 3;
+            sh[e] = reduce_chunks(partial, cn.wv + k * LDV + j0 + c, n_chunks, amax);       // G[k][j0 + c] at sh[4 k + c]
+        }
+        __syncthreads();
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < WV; ++k) {
+            const float a = params[cn.wv + k * LDV + i];
+            const f32x4 g = *reinterpret_cast<const f32x4*>(sh + 4 * k);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[c] = fmaf(a, g[c], acc[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            dst = cn.wf + i * W + j0 + c;
+            grad[dst] = accumulate ? grad[dst] + acc[c] : acc[c];
+        }
+    } else {                                            // dbf[i]
+        const int i = tid;
+        if (tid < WV) sh[tid] = reduce_chunks(partial, cn.bv + tid, n_chunks, amax);
+        __syncthreads();
+        float acc = 0.0f;
+        for (int k = 0; k < WV; ++k) acc = fmaf(params[cn.wv + k * LDV + i], sh[k], acc);
+        dst = cn.bf + i;
+        grad[dst] = accumulate ? grad[dst] + acc : acc;
+    }
 }
 
 // ------------------------------------------------------------------ host side
@@ -955,10 +1043,9 @@ template <typename SP, bool LO = false>
 __global__ void replicate_dir_bf16_kernel(const float* __restrict__ dir_ray, u32x4* __restrict__ dir_rep, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;     // (ray, feature)
     if (i >= n) return;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = LO ? split_rem<SP>(dir_ray[i]) : dir_ray[i];
-    dir_rep[i] = pack8_sp<SP>(v);
+    unsigned w[4];
+    dir_record<SP, LO>(dir_ray[i], w);      // (launchers.h: the one definition, shared with bwd_prologue_kernel)
+    dir_rep[i] = u32x4{w[0], w[1], w[2], w[3]};
 }
 
 // ---- the weight-gradient GEMM.  Split datapaths: 16-bit operands streamed by wgrad1_kernel, rows saved by the 16-point forward (16-point
@@ -1019,6 +1106,13 @@ static hipError_t wgrad_expand_dir(const DatapathDesc& dp, const WgradOperands& 
                            reinterpret_cast<const f32x4*>(o.dir), reinterpret_cast<f32x4*>(o.dir_pt), P, S);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_replicate_dir(const float* act, int n_rays, int S, Datapath datapath, hipStream_t stream) {
+    const DatapathDesc& dp = desc(datapath);
+    if (!dp.split || S % 32 != 0) return hipErrorInvalidValue;
+    const long P = (long)n_rays * S;
+    return wgrad_expand_dir(dp, wgrad_operands(dp, act, act, act, P, n_rays), P, n_rays, S, stream);       // (only the operands inside act are used)
 }
 
 // the job table: the same for both families except the folded feature layer and the merged alpha row.  Returns the job count.
@@ -1147,6 +1241,11 @@ static hipError_t wgrad_launch(const DatapathDesc& dp, const WgradArgs& wa, int 
     }
     if (phases & 4) {
         float* scratch = partial + wgrad_partial_floats(P) - N_DERIVED;
+        if (fold && fold_launches()) {
+            hipLaunchKernelGGL(wgrad_reduce_fold_kernel, dim3(FOLD_WGS + (N_PARAMS + 255) / 256), dim3(256), 0, stream,
+                               (const float*)partial, n_chunks, params, grad, accumulate, o.amax);
+            return hipGetLastError();
+        }
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((N_PARAMS + 255) / 256), dim3(256), 0, stream,
                            (const float*)partial, n_chunks, grad, accumulate, fold ? 1 : 0, scratch, o.amax);
         if (fold)
@@ -1167,8 +1266,11 @@ hipError_t launch_field_wgrad(const float* act, const float* delta, const float*
     if (P <= 0) return hipSuccess;
     const WgradOperands o = wgrad_operands(dp, act, delta, d_raw, P, n_rays);
     if (phases & 1) {
-        hipError_t e = wgrad_expand_dir(dp, o, P, n_rays, S, stream);
-        if (e != hipSuccess) return e;
+        // (with a live-tile list and whole-tile rays the delta chain's call has replicated the directions: launchers.h)
+        if (!(live && S % 32 == 0)) {
+            hipError_t e = wgrad_expand_dir(dp, o, P, n_rays, S, stream);
+            if (e != hipSuccess) return e;
+        }
     }
     WgradArgs wa{};
     const int nj = wgrad_jobs(dp, o, S, wa);

@@ -51,9 +51,10 @@ __device__ inline void apply_mask3r(float (&d)[NV], const f32x16* acc, u32x4 m) 
 // word with (bits & 0x7fffffff) != 0: NaN, Inf and subnormals are live, +-0 is not).  No atomics: every bitmap word has one writer.
 // gmask (NERF_LIVE_GROUPS builds only, else null; launchers.h, LiveGroups): the same ballot at 8-point granularity -- eight lanes one group, a wave's two tiles one
 // byte, an iteration FOUR words of group masks, each with one writer.
+// (the body, for workgroup `blk` of `nblk`: delta_amax_kernel runs it over its whole grid, bwd_prologue_kernel over a part of its own)
 template <bool LIVE>
-__global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restrict__ d_raw, long n4, unsigned* __restrict__ slot,
-                                                          unsigned* __restrict__ bitmap, unsigned* __restrict__ gmask) {
+__device__ inline void delta_amax_body(const f32x4* __restrict__ d_raw, long n4, unsigned* __restrict__ slot,
+                                       unsigned* __restrict__ bitmap, unsigned* __restrict__ gmask, unsigned blk, unsigned nblk) {
     float m = 0.0f;
     __shared__ float wm[16];
     __shared__ unsigned wb[2][16];
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restric
     if constexpr (LIVE) {
         const long n_it = (n4 + 1023) / 1024;           // = bitmap words
         int par = 0;
-        for (long it = blockIdx.x; it < n_it; it += gridDim.x, par ^= 1) {
+        for (long it = blk; it < n_it; it += nblk, par ^= 1) {
             const long i = it * 1024 + threadIdx.x;
             unsigned any = 0u;
             if (i < n4) {
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restric
         }
         if (!slot) return;
     } else {
-        for (long i = (long)blockIdx.x * 1024 + threadIdx.x; i < n4; i += (long)gridDim.x * 1024) {
+        for (long i = (long)blk * 1024 + threadIdx.x; i < n4; i += (long)nblk * 1024) {
             const f32x4 v = d_raw[i];
             m = fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))), m);     // (NaN: fmaxf keeps the other operand)
         }
@@ -109,6 +110,11 @@ __global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restric
         for (int o = 8; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
         if (threadIdx.x == 0) atomicMax(slot, __float_as_uint(m));
     }
+}
+template <bool LIVE>
+__global__ __launch_bounds__(1024) void delta_amax_kernel(const f32x4* __restrict__ d_raw, long n4, unsigned* __restrict__ slot,
+                                                          unsigned* __restrict__ bitmap, unsigned* __restrict__ gmask) {
+    delta_amax_body<LIVE>(d_raw, n4, slot, bitmap, gmask, blockIdx.x, gridDim.x);
 }
 
 // bitmap -> the ascending list of live tile numbers, its count, and per bitmap word the number of live tiles before it (the
@@ -189,6 +195,37 @@ __global__ __launch_bounds__(1024) void live_scan_kernel(unsigned* __restrict__ 
         }
         if (threadIdx.x < LIVE_ZERO_WORDS) live[lg.zero + threadIdx.x] = 0u;
     }
+}
+
+// delta_amax_kernel<true> and (from behind the chain) replicate_dir_bf16_kernel in ONE launch in front of the sparse delta chain.
+// Workgroups [0, n_rep) replicate the per-ray direction encoding for the weight-gradient GEMM (it depends on the forward's save
+// alone; n_rep = 0 when a ray's samples do not fill whole tiles); workgroups [n_rep, n_rep + n_amax) are delta_amax_body<true>'s
+// grid.  Nothing is handed from one workgroup to another.  live_scan_kernel stays a launch of its own behind this one: the form
+// in which the last workgroup to finish ran the scan itself (an acq_rel ticket at agent scope in a spare scale word) was built,
+// gave the same words, and measured SLOWER than the kernels it replaced -- 24.5 us per launch against 8.9 + 8.5 + 5.2 -- every one of
+// the 768 workgroups pays the L2 write-back of an agent-scope release, and the scan's latency is on the critical path either way
+// (profiles/r33_measurements.md).
+template <typename SP, bool TWO>
+__global__ __launch_bounds__(1024) void bwd_prologue_kernel(const f32x4* __restrict__ d_raw, long n4, unsigned* __restrict__ amax,
+                                                           unsigned* __restrict__ live, unsigned n_tiles, unsigned group, unsigned n_rep,
+                                                           unsigned n_amax, const float* __restrict__ dir_ray, u32x4* __restrict__ dir_rep,
+                                                           u32x4* __restrict__ dir_rep_lo, long n_dir) {
+    if (blockIdx.x < n_rep) {
+        const long i = (long)blockIdx.x * 1024 + threadIdx.x;       // (ray, feature)
+        if (i >= n_dir) return;
+        const float x = dir_ray[i];
+        unsigned w[4];
+        dir_record<SP, false>(x, w);
+        dir_rep[i] = u32x4{w[0], w[1], w[2], w[3]};
+        if constexpr (TWO) {
+            dir_record<SP, true>(x, w);
+            dir_rep_lo[i] = u32x4{w[0], w[1], w[2], w[3]};
+        }
+        return;
+    }
+    const LiveTiles lt = live_tiles(n_tiles);
+    unsigned* gmask = (NERF_LIVE_GROUPS && group) ? live + live_groups(n_tiles).gmask : nullptr;
+    delta_amax_body<true>(d_raw, n4, amax, live + lt.bitmap, gmask, blockIdx.x - n_rep, n_amax);
 }
 
 // TWO (round 6, "fp16x3w"): every delta leaves as TWO 16-bit words, hi = T(v) and lo = T(v - hi) -- the lo words go to the mirror of
@@ -368,13 +405,39 @@ hipError_t launch_field_dgrad3r(const float* packed3, const float* act, const fl
     FieldBwdRingArgs ba{packed3, act, d_raw, delta, n_rays, S, live};
     const unsigned blocks = (unsigned)((P + PTS_PER_WG3 - 1) / PTS_PER_WG3);
     unsigned* slot = nullptr;
+    const bool fused = live && fold_launches();
     if (d.f16) {
         // (the scale word sits in the hi part of the layout: at the same offset in the one- and the two-word layout)
+        // The memset stays: the word's last reader is the chunk reduction of another call that may never come, so no kernel of this
+        // call can leave it cleared for the next, and the buffer table (api.hip) is keyed by address and does not see the caller's
+        // allocator hand an address out again with other contents.
         slot = reinterpret_cast<unsigned*>(delta + delta_layout3((size_t)P).scale);
         hipError_t e = hipMemsetAsync(slot, 0, 16, stream);
         if (e != hipSuccess) return e;
     }
-    if (live) {
+    if (fused) {
+        const LiveTiles lt = live_tiles((unsigned)((P + 31) / 32));
+        const bool groups = group == 16 || group == 8;
+        const unsigned n_amax = (unsigned)min((long)1024, (P + 1023) / 1024);
+        // the replication (field_bwd.hip, wgrad_expand_dir: the same condition and the same destination)
+        const bool rep = S % 32 == 0;
+        const long n_dir = rep ? (long)n_rays * 32 : 0;
+        const unsigned n_rep = (unsigned)((n_dir + 1023) / 1024);
+        const ActLayout3 al = act_layout3((size_t)P, (size_t)n_rays, d.two_word);
+        float* act_w = const_cast<float*>(act);     // (dir_pt is scratch inside the save buffer, as in wgrad_operands)
+        u32x4* dst = reinterpret_cast<u32x4*>(act_w + al.dir_pt);
+        u32x4* dst_lo = reinterpret_cast<u32x4*>(act_w + al.lo + al.dir_pt);
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(n_rep + n_amax), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot, live,
+                               lt.n_tiles, groups ? (unsigned)group : 0u, n_rep, n_amax, act + al.dir, dst, dst_lo, n_dir);
+        };
+        if (d.two_word) go(bwd_prologue_kernel<SplitF16, true>);
+        else if (d.f16) go(bwd_prologue_kernel<SplitF16, false>);
+        else go(bwd_prologue_kernel<SplitBF16, false>);
+        hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, stream, live, lt.n_tiles, groups ? (unsigned)group : 0u);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    } else if (live) {
         // one bitmap word per 1024 points and workgroup iteration: a grid of up to 1024 workgroups strides over them
         const LiveTiles lt = live_tiles((unsigned)((P + 31) / 32));
         const bool groups = group == 16 || group == 8;
@@ -384,6 +447,10 @@ hipError_t launch_field_dgrad3r(const float* packed3, const float* act, const fl
         hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, stream, live, lt.n_tiles, groups ? (unsigned)group : 0u);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
+        if (S % 32 == 0) {      // (the separate form of the prologue's replication: launchers.h)
+            e = launch_replicate_dir(act, n_rays, S, dp, stream);
+            if (e != hipSuccess) return e;
+        }
     } else if (d.f16) {
         const unsigned sb = (unsigned)min((long)1024, (P + 1023) / 1024);      // one 16-byte load per thread: the launch is latency, not bytes
         hipLaunchKernelGGL(delta_amax_kernel<false>, dim3(sb), dim3(1024), 0, stream, reinterpret_cast<const f32x4*>(d_raw), P, slot, (unsigned*)nullptr, (unsigned*)nullptr);

@@ -192,6 +192,32 @@ __host__ __device__ inline LiveTiles live_tiles(unsigned n_tiles) {
     l.total = (l.prefix + l.n_words + 1 + 3) & ~(size_t)3;
     return l;
 }
+// NERF_BWD_FOLD_LAUNCHES=0 in the environment (read per call, as NERF_WG_MERGE_ALPHA is): the small launches around the heavy
+// kernels in their separate forms -- delta_amax_kernel<true> and replicate_dir_bf16_kernel instead of bwd_prologue_kernel,
+// wgrad_reduce_kernel + wgrad_fold_kernel instead of wgrad_reduce_fold_kernel, derive_folded_kernel + pack3_all_kernel instead of
+// pack3_fused_kernel.  Same bits either way: the comparison side of tests/test_gpu_bwd_prologue.py, test_gpu_reduce_fold.py and
+// test_gpu_repack_one_launch.py.
+inline bool fold_launches() {
+    const char* e = getenv("NERF_BWD_FOLD_LAUNCHES");
+    return !(e && e[0] == '0');
+}
+// The per-ray direction encoding replicated for the weight-gradient GEMM ([ray][feature][8 copies], field_bwd.hip) when a ray's
+// samples fill whole tiles (S % 32 == 0): with a live-tile list it is launch_field_dgrad3r that writes it into the save buffer
+// (it depends on the forward's save alone) and launch_field_wgrad that relies on it -- a contract of the two *_live entry points
+// (include/nerf_hip.h), no state in between.  Without a list, or with ragged rays, the weight-gradient call expands as ever.
+hipError_t launch_replicate_dir(const float* act, int n_rays, int S, Datapath dp, hipStream_t stream);
+// one 16-byte record of that replication: eight copies of the 16-bit hi word of x (LO: of the remainder x - hi); SP: split_types.h
+template <typename SP, bool LO>
+__device__ inline void dir_record(float x, unsigned (&w)[4]) {
+    if (LO) {
+        const unsigned short h = SP::cvt1(x);
+        if constexpr (SP::F16) x = x - (float)__builtin_bit_cast(_Float16, h);
+        else x = x - __uint_as_float((unsigned)h << 16);
+    }
+    const unsigned pk = SP::cvt_pk(x, x);
+    w[0] = w[1] = w[2] = w[3] = pk;
+}
+
 // ---- EXPERIMENT, not in the default build (NERF_LIVE_GROUPS = 0): dead point groups inside live tiles.  Measured slower than whole
 // tiles (profiles/r16_dead_groups_measurements.md); the source stays so that those rows can be reproduced:
 //   tools/build_variant.sh groups -DNERF_LIVE_GROUPS=1    (2: the dead pieces are zero-filled in LDS instead of fetched from the zero line)

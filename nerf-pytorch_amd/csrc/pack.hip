@@ -180,13 +180,19 @@ void pack3_table_host(int* out) {
 // the fragment streams to write: bit 0 = 16-point forward (P16F), bit 2 = transposed (hi, lo) streams of the delta chain (P3B)
 // (bits 1 and 3 named streams of kernels that no longer exist).  The small fp32 parameters are always written.
 // SP (split_types.h): the 16-bit type the weights are split into -- the same buffer layout either way.
-template <typename SP>
-__global__ void pack3_all_kernel(PackPair pp, int n16f, int n3b) {
-    const float* __restrict__ canon_params = pp.params[blockIdx.y];
-    float* __restrict__ packed = pp.packed[blockIdx.y];
+// pack3_element: element `idx` of that launch.  FOLDED = true (pack3_fused_kernel): the elements made of W' -- the view trunk's units of
+// both streams -- and b' are somebody else's.
+constexpr int FOLD16_E0 = 2 * P16F_VIEWS, FOLD_ELEMS = 2 * WV * W;       // 16-bit elements of a stream that hold W' (hi and lo)
+static_assert(FOLD_ELEMS == KS16_H * 2 * KSTEP16_W8 && FOLD_ELEMS == 2 * (P3B_FEAT - P3B_VIEWS) && P3B_VIEWS == 0, "the view trunk's units");
+template <typename SP, bool FOLDED>
+__device__ inline void pack3_element(const float* __restrict__ canon_params, float* __restrict__ packed, long idx, int n16f, int n3b) {
     const float* __restrict__ derived = packed + P3_DERIVED;
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned short* p16 = reinterpret_cast<unsigned short*>(packed);
+    if (FOLDED) {
+        if (idx < n16f) { if (idx >= FOLD16_E0 && idx < FOLD16_E0 + FOLD_ELEMS) return; }
+        else if (idx - n16f < n3b) { if (idx - n16f < FOLD_ELEMS) return; }
+        else if (idx - n16f - n3b >= SM_BVIEWS - SM_BIAS && idx - n16f - n3b < SM_WALPHA - SM_BIAS) return;
+    }
     auto emit = [&](unsigned short* dst, int src, int is_lo) {
         unsigned short v = 0;
         if (src >= 0) {
@@ -214,6 +220,105 @@ __global__ void pack3_all_kernel(PackPair pp, int n16f, int n3b) {
         if (pidx >= SM_BVIEWS && pidx < SM_WALPHA) { packed[P3_SMALL + i] = derived[WV * W + (pidx - SM_BVIEWS)]; return; }
         const int src = pack_source(pidx);
         packed[P3_SMALL + i] = src < 0 ? 0.0f : canon_params[src];
+    }
+}
+template <typename SP>
+__global__ void pack3_all_kernel(PackPair pp, int n16f, int n3b) {
+    pack3_element<SP, false>(pp.params[blockIdx.y], pp.packed[blockIdx.y], (long)blockIdx.x * blockDim.x + threadIdx.x, n16f, n3b);
+}
+
+// derive_folded_kernel and pack3_all_kernel in ONE launch for both networks (both streams selected).  Nobody waits for `derived`:
+// a workgroup that packs elements made of W' computes those W' values itself.
+//   workgroups [0, 64)      one 1024-element group each of the 16-point stream's view trunk: 512 values W'[k][col] (16 rows x 32
+//                           columns), each as its hi word and, 512 elements on, its lo word (same source in both tables:
+//                           tests/test_gpu_repack_one_launch.py); they also write `derived` (every W' element occurs exactly once there)
+//   workgroups [64, 128)    the same for the transposed stream (again 16 rows x 32 columns a group)
+//   workgroup  128          b' -> `derived` and the small parameters, in derive_folded_kernel's own eight-lane form
+//   workgroups [129, ...)   pack3_all_kernel's grid without those elements
+// Bits.  derive_folded_kernel sums W'[k][j] in fp64 as eight interleaved partial sums a_p = sum over i = p, p + 8, ... (in that
+// order) and combines them with xor-shuffles 1, 2, 4: ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)) in lane 0, fp64 addition
+// being commutative.  Here one thread forms the same eight sums in the same order and the same tree, rounds once to fp32, and
+// splits that float with the functions pack3_all_kernel uses: every word has the bits it had.
+// A group's operands (16 rows of Wv[:, :256], 32 columns of Wf) are staged in LDS and read from there by the 512 dot products.
+constexpr int FOLD_GROUPS = FOLD_ELEMS / 1024, FOLD_WGS3 = 2 * FOLD_GROUPS + 1;
+static_assert(FOLD_GROUPS * 512 == WV * W && W == 256 && WV == 128, "64 groups of 512 values; 256 threads stage 256-long rows");
+template <typename SP>
+__global__ __launch_bounds__(256, 6) void pack3_fused_kernel(PackPair pp, int n16f, int n3b) {
+    constexpr Canon c = canon();
+    constexpr int LDV = W + IN_DIR;
+    const float* __restrict__ p = pp.params[blockIdx.y];
+    float* __restrict__ packed = pp.packed[blockIdx.y];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    if (b >= FOLD_WGS3) {
+        pack3_element<SP, true>(p, packed, (long)(b - FOLD_WGS3) * 256 + tid, n16f, n3b);
+        return;
+    }
+    float* __restrict__ derived = packed + P3_DERIVED;
+    if (b == 2 * FOLD_GROUPS) {                         // b'[k], k = 32 pass + tid / 8
+        const int part = tid & 7;
+        for (int pass = 0; pass < WV / 32; ++pass) {
+            const int k = 32 * pass + (tid >> 3);
+            double acc = 0.0;
+#pragma unroll 8
+            for (int i = part; i < W; i += 8) acc += (double)p[c.wv + k * LDV + i] * (double)p[c.bf + i];
+            if (part == 0) acc += (double)p[c.bv + k];
+            acc += __shfl_xor(acc, 1);
+            acc += __shfl_xor(acc, 2);
+            acc += __shfl_xor(acc, 4);
+            if (part == 0) {
+                derived[WV * W + k] = (float)acc;
+                packed[P3_SMALL + (SM_BVIEWS - SM_BIAS) + k] = (float)acc;
+            }
+        }
+        return;
+    }
+    // (staged in four passes of 64 contraction indices: 12 KiB of LDS and few registers, so that the thousands of pack3_element
+    // workgroups of the same launch keep their occupancy)
+    constexpr int KP = 64;
+    __shared__ float wv_s[16][KP + 1];                  // (+1: lanes of different rows read the same i)
+    __shared__ float wf_s[KP][32];
+    __shared__ int rows_s[16], cols_s[32];
+    const bool t16 = b < FOLD_GROUPS;
+    const int e0 = (t16 ? b : b - FOLD_GROUPS) * 1024;  // first element of the group inside the stream's W' units
+    unsigned short* out = reinterpret_cast<unsigned short*>(packed) + (t16 ? 2L * P16F + FOLD16_E0 : 2L * P3B_VIEWS) + e0;
+    int src[2], rid[2], cid[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int q = tid + 256 * t, lane = q >> 3, j = q & 7;      // slot q of the group: hi word at e0 + q, lo word at e0 + 512 + q
+        int lo;
+        src[t] = (t16 ? pack16_source(FOLD16_E0 + e0 + q, &lo) : pack3_source(e0 + q, &lo)) - DERIVED_WVF;
+        // 16-point stream: row = 16 nb + (lane & 15), column from (lane >> 4, j); transposed: row from (lane >> 5, j), column = 32 nb + (lane & 31)
+        rid[t] = t16 ? (lane & 15) : 8 * (lane >> 5) + j;
+        cid[t] = t16 ? 8 * (lane >> 4) + j : (lane & 31);
+        rows_s[rid[t]] = src[t] / W;                                // (every writer of an entry writes the same value)
+        cols_s[cid[t]] = src[t] % W;
+    }
+    double a[2][8];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) a[t][q] = 0.0;
+#pragma unroll 1
+    for (int k0 = 0; k0 < W; k0 += KP) {
+        __syncthreads();                                            // (first pass: rows_s / cols_s; later: the previous pass's readers)
+        for (int e = tid; e < 16 * KP; e += 256) wv_s[e / KP][e % KP] = p[c.wv + rows_s[e / KP] * LDV + k0 + e % KP];
+        for (int e = tid; e < KP * 32; e += 256) wf_s[e >> 5][e & 31] = p[c.wf + (k0 + (e >> 5)) * W + cols_s[e & 31]];
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll 2
+            for (int i0 = 0; i0 < KP; i0 += 8)
+#pragma unroll
+                for (int q = 0; q < 8; ++q) a[t][q] += (double)wv_s[rid[t]][i0 + q] * (double)wf_s[i0 + q][cid[t]];
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const double acc = ((a[t][0] + a[t][1]) + (a[t][2] + a[t][3])) + ((a[t][4] + a[t][5]) + (a[t][6] + a[t][7]));
+        const float x = (float)acc;
+        const int q = tid + 256 * t;
+        out[q] = split_hi<SP>(x);
+        out[512 + q] = split_lo<SP>(x);
+        if (t16) derived[src[t]] = x;
     }
 }
 
@@ -327,6 +432,14 @@ hipError_t launch_pack3_pair(const float* params_a, float* packed_a, const float
     const int threads = 256;
     const unsigned nets = params_b ? 2 : 1;
     PackPair pp{{params_a, params_b ? params_b : params_a}, {packed_a, params_b ? packed_b : packed_a}};
+    if ((streams & 5) == 5 && fold_launches()) {        // both streams: one launch (NERF_BWD_FOLD_LAUNCHES=0: the two below)
+        const int n16f = 2 * P16F_WORDS, n3b = 2 * (P3B_END - P3B_VIEWS);
+        const long total = (long)n16f + n3b + (PACKED_FLOATS - SM_BIAS);
+        const dim3 grid((unsigned)(FOLD_WGS3 + (total + threads - 1) / threads), nets);
+        if (desc(dp).f16) hipLaunchKernelGGL(pack3_fused_kernel<SplitF16>, grid, dim3(threads), 0, stream, pp, n16f, n3b);
+        else hipLaunchKernelGGL(pack3_fused_kernel<SplitBF16>, grid, dim3(threads), 0, stream, pp, n16f, n3b);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(derive_folded_kernel, dim3((8 * N_DERIVED + threads - 1) / threads, nets), dim3(threads), 0, stream, pp);
     const int n16f = (streams & 1) ? 2 * P16F_WORDS : 0, n3b = (streams & 4) ? 2 * (P3B_END - P3B_VIEWS) : 0;
     const long total = (long)n16f + n3b + (PACKED_FLOATS - SM_BIAS);
