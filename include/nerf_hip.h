@@ -826,7 +826,22 @@ int nerf_baked_reg_bwd(const NerfOccGrid* grid, const int* node_index, const int
  *     the device, no host read-back).  scratch: nerf_hash_scratch_words(grid) 64-bit words, 8-byte aligned, ZERO before its first use;
  *     a complete call (phases = 3, or 1 then 2) leaves the accumulator zero (the last word holds the bits of M and is rewritten by every call).  phases: 1 = the maximum and the scatter, 2 = the finishing pass,
  *     3 = both (1 and 2 as two calls with the same arguments give the bits of 3; they exist so the two can be timed apart).
- *     No gradient with respect to the points is computed. */
+ *     No gradient with respect to the points is computed by this entry point.
+ *   nerf_hash_input_grad (csrc/hash_input_grad.hip): the gradient with respect to the POINTS, a gather of the forward's
+ *     rows with the forward's cell, weights and slots.  d_x [n_points][ld_d_x] holds dL/d(encoding) in columns 0 .. L F.  Per point
+ *     and level, in fp32 without contraction:  v_c = sum_k d_x[p][l F + k] E[row_c][k] (k ascending from the first product);
+ *     df_x = sum_c +-((wy wz) v_c), + where bit 0 of c is set, accumulated in ascending c from -((wy wz) v_0); df_y with (wx wz) and
+ *     bit 1, df_z with (wx wy) and bit 2;  g_a = sum_l (df_a R_l) inv_extent[a] in ascending l from 0, a level's term replaced by an
+ *     exact 0 on an axis whose unclamped t = (x - lo) inv_extent is < 0 or > 1 (on the faces: the derivative of the cell the forward
+ *     picks).  Point mode (`points` given): writes d_points [n_points][3]; d_rays, workspace NULL, views_col = -1, accumulate = 0.
+ *     Ray mode (`rays` + z_vals): two launches -- the same lane-per-point kernel into `workspace` (the workspace_floats function below:
+ *     3 n_points floats), then one wavefront per ray: lane j takes samples j, j + 64, .. in ascending order, a fixed xor butterfly (32,
+ *     16, .., 1) -- and writes d_rays [n_rays][11] by nerf_field_input_grad's column contract: 0:3 = sum_s g_s, 3:6 = sum_s z_s g_s (one
+ *     fp32 product each), 6:8 = 0, 8:11 = the adjoint of the view columns [v, sin 2^0 v, cos 2^0 v, ..] (3 + 6 multires_views columns
+ *     of d_x from views_col on, as nerf_build_inputs writes them; multires_views = -1: the identity's 3) applied once to the column
+ *     sums over the ray's samples, or 0 when views_col < 0.  z_vals, near and far are constants.  accumulate != 0 adds to d_rays and
+ *     leaves columns 6:8 alone.  No atomics: two calls give the same bits; with n_samples = 1 columns 0:3 are point mode's bits.
+ *     A non-finite coordinate reads inside the table; its own row of the output is unspecified.  n_points == 0 launches nothing. */
 #define NERF_HASH_MAX_LEVELS 32
 typedef struct NerfHashGrid {
     int n_levels, n_features, log2_hashmap_size, reserved;
@@ -841,6 +856,11 @@ int nerf_hash_encode_fwd(const NerfHashGrid* grid, const float* embeddings, cons
 int nerf_hash_encode_bwd(const NerfHashGrid* grid, const float* points /* nullable */, const float* rays /* nullable */, int ray_stride,
                          const float* z_vals /* nullable */, int n_samples, long n_points, const float* d_out, int ld_d_out, long long* scratch,
                          float* d_embeddings, int phases, void* stream);
+size_t nerf_hash_input_grad_workspace_floats(long n_points);
+int nerf_hash_input_grad(const NerfHashGrid* grid, const float* embeddings, const float* points /* nullable */, const float* rays /* nullable */,
+                         int ray_stride, const float* z_vals /* nullable */, int n_samples, long n_points, const float* d_x, int ld_d_x,
+                         int views_col, int multires_views, float* d_points /* point mode */, float* d_rays /* ray mode */,
+                         float* workspace /* ray mode */, int accumulate, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,8 +16,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libnerf_hip.so")
 STAMP_PATH = os.path.join(PKG_DIR, "libnerf_hip.stamp")
 RESOURCE_PATH = os.path.join(PKG_DIR, "libnerf_hip.resources.json")
-SOURCES = ["api.hip", "render_abi.hip", "pack.hip", "ray_ops.hip", "field_fwd.hip", "field_bwd.hip", "field_fwd_ring.hip", "field_bwd_ring.hip", "render_fused.hip", "dense.hip", "field_input_grad.hip", "occupancy.hip", "isosurface.hip", "baked.hip", "baked_train.hip", "baked_reg.hip", "baked_rays.hip", "hash_encode.hip"]
-HEADERS = ["nerf_common.h", "field_device.h", "split_types.h", "field_ring.h", "field_ring8.h", "field_fwd_ring_body.h", "ray_device.h", "api_util.h", "launchers.h", "scan_device.h", "iso_tables.h", "grid_device.h", "baked_device.h", "hash_device.h", os.path.join("..", "..", "include", "nerf_hip.h")]
+SOURCES = ["api.hip", "render_abi.hip", "pack.hip", "ray_ops.hip", "field_fwd.hip", "field_bwd.hip", "field_fwd_ring.hip", "field_bwd_ring.hip", "render_fused.hip", "dense.hip", "field_input_grad.hip", "occupancy.hip", "isosurface.hip", "baked.hip", "baked_train.hip", "baked_reg.hip", "baked_rays.hip", "hash_encode.hip", "hash_input_grad.hip"]
+HEADERS = ["nerf_common.h", "field_device.h", "split_types.h", "field_ring.h", "field_ring8.h", "field_fwd_ring_body.h", "ray_device.h", "api_util.h", "launchers.h", "scan_device.h", "iso_tables.h", "grid_device.h", "baked_device.h", "hash_device.h", "hash_host.h", os.path.join("..", "..", "include", "nerf_hip.h")]
 # -ffp-contract=off: the per-ray arithmetic is written in the reference's operation
 # order (separate multiply / add) so z_vals, dists and sample points round identically.
 # -Rpass-analysis=kernel-resource-usage: the register / scratch / LDS table of every kernel is recorded at every build

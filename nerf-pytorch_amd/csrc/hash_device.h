@@ -54,6 +54,18 @@ __device__ inline Cell locate(const Levels& lv, int l, const float (&x)[3]) {
     return c;
 }
 
+// bit a: axis a of x lies outside the box, t = (x - lo) inv_extent < 0 or > 1 with locate's own t (before its clamp): there the
+// encoding does not depend on that coordinate.  A NaN compares false: not outside.
+__device__ inline unsigned outside_axes(const Levels& lv, const float (&x)[3]) {
+    unsigned m = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float t = (x[a] - lv.lo[a]) * lv.inv_extent[a];
+        m |= (t < 0.0f || t > 1.0f) ? 1u << a : 0u;
+    }
+    return m;
+}
+
 // corner: bit 0 x, bit 1 y, bit 2 z;  w = (wx wy) wz
 __device__ inline float corner_weight(const Cell& c, int corner) {
     const float wx = (corner & 1) ? c.f[0] : 1.0f - c.f[0];
@@ -70,6 +82,18 @@ __device__ inline unsigned corner_slot(const Levels& lv, int l, const Cell& c, i
         return ix + iy * n + iz * n * n;
     }
     return (ix ^ (iy * 2654435761u) ^ (iz * 805459861u)) & lv.hash_mask;
+}
+
+// one row of the table: F floats in one 4 F byte load
+template <int F> struct RowT;
+template <> struct RowT<1> { using type = float; };
+template <> struct RowT<2> { using type = float2; };
+template <> struct RowT<4> { using type = float4; };
+template <int F> __device__ inline void load_row(const float* __restrict__ E, long long row, float (&v)[F]) {
+    const typename RowT<F>::type r = reinterpret_cast<const typename RowT<F>::type*>(E)[row];       // one 4 F byte load (rows are aligned)
+    const float* rf = reinterpret_cast<const float*>(&r);
+#pragma unroll
+    for (int k = 0; k < F; ++k) v[k] = rf[k];
 }
 
 // q = 61 - e - ceil(log2 P) with M = m 2^e, 0.5 <= m < 1 (frexp), from the bit pattern of a finite M > 0

@@ -106,7 +106,9 @@ class _DenseMLP(torch.autograd.Function):
         d_out = d_out.to(torch.float32).contiguous()
         P, dev = x.shape[0], x.device
         new = lambda n: torch.empty((P, n), dtype=torch.float32, device=dev)
-        g = {n: torch.empty_like(p) for n, p in m.named_parameters()}
+        # (frozen layers behind an input that requires grad -- localisation against a hashgrid.HashNeRF: no weight-gradient launch)
+        g = {n: torch.empty_like(p) if ctx.needs else None for n, p in m.named_parameters()}
+        wgrad = _wgrad if ctx.needs else (lambda *a, **k: None)
         h = hs[-1]
         d_h = new(W)
         # d_x [P, input_ch + input_ch_views], only when x requires grad: the first layer's dgrad plus that of every layer behind a
@@ -117,22 +119,22 @@ class _DenseMLP(torch.autograd.Function):
             feat, hv = saved[1 + D], saved[2 + D]
             cd, Wh = m.input_ch_views, W // 2
             vl = m.views_linears[0]
-            _wgrad(d_out, 0, 3, hv, 0, Wh, g["rgb_linear.weight"], 0, g["rgb_linear.bias"])
+            wgrad(d_out, 0, 3, hv, 0, Wh, g["rgb_linear.weight"], 0, g["rgb_linear.bias"])
             d_hv = new(Wh)
             _dgrad(d_out, 0, 3, m.rgb_linear.weight, 0, d_hv, Wh, act=hv)
-            _wgrad(d_hv, 0, Wh, feat, 0, W, g["views_linears.0.weight"], 0, g["views_linears.0.bias"])
-            _wgrad(d_hv, 0, Wh, x, cx, cd, g["views_linears.0.weight"], W)
+            wgrad(d_hv, 0, Wh, feat, 0, W, g["views_linears.0.weight"], 0, g["views_linears.0.bias"])
+            wgrad(d_hv, 0, Wh, x, cx, cd, g["views_linears.0.weight"], W)
             if x_grad:
                 _dgrad(d_hv, 0, Wh, vl.weight, W, d_x, cd, dx_lo=cx)
             d_feat = new(W)
             _dgrad(d_hv, 0, Wh, vl.weight, 0, d_feat, W)
-            _wgrad(d_feat, 0, W, h, 0, W, g["feature_linear.weight"], 0, g["feature_linear.bias"])
-            _wgrad(d_out, 3, 1, h, 0, W, g["alpha_linear.weight"], 0, g["alpha_linear.bias"])
+            wgrad(d_feat, 0, W, h, 0, W, g["feature_linear.weight"], 0, g["feature_linear.bias"])
+            wgrad(d_out, 3, 1, h, 0, W, g["alpha_linear.weight"], 0, g["alpha_linear.bias"])
             _dgrad(d_feat, 0, W, m.feature_linear.weight, 0, d_h, W)
             _dgrad(d_out, 3, 1, m.alpha_linear.weight, 0, d_h, W, accumulate=True, act=h)
         else:
             oc = m.output_ch
-            _wgrad(d_out, 0, oc, h, 0, W, g["output_linear.weight"], 0, g["output_linear.bias"])
+            wgrad(d_out, 0, oc, h, 0, W, g["output_linear.weight"], 0, g["output_linear.bias"])
             _dgrad(d_out, 0, oc, m.output_linear.weight, 0, d_h, W, act=h)
             g["views_linears.0.weight"] = g["views_linears.0.bias"] = None           # unused without view directions (helpers:82)
             if x_grad and x.shape[1] > cx:
@@ -141,20 +143,20 @@ class _DenseMLP(torch.autograd.Function):
             lin = m.pts_linears[i]
             wn, bn = f"pts_linears.{i}.weight", f"pts_linears.{i}.bias"
             if i == 0:
-                _wgrad(d_h, 0, W, x, 0, cx, g[wn], 0, g[bn])
+                wgrad(d_h, 0, W, x, 0, cx, g[wn], 0, g[bn])
                 if x_grad:
                     _dgrad(d_h, 0, W, lin.weight, 0, d_x, cx, accumulate=x_acc)
                 break
             d_prev = new(W)
             if (i - 1) in m.skips:
-                _wgrad(d_h, 0, W, x, 0, cx, g[wn], 0, g[bn])
+                wgrad(d_h, 0, W, x, 0, cx, g[wn], 0, g[bn])
                 if x_grad:
                     _dgrad(d_h, 0, W, lin.weight, 0, d_x, cx, accumulate=x_acc)
                     x_acc = True
-                _wgrad(d_h, 0, W, hs[i - 1], 0, W, g[wn], cx)
+                wgrad(d_h, 0, W, hs[i - 1], 0, W, g[wn], cx)
                 _dgrad(d_h, 0, W, lin.weight, cx, d_prev, W, act=hs[i - 1])
             else:
-                _wgrad(d_h, 0, W, hs[i - 1], 0, W, g[wn], 0, g[bn])
+                wgrad(d_h, 0, W, hs[i - 1], 0, W, g[wn], 0, g[bn])
                 _dgrad(d_h, 0, W, lin.weight, 0, d_prev, W, act=hs[i - 1])
             d_h = d_prev
         return (None, d_x) + tuple(g[n] for n in ctx.names)

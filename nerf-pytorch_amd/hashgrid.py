@@ -4,8 +4,10 @@ fixed-point integers -- and ``HashNeRF``, that encoding in front of the layer st
 general-network path.
 
 The host computes every number a level is defined by (resolution, first row, dense or hashed) in Python float64 and integers; the
-kernels and the torch definitions below (``encode_reference``, ``table_grad_reference``) read the same tables.  No gradient reaches the
-points: the encoding is a function of constant positions here.
+kernels and the torch definitions below (``encode_reference``, ``table_grad_reference``, ``point_grad_reference``) read the same tables.
+By default no gradient reaches the points: the encoding is a function of constant positions.  ``point_grad=True`` at construction
+ keeps points and rays in the graph: nerf_hash_input_grad, a gather of the forward's rows, gives d loss / d points and,
+for HashNeRF.query, d loss / d ray records -- pose refinement, localisation against a trained field, surface normals.
 """
 import math
 
@@ -48,13 +50,34 @@ def level_tables(n_levels, log2_hashmap_size, base_resolution, finest_resolution
     return res, offset, dense
 
 
+def views_grad_reference(viewdirs, d_cols, multires_views, dtype=torch.float32):
+    """the adjoint of the view columns as nerf_build_inputs writes them: d_cols [..., 3] (multires_views < 0: the identity) or
+    [..., 3 + 6 Lv] = d loss / d [v, sin 2^0 v, cos 2^0 v, .., sin 2^(Lv-1) v, cos 2^(Lv-1) v] -> d loss / d v [..., 3] in `dtype`:
+
+        g = d_cols[0:3];   for k = 0 .. Lv - 1 ascending:   a = v 2^k;   g = g + 2^k (d_sin_k cos a - d_cos_k sin a)
+
+    every multiply, subtract and add a separate torch op in that order"""
+    v, d = viewdirs.to(dtype), d_cols.to(device=viewdirs.device, dtype=dtype)
+    Lv = max(int(multires_views), 0)
+    if d.shape[-1] != 3 + 6 * Lv or v.shape[-1] != 3:
+        raise ValueError(f"views_grad_reference: {d.shape[-1]} columns for multires_views={multires_views}")
+    g = d[..., 0:3]
+    for k in range(Lv):
+        f = float(2 ** k)
+        a = v * f
+        g = g + f * (d[..., 3 + 6 * k:6 + 6 * k] * torch.cos(a) - d[..., 6 + 6 * k:9 + 6 * k] * torch.sin(a))
+    return g
+
+
 class _HashEncode(torch.autograd.Function):
     """x [P, width] whose columns 0 .. L F hold the encoding of the points (points [P, 3], or o + d z of rays and z_vals); `fill`
     writes the other columns first (HashNeRF: the encoded view directions).  Backward: the table's gradient from d_x's first L F
-    columns, read in place through the leading dimension."""
+    columns, read in place through the leading dimension.  With enc.point_grad also d_points / d_rays (nerf_hash_input_grad) for the
+    one that requires grad -- `views` = (first view column of x, multires_views) of the columns `fill` wrote from rays[:, 8:11] -- and
+    the table's scatter only when the table requires grad."""
 
     @staticmethod
-    def forward(ctx, embeddings, enc, points, rays, z_vals, width, fill):
+    def forward(ctx, embeddings, enc, points, rays, z_vals, width, fill, *views):
         P = points.shape[0] if points is not None else z_vals.numel()
         dev = embeddings.device
         x = torch.empty((P, width), dtype=torch.float32, device=dev) if width == enc.out_dim else torch.zeros((P, width), dtype=torch.float32,
@@ -63,14 +86,40 @@ class _HashEncode(torch.autograd.Function):
             fill(x)
         hb.hash_encode_fwd(enc.desc(), embeddings, x, 0, points, rays, z_vals)
         ctx.enc, ctx.points, ctx.rays, ctx.z_vals = enc, points, rays, z_vals
+        if enc.point_grad:
+            ctx.views = views[0] if views else None
+            ctx.n_extra = len(views)
+            ctx.save_for_backward(embeddings)
         return x
 
     @staticmethod
     def backward(ctx, d_x):
         enc = ctx.enc
         d_x = d_x.to(torch.float32).contiguous()
+        if enc.point_grad:
+            return _HashEncode._backward_point_grad(ctx, d_x)
         grad = hb.hash_encode_bwd(enc.desc(), d_x, 0, ctx.points, ctx.rays, ctx.z_vals, scratch=enc._scratch_on(d_x.device))
         return grad, None, None, None, None, None, None
+
+    @staticmethod
+    def _backward_point_grad(ctx, d_x):
+        enc = ctx.enc
+        points, rays, z_vals = ctx.points, ctx.rays, ctx.z_vals
+        det = lambda t: None if t is None else t.detach()
+        grad = d_points = d_rays = None
+        if ctx.needs_input_grad[0]:     # (a frozen table -- localisation -- launches neither the maximum, nor the scatter, nor the finish)
+            grad = hb.hash_encode_bwd(enc.desc(), d_x, 0, det(points), det(rays), det(z_vals), scratch=enc._scratch_on(d_x.device))
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            embeddings, = ctx.saved_tensors
+            if points is not None:
+                d_points = hb.hash_input_grad(enc.desc(), embeddings.detach(), d_x, 0, det(points), None, None, -1, -1)
+            else:
+                views_col, multires_views = ctx.views if ctx.views is not None else (-1, -1)
+                d_rec = hb.hash_input_grad(enc.desc(), embeddings.detach(), d_x, 0, None, det(rays), det(z_vals), views_col, multires_views)
+                C = rays.shape[1]       # (the view direction is a record's last three columns, as nerf_build_inputs reads it)
+                d_rays = d_rec if C == 11 else d_rec[:, :C].contiguous() if C < 11 else torch.cat([d_rec[:, :8], d_rec.new_zeros((rays.shape[0], C - 11)),
+                                                                                                    d_rec[:, 8:]], 1)
+        return (grad, None, d_points, d_rays, None, None, None) + (None,) * ctx.n_extra
 
 
 class HashEncoding(nn.Module):
@@ -80,8 +129,9 @@ class HashEncoding(nn.Module):
     +-1e-4): one tensor for the optimizer.  ``level_resolution`` [L], ``level_offset`` [L + 1] (the last entry is rows_total) and
     ``level_dense`` [L] are plain Python lists."""
 
-    def __init__(self, lo, hi, n_levels=16, n_features=2, log2_hashmap_size=19, base_resolution=16, finest_resolution=512):
+    def __init__(self, lo, hi, n_levels=16, n_features=2, log2_hashmap_size=19, base_resolution=16, finest_resolution=512, point_grad=False):
         super().__init__()
+        self.point_grad = bool(point_grad)      # a plain attribute: the state_dict does not know it, __getstate__ carries it
         if int(n_features) not in (1, 2, 4):
             raise ValueError(f"HashEncoding: n_features must be 1, 2 or 4, got {n_features}")
         self.lo, self.hi = tuple(float(v) for v in lo), tuple(float(v) for v in hi)
@@ -131,9 +181,9 @@ class HashEncoding(nn.Module):
         return self._scratch[key]
 
     def forward(self, points):
-        """[..., 3] -> [..., L F] through the kernels, with autograd to ``embeddings`` (none to the points)"""
+        """[..., 3] -> [..., L F] through the kernels, with autograd to ``embeddings`` (and, with point_grad, to the points)"""
         lead = points.shape[:-1]
-        pts = points.detach().reshape(-1, 3).to(torch.float32).contiguous()
+        pts = (points if self.point_grad else points.detach()).reshape(-1, 3).to(torch.float32).contiguous()
         out = _HashEncode.apply(self.embeddings, self, pts, None, None, self.out_dim, None)
         return out.reshape(*lead, self.out_dim)
 
@@ -177,6 +227,55 @@ class HashEncoding(nn.Module):
             out.append(acc)
         return torch.cat(out, 1).reshape(*lead, self.out_dim)
 
+    def point_grad_reference(self, points, d_out, dtype=torch.float32, embeddings=None):
+        """the definition of the gradient with respect to the points: [P, 3] in `dtype`, the gradient of sum(encode(points) * d_out)
+        (d_out [P, L F]) with respect to `points`, in closed form.  Per level l of resolution R, with encode_reference's u, p, i, f and
+        rows, every multiply, add and subtract a separate torch op in this order:
+
+            v_c   = d_out[:, l F] * E[row_c, 0];  then for k = 1 .. F - 1:  v_c = v_c + d_out[:, l F + k] * E[row_c, k]     (c = 0 .. 7)
+            df_x  = -((w_y * w_z) * v_0);  then for c = 1 .. 7:  df_x = df_x + (w_y * w_z) * v_c where bit 0 of c is set, else
+                    df_x = df_x - (w_y * w_z) * v_c, with w_y = f_y where bit 1 of c is set else 1 - f_y, w_z likewise (bit 2);
+                    df_y with (w_x * w_z) and bit 1, df_z with (w_x * w_y) and bit 2
+            g_a   = g_a + (df_a * R) * inv_extent[a],  g_a = 0 before level 0, levels ascending; the level's term is replaced by an
+                    exact 0 on an axis whose UNCLAMPED t = (x - lo) * inv_extent is < 0 or > 1
+
+        Inside a cell the encoding is trilinear: the derivative along an axis is constant in that axis and, at a lattice plane, that of
+        the cell ``_corners`` picks (right-continuous; on the upper face the last cell).  Outside the box the clamp makes the encoding
+        constant in that coordinate: exactly on a face (t = 0 or 1) the derivative is the cell's, as torch.clamp's backward is inclusive
+        at its bounds.  nerf_hash_input_grad in point mode is held to this function (float32) bit for bit."""
+        E = (self.embeddings.detach() if embeddings is None else embeddings).to(dtype)
+        x = points.reshape(-1, 3).to(device=E.device, dtype=dtype)
+        d = d_out.reshape(-1, self.out_dim).to(device=E.device, dtype=dtype)
+        F = self.n_features
+        lo, inv = self._lo32.to(device=x.device, dtype=dtype), self._inv32.to(device=x.device, dtype=dtype)
+        t = (x - lo) * inv
+        outside = (t < 0.0) | (t > 1.0)
+        u = torch.clamp(t, 0.0, 1.0)
+        zero = torch.zeros((), dtype=dtype, device=x.device)
+        g = torch.zeros_like(x)
+        for l in range(self.n_levels):
+            R = self.level_resolution[l]
+            rows, _ = self._corners(x, l, dtype)
+            p = u * float(R)
+            i = torch.clamp(torch.floor(p).to(torch.int64), 0, R - 1)
+            f = p - i.to(dtype)
+            df = [None, None, None]
+            for c in range(8):
+                e = E[rows[:, c]]
+                v = d[:, l * F] * e[:, 0]
+                for k in range(1, F):
+                    v = v + d[:, l * F + k] * e[:, k]
+                w = [f[:, a] if (c >> a) & 1 else 1.0 - f[:, a] for a in range(3)]
+                terms = ((w[1] * w[2]) * v, (w[0] * w[2]) * v, (w[0] * w[1]) * v)
+                for a in range(3):
+                    if c == 0:
+                        df[a] = -terms[a]
+                    else:
+                        df[a] = df[a] + terms[a] if (c >> a) & 1 else df[a] - terms[a]
+            contrib = torch.stack([(df[a] * float(R)) * inv[a] for a in range(3)], 1)
+            g = g + torch.where(outside, zero, contrib)
+        return g
+
     def table_grad_reference(self, points, d_out):
         """the fixed-point rule of nerf_hash_encode_bwd in torch: fp32 [rows_total, F] from d_out [P, L F]"""
         pts = points.reshape(-1, 3).to(torch.float32)
@@ -207,9 +306,9 @@ class HashNeRF(DenseNeRF):
     columns)."""
 
     def __init__(self, lo, hi, D=2, W=64, input_ch_views=27, output_ch=4, skips=(), use_viewdirs=True, n_levels=16, n_features=2,
-                 log2_hashmap_size=19, base_resolution=16, finest_resolution=512):
+                 log2_hashmap_size=19, base_resolution=16, finest_resolution=512, point_grad=False):
         nn.Module.__init__(self)        # (not DenseNeRF's: the layers live in self.mlp, once)
-        self.encoding = HashEncoding(lo, hi, n_levels, n_features, log2_hashmap_size, base_resolution, finest_resolution)
+        self.encoding = HashEncoding(lo, hi, n_levels, n_features, log2_hashmap_size, base_resolution, finest_resolution, point_grad=point_grad)
         if not use_viewdirs:
             input_ch_views = 0
         self.mlp = DenseNeRF(D=D, W=W, input_ch=self.encoding.out_dim, input_ch_views=input_ch_views, output_ch=output_ch, skips=list(skips),
@@ -243,6 +342,11 @@ class HashNeRF(DenseNeRF):
     @property
     def multires(self):
         raise NotImplementedError("HashNeRF: the points go through a hash encoding, not a positional one")
+
+    @property
+    def point_grad(self):
+        """whether points and rays stay in the graph (the encoding's flag)"""
+        return self.encoding.point_grad
 
     def _mlp_params(self):
         return [p for _, p in self.mlp.named_parameters()]
@@ -280,7 +384,18 @@ class HashNeRF(DenseNeRF):
                               for i in range(0, n, rays_per_slice)], 0)
         if self.use_viewdirs and rays.shape[1] < 11:
             raise ValueError("HashNeRF.query: a network with view directions needs ray records with 11 columns")
-        rays_c, z_c = rays.detach().to(torch.float32).contiguous(), z_vals.detach().to(torch.float32).contiguous()
+        z_c = z_vals.detach().to(torch.float32).contiguous()
+        if self.point_grad and torch.is_grad_enabled() and rays.requires_grad:
+            # the rays stay in the graph: the one _HashEncode node owns all of x, so its backward takes the hash columns AND the view
+            # columns of _DenseMLP's d_x to d_rays in one call (depths are constants)
+            rays_c = rays.to(torch.float32).contiguous()
+            rays_k = rays_c.detach()
+            views = (self.input_ch, self.multires_views) if self.use_viewdirs else None
+            x = _HashEncode.apply(self.encoding.embeddings, self.encoding, None, rays_c, z_c, self.input_ch + self.input_ch_views,
+                                  lambda m: self._fill_views(rays_k, z_c, m), views)
+            out = _DenseMLP.apply(self.mlp, x, *self._mlp_params())
+            return out.reshape(n, S, out.shape[-1])
+        rays_c = rays.detach().to(torch.float32).contiguous()
         x = _HashEncode.apply(self.encoding.embeddings, self.encoding, None, rays_c, z_c, self.input_ch + self.input_ch_views,
                               lambda m: self._fill_views(rays_c, z_c, m))
         out = _DenseMLP.apply(self.mlp, x, *self._mlp_params())

@@ -118,6 +118,8 @@ def _declare(lib):
         "nerf_hash_scratch_words": (sz, [p]),
         "nerf_hash_encode_fwd": (i, [p, p, p, p, i, p, i, l, p, i, p]),
         "nerf_hash_encode_bwd": (i, [p, p, p, i, p, i, l, p, i, p, p, i, p]),
+        "nerf_hash_input_grad_workspace_floats": (sz, [l]),
+        "nerf_hash_input_grad": (i, [p, p, p, p, i, p, i, l, p, i, i, i, p, p, p, i, p]),
         "nerf_live_tiles_words": (sz, [i, i]),
         "nerf_bwd_skip_dead": (i, []),
         "nerf_field_dgrad_split_live": (i, [p, p, p, i, i, p, i, p, p]),
@@ -151,6 +153,7 @@ EXPORTS = ["nerf_abi_version", "nerf_last_error", "nerf_param_count", "nerf_para
            "nerf_baked_train_bwd_rays",
            "nerf_baked_reg_fwd", "nerf_baked_reg_bwd",
            "nerf_hash_scratch_words", "nerf_hash_encode_fwd", "nerf_hash_encode_bwd",
+           "nerf_hash_input_grad_workspace_floats", "nerf_hash_input_grad",
            "nerf_live_tiles_words", "nerf_bwd_skip_dead", "nerf_field_dgrad_split_live", "nerf_field_wgrad_phase_live",
            "nerf_distortion_fwd", "nerf_distortion_bwd", "nerf_interlevel_fwd", "nerf_interlevel_bwd"]
 
@@ -1798,6 +1801,47 @@ def hash_encode_bwd(desc, d_out, col=0, points=None, rays=None, z_vals=None, scr
         with _timed("hash_finish_kernel", 0.0, rows * F * 20.0):
             _check(lib().nerf_hash_encode_bwd(*args(2)), "nerf_hash_encode_bwd")
     return d_embeddings
+
+
+def hash_input_grad(desc, embeddings, d_x, col, points, rays, z_vals, views_col, multires_views, accumulate=False):
+    """nerf_hash_input_grad: the gradient with respect to the points from columns col .. col + L F of d_x [P, >= col + L F] (DESIGN.md
+    3.28).  Point mode (points [P, 3]): returns d_points [P, 3].  Ray mode (rays [N, >= 6] + z_vals [N, S]): returns d_rays [N, 11] by
+    nerf_field_input_grad's column contract, columns 8:11 from the 3 + 6 multires_views view columns of d_x at views_col (an index into
+    d_x's columns, not relative to col; < 0: none, zeros); `accumulate`: a d_rays [N, 11] tensor to add to (its columns 6:8 stay),
+    returned.  No atomics: two calls give the same bits."""
+    pp, rp, stride, zp, S, P = _hash_points("hash_input_grad", points, rays, z_vals)
+    L, F = desc.n_levels, desc.n_features
+    if tuple(embeddings.shape) != (desc.level_offset[L], F):
+        raise NerfHipError(f"hash_input_grad: embeddings must be [{desc.level_offset[L]}, {F}]")
+    dp, ld = _hash_cols("hash_input_grad", d_x, col, L * F, P)
+    ray_mode = points is None
+    if not ray_mode and (views_col >= 0 or (accumulate is not None and accumulate is not False)):
+        raise NerfHipError("hash_input_grad: view columns and accumulate belong to ray mode")
+    if ray_mode and rays.shape[1] < 11 and views_col >= 0:
+        raise NerfHipError("hash_input_grad: view columns need ray records of 11 columns")
+    vc = -1 if views_col < 0 else int(views_col) - int(col)         # (the library counts from the pointer it is handed)
+    dev = d_x.device
+    d_points = d_rays = work = None
+    acc = 0
+    if ray_mode:
+        N = int(rays.shape[0])
+        if isinstance(accumulate, torch.Tensor):
+            if tuple(accumulate.shape) != (N, 11):
+                raise NerfHipError(f"hash_input_grad: accumulate must be a d_rays tensor [{N}, 11]")
+            d_rays, acc = accumulate, 1
+        elif accumulate:
+            raise NerfHipError("hash_input_grad: accumulate is False or the d_rays tensor to add to")
+        else:
+            d_rays = (torch.empty if P else torch.zeros)((N, 11), dtype=torch.float32, device=dev)      # (no samples: nothing is launched)
+        work = torch.empty(lib().nerf_hash_input_grad_workspace_floats(P), dtype=torch.float32, device=dev)
+    else:
+        d_points = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    opt = lambda t: None if t is None or t.numel() == 0 else _ptr(t)
+    # per point and level 8 rows in (the forward's), L F floats of d_x; 12 bytes out (ray mode: written and read once more)
+    with _timed("hash_point_grad_kernel", 0.0, P * L * (8.0 * 4 * F + 4.0 * F) + 12.0 * P):
+        _check(lib().nerf_hash_input_grad(ctypes.byref(desc), _ptr(embeddings, "embeddings"), pp, rp, stride, zp, S, P, dp, ld, vc,
+                                          int(multires_views), opt(d_points), opt(d_rays), opt(work), acc, _stream()), "nerf_hash_input_grad")
+    return d_rays if ray_mode else d_points
 
 
 # Bumped by every raw-pointer update of parameters (the fused Adam kernel writes through data_ptr(), which does not

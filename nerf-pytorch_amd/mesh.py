@@ -214,10 +214,11 @@ def _res_nodes(who, resolution):
 def density_volume(model, lo, hi, resolution, viewdir=(0.0, 0.0, 1.0)):
     """fp32 [nx, ny, nz] on the model's device: raw[:, 3] -- the density before the ReLU, what DensityGrid.update accumulates -- of a fused
     NeRF at the nodes of the lattice of `resolution` nodes (an int means cubic) from lo to hi, through query_points under no_grad in
-    slices, with one fixed view direction (the density does not depend on it).  Fused NeRF modules only."""
+    slices, with one fixed view direction (the density does not depend on it).  Fused NeRF modules and hashgrid.HashNeRF only."""
     from .field import NeRF
+    from .hashgrid import HashNeRF
     from .render import query_points
-    if not isinstance(model, NeRF):
+    if not isinstance(model, (NeRF, HashNeRF)):
         raise NotImplementedError("density_volume: a fused-kernel NeRF module is required (not a DenseNeRF / other module)")
     n = _res_nodes("density_volume", resolution)
     _lattice_step("density_volume", lo, hi, n)
@@ -235,7 +236,8 @@ def density_volume(model, lo, hi, resolution, viewdir=(0.0, 0.0, 1.0)):
 
 def vertex_normals(model, points, viewdir=(0.0, 0.0, 1.0)):
     """fp32 [V, 3]: -grad / |grad| of query_points(model, points, viewdir)[:, 3] with respect to the points (autograd, the input-gradient
-    kernel in point mode): the density grows inwards, the normal points out.  A zero or non-finite gradient gives a zero normal."""
+    kernel in point mode; for a hashgrid.HashNeRF, which must be built with point_grad=True, nerf_hash_input_grad): the density grows
+    inwards, the normal points out.  A zero or non-finite gradient gives a zero normal."""
     from .render import query_points
     out = torch.zeros((points.shape[0], 3), dtype=torch.float32, device=points.device)
     vd = torch.tensor([float(v) for v in viewdir], dtype=torch.float32, device=points.device)

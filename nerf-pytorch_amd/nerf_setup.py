@@ -70,6 +70,8 @@ _HASH_FLAGS = [
     ("base_resolution", dict(type=int, default=16, help="cells per axis of the coarsest level")),
     ("finest_resolution", dict(type=int, default=512, help="cells per axis of the finest level")),
     ("hash_bound", dict(type=float, default=1.5, help="half side of the hash grid's cube about the origin")),
+    ("hash_point_grad", dict(action="store_true", help="keep points and rays in the graph of the hash-grid networks (pose refinement, "
+                                                       "localisation, normals)")),
 ]
 
 
@@ -158,12 +160,13 @@ def _create_hash_nerf(args, device, embed_fn, embeddirs_fn, input_ch_views, outp
     """create_nerf for --i_embed 1: HashNeRF networks of --netdepth x --netwidth layers (the skip connection of the reference only where
     a layer 5 exists), each with a table of its own over the cube [-hash_bound, hash_bound]^3; torch.optim.Adam over layers and tables"""
     from .hashgrid import HashNeRF
-    opt = {name: getattr(args, name, kw["default"]) for name, kw in _HASH_FLAGS}
+    opt = {name: getattr(args, name, kw.get("default", False)) for name, kw in _HASH_FLAGS}
     bound = float(opt["hash_bound"])
     grid = dict(n_levels=opt["hash_levels"], n_features=opt["hash_features"], log2_hashmap_size=opt["log2_hashmap_size"],
                 base_resolution=opt["base_resolution"], finest_resolution=opt["finest_resolution"])
     make = lambda D, W: HashNeRF([-bound] * 3, [bound] * 3, D=D, W=W, input_ch_views=input_ch_views, output_ch=output_ch,
-                                 skips=[4] if D > 5 else [], use_viewdirs=args.use_viewdirs, **grid).to(device)
+                                 skips=[4] if D > 5 else [], use_viewdirs=args.use_viewdirs, point_grad=bool(opt["hash_point_grad"]),
+                                 **grid).to(device)
     model = make(args.netdepth, args.netwidth)
     grad_vars = list(model.parameters())
     model_fine = None

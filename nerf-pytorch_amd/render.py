@@ -641,10 +641,19 @@ def interlevel_loss_reference(proposal_weights, proposal_z, weights, z_vals):
 def query_points(model, pts, viewdirs_per_point):
     """Evaluate the field at explicit points: every point is its own ray record
     (o = pt, d = 0, z = 0  =>  o + d*z == pt exactly).  Points / view directions that require grad receive d_pts / d_viewdirs
-    (the input-gradient kernel in point mode)."""
+    (the input-gradient kernel in point mode).  A hashgrid.HashNeRF goes through its own query (columns 0:4 of its output); gradients
+    to its points and view directions need HashNeRF(point_grad=True)."""
     grad_on = torch.is_grad_enabled()
     in_grad = grad_on and (pts.requires_grad or viewdirs_per_point.requires_grad)
     n = pts.shape[0]
+    from .hashgrid import HashNeRF
+    if isinstance(model, HashNeRF):
+        if in_grad and not model.point_grad:
+            raise NotImplementedError("query_points: gradients to the points / view directions of a HashNeRF need a network built with "
+                                      "point_grad=True (without it the positions are constants of the graph)")
+        pts, vd = pts.to(torch.float32), viewdirs_per_point.to(torch.float32)
+        rays = torch.cat([pts, torch.zeros((n, 5), dtype=torch.float32, device=pts.device), vd], -1)
+        return model.query(rays, torch.zeros((n, 1), dtype=torch.float32, device=pts.device)).reshape(n, -1)[:, :4]
     if in_grad:
         pts = pts.to(torch.float32).contiguous()
         vd = viewdirs_per_point.to(torch.float32).contiguous()
@@ -1220,7 +1229,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     if not dense and ray_batch.shape[-1] <= 8:
         raise ValueError("render_rays: these networks use view directions; the ray records need 11 columns (render(use_viewdirs=True))")
     rays_grad = torch.is_grad_enabled() and ray_batch.requires_grad
-    if rays_grad and dense:
+    # (general networks: only a call whose networks are all HashNeRF(point_grad=True) takes rays in the graph -- hashgrid.HashNeRF.query)
+    if rays_grad and dense and not all(getattr(m, "point_grad", False) for m in nets):
         raise NotImplementedError("render_rays: gradients to rays / sample points / camera poses are implemented for the fused "
                                   "NeRF architecture only, not for general (DenseNeRF) networks")
     # rays that require grad stay in the graph (d loss / d ray records: nerf_field_input_grad + the compositing's |d| term)
